@@ -34,6 +34,12 @@ run (three rocprofv3 child runs of `bench.py --steps 1` on the same workload: FE
 `counters_source` says which).  `cpu_baseline` times the CPU restatement under oracle/ (the checker, never the
 product) on a bounded sample of the same workload on the host cores.
 
+A plain run does only what the headline needs: set-up, --warmup frames, --steps timed frames, the line (`ms_per_step` = wall
+time of one timed frame).  `roofline*`, `kernels_isolated_ms_per_frame`, `cpu_baseline` and, for N > 1, the second scheduler's
+timed region and the exchange proof are measured with `--full` only (`roofline` / `cpu_baseline` are null otherwise; `full` says
+which).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy; the inputs are fixed, so two builds
+run with the same arguments can be compared output for output.
+
 `--inproc` runs the same frame the way the reference itself does: ONE process, one worker thread per
 GPU (polaris_amd/host/renderer.cpp), blocks merged into the primary by polaris_hip_merge over xGMI
 peer access, `--scheduler naive|perfect` (tracer/scheduler.go) -- no torch.distributed, no collective.
@@ -103,7 +109,7 @@ def kernel_algorithmic_bytes(st, shade_counts, B: int, packet_camera: bool):
 
 def committed_counters(symbol: str, workload_is_headline: bool):
     """The FALLBACK for live_counters() below (which collects the PMC counters of this build on this machine with rocprofv3 child runs
-    at the end of every N = 1 run): the newest committed profile of the headline workload (scripts/traffic.sh, scripts/pmc.sh), keyed by
+    at the end of every N = 1 run with --full): the newest committed profile of the headline workload (scripts/traffic.sh, scripts/pmc.sh), keyed by
     kernel symbol -- used when the profiler is missing, a pass fails, or --no-live-counters is given.  Returns (hbm bytes per launch,
     lane utilisation, wave-level VALU instructions per launch, description of the source) -- None where there is no committed
     number for this symbol."""
@@ -232,6 +238,23 @@ def host_cpu() -> str:
         return f"{os.cpu_count()} logical CPUs"
 
 
+DUMP_MAX_BYTES = 64 << 20   # all arrays of one --dump-outputs together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs`: every array as out_dir/<name>.npy in float32.  Each array may take an equal share of DUMP_MAX_BYTES; one above
+    its share is replaced by a fixed, seeded sample of its pixels (the same pixels for the same shape, whatever the build), in pixel order."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) - 4096   # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = share // (px.shape[1] * 4)
+            a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_inproc(args) -> None:
     """`--inproc`: the frame loop of renderer/default.go:106-196 as the reference runs it -- one process, one worker thread per
     tracer (polaris_amd/host/renderer.cpp), every tracer Trace()s the rows the scheduler hands it, the workers MergeOutput
@@ -277,6 +300,9 @@ def run_inproc(args) -> None:
         elapsed = time.perf_counter() - t0
         trace_ms = [round(r.tracer_stats(i)[1], 3) for i in range(len(devices))]
         merge_counts = r.merge_counts()
+        if args.dump_outputs:
+            fb, acc = r.read()
+            dump_outputs(args.dump_outputs, {"frame_accumulator": acc, "framebuffer": fb})
         if args.save_accumulator:
             np.save(args.save_accumulator, r.read()[1])
         if args.save_png:
@@ -319,6 +345,13 @@ def main() -> None:
     ap.add_argument("--no-kernel-timers", action="store_true")
     ap.add_argument("--no-live-counters", action="store_true", help="do not collect the PMC counters (HBM traffic, live lanes, VALU instructions) with rocprofv3 child runs "
                     "at the end (N = 1 only; ~25 s); `roofline.traffic` then comes from the newest committed profile of the headline workload")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the per-kernel "
+                    "roofline (one extra frame with kernel timers, the live PMC counter passes), the CPU baseline, and for N > 1 the second "
+                    "scheduler's timed region and the exchange proof.  Off by default: a plain run sets up, warms up, times --steps frames "
+                    "and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, rank 0 writes what the last timed step computed "
+                    "as DIR/<name>.npy (float32, 64 MB in all: a fixed, seeded sample of a larger frame): the trace accumulator of its Trace, the "
+                    "frame accumulator, the tone-mapped frame buffer")
     ap.add_argument("--save-png", default="")
     ap.add_argument("--save-accumulator", default="", help="rank 0 writes its frame accumulator of the last frame as .npy (tests)")
     ap.add_argument("--opt", action="append", default=[], help="tracer option key=value (polaris_hip_set_option)")
@@ -676,10 +709,15 @@ def main() -> None:
     main_rows = list(rows)                         # (the second region below schedules its own)
     if args.save_accumulator and rank == 0:
         np.save(args.save_accumulator, tr.read_accumulator(1))  # the primary's frame accumulator of the last frame (tests)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as its caller receives them: rank 0's own Trace output, the frame accumulator every block of
+        # the frame was merged into, the tone-mapped RGBA8 frame buffer
+        dump_outputs(args.dump_outputs, {"trace_accumulator": tr.read_accumulator(0), "frame_accumulator": tr.read_accumulator(1),
+                                         "framebuffer": tr.read_framebuffer()})
 
     # N > 1: the same frames under the OTHER block scheduler, as a second timed region (reported beside the headline, never as it)
     second = None
-    if world > 1 and not args.no_second_scheduler and not args.emulate_rank:
+    if args.full and world > 1 and not args.no_second_scheduler and not args.emulate_rank:
         other = "perfect" if args.scheduler == "naive" else "naive"
         if px is not None:
             px.set_scheduler(other)
@@ -699,7 +737,7 @@ def main() -> None:
     # accumulator (the ring slot its last Trace wrote), rank 0 gathers them over gloo -- a path that shares nothing with the exchange -- and
     # compares them with the same rows of its frame accumulator (Reset + one merge per block: 0 + x, so the floats must be EQUAL, whatever
     # branch carried them: a peer read over xGMI, a staged copy, a strip over RCCL or gloo).  After the timed regions, never inside one.
-    if world > 1 and not args.emulate_rank:
+    if args.full and world > 1 and not args.emulate_rank:
         proof = {"frame": "the last frame of the last timed region", "rows": list(rows)}
         try:
             mine = np.ascontiguousarray(tr.read_accumulator(0)[block_y:block_y + block_h])
@@ -760,6 +798,9 @@ def main() -> None:
                        # the ray population of rank 0's block in the last timed frame, per bounce (PolarisTraceStats): what anyone reasoning about
                        # the any-hit kernel needs first -- how many shadow rays there are and how many of them are blocked
                        "ray_counts": ray_counts(last_counts[0], B)},
+            "full": args.full,
+            "roofline": None,
+            "cpu_baseline": None,
         }
         # ---- roofline, per kernel symbol -----------------------------------------------------------
         # Kernel durations are HIP events on the tracer's own streams (the library brackets every launch
@@ -769,7 +810,7 @@ def main() -> None:
         # symbol with the largest isolated time (the top row of `rocprofv3 --kernel-trace --stats` on the same
         # command, profiles/r*_kernel_stats_overlap1.csv); `roofline_per_kernel` holds the same object for every
         # symbol that moves ray streams.
-        if not args.no_kernel_timers:
+        if args.full and not args.no_kernel_timers:
             tr.set_option("overlap", 1)
             tr.set_option("time_kernels", 1)
             for name in KERNELS:
@@ -784,10 +825,10 @@ def main() -> None:
             live, live_src = (None, None)
             under_profiler = "rocprof" in (os.environ.get("LD_PRELOAD", "") + os.environ.get("ROCP_TOOL_LIBRARIES", "") + os.environ.get("ROCPROFILER_REGISTER_FORCE_LOAD", "")).lower()
             if world == 1 and not args.no_live_counters and not args.emulate_rank and not under_profiler:   # (never a profiler inside a profiler)
-                workload = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",)]
+                workload = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline", "--full")]   # (the child passes are plain runs)
                 # (the child runs repeat the workload's own arguments and append their own --steps 1 --warmup 0: argparse keeps the last
                 # occurrence.  What must not be repeated -- output files -- is dropped here in both spellings, `--opt value` and `--opt=value`)
-                skip, keep = {"--save-png", "--save-accumulator"}, []
+                skip, keep = {"--save-png", "--save-accumulator", "--dump-outputs"}, []
                 it = iter(workload)
                 for a in it:
                     if a in skip:
@@ -835,7 +876,7 @@ def main() -> None:
         # ---- CPU baseline: the oracle (checker) on a bounded sample of the same workload ----
         # Sample-parallel mode of the restatement (threads take whole samples; same paths as the
         # reference order, per-pixel sums re-associated): the fastest way to run this path on CPU cores.
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 from oracle import pybind as ob
 

@@ -64,7 +64,7 @@ def config_c1():
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "rXX"
-    out = {"command": "python bench.py --steps 3 --warmup 1 --no-cpu-baseline <args>", "configs": {}}
+    out = {"command": "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline <args>", "configs": {}}
     try:
         out["configs"]["C1"] = config_c1()
         print("C1", out["configs"]["C1"]["sample_parallel"], flush=True)
@@ -74,7 +74,7 @@ def main():
         base = ["--steps", "3", "--warmup", "1"]
         if "--steps" in args:
             base = ["--warmup", "1"]
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *base, "--no-cpu-baseline", "--no-live-counters", *args], capture_output=True, text=True, cwd=ROOT)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *base, "--no-cpu-baseline", "--no-live-counters", *args], capture_output=True, text=True, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if p.returncode != 0 or not line:
             out["configs"][key] = {"what": what, "error": p.stderr[-400:]}

@@ -15,7 +15,7 @@ for l in sys.stdin:
   echo "== $c: bench (default overlap), alternating"
   for i in 1 2 3; do
     for o in "" "--opt trace_spill=1" "--opt trace_spill=1 --opt trace_wgs_per_cu=6" "--opt trace_spill=1 --opt trace_wgs_per_cu=5"; do
-      timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-live-counters ${CFG[$c]} $o 2>/dev/null | python3 -c "
+      timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-live-counters ${CFG[$c]} $o 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

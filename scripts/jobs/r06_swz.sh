@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 run() { # name lib args
   local L=gpurun_in/variants/$2.so; shift; shift
-  POLARIS_HIP_LIB=$L timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-live-counters "$@" 2>/dev/null | python3 -c "
+  POLARIS_HIP_LIB=$L timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-live-counters "$@" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,9 @@ export TMPDIR=/tmp
 tag=$1
 R=$GRAFT_REPO_ROOT
 cd $R
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+# the full line (roofline, counters, CPU baseline: DESIGN.md section 6 reads them) into $BENCH_OUT (default: $TMPDIR)
+out=${BENCH_OUT:-$TMPDIR}
+python3 bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 for ov in 1 4; do
   rm -rf gpurun_out/prof_$ov
   rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$ov -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-counters --opt overlap=$ov > gpurun_out/${tag}_bench_under_rocprof_overlap$ov.json 2>/dev/null
@@ -20,4 +22,4 @@ bash scripts/traffic.sh > gpurun_out/${tag}_traffic.txt 2>&1
 cp gpurun_out/traffic.json gpurun_out/${tag}_traffic.json
 bash scripts/pmc.sh ${tag} > gpurun_out/${tag}_pmc.log 2>&1 || echo "profile_round.sh: the SQ counter pass failed, see gpurun_out/${tag}_pmc.log"
 head -12 gpurun_out/${tag}_kernel_stats_overlap1.csv
-cat gpurun_out/${tag}_bench.json | cut -c1-1500
+cut -c1-1500 "$out/${tag}_bench.json"

@@ -1,8 +1,8 @@
 """pytest configuration: the `gpu` marker, library builds and shared helpers.
 
-`-m "not gpu"`: oracle vs golden vectors (and vs the compiled reference where /root/reference
-exists), host logic, C-ABI surface.  `-m gpu`: parity of the HIP path through the C ABI.
-Nothing here reads /root/reference except the optional compiled-reference build.
+`-m "not gpu"`: oracle vs golden vectors and vs the compiled reference (live where oracle/_ref was built,
+its recorded answers under tests/golden elsewhere), host logic, C-ABI surface.  `-m gpu`: parity of the
+HIP path through the C ABI.
 """
 import glob
 import os
@@ -40,13 +40,31 @@ def oracle(built):
     return ob.Oracle("oracle")
 
 
+def _reference(kind):
+    """The compiled reference (oracle/_ref) where it was built; elsewhere its recorded answers (tests/reference_record.py)."""
+    from oracle import pybind as ob
+    from reference_record import Recorder, Replay
+
+    if not ob.available(kind):
+        yield Replay(kind)
+        return
+    live = ob.Oracle(kind)
+    if not os.environ.get("POLARIS_RECORD_REFERENCE"):
+        yield live
+        return
+    rec = Recorder(live)
+    yield rec
+    rec.save()
+
+
 @pytest.fixture(scope="session")
 def ref_pm(built):
-    from oracle import pybind as ob
+    yield from _reference("ref_pm")
 
-    if not ob.available("ref_pm"):
-        pytest.skip("compiled reference (oracle/_ref) not built: /root/reference is absent on this machine")
-    return ob.Oracle("ref_pm")
+
+@pytest.fixture(scope="session")
+def ref_libm(built):
+    yield from _reference("ref_libm")
 
 
 def golden_files():

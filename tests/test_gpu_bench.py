@@ -31,7 +31,7 @@ SMALL = ["--width", "128", "--height", "97", "--spp", "8", "--steps", "2", "--wa
 
 
 def test_bench_single_gpu_line(built):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *SMALL], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -58,6 +58,33 @@ def test_bench_single_gpu_line(built):
     assert "THIS run" in r["counters_source"], r["counters_source"]
     assert r["traffic"] > 0 and 0.0 < r["lane_util"] <= 1.0 and 0.0 < d["roofline_issue"]["frac"] < 1.0
     assert all(e["roofline_issue"] and e["traffic"] for e in d["roofline_per_kernel"].values())
+
+
+def test_bench_plain_line_and_dumped_outputs(built, tmp_path):
+    """A plain run (no --full) times exactly --steps frames and measures nothing else; --dump-outputs writes the last timed frame's
+    results in float32, and a second run with the same arguments writes the same results bit for bit (exact_accumulate=1); on one GPU
+    the frame accumulator holds the last frame's one block: its rows equal the trace accumulator's."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        d_out = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--steps", "3", "--opt", "exact_accumulate=1", "--dump-outputs", str(d_out)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        assert d["full"] is False and d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "roofline_per_kernel" not in d and "kernels_isolated_ms_per_frame" not in d
+        assert d["config"]["rays_per_frame"] > 0
+        got = {p.stem: np.load(p) for p in d_out.glob("*.npy")}
+        assert sorted(got) == ["frame_accumulator", "framebuffer", "trace_accumulator"]
+        assert all(a.dtype == np.float32 and a.shape == (97, 128, 4) for a in got.values())
+        runs.append(got)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    trace, frame = runs[0]["trace_accumulator"], runs[0]["frame_accumulator"]
+    assert trace[..., :3].mean() > 0 and runs[0]["framebuffer"][..., :3].max() > 0
+    assert np.array_equal(frame[..., :3], trace[..., :3])      # the frame's one block, merged into the frame accumulator
 
 
 def _two_rank_frame_matches_the_oracle(d, acc_path):
@@ -93,7 +120,7 @@ def test_bench_two_ranks_bare_launch_and_frame(built, tmp_path):
     frame the primary assembled from the gathered strips equals the per-block oracle bit for bit."""
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--same-device", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *SMALL, "--same-device", "--no-cpu-baseline",
            "--opt", "exact_accumulate=1", "--save-accumulator", acc]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -138,7 +165,7 @@ def test_bench_two_ranks_strip_fallback(built, tmp_path):
     the strips (here over gloo, staged through the host; RCCL needs two GPUs), merged with polaris_hip_merge_device."""
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--exchange", "strips", "--backend", "gloo", "--same-device", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *SMALL, "--exchange", "strips", "--backend", "gloo", "--same-device", "--no-cpu-baseline",
            "--no-second-scheduler", "--opt", "exact_accumulate=1", "--save-accumulator", acc]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -154,7 +181,7 @@ def test_bench_falls_back_inside_the_same_processes_when_a_mapping_cannot_be_ope
     GPUs -- say so in config.exchange, and still assemble the right frame."""
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--test-ipc-failure", "--backend", "gloo", "--same-device", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *SMALL, "--test-ipc-failure", "--backend", "gloo", "--same-device", "--no-cpu-baseline",
            "--no-second-scheduler", "--opt", "exact_accumulate=1", "--save-accumulator", acc]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -211,7 +238,7 @@ def test_bench_two_ranks_perfect_scheduler(built, tmp_path):
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     small = ["--width", "128", "--height", "97", "--spp", "8", "--steps", "4", "--warmup", "3"]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *small, "--same-device", "--no-cpu-baseline", "--no-kernel-timers",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *small, "--same-device", "--no-cpu-baseline", "--no-kernel-timers",
            "--scheduler", "perfect", "--no-second-scheduler", "--opt", "exact_accumulate=1", "--save-accumulator", acc,
            "--control", "gloo"]    # (the per-frame message as a gloo all_gather: what ranks that cannot map a common /dev/shm file fall back to)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -249,7 +276,7 @@ def test_bench_two_ranks_with_a_different_frame_every_step(built, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     steps, warmup = 5, 2
     small = ["--width", "128", "--height", "97", "--spp", "8", "--steps", str(steps), "--warmup", str(warmup)]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *small, "--same-device", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *small, "--same-device", "--no-cpu-baseline",
            "--no-kernel-timers", "--no-second-scheduler", "--opt", "exact_accumulate=1", "--save-accumulator", acc, "--test-seeds"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -302,7 +329,7 @@ def test_bench_four_ranks_bare_launch_headline_blocks_one_rank_held_back(built, 
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     W, H, spp, B, steps, warmup = 128, 256, 4, 5, 4, 1
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp), "--steps", str(steps),
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp), "--steps", str(steps),
            "--warmup", str(warmup), "--same-device", "--no-cpu-baseline", "--no-kernel-timers", "--opt", "exact_accumulate=1", "--save-accumulator", acc,
            "--test-seeds", "--test-delay-rank", "3:60"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -329,7 +356,7 @@ def test_bench_four_ranks_under_the_drivers_launcher_c4_blocks_perfect_scheduler
     acc = str(tmp_path / "frame.npy")
     W, H, spp, B, steps, warmup = 96, 541, 2, 5, 4, 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp),
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp),
            "--steps", str(steps), "--warmup", str(warmup), "--same-device", "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler",
            "--scheduler", "perfect", "--opt", "exact_accumulate=1", "--save-accumulator", acc, "--test-seeds"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -350,7 +377,7 @@ def test_bench_three_ranks_fall_back_together_when_an_export_fails(built, tmp_pa
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     W, H, spp, B = 128, 97, 8, 5
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", *SMALL, "--test-ipc-failure", "export", "--backend", "gloo", "--same-device",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "3", *SMALL, "--test-ipc-failure", "export", "--backend", "gloo", "--same-device",
            "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler", "--opt", "exact_accumulate=1", "--save-accumulator", acc]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -539,7 +566,7 @@ def test_bench_refuses_more_gpus_than_visible(built):
 
 def test_bench_two_ranks_under_the_drivers_launcher(built):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--same-device",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *SMALL, "--same-device",
            "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -562,7 +589,7 @@ def test_bench_four_ranks_masked_to_one_visible_device_each(built, tmp_path):
     W, H, spp, B, steps, warmup = 96, 128, 2, 5, 3, 1
     env = dict(os.environ, HIP_VISIBLE_DEVICES="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp),
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp),
            "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler",
            "--opt", "exact_accumulate=1", "--save-accumulator", acc, "--test-seeds"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -587,7 +614,7 @@ def test_bench_four_ranks_sixty_frames_under_random_delays(built, tmp_path):
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     W, H, spp, B, steps, warmup = 96, 122, 2, 4, 60, 2
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp), "--bounces", str(B),
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--width", str(W), "--height", str(H), "--spp", str(spp), "--bounces", str(B),
            "--steps", str(steps), "--warmup", str(warmup), "--same-device", "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler",
            "--scheduler", "perfect", "--opt", "exact_accumulate=1", "--save-accumulator", acc, "--test-seeds", "--test-random-delays", "11"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -608,7 +635,7 @@ def test_merge_ipc_through_the_staging_strip(built, tmp_path):
     for every peer, the library counted every peer merge under that branch, and the frame is the per-block oracle's, bit for bit."""
     acc = str(tmp_path / "frame.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", *SMALL, "--same-device", "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "3", *SMALL, "--same-device", "--no-cpu-baseline", "--no-kernel-timers", "--no-second-scheduler",
            "--opt", "exact_accumulate=1", "--opt", "ipc_staged=1", "--save-accumulator", acc]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]

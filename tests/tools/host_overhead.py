@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))  # the repository root
 import numpy as np
 from polaris_amd import scenes, ctypes_api as T
 from polaris_amd.tracer import HipTracer, UpdateMode, ChangeType

@@ -1,7 +1,7 @@
 """Host-side cost of what rank 0 of an 8-GPU frame does per frame besides its Trace (bench.py, one process per GPU):
 export of its strip, Reset + merge of the assembled frame + tone-map.  Run on one MI355X."""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))  # the repository root
 import numpy as np
 import torch
 torch.cuda.init()
