@@ -280,8 +280,44 @@ int polaris_hip_reset_epoch(polaris_hip_tracer *h, uint64_t *epoch);
 int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch); /* POLARIS_E_TIMEOUT after 120 s without that Reset */
 
 /* Tracer.SyncFramebuffer: wait for pending merges, then tonemapSimpleReinhard over rows of
- * req with weight 1/(accumulated_samples+samples_per_pixel) into the RGBA8 frame buffer. */
+ * req with weight 1/(accumulated_samples+samples_per_pixel) into the RGBA8 frame buffer.
+ * With denoising on (polaris_hip_set_denoise, iterations > 0) the rows of req are first filtered into the DENOISED plane
+ * (edge-avoiding a-trous wavelet filter over the running mean, guided by the first-hit G-buffer, which is computed at the first
+ * denoised sync after a resize / upload_scene / set_camera), and that plane is tone-mapped with weight 1 instead.  The
+ * accumulators are never written by the filter; rows outside req keep their frame buffer bytes.  Denoising needs a camera. */
 int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockRequest *req);
+
+/* Denoising of the synced frame (no reference counterpart: the reference's SyncFramebuffer only tone-maps; "run post-process
+ * filters to the accumulated trace data", tracer/tracer.go:108-110).  Off by default; with it off sync_framebuffer allocates and
+ * launches nothing new.  Per pixel i of the request's rows, with c = frame accumulator rgb * weight, the G-buffer's shading normal n
+ * and hit distance t, and the first hit's albedo a:  r0 = c / max(a, 1e-3); K iterations k of a 5 x 5 B3-spline kernel at stride
+ * 2^k whose taps j are weighted by max(0, n_i . n_j)^(2^P) * exp(-|t_i - t_j| / (sigma_depth * 2^k * t_i))
+ * * exp(-|m(r_i) - m(r_j)|^2 / (sigma_luminance^2 * 2^-k)), m(x) = x / (x + 1); result r_K * max(a, 1e-3).  Misses and emitters
+ * pass through and are never taps; taps outside the request's rows are skipped.  DESIGN.md 10 has the exact arithmetic.
+ * Suggested settings (chosen on the CPU restatement): iterations 4, normal_power_log2 5, sigma_depth 0.1,
+ * sigma_luminance 4.0.  A field out of range is POLARIS_E_BAD_ARGUMENT: iterations 0..8 (0 = off, the default),
+ * normal_power_log2 0..10, sigmas 0 (term off) or within [1e-6, 1e6].  Set struct_size = sizeof(PolarisDenoiseParams). */
+typedef struct PolarisDenoiseParams {
+	uint32_t struct_size;        /* sizeof(PolarisDenoiseParams), as PolarisBvhBuildInput does */
+	uint32_t iterations;         /* K: 0 = off (default), 1..8 */
+	uint32_t normal_power_log2;  /* P: 0..10 */
+	float    sigma_depth;        /* >= 0, finite; 0 = term off */
+	float    sigma_luminance;    /* >= 0, finite; 0 = term off */
+} PolarisDenoiseParams;
+int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p);
+
+/* Frame-sized float4 planes of the denoiser (n_floats >= frame_w*frame_h*4, row-major):
+ *   GUIDE     first-hit shading normal xyz (after bump / normal maps) | hit distance; miss: 0, 0, 0, FLT_MAX
+ *   ALBEDO    first-hit albedo rgb (clamp(tint * k, 0, 1) for diffuse / conductor / rough conductor leaves, 1 otherwise) | the
+ *             selected leaf's type as int bits; miss: 1, 1, 1 | -1
+ *   DENOISED  the filtered running mean of the last denoised sync (rows outside its request: whatever an earlier sync left)
+ * The G-buffer is ONE ray per pixel through the pixel centre, computed on first use and kept until resize / upload_scene /
+ * set_camera.  GUIDE / ALBEDO: POLARIS_E_NO_SCENE_DATA without a scene, POLARIS_E_BAD_ARGUMENT without a camera; DENOISED:
+ * POLARIS_E_BAD_ARGUMENT before any denoised sync. */
+#define POLARIS_AOV_GUIDE    0
+#define POLARIS_AOV_ALBEDO   1
+#define POLARIS_AOV_DENOISED 2
+int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats);
 
 /* frame_w*frame_h*4 bytes RGBA8 (pipeline.go:226-232). */
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes);
@@ -373,7 +409,7 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * timer since the last call for that name.  Timers: "generate", "intersect_packet" (camera rays through
  * the wave-packet kernel), "intersect" (closest hit), "shade_first" / "shade_sort" /
  * "shade_plain" / "shade_wave" (one per shade kernel symbol), "scan", "occlusion", "fold" (the batch's NEE records into the
- * per-path radiance), "resolve", "aggregate", "tonemap". */
+ * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

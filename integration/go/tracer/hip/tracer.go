@@ -249,6 +249,30 @@ func (tr *Tracer) SyncFramebuffer(blockReq *tracer.BlockRequest) (time.Duration,
 	return time.Since(start), tr.check(C.polaris_hip_sync_framebuffer(tr.handle, &creq))
 }
 
+// DenoiseParams configures the edge-avoiding a-trous filter SyncFramebuffer runs over the running mean (PolarisDenoiseParams,
+// include/polaris_hip.h; DESIGN.md section 10).  Iterations = 0 turns it off (the default); DefaultDenoise holds the settings
+// chosen on the CPU restatement.
+type DenoiseParams struct {
+	Iterations      uint32  // K: 0 = off, 1..8
+	NormalPowerLog2 uint32  // P: 0..10
+	SigmaDepth      float32 // 0 = term off, else [1e-6, 1e6]
+	SigmaLuminance  float32 // 0 = term off, else [1e-6, 1e6]
+}
+
+var DefaultDenoise = DenoiseParams{Iterations: 4, NormalPowerLog2: 5, SigmaDepth: 0.1, SigmaLuminance: 4.0}
+
+// SetDenoise turns denoising of the synced frame on or off (the filter's "post-process filters" slot of
+// tracer/tracer.go:108-110).  The accumulators stay the reference result; only the frame buffer shows the filtered image.
+func (tr *Tracer) SetDenoise(p DenoiseParams) error {
+	var c C.PolarisDenoiseParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.iterations = C.uint32_t(p.Iterations)
+	c.normal_power_log2 = C.uint32_t(p.NormalPowerLog2)
+	c.sigma_depth = C.float(p.SigmaDepth)
+	c.sigma_luminance = C.float(p.SigmaLuminance)
+	return tr.check(C.polaris_hip_set_denoise(tr.handle, &c))
+}
+
 // ReadFrameBuffer is what opencl.SaveFrameBuffer reads (tracer/opencl/pipeline.go:226-232).
 func (tr *Tracer) ReadFrameBuffer(pix []uint8) error {
 	if len(pix) == 0 {

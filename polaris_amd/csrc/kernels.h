@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "denoise.h"
 #include "scene_layout.h"
 #include "shading.h"
 
@@ -1640,6 +1641,96 @@ __global__ __launch_bounds__(WG) void k_tonemap(const float4 *acc, uchar4 *fb, u
 		o[k] = (unsigned char)v; // truncation (hdr.cl:22-27)
 	}
 	fb[i] = make_uchar4(o[0], o[1], o[2], 255);
+}
+
+// ------------------------------------------------------------------------------------------
+// Denoising (polaris_hip_set_denoise).  Neither kernel touches an accumulator: the filtered image is a product of
+// its own, and frame_acc / trace_acc stay the reference result.
+// ------------------------------------------------------------------------------------------
+// First-hit guide buffer: ONE deterministic ray per pixel through the pixel centre (k_generate's arithmetic with the offset
+// fixed at 0.5, no seed), its closest hit through the per-ray traversal (k_intersect's: every traversal kernel returns the same
+// hit, bit for bit), surfaceInit as in shade_ray, and the material-tree walk of the reference's debug normal kernel (PRNG state
+// (p, p), no path flags).  GUIDE = n after bump / normal maps | t (miss: 0, 0, 0, FLT_MAX); ALBEDO = clamp(tint * kcol, 0, 1)
+// for diffuse and (rough) conductor leaves, 1 for the other leaves | the leaf type's bits (miss: 1, 1, 1 | -1).
+__global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo) {
+	__shared__ int stk[kTraversalStack][WG];
+	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
+	if (idx >= n) return;
+	const uint32_t gx = idx % W, gy = idx / W;
+	const float tx = ((float)gx + 0.5f) * cam.texel.x;
+	const float ty = ((float)gy + 0.5f) * cam.texel.y;
+	float lx = pm_mix(cam.tl.x, cam.bl.x, ty), ly = pm_mix(cam.tl.y, cam.bl.y, ty), lz = pm_mix(cam.tl.z, cam.bl.z, ty), lw = pm_mix(cam.tl.w, cam.bl.w, ty);
+	float rx = pm_mix(cam.tr.x, cam.br.x, ty), ry = pm_mix(cam.tr.y, cam.br.y, ty), rz = pm_mix(cam.tr.z, cam.br.z, ty), rw = pm_mix(cam.tr.w, cam.br.w, ty);
+	float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
+	const float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
+	const f3 d = mk3(dx * inv, dy * inv, dz * inv);
+	HitRec h;
+	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), d, kFltMax, stk, h);
+	if (h.tri < 0) {
+		guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
+		albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
+		return;
+	}
+	const int tri = h.tri & (int)((1u << S.tri_bits) - 1u); // (the shading class rides above the index)
+	// surfaceInit, util/surface.cl:12-33 (as shade_ray)
+	const float bu = h.u, bv = h.v, bw = 1.0f - (bu + bv);
+	const uint32_t off = (uint32_t)tri * 3;
+	Surf sf;
+	{
+		float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
+		sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
+		a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
+		sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
+		float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
+		sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
+	}
+	uint32_t flags = 0;
+	f3 tint = splat(1.0f);
+	Rng rng = {idx, idx}; // debug.cl:89-91
+	MatT<false> m = select_material(S.mat_index[tri], sf, flags, tint, rng, S);
+	material_params(sf, m, S);
+	guide[idx] = make_float4(sf.n.x, sf.n.y, sf.n.z, h.t);
+	f3 a = splat(1.0f);
+	if (m.type == POLARIS_BXDF_DIFFUSE || m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_ROUGH_CONDUCTOR) {
+		const f3 c = tint * m.kcol;
+		a = mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
+	}
+	albedo[idx] = make_float4(a.x, a.y, a.z, ibits((int)m.type));
+}
+
+// One a-trous iteration over the rows [y0, y1) (n = (y1 - y0) * W pixels, rows in order from y0 * W).  r_in = null: iteration 0,
+// the taps demodulate the frame accumulator on the fly (c / max(albedo, 1e-3), c = acc * weight); otherwise r_in holds r^k.
+// last = 1: the result is remodulated (* max(albedo, 1e-3)) -- the DENOISED plane.  A pixel that is not filtered passes c through.
+__global__ __launch_bounds__(WG) void k_denoise(const float4 *acc, float weight, const float4 *guide, const float4 *albedo, const float4 *r_in,
+                                                float4 *out, uint32_t W, uint32_t y0, uint32_t y1, DnIter it, int last) {
+	const uint32_t i = y0 * W + blockIdx.x * WG + threadIdx.x;
+	if (i >= y1 * W) return;
+	const float4 ai = albedo[i];
+	const float4 c4 = acc[i];
+	if (!dn_filtered(ai.w)) {
+		out[i] = make_float4(c4.x * weight, c4.y * weight, c4.z * weight, 0.0f);
+		return;
+	}
+	auto load = [&](uint32_t j, DnTap &t) -> bool {
+		const float4 aj = albedo[j];
+		if (!dn_filtered(aj.w)) return false;
+		const float4 g = guide[j];
+		t.nx = g.x; t.ny = g.y; t.nz = g.z; t.t = g.w;
+		if (r_in) {
+			const float4 r = r_in[j];
+			t.r = r.x; t.g = r.y; t.b = r.z;
+		} else {
+			const float4 c = acc[j];
+			t.r = (c.x * weight) / dn_demod_albedo(aj.x); t.g = (c.y * weight) / dn_demod_albedo(aj.y); t.b = (c.z * weight) / dn_demod_albedo(aj.z);
+		}
+		return true;
+	};
+	DnTap ci;
+	(void)load(i, ci);
+	float r[3];
+	dn_step(i % W, i / W, W, y0, y1, ci, it, load, r);
+	if (last) out[i] = make_float4(r[0] * dn_demod_albedo(ai.x), r[1] * dn_demod_albedo(ai.y), r[2] * dn_demod_albedo(ai.z), 0.0f);
+	else out[i] = make_float4(r[0], r[1], r[2], 0.0f);
 }
 
 } // namespace pol

@@ -110,6 +110,15 @@ struct polaris_hip_tracer {
 	bool have_camera = false;
 	CameraArgs cam{};
 
+	// denoising of the synced frame (polaris_hip_set_denoise; kernels.h k_gbuffer / k_denoise).  Nothing is allocated while it
+	// is off: the G-buffer planes on first use (denoised sync or read_aov), the filter's three planes at the first denoised sync.
+	// All five are frame-sized float4 (80 B per pixel) and go with the frame buffers on resize.
+	PolarisDenoiseParams dn{sizeof(PolarisDenoiseParams), 0, 0, 0.0f, 0.0f};
+	float4 *gb_guide = nullptr, *gb_albedo = nullptr; // GUIDE / ALBEDO planes
+	bool gb_valid = false;                            // computed for the current scene, camera and frame size
+	float4 *dn_out = nullptr, *dn_ping = nullptr, *dn_pong = nullptr; // DENOISED plane, iteration buffers
+	bool dn_valid = false;                            // a denoised sync has written dn_out since the last resize
+
 	// wavefront batch state: up to kMaxPipes pipelines (option "overlap", default 4; a Trace uses min(overlap, #batches) of
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
 	// bounces of batch i+1 on another stream
@@ -385,6 +394,32 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 }
 
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
+
+void free_denoise(polaris_hip_tracer *h) { // caller holds mu, every stream idle
+	for (float4 **p : {&h->gb_guide, &h->gb_albedo, &h->dn_out, &h->dn_ping, &h->dn_pong}) {
+		if (*p) (void)hipFree(*p);
+		*p = nullptr;
+	}
+	h->gb_valid = h->dn_valid = false;
+}
+
+// The GUIDE / ALBEDO planes of the current scene, camera and frame size, computed if they are not (caller holds mu; checks done).
+int ensure_gbuffer(polaris_hip_tracer *h) {
+	if (h->gb_valid) return POLARIS_OK;
+	const size_t F = (size_t)h->W * h->H;
+	if (!h->gb_guide) HIP_TRY(h, hipMalloc((void **)&h->gb_guide, F * sizeof(float4)));
+	if (!h->gb_albedo) HIP_TRY(h, hipMalloc((void **)&h->gb_albedo, F * sizeof(float4)));
+	CameraArgs cam = h->cam;
+	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
+	{
+		Timed t(h, "gbuffer");
+		if (h->opt_time_kernels) h->timer_symbol["gbuffer"] = "pol::k_gbuffer";
+		hipLaunchKernelGGL(k_gbuffer, dim3(grid_for(F)), dim3(WG), 0, h->stream, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo);
+	}
+	HIP_TRY(h, hipGetLastError());
+	h->gb_valid = true;
+	return POLARIS_OK;
+}
 
 // k_trace<ANY_HIT, STACK, NODES> of the uploaded scene: STACK from the exact depth the scene needs, NODES from its size
 // (kernels.h, NodeMode).  fn = the kernel (for the occupancy query), block = its workgroup size.
@@ -730,6 +765,7 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 			if (h->pipe[p].q) (void)hipStreamDestroy(h->pipe[p].q);
 		free_pool(h->scene_bufs);
 		free_ring(h);
+		free_denoise(h);
 		for (auto &e : h->ev_ipc_done)
 			if (e) { (void)hipEventDestroy(e); e = nullptr; }
 		{
@@ -777,6 +813,7 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	std::lock_guard<std::mutex> lk_merge(h->merge_mu); // (the frame accumulator is the merge stream's)
 	HIP_TRY(h, sync_all(h));
 	free_ring(h); // (an IPC export dies with the buffers: peers close, the tracer exports again)
+	free_denoise(h);
 	if (h->frame_acc) (void)hipFree(h->frame_acc);
 	if (h->framebuffer) (void)hipFree(h->framebuffer);
 	h->frame_acc = nullptr;
@@ -815,6 +852,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	HIP_TRY(h, sync_all(h));
 	free_pool(h->scene_bufs);
 	h->have_scene = false;
+	h->gb_valid = false;
 	int rc = 0;
 	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
 	rc |= dev_upload(h, h->scene_bufs, &pairs, L.pairs.data(), L.pairs.size());
@@ -924,6 +962,7 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
 	HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
 	h->have_camera = true;
+	h->gb_valid = false;
 	return POLARIS_OK;
 }
 
@@ -1490,6 +1529,83 @@ int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 	return POLARIS_OK;
 }
 
+} // extern "C"
+
+namespace {
+// polaris_hip_sync_framebuffer with denoising on (caller holds mu; request checked): G-buffer if stale, K filter iterations over
+// the request's rows into the DENOISED plane, then the same tone-map over that plane with weight 1.
+int sync_denoised(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
+	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "denoising needs the camera (UpdateState CameraData)");
+	const size_t F = (size_t)h->W * h->H, off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
+	if (int rc = ensure_gbuffer(h)) return rc;
+	if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
+	if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
+	if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
+	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
+	{
+		Timed t(h, "denoise");
+		if (h->opt_time_kernels) h->timer_symbol["denoise"] = "pol::k_denoise";
+		const uint32_t K = h->dn.iterations, y0 = r->block_y, y1 = r->block_y + r->block_h;
+		const float4 *in = nullptr;
+		for (uint32_t k = 0; k < K; k++) {
+			float4 *out = k + 1 == K ? h->dn_out : (k % 2 == 0 ? h->dn_ping : h->dn_pong);
+			const DnIter it = dn_iter(k, h->dn.normal_power_log2, h->dn.sigma_depth, h->dn.sigma_luminance);
+			hipLaunchKernelGGL(k_denoise, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc, weight, h->gb_guide, h->gb_albedo, in, out, h->W,
+			                   y0, y1, it, k + 1 == K ? 1 : 0);
+			in = out;
+		}
+	}
+	{
+		Timed t(h, "tonemap");
+		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->dn_out + off, h->framebuffer + off, (uint32_t)n, 1.0f,
+		                   r->exposure);
+	}
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	h->dn_valid = true;
+	collect_timers(h);
+	return POLARIS_OK;
+}
+} // namespace
+
+extern "C" {
+
+int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisDenoiseParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_denoise: null params or struct_size != %zu", sizeof(PolarisDenoiseParams));
+	if (dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_denoise: iterations %u (0..%u), normal_power_log2 %u (0..%u), sigmas %g / %g (0 or [%g, %g])",
+		            p->iterations, kDnMaxIterations, p->normal_power_log2, kDnMaxNormalPowerLog2, (double)p->sigma_depth,
+		            (double)p->sigma_luminance, (double)kDnSigmaMin, (double)kDnSigmaMax);
+	h->dn = *p;
+	return POLARIS_OK;
+}
+
+int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const size_t need = (size_t)h->W * h->H * 4;
+	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_DENOISED)
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2}", need);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const float4 *src;
+	if (which == POLARIS_AOV_DENOISED) {
+		if (!h->dn_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no denoised sync since the last resize");
+		src = h->dn_out;
+	} else {
+		if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
+		if (int rc = ensure_gbuffer(h)) return rc;
+		src = which == POLARIS_AOV_GUIDE ? h->gb_guide : h->gb_albedo;
+	}
+	HIP_TRY(h, hipMemcpyAsync(out, src, need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
 int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
@@ -1498,6 +1614,7 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
+	if (h->dn.iterations) return sync_denoised(h, r, weight);
 	HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
 	{
 		Timed t(h, "tonemap");

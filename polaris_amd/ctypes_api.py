@@ -138,6 +138,31 @@ class PeerInfo(C.Structure):
 
 
 assert C.sizeof(DeviceIdentity) == 168 and C.sizeof(PeerInfo) == 72
+
+
+class DenoiseParams(C.Structure):
+    """PolarisDenoiseParams (include/polaris_hip.h): the edge-avoiding a-trous filter of polaris_hip_sync_framebuffer."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+        ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(DenoiseParams) == 20
+# the settings DESIGN.md section 10 chose on the CPU restatement (include/polaris_hip.h)
+DENOISE_DEFAULTS = {"iterations": 4, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_luminance": 4.0}
+AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED = 0, 1, 2
+
+
+def denoise_params(iterations=4, normal_power_log2=5, sigma_depth=0.1, sigma_luminance=4.0) -> DenoiseParams:
+    p = DenoiseParams()
+    p.iterations, p.normal_power_log2 = int(iterations), int(normal_power_log2)
+    p.sigma_depth, p.sigma_luminance = float(sigma_depth), float(sigma_luminance)
+    return p
 MERGE_BRANCHES = ("local", "peer-access", "staged", "ipc-local", "ipc-peer", "ipc-unknown", "device-strip", "ipc-staged")   # POLARIS_MERGE_* (include/polaris_hip.h)
 
 
@@ -214,6 +239,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_ipc_export", "polaris_hip_ipc_open", "polaris_hip_ipc_close", "polaris_hip_merge_ipc",
     "polaris_hip_trace_slot", "polaris_hip_merge_slot", "polaris_hip_build_bvh", "polaris_hip_build_bvh_error",
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
+    "polaris_hip_set_denoise", "polaris_hip_read_aov",
 ]
 
 _lib = None
@@ -309,6 +335,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_can_access_peer.argtypes = [i32, i32, C.POINTER(i32)]
     lib.polaris_hip_peer_info.argtypes = [vp, C.POINTER(PeerInfo)]
     lib.polaris_hip_merge_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.polaris_hip_set_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+    lib.polaris_hip_read_aov.argtypes = [vp, i32, vp, C.c_size_t]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

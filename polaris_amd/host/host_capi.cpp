@@ -132,6 +132,21 @@ int polaris_host_renderer_set_option(void *h, const char *key, int64_t value) {
 		if (int rc = polaris_hip_set_option(t->Handle(), key, value)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// Denoising (polaris_hip_set_denoise) on every tracer, as set_option; only the primary's SyncFramebuffer runs, so only it filters.
+int polaris_host_renderer_set_denoise(void *h, const PolarisDenoiseParams *p) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (int rc = polaris_hip_set_denoise(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	return 0;
+}
+// A plane of the primary's denoiser (polaris_hip_read_aov).
+int polaris_host_renderer_read_aov(void *h, int which, float *out, size_t n_floats) {
+	auto *box = static_cast<RendererBox *>(h);
+	auto *p = dynamic_cast<tracer::hip::HipTracer *>(box->r->Primary());
+	if (!p) return POLARIS_E_UNSUPPORTED;
+	if (int rc = polaris_hip_read_aov(p->Handle(), which, out, n_floats)) { box->error = polaris_hip_last_error(p->Handle()); return rc; }
+	return 0;
+}
 int polaris_host_renderer_render(void *h, uint32_t accumulated, uint32_t *rows_out, double *frame_ms) {
 	auto *box = static_cast<RendererBox *>(h);
 	Error e = box->r->renderFrame(accumulated);

@@ -33,6 +33,10 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_render.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_double)]
         lib.polaris_host_renderer_push_seeds.argtypes = [vp, C.c_uint32, vp, C.c_size_t]
         lib.polaris_host_renderer_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
+        lib.polaris_host_renderer_set_denoise.argtypes = [vp, C.POINTER(T.DenoiseParams)]
+        lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
+        lib.polaris_host_denoise.argtypes = [vp, C.c_float, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.POINTER(T.DenoiseParams), vp]
         lib.polaris_host_renderer_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
         lib.polaris_host_renderer_merge_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
         lib.polaris_host_renderer_tracer_stats.argtypes = [vp, C.c_uint32, C.POINTER(T.TraceStats), C.POINTER(C.c_double)]
@@ -124,6 +128,19 @@ class Renderer:
         if self._lib.polaris_host_renderer_set_option(self._h, key.encode(), int(value)):
             raise RuntimeError(f"set_option failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
+    def set_denoise(self, iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1, sigma_luminance: float = 4.0) -> None:
+        """polaris_hip_set_denoise on every tracer; only the primary syncs, so only the primary filters."""
+        p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
+        if self._lib.polaris_host_renderer_set_denoise(self._h, C.byref(p)):
+            raise RuntimeError(f"set_denoise failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def read_aov(self, which: int) -> np.ndarray:
+        """The primary's (H, W, 4) denoiser plane (polaris_hip_read_aov)."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        if self._lib.polaris_host_renderer_read_aov(self._h, int(which), out.ctypes.data, out.size):
+            raise RuntimeError(f"read_aov failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+        return out
+
     def render(self, accumulated=0):
         rows = np.zeros(self.n, dtype=np.uint32)
         ms = C.c_double()
@@ -166,6 +183,30 @@ class Renderer:
             self._h = None
 
     __del__ = close
+
+
+def denoise(frame_acc, weight: float, guide, albedo, *, block_y: int = 0, block_h: int | None = None, out=None,
+            iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1, sigma_luminance: float = 4.0) -> np.ndarray:
+    """polaris_host_denoise: the CPU restatement of the denoiser's filter (polaris_amd/host/denoise.cpp).  frame_acc, guide and
+    albedo are (H, W, 4) float32; returns the DENOISED plane -- `out` (a copy of it) with the rows [block_y, block_y + block_h)
+    written.  Raises ValueError where the library refuses the arguments."""
+    lib = load()
+    acc = np.ascontiguousarray(frame_acc, dtype=np.float32)
+    g = np.ascontiguousarray(guide, dtype=np.float32)
+    a = np.ascontiguousarray(albedo, dtype=np.float32)
+    H, W = acc.shape[:2]
+    if g.shape != acc.shape or a.shape != acc.shape or acc.shape != (H, W, 4):
+        raise ValueError("denoise: frame_acc, guide and albedo must be (H, W, 4) of one size")
+    res = np.zeros_like(acc) if out is None else np.array(out, dtype=np.float32, copy=True)
+    if res.shape != acc.shape:
+        raise ValueError("denoise: out must be (H, W, 4) like frame_acc")
+    bh = H - block_y if block_h is None else block_h
+    p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
+    rc = lib.polaris_host_denoise(acc.ctypes.data, float(weight), g.ctypes.data, a.ctypes.data, W, H, int(block_y), int(bh), C.byref(p),
+                                  res.ctypes.data)
+    if rc:
+        raise ValueError(f"denoise: bad arguments (code {rc})")
+    return res
 
 
 def bvh_build(boxes, min_leaf: int):

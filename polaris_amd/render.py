@@ -5,12 +5,44 @@
 Flags and defaults are those of `polaris render` (cmd/render.go:17-60, cmd/main.go): the scene goes
 through the C++ reader/compiler (polaris_amd/host), the frame through the C++ DefaultRenderer
 (renderer/default.go's loop) over HipTracers, one per requested device.  RR is disabled the way
-the reference does it (rr-bounces 0 or >= num-bounces -> num-bounces + 1)."""
+the reference does it (rr-bounces 0 or >= num-bounces -> num-bounces + 1).
+
+--denoise N filters the synced frame with N iterations of the edge-avoiding a-trous filter (polaris_hip_set_denoise, the
+other settings at their defaults); --aov-dir DIR also writes the first-hit guide planes as normals.png / depth.png (the byte
+formulas of the reference's debug kernels, tracer/opencl/CL/kernels/debug.cl) and albedo.png."""
 import argparse
+import os
 import sys
 import time
 
+import numpy as np
+
+from . import ctypes_api as T
 from . import host_api
+
+
+def aov_images(guide: np.ndarray, albedo: np.ndarray) -> dict:
+    """RGBA8 images of the GUIDE / ALBEDO planes ((H, W, 4) float32): normals (uchar)((n + 1) * 255 * 0.5) and depth
+    (uchar)(255 * (1 - t / (maxDepth + 1))) with maxDepth = max(1, the largest finite t) -- misses (0, 0, 0, 255) -- and albedo
+    (uchar)(albedo * 255)."""
+    f = np.float32
+    t = guide[..., 3]
+    hit = t < f(3.0e38)
+    max_depth = f(max(1.0, float(t[hit].max()) if hit.any() else 1.0))
+    def u8(x):
+        return np.clip(x, 0, 255).astype(np.uint8)
+    out = {}
+    n = np.zeros(guide.shape, np.uint8)
+    n[..., :3] = u8((guide[..., :3] + f(1)) * f(255) * f(0.5))
+    d = np.zeros(guide.shape, np.uint8)
+    d[..., :3] = u8(f(255) * (f(1) - t / (max_depth + f(1))))[..., None]
+    n[~hit, :3] = 0
+    d[~hit, :3] = 0
+    n[..., 3] = d[..., 3] = 255
+    a = np.full(albedo.shape, 255, np.uint8)
+    a[..., :3] = u8(albedo[..., :3] * f(255))
+    out["normals"], out["depth"], out["albedo"] = n, d, a
+    return out
 
 
 def main(argv=None):
@@ -25,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--out", default="frame.png")
     ap.add_argument("--devices", default="0", help="comma separated HIP device indices (a device may repeat)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--denoise", type=int, default=0, help="a-trous filter iterations at the frame sync (0 = off)")
+    ap.add_argument("--aov-dir", default=None, help="write normals.png, depth.png and albedo.png of the first-hit G-buffer here")
     a = ap.parse_args(argv)
 
     rr = a.rr_bounces
@@ -39,8 +73,15 @@ def main(argv=None):
     r = host_api.Renderer(sc, devs, width=a.width, height=a.height, spp=a.spp, bounces=a.num_bounces, min_rr=rr,
                           exposure=a.exposure, seed=a.seed)
     try:
+        if a.denoise:
+            r.set_denoise(iterations=a.denoise)
         rows, ms = r.render()
         r.save(a.out)  # the SaveFrameBuffer post-process stage (pipeline.go:215-235)
+        if a.aov_dir:
+            os.makedirs(a.aov_dir, exist_ok=True)
+            imgs = aov_images(r.read_aov(T.AOV_GUIDE), r.read_aov(T.AOV_ALBEDO))
+            for name, img in imgs.items():
+                host_api.write_png(os.path.join(a.aov_dir, name + ".png"), img)
     finally:
         r.close()
     print(f"{a.scene}: {sc.vertices.shape[0] // 3} triangles, {len(sc.mesh_instances)} instances, {len(sc.material_nodes)} material nodes; "

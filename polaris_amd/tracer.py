@@ -147,6 +147,19 @@ class HipTracer:
         self._check(self._lib.polaris_hip_read_accumulator(self._h, which, out.ctypes.data, out.size), self._h)
         return out
 
+    def set_denoise(self, iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1, sigma_luminance: float = 4.0) -> None:
+        """Denoise the frame at every SyncFramebuffer (polaris_hip_set_denoise); iterations = 0 turns it off (the default)."""
+        p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
+        self._check(self._lib.polaris_hip_set_denoise(self._h, C.byref(p)), self._h)
+
+    def read_aov(self, which: int) -> np.ndarray:
+        """(H, W, 4) float32 plane of the denoiser: T.AOV_GUIDE (normal | hit distance), T.AOV_ALBEDO (albedo | leaf type bits)
+        or T.AOV_DENOISED (the filtered running mean of the last denoised sync)."""
+        self._commit()
+        out = np.zeros((self._H, self._W, 4), dtype=np.float32)
+        self._check(self._lib.polaris_hip_read_aov(self._h, int(which), out.ctypes.data, out.size), self._h)
+        return out
+
     def read_framebuffer(self) -> np.ndarray:
         out = np.zeros((self._H, self._W, 4), dtype=np.uint8)
         self._check(self._lib.polaris_hip_read_framebuffer(self._h, out.ctypes.data, out.size), self._h)
