@@ -363,6 +363,25 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 int polaris_hip_selftest_rcp(polaris_hip_tracer *h, float lo, float hi, uint64_t *mismatches_inside, uint64_t *mismatches_outside,
                              uint32_t *sample);
 
+/* Self-test of include/polaris_math.h as this library's build compiled it (polaris_amd/csrc/builtin_probe.h): inputs
+ * [first, first + count) of built-in fn (PbFn: unary functions over all 2^32 bit patterns, binary / ternary ones over an edge
+ * grid and 2^28 counter-based draws) evaluated on the device.  fingerprints (may be NULL; first a multiple of 2^20): per chunk
+ * c of 2^20 inputs from first, [2c] = the fingerprint of its inputs inside fn's domain, [2c + 1] outside.  results (may be
+ * NULL; count <= 2^POLARIS_SELFTEST_MAX_RESULTS_LOG2): the result bits per input.  The CPU oracle computes the same
+ * (polaris_oracle_builtins), so every chunk must agree (tests/test_gpu_builtins_device.py). */
+#define POLARIS_SELFTEST_MAX_RESULTS_LOG2 24
+int polaris_hip_selftest_builtins(polaris_hip_tracer *h, uint32_t fn, uint64_t first, uint64_t count, uint64_t *fingerprints,
+                                  uint32_t *results);
+
+/* Test entry of the denoiser's filter on caller planes: acc, guide, albedo are W x H float4 planes as the frame accumulator and
+ * the G-buffer (POLARIS_AOV_GUIDE / _ALBEDO); rows [block_y, block_y + block_h) are filtered with *p (iterations >= 1) and
+ * weight into denoised, then tone-mapped with weight 1 and exposure into rgba (W x H x 4 bytes) -- the launches of a denoised
+ * polaris_hip_sync_framebuffer.  denoised and rgba are in / out: their other rows come back as given.  Uses buffers of its
+ * own; no state of the tracer is read or changed. */
+int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
+                               uint32_t block_y, uint32_t block_h, float weight, float exposure, const PolarisDenoiseParams *p,
+                               float *denoised, uint8_t *rgba);
+
 /*
  * BVH construction on the device -- an ALTERNATIVE producer of the scene's two-level BVH (the stretch; the
  * reference's own builder, asset/compiler/bvh/bvh_builder.go:100-308, scores ~1024 / (depth + 1) candidate planes per axis with

@@ -92,6 +92,11 @@ typedef struct PolarisOracleTaps {
 POLARIS_ORACLE_DECL(polaris_oracle)
 POLARIS_ORACLE_DECL(polaris_ref)
 
+/* The CPU side of polaris_hip_selftest_builtins (include/polaris_hip.h; polaris_amd/csrc/builtin_probe.h), built with the
+ * oracle's flags: the same fingerprints / result bits, plus the inputs (x, y, z) per input when `inputs` is not NULL (count
+ * <= 2^24 then, as for results).  The tone-map byte comes from the oracle's own tone-map.  0 = done, 2 = bad arguments. */
+int polaris_oracle_builtins(uint32_t fn, uint64_t first, uint64_t count, uint64_t *fingerprints, uint32_t *results, float *inputs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include <cstring>
 #include <vector>
 
+#include "builtin_probe.h"
 #include "oracle_api.h"
 #include "polaris_math.h"
 
@@ -1146,18 +1147,52 @@ extern "C" int polaris_oracle_trace(const PolarisSceneView *sc, const float eye[
 }
 
 
+// One channel of tonemapSimpleReinhard (kernels/hdr.cl:20-27), hdr = radiance * weight * exposure
+static uint8_t tonemap_channel(float hdr) {
+	const float mapped = hdr / (hdr + 1.0f);
+	const float e = 1.0f / 2.2f;
+	return (uint8_t)(pm_clamp(pm_pow(mapped, e), 0.0f, 1.0f) * 255.0f); // truncation, hdr.cl:22-27
+}
+
 extern "C" int polaris_oracle_tonemap(const float *accum, uint32_t n_pixels, float sample_weight, float exposure,
                                       uint8_t *rgba) { // kernels/hdr.cl:5-28
 	for (uint32_t g = 0; g < n_pixels; g++) {
 		V3 hdr = ld3(accum + 4 * (size_t)g) * sample_weight * exposure;
-		V3 mapped = hdr / (hdr + 1.0f);
-		const float e = 1.0f / 2.2f;
-		V3 p = {pm_pow(mapped.x, e), pm_pow(mapped.y, e), pm_pow(mapped.z, e)};
-		V3 out = {pm_clamp(p.x, 0.0f, 1.0f) * 255.0f, pm_clamp(p.y, 0.0f, 1.0f) * 255.0f, pm_clamp(p.z, 0.0f, 1.0f) * 255.0f};
-		rgba[4 * (size_t)g + 0] = (uint8_t)out.x; // truncation, hdr.cl:22-27
-		rgba[4 * (size_t)g + 1] = (uint8_t)out.y;
-		rgba[4 * (size_t)g + 2] = (uint8_t)out.z;
+		rgba[4 * (size_t)g + 0] = tonemap_channel(hdr.x);
+		rgba[4 * (size_t)g + 1] = tonemap_channel(hdr.y);
+		rgba[4 * (size_t)g + 2] = tonemap_channel(hdr.z);
 		rgba[4 * (size_t)g + 3] = 255;
+	}
+	return 0;
+}
+
+extern "C" int polaris_oracle_builtins(uint32_t fn, uint64_t first, uint64_t count, uint64_t *fingerprints, uint32_t *results, float *inputs) {
+	const uint64_t chunk = 1ull << PB_CHUNK_LOG2, block = 1ull << 16;
+	if (fn >= PB_NUM_FN || count == 0 || first > pb_inputs(fn) || count > pb_inputs(fn) - first || (!fingerprints && !results && !inputs) ||
+	    (fingerprints && first % chunk) || ((results || inputs) && count > (1ull << 24)))
+		return 2;
+	if (fingerprints) memset(fingerprints, 0, 2 * ((count + chunk - 1) / chunk) * sizeof(uint64_t));
+	const int64_t blocks = (int64_t)((count + block - 1) / block); // a block of 2^16 never straddles a chunk
+#pragma omp parallel for schedule(dynamic, 16)
+	for (int64_t b = 0; b < blocks; b++) {
+		uint64_t s[2] = {0, 0};
+		const uint64_t end = std::min(count, (uint64_t)(b + 1) * block);
+		for (uint64_t o = (uint64_t)b * block; o < end; o++) {
+			const uint64_t i = first + o;
+			float x, y, z;
+			pb_input(fn, i, x, y, z);
+			const uint32_t r = pb_eval(fn, i, x, y, z, tonemap_channel);
+			if (results) results[o] = r;
+			if (inputs) { inputs[3 * o] = x; inputs[3 * o + 1] = y; inputs[3 * o + 2] = z; }
+			s[pb_in_domain(fn, x, y) ? 0 : 1] += pb_mix64(i, r);
+		}
+		if (fingerprints) {
+			const uint64_t c = ((uint64_t)b * block) >> PB_CHUNK_LOG2;
+#pragma omp atomic
+			fingerprints[2 * c] += s[0];
+#pragma omp atomic
+			fingerprints[2 * c + 1] += s[1];
+		}
 	}
 	return 0;
 }

@@ -86,6 +86,9 @@ class Oracle:
         self._emissive.argtypes = [C.POINTER(T.SceneView), C.c_uint32, vp, vp, vp, vp, vp]
         self._emissive.restype = None
         self._describe.restype = C.c_char_p
+        if kind == "oracle":
+            self._builtins = self.lib.polaris_oracle_builtins
+            self._builtins.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp]
 
     def describe(self) -> str:
         return self._describe().decode()
@@ -119,6 +122,22 @@ class Oracle:
         out = np.zeros((a.shape[0], 4), dtype=np.uint8)
         self._tonemap(a.ctypes.data, a.shape[0], sample_weight, exposure, out.ctypes.data)
         return out
+
+    def builtins(self, fn: int, first: int = 0, count: int | None = None, *, results: bool = False):
+        """polaris_oracle_builtins, the CPU side of polaris_hip_selftest_builtins (polaris_amd/csrc/builtin_probe.h): the (chunks, 2)
+        uint64 fingerprints of built-in fn over inputs [first, first + count), or with results=True the pair (result bits (count,),
+        inputs (count, 3) float32)."""
+        if count is None:
+            count = T.builtin_inputs(fn) - first
+        if results:
+            raw, xyz = np.zeros(count, np.uint32), np.zeros((count, 3), np.float32)
+            rc = self._builtins(int(fn), int(first), int(count), None, raw.ctypes.data, xyz.ctypes.data)
+        else:
+            fp = np.zeros((-(-count // T.BUILTIN_CHUNK), 2), np.uint64)
+            rc = self._builtins(int(fn), int(first), int(count), fp.ctypes.data, None, None)
+        if rc != 0:
+            raise ValueError(f"builtins: bad arguments fn={fn} first={first} count={count}")
+        return (raw, xyz) if results else fp
 
     def random(self, state):
         st = np.array(state, dtype=np.uint32)

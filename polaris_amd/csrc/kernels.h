@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "builtin_probe.h"
 #include "denoise.h"
 #include "scene_layout.h"
 #include "shading.h"
@@ -1626,21 +1627,52 @@ __global__ __launch_bounds__(WG) void k_aggregate(const float4 *src, float4 *dst
 	dst[i] = a;
 }
 
+// One channel of tonemapSimpleReinhard (kernels/hdr.cl:20-27), c = radiance * weight * exposure; also swept by
+// k_builtin_sweep (PB_TONEMAP) against the oracle's tone-map.
+__device__ __forceinline__ unsigned char tonemap_byte(float c) {
+	const float m = c / (c + 1.0f);
+	const float v = pm_clamp(pm_pow(m, 1.0f / 2.2f), 0.0f, 1.0f) * 255.0f;
+	return (unsigned char)v; // truncation (hdr.cl:22-27)
+}
+
 // tonemapSimpleReinhard, kernels/hdr.cl:5-28
 __global__ __launch_bounds__(WG) void k_tonemap(const float4 *acc, uchar4 *fb, uint32_t n, float weight, float exposure) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= n) return;
 	const float4 a = acc[i];
-	const float e = 1.0f / 2.2f;
-	float c[3] = {a.x * weight * exposure, a.y * weight * exposure, a.z * weight * exposure};
-	unsigned char o[3];
-#pragma unroll
-	for (int k = 0; k < 3; k++) {
-		float m = c[k] / (c[k] + 1.0f);
-		float v = pm_clamp(pm_pow(m, e), 0.0f, 1.0f) * 255.0f;
-		o[k] = (unsigned char)v; // truncation (hdr.cl:22-27)
+	fb[i] = make_uchar4(tonemap_byte(a.x * weight * exposure), tonemap_byte(a.y * weight * exposure), tonemap_byte(a.z * weight * exposure), 255);
+}
+
+// polaris_hip_selftest_builtins (builtin_probe.h): inputs [first, first + count) of function fn, kSweepPerThread per thread.
+// fp != null: first is chunk aligned, fp[2 * c + d] += the fingerprint of chunk c (counted from first), d = 0 inside the
+// domain, 1 outside (a block's span, WG * kSweepPerThread inputs, never straddles a chunk); raw != null: raw[o] = result bits.
+constexpr int kSweepPerThread = 16;
+__global__ __launch_bounds__(WG) void k_builtin_sweep(uint32_t fn, uint64_t first, uint64_t count, unsigned long long *fp, uint32_t *raw) {
+	__shared__ unsigned long long red[2][WG];
+	const uint64_t base = (uint64_t)blockIdx.x * (WG * kSweepPerThread);
+	unsigned long long s[2] = {0ull, 0ull};
+	for (int k = 0; k < kSweepPerThread; k++) {
+		const uint64_t o = base + (uint64_t)k * WG + threadIdx.x;
+		if (o >= count) break;
+		const uint64_t i = first + o;
+		float x, y, z;
+		pb_input(fn, i, x, y, z);
+		const uint32_t r = pb_eval(fn, i, x, y, z, [](float c) { return tonemap_byte(c); });
+		if (raw) raw[o] = r;
+		s[pb_in_domain(fn, x, y) ? 0 : 1] += pb_mix64(i, r);
 	}
-	fb[i] = make_uchar4(o[0], o[1], o[2], 255);
+	if (!fp) return; // (uniform across the block)
+	red[0][threadIdx.x] = s[0];
+	red[1][threadIdx.x] = s[1];
+	__syncthreads();
+	for (int w = WG / 2; w > 0; w >>= 1) {
+		if ((int)threadIdx.x < w) {
+			red[0][threadIdx.x] += red[0][threadIdx.x + w];
+			red[1][threadIdx.x] += red[1][threadIdx.x + w];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x < 2 && red[threadIdx.x][0]) atomicAdd(&fp[2 * (base >> PB_CHUNK_LOG2) + threadIdx.x], red[threadIdx.x][0]);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1532,34 +1532,43 @@ int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 } // extern "C"
 
 namespace {
+// The filter and its tone-map on stream q (caller holds mu): the p.iterations a-trous iterations over the rows [y0, y1) of acc * weight
+// guided by (guide, albedo), through ping / pong into the DENOISED plane out, then out's rows tone-mapped with weight 1 into fb.
+// polaris_hip_sync_framebuffer and the test entry polaris_hip_denoise_planes both launch the filter through here.
+void launch_denoise(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, float weight, const float4 *guide, const float4 *albedo,
+                    float4 *ping, float4 *pong, float4 *out, uchar4 *fb, uint32_t W, uint32_t y0, uint32_t y1, float exposure,
+                    const PolarisDenoiseParams &p) {
+	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
+	{
+		Timed t(h, "denoise", q);
+		if (h->opt_time_kernels) h->timer_symbol["denoise"] = "pol::k_denoise";
+		const uint32_t K = p.iterations;
+		const float4 *in = nullptr;
+		for (uint32_t k = 0; k < K; k++) {
+			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
+			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, p.sigma_luminance);
+			hipLaunchKernelGGL(k_denoise, dim3(grid_for(n)), dim3(WG), 0, q, acc, weight, guide, albedo, in, dst, W, y0, y1, it, k + 1 == K ? 1 : 0);
+			in = dst;
+		}
+	}
+	{
+		Timed t(h, "tonemap", q);
+		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
+	}
+}
+
 // polaris_hip_sync_framebuffer with denoising on (caller holds mu; request checked): G-buffer if stale, K filter iterations over
 // the request's rows into the DENOISED plane, then the same tone-map over that plane with weight 1.
 int sync_denoised(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "denoising needs the camera (UpdateState CameraData)");
-	const size_t F = (size_t)h->W * h->H, off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
+	const size_t F = (size_t)h->W * h->H;
 	if (int rc = ensure_gbuffer(h)) return rc;
 	if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
 	if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
 	if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	{
-		Timed t(h, "denoise");
-		if (h->opt_time_kernels) h->timer_symbol["denoise"] = "pol::k_denoise";
-		const uint32_t K = h->dn.iterations, y0 = r->block_y, y1 = r->block_y + r->block_h;
-		const float4 *in = nullptr;
-		for (uint32_t k = 0; k < K; k++) {
-			float4 *out = k + 1 == K ? h->dn_out : (k % 2 == 0 ? h->dn_ping : h->dn_pong);
-			const DnIter it = dn_iter(k, h->dn.normal_power_log2, h->dn.sigma_depth, h->dn.sigma_luminance);
-			hipLaunchKernelGGL(k_denoise, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc, weight, h->gb_guide, h->gb_albedo, in, out, h->W,
-			                   y0, y1, it, k + 1 == K ? 1 : 0);
-			in = out;
-		}
-	}
-	{
-		Timed t(h, "tonemap");
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->dn_out + off, h->framebuffer + off, (uint32_t)n, 1.0f,
-		                   r->exposure);
-	}
+	launch_denoise(h, h->stream, h->frame_acc, weight, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W,
+	               r->block_y, r->block_y + r->block_h, r->exposure, h->dn);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	h->dn_valid = true;
@@ -1810,6 +1819,71 @@ int polaris_hip_selftest_rcp(polaris_hip_tracer *h, float lo, float hi, uint64_t
 	*mismatches_inside = res[0];
 	*mismatches_outside = res[1];
 	if (sample) *sample = (uint32_t)res[2];
+	return POLARIS_OK;
+}
+
+int polaris_hip_selftest_builtins(polaris_hip_tracer *h, uint32_t fn, uint64_t first, uint64_t count, uint64_t *fingerprints, uint32_t *results) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const uint64_t chunk = 1ull << PB_CHUNK_LOG2;
+	if (fn >= PB_NUM_FN || count == 0 || first > pb_inputs(fn) || count > pb_inputs(fn) - first || (!fingerprints && !results) ||
+	    (fingerprints && first % chunk) || (results && count > (1ull << POLARIS_SELFTEST_MAX_RESULTS_LOG2)))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "selftest_builtins: fn %u (< %u), inputs [%llu, +%llu) of %llu, fingerprints from a chunk start, "
+		            "at most 2^%d results", fn, (unsigned)PB_NUM_FN, (unsigned long long)first, (unsigned long long)count,
+		            (unsigned long long)(fn < PB_NUM_FN ? pb_inputs(fn) : 0), POLARIS_SELFTEST_MAX_RESULTS_LOG2);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t n_fp = fingerprints ? 2 * (size_t)((count + chunk - 1) / chunk) : 0, n_raw = results ? (size_t)count : 0;
+	char *d = nullptr;
+	HIP_TRY(h, hipMalloc((void **)&d, n_fp * sizeof(uint64_t) + n_raw * sizeof(uint32_t)));
+	unsigned long long *d_fp = n_fp ? (unsigned long long *)d : nullptr;
+	uint32_t *d_raw = n_raw ? (uint32_t *)(d + n_fp * sizeof(uint64_t)) : nullptr;
+	hipError_t e = n_fp ? hipMemsetAsync(d_fp, 0, n_fp * sizeof(uint64_t), h->stream) : hipSuccess;
+	if (e == hipSuccess) {
+		const uint64_t span = (uint64_t)WG * kSweepPerThread, blocks = (count + span - 1) / span; // <= 2^32 / 4096
+		hipLaunchKernelGGL(k_builtin_sweep, dim3((uint32_t)blocks), dim3(WG), 0, h->stream, fn, first, count, d_fp, d_raw);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && n_fp) e = hipMemcpyAsync(fingerprints, d_fp, n_fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess && n_raw) e = hipMemcpyAsync(results, d_raw, n_raw * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+	const hipError_t e2 = hipStreamSynchronize(h->stream);
+	(void)hipFree(d);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "selftest_builtins: %s", hipGetErrorString(e));
+	return POLARIS_OK;
+}
+
+int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
+                               uint32_t block_y, uint32_t block_h, float weight, float exposure, const PolarisDenoiseParams *p,
+                               float *denoised, uint8_t *rgba) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!acc || !guide || !albedo || !denoised || !rgba || !p || p->struct_size != sizeof(PolarisDenoiseParams) || W == 0 || H == 0 ||
+	    (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H || block_h > H - block_y || p->iterations == 0 ||
+	    dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "denoise_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), or params "
+		            "(iterations 1..%u)", W, H, block_y, block_h, kDnMaxIterations);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
+	char *d = nullptr;
+	HIP_TRY(h, hipMalloc((void **)&d, 6 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
+	float4 *d_acc = (float4 *)d, *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_ping = d_albedo + F, *d_pong = d_ping + F, *d_out = d_pong + F;
+	uchar4 *d_fb = (uchar4 *)(d_out + F);
+	hipError_t e = hipSuccess;
+	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_out, denoised}};
+	for (const auto &c : in)
+		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) {
+		launch_denoise(h, h->stream, d_acc, weight, d_guide, d_albedo, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure, *p);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream);
+	const hipError_t e2 = hipStreamSynchronize(h->stream);
+	(void)hipFree(d);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "denoise_planes: %s", hipGetErrorString(e));
+	collect_timers(h);
 	return POLARIS_OK;
 }
 

@@ -157,6 +157,20 @@ assert C.sizeof(DenoiseParams) == 20
 DENOISE_DEFAULTS = {"iterations": 4, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_luminance": 4.0}
 AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED = 0, 1, 2
 
+# polaris_hip_selftest_builtins / polaris_oracle_builtins: the probed built-ins (enum PbFn, polaris_amd/csrc/builtin_probe.h)
+BUILTINS_UNARY = ("sqrt", "rcp", "floor", "fabs", "sign", "sin", "cos", "atan", "acos", "log", "exp", "pow_gamma", "convert_float_uint",
+                  "tonemap")
+BUILTINS_MULTI = ("atan2", "pow", "divide", "min", "max", "fmin", "fmax", "clamp", "mix")
+BUILTINS = {name: fn for fn, name in enumerate(BUILTINS_UNARY + BUILTINS_MULTI)}
+BUILTIN_CHUNK = 1 << 20
+BUILTIN_EDGES, BUILTIN_DRAWS = 24, 1 << 28
+SELFTEST_MAX_RESULTS = 1 << 24   # POLARIS_SELFTEST_MAX_RESULTS_LOG2
+
+
+def builtin_inputs(fn: int) -> int:
+    """Inputs of built-in fn: every 2^32 bit pattern (unary) or the 24^3 edge grid and 2^28 draws."""
+    return 1 << 32 if fn < len(BUILTINS_UNARY) else BUILTIN_EDGES ** 3 + BUILTIN_DRAWS
+
 
 def denoise_params(iterations=4, normal_power_log2=5, sigma_depth=0.1, sigma_luminance=4.0) -> DenoiseParams:
     p = DenoiseParams()
@@ -239,7 +253,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_ipc_export", "polaris_hip_ipc_open", "polaris_hip_ipc_close", "polaris_hip_merge_ipc",
     "polaris_hip_trace_slot", "polaris_hip_merge_slot", "polaris_hip_build_bvh", "polaris_hip_build_bvh_error",
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
-    "polaris_hip_set_denoise", "polaris_hip_read_aov",
+    "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
 ]
 
 _lib = None
@@ -337,6 +351,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_merge_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.polaris_hip_set_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     lib.polaris_hip_read_aov.argtypes = [vp, i32, vp, C.c_size_t]
+    lib.polaris_hip_selftest_builtins.argtypes = [vp, u32, C.c_uint64, C.c_uint64, vp, vp]
+    lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

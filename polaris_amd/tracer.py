@@ -203,6 +203,35 @@ class HipTracer:
         self._check(self._lib.polaris_hip_selftest_rcp(self._h, lo, hi, C.byref(a), C.byref(b), C.byref(smp)), self._h)
         return a.value, b.value, smp.value
 
+    def selftest_builtins(self, fn: int, first: int = 0, count: int | None = None, *, results: bool = False) -> np.ndarray:
+        """polaris_hip_selftest_builtins: built-in fn of polaris_math.h on the device over inputs [first, first + count).
+        Returns the (chunks, 2) uint64 fingerprints (inside / outside the domain), or with results=True the (count,) result bits."""
+        if count is None:
+            count = T.builtin_inputs(fn) - first
+        fp = None if results else np.zeros((-(-count // T.BUILTIN_CHUNK), 2), np.uint64)
+        raw = np.zeros(count, np.uint32) if results else None
+        self._check(self._lib.polaris_hip_selftest_builtins(self._h, int(fn), int(first), int(count), None if fp is None else fp.ctypes.data,
+                                                            None if raw is None else raw.ctypes.data), self._h)
+        return raw if results else fp
+
+    def denoise_planes(self, acc, guide, albedo, *, weight: float, exposure: float, block_y: int = 0, block_h: int | None = None,
+                       denoised=None, rgba=None, iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1,
+                       sigma_luminance: float = 4.0) -> tuple[np.ndarray, np.ndarray]:
+        """polaris_hip_denoise_planes: the launches of a denoised sync on caller (H, W, 4) float32 planes.  Returns (DENOISED plane,
+        RGBA8 frame); rows outside [block_y, block_y + block_h) come back as `denoised` / `rgba` gave them (zeros by default)."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        acc, guide, albedo = f(acc), f(guide), f(albedo)
+        H, W = acc.shape[:2]
+        out = np.zeros((H, W, 4), np.float32) if denoised is None else np.array(denoised, np.float32, copy=True, order="C")
+        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
+        assert guide.shape == albedo.shape == out.shape == fb.shape == (H, W, 4)
+        p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
+        bh = H - block_y if block_h is None else block_h
+        self._check(self._lib.polaris_hip_denoise_planes(self._h, acc.ctypes.data, guide.ctypes.data, albedo.ctypes.data, W, H, int(block_y),
+                                                         int(bh), float(weight), float(exposure), C.byref(p), out.ctypes.data,
+                                                         fb.ctypes.data), self._h)
+        return out, fb
+
     def kernel_ms(self, name: str) -> tuple[float, int]:
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._lib.polaris_hip_kernel_ms(self._h, name.encode(), C.byref(ms), C.byref(n)), self._h)

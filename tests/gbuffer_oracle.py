@@ -96,6 +96,33 @@ def gbuffer(oracle, sc, W: int, H: int):
     return guide.reshape(H, W, 4), albedo.reshape(H, W, 4), {"tint": tint.reshape(H, W, 3), "textured": textured.reshape(H, W)}
 
 
+LEAVES = np.array([T.BXDF_DIFFUSE, T.BXDF_CONDUCTOR, T.BXDF_ROUGH_CONDUCTOR, T.BXDF_DIELECTRIC, T.BXDF_EMISSIVE, -1], np.int32)
+
+
+def leaf_word(types):
+    return np.asarray(types, np.int32).view(F)
+
+
+def random_planes(rng, H, W):
+    """Radiance sums, a guide of mostly aligned normals with depth steps, albedo with dark channels, misses and emitters."""
+    acc = np.zeros((H, W, 4), F)
+    acc[..., :3] = (rng.random((H, W, 3)) ** 3 * 40).astype(F)
+    n = np.array([0.2, 0.3, 1.0]) + 0.35 * rng.standard_normal((H, W, 3))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    guide = np.zeros((H, W, 4), F)
+    guide[..., :3] = n
+    guide[..., 3] = (1.0 + rng.random((H, W)) * 0.2 + (np.arange(W) >= W // 2) * 1.5).astype(F)
+    albedo = np.zeros((H, W, 4), F)
+    albedo[..., :3] = rng.random((H, W, 3))
+    albedo[..., :3][rng.random((H, W, 3)) < 0.05] = 0.0
+    leaves = LEAVES[rng.choice(len(LEAVES), size=(H, W), p=[0.55, 0.1, 0.1, 0.1, 0.05, 0.1])]
+    albedo[..., 3] = leaf_word(leaves)
+    miss = leaves == -1
+    guide[miss] = [0, 0, 0, FLT_MAX]
+    albedo[miss, :3] = 1.0
+    return acc, guide, albedo
+
+
 def filtered_mask(albedo: np.ndarray) -> np.ndarray:
     leaf = np.ascontiguousarray(albedo[..., 3]).view(np.uint32)
     return (leaf != LEAF_MISS) & (leaf != T.BXDF_EMISSIVE)

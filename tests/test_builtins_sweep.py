@@ -8,6 +8,8 @@ tests/tools/builtin_sweep.cpp measures every function against double-precision g
   use, held to the OpenCL 1.2 full-profile ULP bounds (section 7.4);
 * binary / ternary functions on 1e8 random inputs plus a 24^3 grid of edge values (zeros, subnormals, 1 +- ulp,
   FLT_MAX, infinities, NaNs);
+* exp on [-87, 88.72] and log over every positive finite input, held to what polaris_math.h promises (1.5 / 1.0 ulp), and
+  exp's flush to 0 on (-104, -87) to an absolute error below 2^-125;
 * every built-in whose result the specification fixes (fabs, floor, sign, min, max, fmin, fmax, clamp, mix,
   uint -> float conversion; sqrt, reciprocal and division, which are correctly rounded in this build) must equal an
   independent formulation bit for bit.
@@ -23,16 +25,17 @@ from conftest import ROOT
 SRC = os.path.join(ROOT, "tests", "tools", "builtin_sweep.cpp")
 EXE = os.path.join(ROOT, "tests", "_build", "builtin_sweep")
 
-ULP = ("sin", "cos", "atan", "acos", "pow_gamma", "atan2", "pow")
+ULP = ("sin", "cos", "atan", "acos", "pow_gamma", "atan2", "pow", "exp", "log")
 EXACT = ("sqrt", "recip", "divide", "fabs", "floor", "sign", "min", "max", "fmin", "fmax", "clamp", "mix", "convert_float_uint")
 
 
 @pytest.fixture(scope="module")
 def sweep_exe():
     os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    deps = [SRC, os.path.join(ROOT, "include", "polaris_math.h")]
+    deps = [SRC, os.path.join(ROOT, "include", "polaris_math.h"), os.path.join(ROOT, "polaris_amd", "csrc", "builtin_probe.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-fopenmp", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), SRC, "-o", EXE])
+        subprocess.check_call(["g++", "-O2", "-fopenmp", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
+                               "-I" + os.path.join(ROOT, "polaris_amd", "csrc"), SRC, "-o", EXE])
     return EXE
 
 
@@ -41,8 +44,12 @@ def check(d, exhaustive):
         assert d[k]["max_ulp"] <= d[k]["opencl_bound_ulp"], (k, d[k])
         assert d[k]["inputs"] > 500_000, (k, d[k])
     # tighter than the OpenCL bounds: what polaris_math.h promises about itself
-    for k, bound in (("sin", 2.0), ("cos", 2.0), ("atan", 3.0), ("acos", 2.0)):
+    for k, bound in (("sin", 2.0), ("cos", 2.0), ("atan", 3.0), ("acos", 2.0), ("exp", 1.5), ("log", 1.0)):
         assert d[k]["max_ulp"] <= bound, (k, d[k])
+    # below -87 pm_exp flushes to 0 where exp(x) is still a (sub)normal float: an absolute error below 2^-125 (the denoiser's
+    # weights take exp of (-inf, 0], exp_denoise; a weight that small is 0 beside the centre tap's 9/64 either way)
+    assert d["exp_underflow"]["max_abs_err"] < 2.0 ** -125 and d["exp_underflow"]["inputs"] > 500, d["exp_underflow"]
+    assert d["exp_denoise"]["inputs"] > 500_000, d["exp_denoise"]
     # near a zero crossing the ulp of the result shrinks without bound; there the absolute error is what matters (and the reference
     # only calls native_sin / native_cos, whose accuracy OpenCL leaves to the implementation): < 2^-23 everywhere on [-2pi, 2pi]
     for k in ("sin_all", "cos_all"):
@@ -51,6 +58,7 @@ def check(d, exhaustive):
         assert d[k]["mismatches"] == 0 and d[k]["inputs"] > 1_000_000, (k, d[k])
     if exhaustive:
         assert d["stride"] == 1 and d["atan"]["inputs"] == 2 * 0x7F800000  # every finite binary32 value
+        assert d["log"]["inputs"] == 0x7F7FFFFF  # every positive finite binary32 value, subnormals included
         assert d["sqrt"]["inputs"] == 2 ** 32 and d["recip"]["inputs"] == 2 ** 32 and d["convert_float_uint"]["inputs"] == 2 ** 32
 
 
@@ -74,3 +82,26 @@ def test_builtins_exhaustive_sweep_on_the_gpu_box(sweep_exe):
     out = subprocess.run([sweep_exe, "1", "100000000"], capture_output=True, text=True, timeout=3000)
     assert out.returncode == 0, out.stderr[-2000:]
     check(json.loads(out.stdout), exhaustive=True)
+
+
+def test_oracle_fingerprints_equal_a_plain_loop(sweep_exe, oracle):
+    """The CPU side of the device self-test (polaris_oracle_builtins; tests/test_gpu_builtins_device.py compares the device with
+    it) against `builtin_sweep fp`, which calls the same pm_* functions in a plain loop: a wrong entry of builtin_probe.h's
+    table, chunking or summation -- which the device shares, and which would agree with itself -- fails here.  Every 256th
+    chunk: 16 per unary function, the edge-grid chunk and the partial last chunk of the others."""
+    from polaris_amd import ctypes_api as T
+
+    out = subprocess.run([sweep_exe, "fp", "256"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    plain = json.loads(out.stdout)
+    assert sorted(plain) == sorted(T.BUILTINS)
+    for name, fn in T.BUILTINS.items():
+        n = T.builtin_inputs(fn)
+        assert sorted(int(c) for c in plain[name]) == list(range(0, -(-n // T.BUILTIN_CHUNK), 256)), name
+        for c, want in plain[name].items():
+            first = int(c) * T.BUILTIN_CHUNK
+            got = oracle.builtins(fn, first, min(T.BUILTIN_CHUNK, n - first))
+            assert got.shape == (1, 2)
+            assert (int(got[0, 0]) + int(got[0, 1])) % 2 ** 64 == want, (name, c)
+        fps = set(plain[name].values())
+        assert 0 not in fps and len(fps) == len(plain[name]), name   # no two chunks of a function alike

@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 import gbuffer_oracle as G
+from gbuffer_oracle import leaf_word, random_planes
 from polaris_amd import ctypes_api as T
 
 F = np.float32
-LEAVES = np.array([T.BXDF_DIFFUSE, T.BXDF_CONDUCTOR, T.BXDF_ROUGH_CONDUCTOR, T.BXDF_DIELECTRIC, T.BXDF_EMISSIVE, -1], np.int32)
 PARAMS = [dict(iterations=4, normal_power_log2=5, sigma_depth=0.1, sigma_luminance=4.0),
           dict(iterations=5, normal_power_log2=7, sigma_depth=0.1, sigma_luminance=1.0),
           dict(iterations=2, normal_power_log2=0, sigma_depth=0.0, sigma_luminance=0.0),
@@ -22,30 +22,6 @@ def host(built):
     from polaris_amd import host_api
 
     return host_api
-
-
-def leaf_word(types):
-    return np.asarray(types, np.int32).view(F)
-
-
-def random_planes(rng, H, W):
-    """Radiance sums, a guide of mostly aligned normals with depth steps, albedo with dark channels, misses and emitters."""
-    acc = np.zeros((H, W, 4), F)
-    acc[..., :3] = (rng.random((H, W, 3)) ** 3 * 40).astype(F)
-    n = np.array([0.2, 0.3, 1.0]) + 0.35 * rng.standard_normal((H, W, 3))
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    guide = np.zeros((H, W, 4), F)
-    guide[..., :3] = n
-    guide[..., 3] = (1.0 + rng.random((H, W)) * 0.2 + (np.arange(W) >= W // 2) * 1.5).astype(F)
-    albedo = np.zeros((H, W, 4), F)
-    albedo[..., :3] = rng.random((H, W, 3))
-    albedo[..., :3][rng.random((H, W, 3)) < 0.05] = 0.0
-    leaves = LEAVES[rng.choice(len(LEAVES), size=(H, W), p=[0.55, 0.1, 0.1, 0.1, 0.05, 0.1])]
-    albedo[..., 3] = leaf_word(leaves)
-    miss = leaves == -1
-    guide[miss] = [0, 0, 0, G.FLT_MAX]
-    albedo[miss, :3] = 1.0
-    return acc, guide, albedo
 
 
 @pytest.mark.parametrize("W,H,block_y,block_h", [(61, 37, 0, None), (300, 9, 0, None), (97, 61, 13, 29), (257, 20, 19, 1)])

@@ -3,12 +3,13 @@
 // reproduced bit for bit by all three and every parity test would stay green -- so the functions themselves are
 // measured here against double-precision glibc over ALL binary32 inputs (unary) or >= 1e8 random + edge-grid inputs
 // (binary / ternary), and the error is held against the OpenCL 1.2 full-profile ULP bounds (section 7.4):
-//     sin, cos <= 4 ulp   atan <= 5   atan2 <= 6   acos <= 4   pow <= 16   sqrt <= 3   x / y, 1 / x <= 2.5
+//     sin, cos <= 4 ulp   atan <= 5   atan2 <= 6   acos <= 4   pow <= 16   exp, log <= 3   sqrt <= 3   x / y, 1 / x <= 2.5
 // Functions whose result the specification FIXES (fabs, floor, sign, min, max, fmin, fmax, clamp, mix, conversions,
 // and sqrt / reciprocal, which this build rounds correctly) must be bit-equal to an independent formulation.
 //
-// Test tool, not product.  g++ -O2 -fopenmp -ffp-contract=off -Iinclude builtin_sweep.cpp -o builtin_sweep
-//   builtin_sweep <stride> : visits bit patterns 0, stride, 2*stride, ... (stride 1 = all 2^32) and prints one JSON object.
+// Test tool, not product.  g++ -O2 -fopenmp -ffp-contract=off -Iinclude -Ipolaris_amd/csrc builtin_sweep.cpp -o builtin_sweep
+//   builtin_sweep <stride> [random] : visits bit patterns 0, stride, 2*stride, ... (stride 1 = all 2^32) and prints one JSON object.
+//   builtin_sweep fp <chunk stride> : the device self-test's chunk fingerprints by a plain loop (see fingerprints() below).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "builtin_probe.h"
 #include "polaris_math.h"
 
 static inline float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
@@ -119,6 +121,10 @@ static float pm_acos_(float x) { return pm_acos(x); }
 static const float kInvGamma = 1.0f / 2.2f;                            // the tone-mapper's exponent (kernels/hdr.cl:8,22)
 static float pm_pow_gamma(float x) { return pm_pow(x, kInvGamma); }
 static double ref_pow_gamma(double x) { return std::pow(x, (double)kInvGamma); }
+static float pm_exp_(float x) { return pm_exp(x); }
+static float pm_log_(float x) { return pm_log(x); }
+static double ref_exp(double x) { return std::exp(x); }
+static double ref_log(double x) { return std::log(x); }
 static double ref_sin(double x) { return std::sin(x); }
 static double ref_cos(double x) { return std::cos(x); }
 static double ref_atan(double x) { return std::atan(x); }
@@ -131,17 +137,79 @@ static inline uint64_t splitmix(uint64_t &s) {
 	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
 	return z ^ (z >> 31);
 }
-static const uint32_t kEdgeBits[] = {0x00000000u, 0x80000000u, 0x00000001u, 0x80000001u, 0x007fffffu, 0x00800000u, 0x80800000u, 0x3f800000u,
-                                     0xbf800000u, 0x3f7fffffu, 0x3f800001u, 0x7f7fffffu, 0xff7fffffu, 0x7f800000u, 0xff800000u, 0x7fc00000u,
-                                     0xffc00000u, 0x3f000000u, 0x40000000u, 0x40490fdbu, 0xc0490fdbu, 0x33800000u, 0x4b000000u, 0x4b800000u};
-static const int kEdges = (int)(sizeof kEdgeBits / sizeof kEdgeBits[0]);
+// the edge grid (zeros, subnormals, 1 +- ulp, FLT_MAX, infinities, NaNs): polaris_amd/csrc/builtin_probe.h, which the device
+// self-test of the same functions draws from too
+static const int kEdges = (int)PB_EDGES;
+static inline uint32_t edge(int k) { return pb_edge((uint32_t)k); }
 
 static float ref_min(float x, float y) { return y < x ? y : x; }                       // s6.12.4
 static float ref_max(float x, float y) { return x < y ? y : x; }
 static float ref_fmin(float x, float y) { if (x != x) return y; if (y != y) return x; return y < x ? y : x; } // s6.12.2
 static float ref_fmax(float x, float y) { if (x != x) return y; if (y != y) return x; return x < y ? y : x; }
 
+// ---- fingerprints of the device self-test (polaris_amd/csrc/builtin_probe.h), by a plain loop over the pm_* calls --------------
+// `builtin_sweep fp <chunk stride>`: for every probed function, the fingerprint (both domain halves summed) of chunks 0, stride,
+// 2 * stride, ... -- what the oracle's polaris_oracle_builtins must reproduce, so that a broken table, chunking or summation
+// there (and so on the device, which shares them) cannot pass unnoticed.
+static uint32_t canon(float r) { return r != r ? 0x7fc00000u : f2u(r); }
+static uint32_t tonemap_byte(float c) { return (uint8_t)(pm_clamp(pm_pow(c / (c + 1.0f), kInvGamma), 0.0f, 1.0f) * 255.0f); }
+struct PlainFn { const char *name; uint32_t (*f)(uint64_t i, float x, float y, float z); };
+static const PlainFn kPlain[] = {
+	{"sqrt", [](uint64_t, float x, float, float) { return canon(pm_sqrt(x)); }},
+	{"rcp", [](uint64_t, float x, float, float) { return canon(pm_rcp(x)); }},
+	{"floor", [](uint64_t, float x, float, float) { return canon(pm_floor(x)); }},
+	{"fabs", [](uint64_t, float x, float, float) { return canon(pm_fabs(x)); }},
+	{"sign", [](uint64_t, float x, float, float) { return canon(pm_sign(x)); }},
+	{"sin", [](uint64_t, float x, float, float) { return canon(pm_sin(x)); }},
+	{"cos", [](uint64_t, float x, float, float) { return canon(pm_cos(x)); }},
+	{"atan", [](uint64_t, float x, float, float) { return canon(pm_atan(x)); }},
+	{"acos", [](uint64_t, float x, float, float) { return canon(pm_acos(x)); }},
+	{"log", [](uint64_t, float x, float, float) { return canon(pm_log(x)); }},
+	{"exp", [](uint64_t, float x, float, float) { return canon(pm_exp(x)); }},
+	{"pow_gamma", [](uint64_t, float x, float, float) { return canon(pm_pow(x, kInvGamma)); }},
+	{"convert_float_uint", [](uint64_t i, float, float, float) { return canon((float)(uint32_t)i); }},
+	{"tonemap", [](uint64_t, float x, float, float) { return tonemap_byte(x); }},
+	{"atan2", [](uint64_t, float x, float y, float) { return canon(pm_atan2(x, y)); }},
+	{"pow", [](uint64_t, float x, float y, float) { return canon(pm_pow(x, y)); }},
+	{"divide", [](uint64_t, float x, float y, float) { return canon(x / y); }},
+	{"min", [](uint64_t, float x, float y, float) { return canon(pm_min(x, y)); }},
+	{"max", [](uint64_t, float x, float y, float) { return canon(pm_max(x, y)); }},
+	{"fmin", [](uint64_t, float x, float y, float) { return canon(pm_fmin(x, y)); }},
+	{"fmax", [](uint64_t, float x, float y, float) { return canon(pm_fmax(x, y)); }},
+	{"clamp", [](uint64_t, float x, float y, float z) { return canon(pm_clamp(x, y, z)); }},
+	{"mix", [](uint64_t, float x, float y, float z) { return canon(pm_mix(x, y, z)); }},
+};
+
+static int fingerprints(uint64_t chunk_stride) {
+	const int n_fn = (int)(sizeof kPlain / sizeof kPlain[0]);
+	static_assert(sizeof kPlain / sizeof kPlain[0] == PB_NUM_FN, "one plain function per probed built-in");
+	std::string out = "{";
+	for (int fn = 0; fn < n_fn; fn++) {
+		const uint64_t n = pb_inputs((uint32_t)fn), chunk = 1ull << PB_CHUNK_LOG2;
+		std::vector<uint64_t> cs;
+		for (uint64_t c = 0; c * chunk < n; c += chunk_stride) cs.push_back(c);
+		std::vector<uint64_t> fp(cs.size(), 0);
+#pragma omp parallel for schedule(dynamic, 1)
+		for (int64_t k = 0; k < (int64_t)cs.size(); k++) {
+			uint64_t sum = 0;
+			for (uint64_t i = cs[k] * chunk; i < std::min(n, (cs[k] + 1) * chunk); i++) {
+				float x, y, z;
+				pb_input((uint32_t)fn, i, x, y, z);
+				sum += pb_mix64(i, kPlain[fn].f(i, x, y, z));
+			}
+			fp[k] = sum;
+		}
+		out += std::string(fn ? ", " : "") + "\"" + kPlain[fn].name + "\": {";
+		for (size_t k = 0; k < cs.size(); k++)
+			out += std::string(k ? ", " : "") + "\"" + std::to_string(cs[k]) + "\": " + std::to_string(fp[k]);
+		out += "}";
+	}
+	puts((out + "}").c_str());
+	return 0;
+}
+
 int main(int argc, char **argv) {
+	if (argc > 2 && !strcmp(argv[1], "fp")) return fingerprints(strtoull(argv[2], nullptr, 10));
 	const uint64_t stride = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
 	const uint64_t n_random = argc > 2 ? strtoull(argv[2], nullptr, 10) : 100000000ull;
 	std::string out = "{";
@@ -174,6 +242,13 @@ int main(int argc, char **argv) {
 	// byte 0, i.e. only x >= (1/255)^2.2 = 5.1e-6 can change an output; the whole unit interval is reported beside it
 	put_ulp("pow_gamma", "x in [2^-20, 1], y = 1/2.2 (hdr.cl:22): every input that can reach a non-zero byte", sweep_ulp(pm_pow_gamma, ref_pow_gamma, 9.5367431640625e-7f, 1.0f, stride), 16.0);
 	put_ulp("pow_gamma_unit", "x in [0, 1], y = 1/2.2 (informational: below 2^-20 the byte is 0 whatever the ulp error)", sweep_ulp(pm_pow_gamma, ref_pow_gamma, 0.0f, 1.0f, stride), 16.0);
+	// exp: the tone-mapper's pow and the denoiser's edge-stopping weights (denoise.h dn_weight: exp of arguments in (-inf, 0]).
+	// Below -87 pm_exp returns 0 where exp is still a (sub)normal float: there its ABSOLUTE error is what is asserted
+	put_ulp("exp", "[-87, 88.72]", sweep_ulp(pm_exp_, ref_exp, -87.0f, 88.72f, stride), 3.0);
+	put_ulp("exp_underflow", "(-104, -87): returns 0 (informational ulp; max_abs_err is what is asserted)",
+	        sweep_ulp(pm_exp_, ref_exp, std::nextafter(-104.0f, 0.0f), std::nextafter(-87.0f, -200.0f), stride), 3.0);
+	put_ulp("exp_denoise", "[-104, 0]: the arguments of dn_weight (informational)", sweep_ulp(pm_exp_, ref_exp, -104.0f, 0.0f, stride), 3.0);
+	put_ulp("log", "(0, FLT_MAX], subnormals included", sweep_ulp(pm_log_, ref_log, 1.4e-45f, PM_FLT_MAX, stride), 3.0);
 	put_eq("sqrt", sweep_equal(pm_sqrt_, ref_sqrt, stride));
 	put_eq("recip", sweep_equal(pm_rcp_, ref_rcp, stride));
 	put_eq("fabs", sweep_equal(pm_fabs_, ref_fabs, stride));
@@ -227,7 +302,7 @@ int main(int argc, char **argv) {
 		}
 #pragma omp for schedule(static)
 		for (int i = 0; i < kEdges * kEdges * kEdges; i++)
-			one(u2f(kEdgeBits[i % kEdges]), u2f(kEdgeBits[(i / kEdges) % kEdges]), u2f(kEdgeBits[i / (kEdges * kEdges)]));
+			one(u2f(edge(i % kEdges)), u2f(edge((i / kEdges) % kEdges)), u2f(edge(i / (kEdges * kEdges))));
 #pragma omp critical
 		{
 			atan2_a.merge(l_atan2); pow_a.merge(l_pow); div_a.merge(l_div); eq_min.merge(l_min); eq_max.merge(l_max); eq_fmin.merge(l_fmin);
