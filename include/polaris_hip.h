@@ -317,7 +317,35 @@ int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p
 #define POLARIS_AOV_GUIDE    0
 #define POLARIS_AOV_ALBEDO   1
 #define POLARIS_AOV_DENOISED 2
+/*   TEMPORAL  the running mean blended with the history of the last temporal sync (rgb | effective sample count n + m)
+ *   PRIOR     the history reprojected into the current camera (rgb h | m, m = 0: no history)
+ * TEMPORAL / PRIOR: POLARIS_E_BAD_ARGUMENT before any temporal sync (polaris_hip_set_temporal) under the current camera. */
+#define POLARIS_AOV_TEMPORAL 3
+#define POLARIS_AOV_PRIOR    4
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats);
+
+/* Temporal reuse of the synced frame across camera moves (no reference counterpart: the reference's interactive renderer resets
+ * its accumulation on every move, renderer/opengl.go:294-301).  Off by default (max_history = 0); with it off sync_framebuffer,
+ * set_camera, resize and upload_scene allocate and launch nothing new.  With it on the tracer keeps a HISTORY: the TEMPORAL plane,
+ * G-buffer and camera of the last temporal sync before the latest set_camera (pointer swaps, no copies).  At the first temporal
+ * sync under a camera the history is reprojected into the PRIOR: for every filtered pixel i (a first hit that is not an emitter)
+ * p = eye + t_i d_i is projected into the history camera, and of the 2 x 2 history pixels around it those with a count > 0,
+ * finite rgb, pixel i's leaf type, n_i . n_j >= normal_threshold and |t_j - |p - eye'|| <= depth_threshold |p - eye'| are
+ * blended bilinearly (weights renormalised): h, m = min(count, max_history).  Every temporal sync then writes the request's rows of
+ * TEMPORAL = (acc + m h) / (n + m) where m > 0 and acc / n (sync's expression, bit for bit) where m = 0, n = accumulated_samples +
+ * samples_per_pixel, and the denoiser (if on) or the tone-map runs on TEMPORAL with weight 1.  The accumulators are never
+ * written.  A history camera whose frustum corners are not a parallelogram (some w != 0, or |tl + br - tr - bl| >
+ * 1e-3 |tr - tl|) gives no history.  Resize, upload_scene and max_history = 0 drop the history.  DESIGN.md 10b has the exact
+ * arithmetic.  Suggested settings (chosen on the CPU restatement): max_history 32, normal_threshold 0.9,
+ * depth_threshold 0.1.  A field out of range is POLARIS_E_BAD_ARGUMENT: max_history 0..4096, normal_threshold within [-1, 1],
+ * depth_threshold within [0, 1e6].  Set struct_size = sizeof(PolarisTemporalParams). */
+typedef struct PolarisTemporalParams {
+	uint32_t struct_size;       /* sizeof(PolarisTemporalParams) */
+	uint32_t max_history;       /* cap on the history's sample count m: 0 = off (default), 1..4096 */
+	float    normal_threshold;  /* a history tap needs n_i . n_j >= this */
+	float    depth_threshold;   /* ... and |t_j - d| <= this * d, d = the point's distance from the history eye */
+} PolarisTemporalParams;
+int polaris_hip_set_temporal(polaris_hip_tracer *h, const PolarisTemporalParams *p);
 
 /* frame_w*frame_h*4 bytes RGBA8 (pipeline.go:226-232). */
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes);
@@ -382,6 +410,15 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
                                uint32_t block_y, uint32_t block_h, float weight, float exposure, const PolarisDenoiseParams *p,
                                float *denoised, uint8_t *rgba);
 
+/* Test entry of the temporal reprojection on caller planes: history (rgb | count), prev_guide, prev_albedo seen under the camera
+ * (prev_eye, prev_frustum), and the current guide, albedo under (eye, frustum), all W x H float4 planes; the PRIOR plane of every
+ * pixel into prior -- the launch of the first temporal sync after a set_camera.  Uses buffers of its own; no state of the tracer
+ * is read or changed. */
+int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                 const float prev_eye[3], const float prev_frustum[16], const float *guide, const float *albedo,
+                                 const float eye[3], const float frustum[16], uint32_t W, uint32_t H, const PolarisTemporalParams *p,
+                                 float *prior);
+
 /*
  * BVH construction on the device -- an ALTERNATIVE producer of the scene's two-level BVH (the stretch; the
  * reference's own builder, asset/compiler/bvh/bvh_builder.go:100-308, scores ~1024 / (depth + 1) candidate planes per axis with
@@ -428,7 +465,8 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * timer since the last call for that name.  Timers: "generate", "intersect_packet" (camera rays through
  * the wave-packet kernel), "intersect" (closest hit), "shade_first" / "shade_sort" /
  * "shade_plain" / "shade_wave" (one per shade kernel symbol), "scan", "occlusion", "fold" (the batch's NEE records into the
- * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise). */
+ * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
+ * (polaris_hip_set_temporal). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

@@ -273,6 +273,29 @@ func (tr *Tracer) SetDenoise(p DenoiseParams) error {
 	return tr.check(C.polaris_hip_set_denoise(tr.handle, &c))
 }
 
+// TemporalParams configures temporal reuse of the synced frame across camera moves (PolarisTemporalParams, include/polaris_hip.h;
+// DESIGN.md section 10b).  MaxHistory = 0 turns it off (the default) and drops the history; DefaultTemporal holds the settings
+// chosen on the CPU restatement.
+type TemporalParams struct {
+	MaxHistory      uint32  // cap on the reused sample count: 0 = off, 1..4096
+	NormalThreshold float32 // a history tap needs n_i . n_j >= this, within [-1, 1]
+	DepthThreshold  float32 // ... and a hit distance within this fraction, within [0, 1e6]
+}
+
+var DefaultTemporal = TemporalParams{MaxHistory: 32, NormalThreshold: 0.9, DepthThreshold: 0.1}
+
+// SetTemporal turns temporal reuse on or off: while the camera moves (UpdateState CameraData, as the interactive renderer's
+// renderer/opengl.go:294-301), SyncFramebuffer blends the running mean with the last view's, reprojected.  The accumulators stay
+// the reference result; only the frame buffer shows the blend.
+func (tr *Tracer) SetTemporal(p TemporalParams) error {
+	var c C.PolarisTemporalParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.max_history = C.uint32_t(p.MaxHistory)
+	c.normal_threshold = C.float(p.NormalThreshold)
+	c.depth_threshold = C.float(p.DepthThreshold)
+	return tr.check(C.polaris_hip_set_temporal(tr.handle, &c))
+}
+
 // ReadFrameBuffer is what opencl.SaveFrameBuffer reads (tracer/opencl/pipeline.go:226-232).
 func (tr *Tracer) ReadFrameBuffer(pix []uint8) error {
 	if len(pix) == 0 {

@@ -33,6 +33,7 @@
 #include "denoise.h"
 #include "scene_layout.h"
 #include "shading.h"
+#include "temporal.h"
 
 namespace pol {
 
@@ -1689,13 +1690,11 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
 	const uint32_t gx = idx % W, gy = idx / W;
-	const float tx = ((float)gx + 0.5f) * cam.texel.x;
-	const float ty = ((float)gy + 0.5f) * cam.texel.y;
-	float lx = pm_mix(cam.tl.x, cam.bl.x, ty), ly = pm_mix(cam.tl.y, cam.bl.y, ty), lz = pm_mix(cam.tl.z, cam.bl.z, ty), lw = pm_mix(cam.tl.w, cam.bl.w, ty);
-	float rx = pm_mix(cam.tr.x, cam.br.x, ty), ry = pm_mix(cam.tr.y, cam.br.y, ty), rz = pm_mix(cam.tr.z, cam.br.z, ty), rw = pm_mix(cam.tr.w, cam.br.w, ty);
-	float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
-	const float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
-	const f3 d = mk3(dx * inv, dy * inv, dz * inv);
+	const float tl[4] = {cam.tl.x, cam.tl.y, cam.tl.z, cam.tl.w}, tr[4] = {cam.tr.x, cam.tr.y, cam.tr.z, cam.tr.w};
+	const float bl[4] = {cam.bl.x, cam.bl.y, cam.bl.z, cam.bl.w}, br[4] = {cam.br.x, cam.br.y, cam.br.z, cam.br.w};
+	float dc[3];
+	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc); // (temporal.h: k_reproject re-derives this ray)
+	const f3 d = mk3(dc[0], dc[1], dc[2]);
 	HitRec h;
 	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), d, kFltMax, stk, h);
 	if (h.tri < 0) {
@@ -1763,6 +1762,43 @@ __global__ __launch_bounds__(WG) void k_denoise(const float4 *acc, float weight,
 	dn_step(i % W, i / W, W, y0, y1, ci, it, load, r);
 	if (last) out[i] = make_float4(r[0] * dn_demod_albedo(ai.x), r[1] * dn_demod_albedo(ai.y), r[2] * dn_demod_albedo(ai.z), 0.0f);
 	else out[i] = make_float4(r[0], r[1], r[2], 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------
+// Temporal reuse (polaris_hip_set_temporal).  Neither kernel touches an accumulator: the history, PRIOR and
+// TEMPORAL planes are products of their own.  One thread per pixel, no LDS; the arithmetic is temporal.h's.
+// ------------------------------------------------------------------------------------------
+// PRIOR of every pixel of the frame (n = W * H): the current G-buffer (guide, albedo) under camera cur, projected into the
+// history camera hist (projectable) with its planes (hist rgb | count, hguide, halbedo).  Up to 2 + 4 x 3 float4 gathers a pixel.
+__global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
+                                                  const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
+                                                  uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior) {
+	const uint32_t i = blockIdx.x * WG + threadIdx.x;
+	if (i >= W * H) return;
+	const float4 g = guide[i];
+	const float gi[4] = {g.x, g.y, g.z, g.w};
+	auto load = [&](uint32_t j, TpTap &t) {
+		const float4 c = hist[j], n = hguide[j];
+		t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
+		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
+		t.leaf = halbedo[j].w;
+	};
+	float o[4];
+	tp_reproject(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o);
+	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// TEMPORAL plane over the rows [y0, y1): the frame accumulator blended with the PRIOR (n = accumulated + spp as a float,
+// weight = sync's 1 / n).
+__global__ __launch_bounds__(WG) void k_temporal(const float4 *acc, const float4 *prior, float4 *out, uint32_t W, uint32_t y0, uint32_t y1,
+                                                 float n, float weight) {
+	const uint32_t i = y0 * W + blockIdx.x * WG + threadIdx.x;
+	if (i >= y1 * W) return;
+	const float4 a4 = acc[i], p4 = prior[i];
+	const float a[4] = {a4.x, a4.y, a4.z, a4.w}, pr[4] = {p4.x, p4.y, p4.z, p4.w};
+	float o[4];
+	tp_combine(a, pr, n, weight, o);
+	out[i] = make_float4(o[0], o[1], o[2], o[3]);
 }
 
 } // namespace pol

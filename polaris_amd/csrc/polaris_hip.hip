@@ -119,6 +119,18 @@ struct polaris_hip_tracer {
 	float4 *dn_out = nullptr, *dn_ping = nullptr, *dn_pong = nullptr; // DENOISED plane, iteration buffers
 	bool dn_valid = false;                            // a denoised sync has written dn_out since the last resize
 
+	// temporal reuse across camera moves (polaris_hip_set_temporal; kernels.h k_reproject / k_temporal).  Nothing is allocated
+	// while it is off.  The history is the TEMPORAL plane, G-buffer and camera of the last temporal sync before the latest
+	// set_camera, which swaps the pointers (tp_out <-> tp_hist, gb_guide <-> tp_hguide, gb_albedo <-> tp_halbedo).  All five
+	// planes are frame-sized float4; resize frees them, upload_scene and max_history = 0 drop the history.
+	PolarisTemporalParams tp{sizeof(PolarisTemporalParams), 0, 0.0f, 0.0f};
+	float4 *tp_out = nullptr, *tp_prior = nullptr;                          // TEMPORAL / PRIOR planes
+	float4 *tp_hist = nullptr, *tp_hguide = nullptr, *tp_halbedo = nullptr; // the history
+	CameraArgs tp_hcam{};
+	bool tp_have_hist = false;
+	bool tp_synced = false;      // a temporal sync ran under the current camera (tp_out and the G-buffer are this camera's)
+	bool tp_prior_valid = false; // tp_prior is the current history reprojected into the current camera with the current params
+
 	// wavefront batch state: up to kMaxPipes pipelines (option "overlap", default 4; a Trace uses min(overlap, #batches) of
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
 	// bounces of batch i+1 on another stream
@@ -394,6 +406,14 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 }
 
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
+
+void free_temporal(polaris_hip_tracer *h) { // caller holds mu, every stream idle
+	for (float4 **p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo}) {
+		if (*p) (void)hipFree(*p);
+		*p = nullptr;
+	}
+	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
+}
 
 void free_denoise(polaris_hip_tracer *h) { // caller holds mu, every stream idle
 	for (float4 **p : {&h->gb_guide, &h->gb_albedo, &h->dn_out, &h->dn_ping, &h->dn_pong}) {
@@ -766,6 +786,7 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 		free_pool(h->scene_bufs);
 		free_ring(h);
 		free_denoise(h);
+		free_temporal(h);
 		for (auto &e : h->ev_ipc_done)
 			if (e) { (void)hipEventDestroy(e); e = nullptr; }
 		{
@@ -814,6 +835,7 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	HIP_TRY(h, sync_all(h));
 	free_ring(h); // (an IPC export dies with the buffers: peers close, the tracer exports again)
 	free_denoise(h);
+	if (h->tp.max_history) free_temporal(h);
 	if (h->frame_acc) (void)hipFree(h->frame_acc);
 	if (h->framebuffer) (void)hipFree(h->framebuffer);
 	h->frame_acc = nullptr;
@@ -853,6 +875,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	free_pool(h->scene_bufs);
 	h->have_scene = false;
 	h->gb_valid = false;
+	if (h->tp.max_history) h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false; // (the history saw the old scene)
 	int rc = 0;
 	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
 	rc |= dev_upload(h, h->scene_bufs, &pairs, L.pairs.data(), L.pairs.size());
@@ -952,6 +975,17 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
+	if (h->tp.max_history) {
+		// the last temporal sync's planes under the old camera become the history (no sync under it: the older history stays)
+		if (h->tp_synced) {
+			std::swap(h->tp_out, h->tp_hist);
+			std::swap(h->gb_guide, h->tp_hguide);
+			std::swap(h->gb_albedo, h->tp_halbedo);
+			h->tp_hcam = h->cam;
+			h->tp_have_hist = true;
+		}
+		h->tp_synced = h->tp_prior_valid = false;
+	}
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
 	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
 	h->cam.bl = make_float4(fr[8], fr[9], fr[10], fr[11]);
@@ -1575,6 +1609,74 @@ int sync_denoised(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	collect_timers(h);
 	return POLARIS_OK;
 }
+
+TpCamera tp_camera(const CameraArgs &c) {
+	return TpCamera{{c.tl.x, c.tl.y, c.tl.z, c.tl.w}, {c.tr.x, c.tr.y, c.tr.z, c.tr.w}, {c.bl.x, c.bl.y, c.bl.z, c.bl.w},
+	                {c.br.x, c.br.y, c.br.z, c.br.w}, {c.eye.x, c.eye.y, c.eye.z}};
+}
+TpCamera tp_camera(const float eye[3], const float fr[16]) {
+	return TpCamera{{fr[0], fr[1], fr[2], fr[3]}, {fr[4], fr[5], fr[6], fr[7]}, {fr[8], fr[9], fr[10], fr[11]}, {fr[12], fr[13], fr[14], fr[15]},
+	                {eye[0], eye[1], eye[2]}};
+}
+
+// The PRIOR plane of a W x H frame on stream q (caller holds mu): the history (hist, hguide, halbedo under hcam; hist = null: none)
+// reprojected onto the G-buffer (guide, albedo) under cam.  polaris_hip_sync_framebuffer and polaris_hip_reproject_planes both
+// launch it through here.
+hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *hist, const float4 *hguide, const float4 *halbedo, const TpCamera &hcam,
+                      const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
+                      float4 *prior) {
+	const size_t F = (size_t)W * H;
+	Timed t(h, "reproject", q);
+	if (!hist || !tp_projectable(hcam) || p.max_history == 0) return hipMemsetAsync(prior, 0, F * sizeof(float4), q); // no history anywhere: m = 0
+	if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject";
+	hipLaunchKernelGGL(k_reproject, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
+	                   p.normal_threshold, p.depth_threshold, prior);
+	return hipGetLastError();
+}
+
+// polaris_hip_sync_framebuffer with temporal reuse on (caller holds mu; request checked): G-buffer if stale, TEMPORAL cleared at
+// the first temporal sync under this camera, PRIOR if stale, the TEMPORAL rows of the request, then the filter (if on) or the
+// tone-map over them with weight 1.
+int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
+	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "temporal reuse needs the camera (UpdateState CameraData)");
+	const size_t F = (size_t)h->W * h->H, off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
+	const uint32_t y0 = r->block_y, y1 = r->block_y + r->block_h;
+	if (int rc = ensure_gbuffer(h)) return rc;
+	if (!h->tp_out) HIP_TRY(h, hipMalloc((void **)&h->tp_out, F * sizeof(float4)));
+	if (!h->tp_prior) HIP_TRY(h, hipMalloc((void **)&h->tp_prior, F * sizeof(float4)));
+	if (h->dn.iterations) {
+		if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
+		if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
+		if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
+	}
+	if (!h->tp_synced) HIP_TRY(h, hipMemsetAsync(h->tp_out, 0, F * sizeof(float4), h->stream)); // (rows no sync reaches: no history)
+	h->tp_synced = true;
+	if (!h->tp_prior_valid) {
+		HIP_TRY(h, launch_reproject(h, h->stream, h->tp_have_hist ? h->tp_hist : nullptr, h->tp_hguide, h->tp_halbedo, tp_camera(h->tp_hcam),
+		                            h->gb_guide, h->gb_albedo, tp_camera(h->cam), h->W, h->H, h->tp, h->tp_prior));
+		h->tp_prior_valid = true;
+	}
+	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
+	{
+		Timed t(h, "temporal");
+		if (h->opt_time_kernels) h->timer_symbol["temporal"] = "pol::k_temporal";
+		const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
+		hipLaunchKernelGGL(k_temporal, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc, h->tp_prior, h->tp_out, h->W, y0, y1, nf, weight);
+	}
+	if (h->dn.iterations) {
+		launch_denoise(h, h->stream, h->tp_out, 1.0f, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W, y0, y1,
+		               r->exposure, h->dn);
+	} else {
+		Timed t(h, "tonemap");
+		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->tp_out + off, h->framebuffer + off, (uint32_t)n, 1.0f,
+		                   r->exposure);
+	}
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	if (h->dn.iterations) h->dn_valid = true;
+	collect_timers(h);
+	return POLARIS_OK;
+}
 } // namespace
 
 extern "C" {
@@ -1592,17 +1694,42 @@ int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p
 	return POLARIS_OK;
 }
 
+int polaris_hip_set_temporal(polaris_hip_tracer *h, const PolarisTemporalParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisTemporalParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_temporal: null params or struct_size != %zu", sizeof(PolarisTemporalParams));
+	if (tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_temporal: max_history %u (0..%u), normal_threshold %g ([-1, 1]), depth_threshold %g ([0, %g])",
+		            p->max_history, kTpMaxHistory, (double)p->normal_threshold, (double)p->depth_threshold, (double)kTpMaxDepthThreshold);
+	if (p->max_history == 0) {
+		if (h->tp.max_history) {
+			HIP_TRY(h, hipSetDevice(h->device));
+			HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every temporal launch is on the main stream)
+			free_temporal(h);
+		}
+	} else if (p->max_history != h->tp.max_history || pm_f2u(p->normal_threshold) != pm_f2u(h->tp.normal_threshold) ||
+	           pm_f2u(p->depth_threshold) != pm_f2u(h->tp.depth_threshold)) {
+		h->tp_prior_valid = false; // (recomputed at the next temporal sync)
+	}
+	h->tp = *p;
+	return POLARIS_OK;
+}
+
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	const size_t need = (size_t)h->W * h->H * 4;
-	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_DENOISED)
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2}", need);
+	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_PRIOR)
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2,3,4}", need);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const float4 *src;
 	if (which == POLARIS_AOV_DENOISED) {
 		if (!h->dn_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no denoised sync since the last resize");
 		src = h->dn_out;
+	} else if (which == POLARIS_AOV_TEMPORAL || which == POLARIS_AOV_PRIOR) {
+		if (!h->tp_synced || !h->tp_prior_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no temporal sync under the current camera");
+		src = which == POLARIS_AOV_TEMPORAL ? h->tp_out : h->tp_prior;
 	} else {
 		if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
@@ -1623,6 +1750,7 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
+	if (h->tp.max_history) return sync_temporal(h, r, weight);
 	if (h->dn.iterations) return sync_denoised(h, r, weight);
 	HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
 	{
@@ -1883,6 +2011,41 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
 	(void)hipFree(d);
 	if (e == hipSuccess) e = e2;
 	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "denoise_planes: %s", hipGetErrorString(e));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                 const float prev_eye[3], const float prev_frustum[16], const float *guide, const float *albedo,
+                                 const float eye[3], const float frustum[16], uint32_t W, uint32_t H, const PolarisTemporalParams *p,
+                                 float *prior) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!history || !prev_guide || !prev_albedo || !prev_eye || !prev_frustum || !guide || !albedo || !eye || !frustum || !prior || !p ||
+	    p->struct_size != sizeof(PolarisTemporalParams) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) ||
+	    tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_planes: null argument, frame %ux%u (1..2^26 pixels), or params (max_history 0..%u, "
+		            "normal_threshold [-1, 1], depth_threshold [0, %g])", W, H, kTpMaxHistory, (double)kTpMaxDepthThreshold);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
+	char *d = nullptr;
+	HIP_TRY(h, hipMalloc((void **)&d, 6 * plane));   // its own planes: no tracer state is read or written
+	float4 *d_hist = (float4 *)d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
+	       *d_prior = d_albedo + F;
+	hipError_t e = hipSuccess;
+	const std::pair<float4 *, const void *> in[] = {{d_hist, history}, {d_hguide, prev_guide}, {d_halbedo, prev_albedo}, {d_guide, guide},
+	                                                {d_albedo, albedo}};
+	for (const auto &c : in)
+		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) {
+		e = launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
+		                     W, H, *p, d_prior);
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream);
+	const hipError_t e2 = hipStreamSynchronize(h->stream);
+	(void)hipFree(d);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "reproject_planes: %s", hipGetErrorString(e));
 	collect_timers(h);
 	return POLARIS_OK;
 }

@@ -1,0 +1,160 @@
+// temporal.h -- per-pixel arithmetic of the temporal reprojection that polaris_hip_sync_framebuffer runs when temporal reuse is
+// on (include/polaris_hip.h, polaris_hip_set_temporal).
+//
+// ONE definition for both sides, as denoise.h: the HIP kernels (kernels.h, k_reproject / k_temporal; k_gbuffer's centre ray) and
+// the CPU restatement the tests compare them with (polaris_amd/host/temporal.cpp) include this header, and both are compiled
+// without FMA contraction and with IEEE division and square root, so the two agree bit for bit.  Plain floats only.
+//
+// The HISTORY is a frame-sized float4 plane (mean rgb | sample count) with the GUIDE / ALBEDO planes and the camera it was seen
+// with.  For a filtered pixel i of the current G-buffer the first hit p = eye + t_i d_i is projected into the history camera, and
+// the 2 x 2 history pixels around it that saw the same surface give the PRIOR (h rgb | m, m = 0: no history).  The TEMPORAL plane
+// then blends the running mean with it: (acc + m h) / (n + m).
+#pragma once
+
+#include <stdint.h>
+
+#include "denoise.h"
+#include "polaris_math.h"
+
+namespace pol {
+
+constexpr uint32_t kTpMaxHistory = 4096;   // max_history: 0 (off) .. this
+constexpr float kTpMaxDepthThreshold = 1e6f;
+constexpr float kTpSkew = 1e-3f;           // |tl + br - tr - bl| <= kTpSkew * |tr - tl|: the corners are a parallelogram
+
+// A camera as CameraData carries it: the four frustum corner directions (eye-relative, w = 0) and the eye.
+struct TpCamera { float tl[4], tr[4], bl[4], br[4], eye[3]; };
+
+// The unit direction through pixel (gx, gy)'s centre, texel = (1 / W, 1 / H): k_generate's bilinear corner blend with the
+// sub-pixel offset fixed at 0.5, over all four components.  k_gbuffer casts this ray, k_reproject re-derives it.
+PM_HD void tp_centre_ray(const float tl[4], const float tr[4], const float bl[4], const float br[4], uint32_t gx, uint32_t gy,
+                         float texel_x, float texel_y, float d[3]) {
+	const float tx = ((float)gx + 0.5f) * texel_x;
+	const float ty = ((float)gy + 0.5f) * texel_y;
+	const float lx = pm_mix(tl[0], bl[0], ty), ly = pm_mix(tl[1], bl[1], ty), lz = pm_mix(tl[2], bl[2], ty), lw = pm_mix(tl[3], bl[3], ty);
+	const float rx = pm_mix(tr[0], br[0], ty), ry = pm_mix(tr[1], br[1], ty), rz = pm_mix(tr[2], br[2], ty), rw = pm_mix(tr[3], br[3], ty);
+	const float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
+	const float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
+	d[0] = dx * inv;
+	d[1] = dy * inv;
+	d[2] = dz * inv;
+}
+
+PM_HD float tp_len3(float x, float y, float z) { return pm_sqrt(x * x + y * y + z * z); }
+
+// A camera is projectable when its corners are a parallelogram (then the bilinear blend of tp_centre_ray is the plane
+// tl + u (tr - tl) + v (bl - tl)): every w is 0 and |tl + br - tr - bl| <= kTpSkew |tr - tl|.  A history camera that is not
+// gives no history anywhere.
+PM_HD bool tp_projectable(const TpCamera &c) {
+	if (c.tl[3] != 0.0f || c.tr[3] != 0.0f || c.bl[3] != 0.0f || c.br[3] != 0.0f) return false;
+	const float sx = ((c.tl[0] + c.br[0]) - c.tr[0]) - c.bl[0], sy = ((c.tl[1] + c.br[1]) - c.tr[1]) - c.bl[1],
+	            sz = ((c.tl[2] + c.br[2]) - c.tr[2]) - c.bl[2];
+	return tp_len3(sx, sy, sz) <= kTpSkew * tp_len3(c.tr[0] - c.tl[0], c.tr[1] - c.tl[1], c.tr[2] - c.tl[2]); // (NaN fails)
+}
+
+// det(a, b, c) = a . (b x c), in this order
+PM_HD float tp_det(const float a[3], const float b[3], const float c[3]) {
+	return a[0] * (b[1] * c[2] - b[2] * c[1]) + a[1] * (b[2] * c[0] - b[0] * c[2]) + a[2] * (b[0] * c[1] - b[1] * c[0]);
+}
+
+// Projection of the point p into camera c (projectable): solves tl + u A + v B = mu q, A = tr - tl, B = bl - tl, q = p - eye, by
+// Cramer's rule: D = det(A, B, q), u = -det(tl, B, q) / D, v = -det(A, tl, q) / D, mu = det(A, B, tl) / D.  Returns false unless
+// mu > 0 (the point lies in front of the camera; D = 0 or a NaN fails too).  dist = |q|.
+PM_HD bool tp_project(const TpCamera &c, const float p[3], float &u, float &v, float &dist) {
+	const float A[3] = {c.tr[0] - c.tl[0], c.tr[1] - c.tl[1], c.tr[2] - c.tl[2]};
+	const float B[3] = {c.bl[0] - c.tl[0], c.bl[1] - c.tl[1], c.bl[2] - c.tl[2]};
+	const float q[3] = {p[0] - c.eye[0], p[1] - c.eye[1], p[2] - c.eye[2]};
+	const float T[3] = {c.tl[0], c.tl[1], c.tl[2]};
+	const float D = tp_det(A, B, q);
+	const float mu = tp_det(A, B, T) / D;
+	if (!(mu > 0.0f)) return false;
+	u = -tp_det(T, B, q) / D;
+	v = -tp_det(A, T, q) / D;
+	dist = tp_len3(q[0], q[1], q[2]);
+	return true;
+}
+
+// One history tap as k_reproject gathers it.
+struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; };
+
+// The tap test: a history count > 0, finite history rgb, the same leaf word as pixel i, n_i . n_j >= normal_threshold and
+// |t_j - dist| <= depth_threshold * dist.
+PM_HD bool tp_finite(float x) { return (pm_f2u(x) & 0x7f800000u) != 0x7f800000u; }
+PM_HD bool tp_tap_ok(const TpTap &j, float leaf_i, float nx, float ny, float nz, float dist, float normal_threshold, float depth_threshold) {
+	if (!(j.count > 0.0f)) return false;
+	if (!tp_finite(j.r) || !tp_finite(j.g) || !tp_finite(j.b)) return false;
+	if (pm_f2u(j.leaf) != pm_f2u(leaf_i)) return false;
+	if (!(nx * j.nx + ny * j.ny + nz * j.nz >= normal_threshold)) return false;
+	return pm_fabs(j.t - dist) <= depth_threshold * dist;
+}
+
+// The PRIOR of pixel (gx, gy) of a W x H frame: guide_i / leaf_i of the current G-buffer, cur / hist the cameras (hist
+// projectable), load(j, tap) fills history tap j (row-major index).  out = h rgb | m; m = 0 (and h = 0) without history.
+// The taps are the 2 x 2 around (u W - 0.5, v H - 0.5) in the order (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1);
+// their bilinear weights are renormalised over the valid ones.
+template <class Load>
+PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const TpCamera &cur,
+                        const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4]) {
+	out[0] = out[1] = out[2] = out[3] = 0.0f;
+	if (!dn_filtered(leaf_i)) return;
+	float d[3];
+	tp_centre_ray(cur.tl, cur.tr, cur.bl, cur.br, gx, gy, 1.0f / (float)W, 1.0f / (float)H, d);
+	const float t = guide_i[3];
+	const float p[3] = {cur.eye[0] + t * d[0], cur.eye[1] + t * d[1], cur.eye[2] + t * d[2]};
+	float u, v, dist;
+	if (!tp_project(hist, p, u, v, dist)) return;
+	const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
+	if (!(x > -1.0f && x < (float)W && y > -1.0f && y < (float)H)) return; // (no tap inside; NaN fails)
+	const float fx0 = pm_floor(x), fy0 = pm_floor(y);
+	const float fx = x - fx0, fy = y - fy0;
+	const int x0 = (int)fx0, y0 = (int)fy0;
+	float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hc = 0.0f;
+	for (int k = 0; k < 4; k++) {
+		const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
+		if (xx < 0 || xx >= (int)W || yy < 0 || yy >= (int)H) continue;
+		const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+		TpTap j;
+		load((uint32_t)yy * W + (uint32_t)xx, j);
+		if (!tp_tap_ok(j, leaf_i, guide_i[0], guide_i[1], guide_i[2], dist, normal_threshold, depth_threshold)) continue;
+		sw += w;
+		hr += w * j.r;
+		hg += w * j.g;
+		hb += w * j.b;
+		hc += w * j.count;
+	}
+	if (!(sw > 0.0f)) return;
+	const float m = pm_min(hc / sw, (float)max_history);
+	if (!(m > 0.0f)) return;
+	out[0] = hr / sw;
+	out[1] = hg / sw;
+	out[2] = hb / sw;
+	out[3] = m;
+}
+
+// The TEMPORAL pixel from the frame accumulator's a[4], the PRIOR's pr[4], n = accumulated_samples + samples_per_pixel as a float
+// and sync's weight 1 / n: m > 0 -> (a + m h) / (n + m) | n + m; m = 0 -> a * weight | n, the running mean sync tone-maps today.
+PM_HD void tp_combine(const float a[4], const float pr[4], float n, float weight, float out[4]) {
+	const float m = pr[3];
+	if (m > 0.0f) {
+		const float s = n + m;
+		out[0] = (a[0] + m * pr[0]) / s;
+		out[1] = (a[1] + m * pr[1]) / s;
+		out[2] = (a[2] + m * pr[2]) / s;
+		out[3] = s;
+	} else {
+		out[0] = a[0] * weight;
+		out[1] = a[1] * weight;
+		out[2] = a[2] * weight;
+		out[3] = n;
+	}
+}
+
+// Parameter check shared by polaris_hip_set_temporal, polaris_hip_reproject_planes and polaris_host_reproject: 0 = valid.
+PM_HD int tp_check(uint32_t max_history, float normal_threshold, float depth_threshold) {
+	if (max_history > kTpMaxHistory) return 1;
+	if (!(normal_threshold >= -1.0f && normal_threshold <= 1.0f)) return 1;       // (NaN fails)
+	if (!(depth_threshold >= 0.0f && depth_threshold <= kTpMaxDepthThreshold)) return 1;
+	return 0;
+}
+
+} // namespace pol

@@ -155,7 +155,28 @@ class DenoiseParams(C.Structure):
 assert C.sizeof(DenoiseParams) == 20
 # the settings DESIGN.md section 10 chose on the CPU restatement (include/polaris_hip.h)
 DENOISE_DEFAULTS = {"iterations": 4, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_luminance": 4.0}
-AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED = 0, 1, 2
+AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED, AOV_TEMPORAL, AOV_PRIOR = 0, 1, 2, 3, 4
+
+
+class TemporalParams(C.Structure):
+    """PolarisTemporalParams (include/polaris_hip.h): temporal reuse of the synced frame across camera moves."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_history", C.c_uint32), ("normal_threshold", C.c_float), ("depth_threshold", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(TemporalParams) == 16
+# the settings DESIGN.md section 10b chose on the CPU restatement (include/polaris_hip.h)
+TEMPORAL_DEFAULTS = {"max_history": 32, "normal_threshold": 0.9, "depth_threshold": 0.1}
+
+
+def temporal_params(max_history=32, normal_threshold=0.9, depth_threshold=0.1) -> TemporalParams:
+    p = TemporalParams()
+    p.max_history = int(max_history)
+    p.normal_threshold, p.depth_threshold = float(normal_threshold), float(depth_threshold)
+    return p
 
 # polaris_hip_selftest_builtins / polaris_oracle_builtins: the probed built-ins (enum PbFn, polaris_amd/csrc/builtin_probe.h)
 BUILTINS_UNARY = ("sqrt", "rcp", "floor", "fabs", "sign", "sin", "cos", "atan", "acos", "log", "exp", "pow_gamma", "convert_float_uint",
@@ -254,6 +275,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_trace_slot", "polaris_hip_merge_slot", "polaris_hip_build_bvh", "polaris_hip_build_bvh_error",
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
+    "polaris_hip_set_temporal", "polaris_hip_reproject_planes",
 ]
 
 _lib = None
@@ -353,6 +375,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_read_aov.argtypes = [vp, i32, vp, C.c_size_t]
     lib.polaris_hip_selftest_builtins.argtypes = [vp, u32, C.c_uint64, C.c_uint64, vp, vp]
     lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
+    lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
+    lib.polaris_hip_reproject_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(TemporalParams), vp]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

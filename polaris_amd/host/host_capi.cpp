@@ -139,6 +139,23 @@ int polaris_host_renderer_set_denoise(void *h, const PolarisDenoiseParams *p) {
 		if (int rc = polaris_hip_set_denoise(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// Temporal reuse (polaris_hip_set_temporal) on every tracer, as set_denoise: only the primary syncs, so only it reprojects.
+int polaris_host_renderer_set_temporal(void *h, const PolarisTemporalParams *p) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (int rc = polaris_hip_set_temporal(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	return 0;
+}
+// A camera move: the CameraData of every tracer, as the interactive renderer's UpdateState (renderer/opengl.go:294-301).
+int polaris_host_renderer_set_camera(void *h, const float eye[3], const float frustum[16]) {
+	auto *box = static_cast<RendererBox *>(h);
+	if (!eye || !frustum) return POLARIS_E_BAD_ARGUMENT;
+	tracer::CameraData cam;
+	memcpy(cam.eye, eye, sizeof cam.eye);
+	memcpy(cam.frustum, frustum, sizeof cam.frustum);
+	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
+	return 0;
+}
 // A plane of the primary's denoiser (polaris_hip_read_aov).
 int polaris_host_renderer_read_aov(void *h, int which, float *out, size_t n_floats) {
 	auto *box = static_cast<RendererBox *>(h);
@@ -309,6 +326,32 @@ void polaris_host_compiled_camera(void *h, float aspect, int invert_y, float par
 	const tracer::CameraData d = cam.Data();
 	if (eye) memcpy(eye, d.eye, sizeof d.eye);
 	if (frustum) memcpy(frustum, d.frustum, sizeof d.frustum);
+}
+// The camera of polaris_host_compiled_camera (params = fov, eye, look, up) after n_moves calls of scene.Camera.Move (camera.go:76-97)
+// on ONE camera object, as the interactive renderer's key handler makes them: dirs[k] = CameraDirection (0 up, 1 down, 2 left,
+// 3 right, 4 forward, 5 backward), offsets[k] its offset.  Writes the moved camera's params (may be NULL) and CameraData.
+int polaris_host_camera_move(const float params_in[10], float aspect, int invert_y, const int *dirs, const float *offsets, uint32_t n_moves,
+                             float params[10], float eye[3], float frustum[16]) {
+	if (!params_in || (n_moves && (!dirs || !offsets)) || !eye || !frustum) return POLARIS_E_BAD_ARGUMENT;
+	for (uint32_t k = 0; k < n_moves; k++)
+		if (dirs[k] < 0 || dirs[k] > 5) return POLARIS_E_BAD_ARGUMENT;
+	scene::Camera cam(params_in[0]);
+	cam.Position = {params_in[1], params_in[2], params_in[3]};
+	cam.LookAt = {params_in[4], params_in[5], params_in[6]};
+	cam.Up = {params_in[7], params_in[8], params_in[9]};
+	cam.InvertY = invert_y != 0;
+	cam.SetupProjection(aspect);
+	for (uint32_t k = 0; k < n_moves; k++) cam.Move((scene::CameraDirection)dirs[k], offsets[k]);
+	if (params) {
+		params[0] = cam.FOV;
+		params[1] = cam.Position.x; params[2] = cam.Position.y; params[3] = cam.Position.z;
+		params[4] = cam.LookAt.x; params[5] = cam.LookAt.y; params[6] = cam.LookAt.z;
+		params[7] = cam.Up.x; params[8] = cam.Up.y; params[9] = cam.Up.z;
+	}
+	const tracer::CameraData d = cam.Data();
+	memcpy(eye, d.eye, sizeof d.eye);
+	memcpy(frustum, d.frustum, sizeof d.frustum);
+	return 0;
 }
 // warnings joined by '\n' (missing textures, ...); returns the length needed
 size_t polaris_host_compiled_warnings(void *h, char *buf, size_t cap) {

@@ -35,6 +35,11 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         lib.polaris_host_renderer_set_denoise.argtypes = [vp, C.POINTER(T.DenoiseParams)]
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
+        lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
+        lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
+        lib.polaris_host_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(T.TemporalParams), vp]
+        lib.polaris_host_temporal_combine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        lib.polaris_host_camera_move.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.c_uint32, vp, vp, vp]
         lib.polaris_host_denoise.argtypes = [vp, C.c_float, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.POINTER(T.DenoiseParams), vp]
         lib.polaris_host_renderer_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
@@ -134,6 +139,19 @@ class Renderer:
         if self._lib.polaris_host_renderer_set_denoise(self._h, C.byref(p)):
             raise RuntimeError(f"set_denoise failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
+    def set_temporal(self, max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> None:
+        """polaris_hip_set_temporal on every tracer; only the primary syncs, so only the primary reprojects."""
+        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+        if self._lib.polaris_host_renderer_set_temporal(self._h, C.byref(p)):
+            raise RuntimeError(f"set_temporal failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_camera(self, eye, frustum) -> None:
+        """A camera move: UpdateState(CameraData) on every tracer (DefaultRenderer::UpdateAll)."""
+        e = np.ascontiguousarray(eye, dtype=np.float32).reshape(3)
+        f = np.ascontiguousarray(frustum, dtype=np.float32).reshape(16)
+        if self._lib.polaris_host_renderer_set_camera(self._h, e.ctypes.data, f.ctypes.data):
+            raise RuntimeError(f"set_camera failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
     def read_aov(self, which: int) -> np.ndarray:
         """The primary's (H, W, 4) denoiser plane (polaris_hip_read_aov)."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
@@ -207,6 +225,61 @@ def denoise(frame_acc, weight: float, guide, albedo, *, block_y: int = 0, block_
     if rc:
         raise ValueError(f"denoise: bad arguments (code {rc})")
     return res
+
+
+def reproject(history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *, max_history: int = 32,
+              normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
+    """polaris_host_reproject: the CPU restatement of the temporal reprojection (polaris_amd/host/temporal.cpp).  The planes are
+    (H, W, 4) float32, the cameras eye (3,) and frustum (4, 4) / (16,); returns the PRIOR plane (h rgb | m).  Raises ValueError where
+    the library refuses the arguments."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
+    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+    H, W = g.shape[:2]
+    if not hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4):
+        raise ValueError("reproject: the planes must be (H, W, 4) of one size")
+    out = np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+    rc = load().polaris_host_reproject(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data,
+                                       a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p), out.ctypes.data)
+    if rc:
+        raise ValueError(f"reproject: bad arguments (code {rc})")
+    return out
+
+
+def temporal_combine(frame_acc, prior, accumulated_samples: int, samples_per_pixel: int, *, block_y: int = 0, block_h: int | None = None,
+                     out=None) -> np.ndarray:
+    """polaris_host_temporal_combine: the TEMPORAL plane (rgb | n + m) of the rows [block_y, block_y + block_h) of a sync with these
+    sample counts; the other rows as `out` gave them (zeros by default)."""
+    acc = np.ascontiguousarray(frame_acc, dtype=np.float32)
+    pr = np.ascontiguousarray(prior, dtype=np.float32)
+    H, W = acc.shape[:2]
+    if pr.shape != acc.shape or acc.shape != (H, W, 4):
+        raise ValueError("temporal_combine: frame_acc and prior must be (H, W, 4) of one size")
+    res = np.zeros_like(acc) if out is None else np.array(out, dtype=np.float32, copy=True)
+    bh = H - block_y if block_h is None else block_h
+    rc = load().polaris_host_temporal_combine(acc.ctypes.data, pr.ctypes.data, int(accumulated_samples), int(samples_per_pixel), W, H,
+                                              int(block_y), int(bh), res.ctypes.data)
+    if rc:
+        raise ValueError(f"temporal_combine: bad arguments (code {rc})")
+    return res
+
+
+CAMERA_MOVES = {"up": 0, "down": 1, "left": 2, "right": 3, "forward": 4, "backward": 5}   # scene.CameraDirection (camera.go:12-19)
+
+
+def camera_move(camera: dict, moves, *, aspect: float = 1.0, invert_y: bool = False):
+    """polaris_host_camera_move: (eye (3,), frustum (4, 4)) of the camera `camera` (read_scene's .camera dict) after the moves
+    [(direction name, offset), ...] of scene.Camera.Move on one camera object, as the interactive renderer makes them."""
+    params = np.concatenate([[camera["fov"]], camera["eye"], camera["look"], camera["up"]]).astype(np.float32)
+    dirs = np.ascontiguousarray([CAMERA_MOVES[d] for d, _ in moves], dtype=np.int32)
+    offs = np.ascontiguousarray([o for _, o in moves], dtype=np.float32)
+    eye = np.zeros(3, np.float32)
+    fr = np.zeros((4, 4), np.float32)
+    if load().polaris_host_camera_move(params.ctypes.data, float(aspect), int(invert_y), dirs.ctypes.data, offs.ctypes.data, len(dirs), None,
+                                       eye.ctypes.data, fr.ctypes.data):
+        raise ValueError("camera_move: bad arguments")
+    return eye, fr
 
 
 def bvh_build(boxes, min_leaf: int):

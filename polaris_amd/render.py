@@ -9,7 +9,12 @@ the reference does it (rr-bounces 0 or >= num-bounces -> num-bounces + 1).
 
 --denoise N filters the synced frame with N iterations of the edge-avoiding a-trous filter (polaris_hip_set_denoise, the
 other settings at their defaults); --aov-dir DIR also writes the first-hit guide planes as normals.png / depth.png (the byte
-formulas of the reference's debug kernels, tracer/opencl/CL/kernels/debug.cl) and albedo.png."""
+formulas of the reference's debug kernels, tracer/opencl/CL/kernels/debug.cl) and albedo.png.
+
+--frames N --move DIR:OFFSET renders N frames, each one render(accumulated=0) after a camera move (scene.Camera.Move, camera.go:76-97,
+DIR one of left, right, up, down, forward, backward), written as <out stem>_000.png, _001.png, ...: what the interactive renderer
+does while the user moves.  --temporal M reuses the last view's mean across the moves with max_history M (polaris_hip_set_temporal,
+the thresholds at their defaults)."""
 import argparse
 import os
 import sys
@@ -45,6 +50,28 @@ def aov_images(guide: np.ndarray, albedo: np.ndarray) -> dict:
     return out
 
 
+def parse_move(move: str):
+    d, _, off = move.partition(":")
+    if d not in host_api.CAMERA_MOVES or not off:
+        raise ValueError(f"--move {move!r}: DIR:OFFSET with DIR one of {', '.join(host_api.CAMERA_MOVES)}")
+    return d, float(off)
+
+
+def frame_paths(out: str, n: int) -> list:
+    stem, ext = os.path.splitext(out)
+    return [f"{stem}_{k:03d}{ext or '.png'}" for k in range(n)]
+
+
+def move_frames(r, sc, n: int, move: str, aspect: float):
+    """Frame k: the scene's camera after k + 1 moves (one camera object, as the interactive renderer's), then render(accumulated=0).
+    Yields (rows, ms) after each frame."""
+    step = parse_move(move)
+    for k in range(n):
+        eye, fr = host_api.camera_move(sc.camera, [step] * (k + 1), aspect=aspect)
+        r.set_camera(eye, fr)
+        yield r.render(0)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m polaris_amd.render", description=__doc__.split("\n")[0])
     ap.add_argument("scene", help="scene.obj")
@@ -59,6 +86,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--denoise", type=int, default=0, help="a-trous filter iterations at the frame sync (0 = off)")
     ap.add_argument("--aov-dir", default=None, help="write normals.png, depth.png and albedo.png of the first-hit G-buffer here")
+    ap.add_argument("--temporal", type=int, default=0, help="max_history of temporal reuse across camera moves (0 = off)")
+    ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
+    ap.add_argument("--move", default="right:0.05", help="DIR:OFFSET of every move with --frames (left, right, up, down, forward, backward)")
     a = ap.parse_args(argv)
 
     rr = a.rr_bounces
@@ -75,8 +105,14 @@ def main(argv=None):
     try:
         if a.denoise:
             r.set_denoise(iterations=a.denoise)
-        rows, ms = r.render()
-        r.save(a.out)  # the SaveFrameBuffer post-process stage (pipeline.go:215-235)
+        if a.temporal:
+            r.set_temporal(max_history=a.temporal)
+        if a.frames:
+            for path, (rows, ms) in zip(frame_paths(a.out, a.frames), move_frames(r, sc, a.frames, a.move, a.width / a.height)):
+                r.save(path)
+        else:
+            rows, ms = r.render()
+            r.save(a.out)  # the SaveFrameBuffer post-process stage (pipeline.go:215-235)
         if a.aov_dir:
             os.makedirs(a.aov_dir, exist_ok=True)
             imgs = aov_images(r.read_aov(T.AOV_GUIDE), r.read_aov(T.AOV_ALBEDO))
@@ -85,7 +121,7 @@ def main(argv=None):
     finally:
         r.close()
     print(f"{a.scene}: {sc.vertices.shape[0] // 3} triangles, {len(sc.mesh_instances)} instances, {len(sc.material_nodes)} material nodes; "
-          f"compiled in {1e3 * (t1 - t0):.0f} ms; {a.width}x{a.height} @ {a.spp} spp on {len(devs)} tracer(s) rows={rows}: {ms:.1f} ms -> {a.out}")
+          f"compiled in {1e3 * (t1 - t0):.0f} ms; {a.width}x{a.height} @ {a.spp} spp on {len(devs)} tracer(s) rows={rows}: {ms:.1f} ms -> {frame_paths(a.out, a.frames)[-1] if a.frames else a.out}")
     return 0
 
 

@@ -152,6 +152,12 @@ class HipTracer:
         p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
         self._check(self._lib.polaris_hip_set_denoise(self._h, C.byref(p)), self._h)
 
+    def set_temporal(self, max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> None:
+        """Reuse the last view's mean across camera moves at every SyncFramebuffer (polaris_hip_set_temporal); max_history = 0 turns
+        it off (the default) and drops the history."""
+        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+        self._check(self._lib.polaris_hip_set_temporal(self._h, C.byref(p)), self._h)
+
     def read_aov(self, which: int) -> np.ndarray:
         """(H, W, 4) float32 plane of the denoiser: T.AOV_GUIDE (normal | hit distance), T.AOV_ALBEDO (albedo | leaf type bits)
         or T.AOV_DENOISED (the filtered running mean of the last denoised sync)."""
@@ -231,6 +237,22 @@ class HipTracer:
                                                          int(bh), float(weight), float(exposure), C.byref(p), out.ctypes.data,
                                                          fb.ctypes.data), self._h)
         return out, fb
+
+    def reproject_planes(self, history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *,
+                         max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
+        """polaris_hip_reproject_planes: the PRIOR plane ((H, W, 4) float32, h rgb | m) of the history planes seen under
+        (prev_eye, prev_frustum), reprojected onto the G-buffer (guide, albedo) under (eye, frustum), on the device."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
+        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+        H, W = g.shape[:2]
+        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4)
+        out = np.zeros((H, W, 4), np.float32)
+        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+        self._check(self._lib.polaris_hip_reproject_planes(self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data,
+                                                           g.ctypes.data, a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p),
+                                                           out.ctypes.data), self._h)
+        return out
 
     def kernel_ms(self, name: str) -> tuple[float, int]:
         ms, n = C.c_double(), C.c_uint64()
