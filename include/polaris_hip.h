@@ -120,6 +120,11 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *   "tiny_one"           NEXT upload: 0 = the general tiny-scene kernel even where the variant for
  *                        single-instance scenes with bounding boxes applies (default 1)
  *   "time_kernels"       1 = bracket every kernel with HIP events (polaris_hip_kernel_ms)
+ *   "moments"            1 = the batch epilogue also adds L_s^2 of every sample (L = Rec. 709 luminance, csrc/variance.h) to
+ *                        the trace accumulator's .w, and merges onto this tracer add .w too (the input of
+ *                        polaris_hip_set_variance); .rgb are the same bit for bit.  Default 0.  POLARIS_E_UNSUPPORTED together
+ *                        with "exact_accumulate" = 1 (in either order: that mode has no per-sample radiance); 0 is
+ *                        POLARIS_E_BAD_ARGUMENT while variance guidance is on
  *   "overlap"            batches in flight on separate streams (1-8, default 4)
  *   "max_leaf_tris"      applies to the NEXT upload_scene: triangle leaves with more triangles
  *                        than this are subdivided where a surface-area split pays (default -1:
@@ -322,6 +327,12 @@ int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p
  * TEMPORAL / PRIOR: POLARIS_E_BAD_ARGUMENT before any temporal sync (polaris_hip_set_temporal) under the current camera. */
 #define POLARIS_AOV_TEMPORAL 3
 #define POLARIS_AOV_PRIOR    4
+/*   VARIANCE  M1 | M2 | n_eff | v: the luminance of the synced mean, the mean of L^2, the effective sample count and the variance
+ *             of the mean (polaris_hip_set_variance); v = 0 for misses and emitters
+ *   PRIOR2    with temporal reuse as well: the history's M2 reprojected into the current camera (h2 | 0 | 0 | m)
+ * VARIANCE / PRIOR2: POLARIS_E_BAD_ARGUMENT before any variance sync (under the current camera with temporal reuse). */
+#define POLARIS_AOV_VARIANCE 5
+#define POLARIS_AOV_PRIOR2   6
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats);
 
 /* Temporal reuse of the synced frame across camera moves (no reference counterpart: the reference's interactive renderer resets
@@ -347,11 +358,30 @@ typedef struct PolarisTemporalParams {
 } PolarisTemporalParams;
 int polaris_hip_set_temporal(polaris_hip_tracer *h, const PolarisTemporalParams *p);
 
+/* Variance-guided denoising (SVGF, Schied et al. 2017; no reference counterpart).  Off by default (sigma_variance = 0); with it off
+ * every sync runs and allocates exactly what it did.  Needs the option "moments" = 1 on this tracer first (else
+ * POLARIS_E_BAD_ARGUMENT).  With it on, every sync writes the request's rows of the VARIANCE plane from the frame accumulator
+ * (rgb | sum L^2), n = accumulated_samples + samples_per_pixel: M1 = lum(mean), M2 = sum L^2 / n (with temporal reuse and a history
+ * m > 0: (sum L^2 + m h2) / (n + m), n_eff = n + m), and for every filtered pixel v = max(0, M2 - M1^2) / (n_eff - 1) where
+ * n_eff >= max(min_samples, 2), else a 7 x 7 spatial estimate weighted by the denoiser's normal and depth terms, divided by n_eff.
+ * With denoise iterations > 0 the a-trous filter's luminance term becomes exp(-|lum(r_i) - lum(r_j)| / (sigma_variance
+ * sqrt(g3x3(v_i)) + 1e-10)) and the variance is filtered alongside (w^2 v / (sum w)^2); the DENOISED plane's .w holds it.  With
+ * iterations = 0 the frame-buffer bytes are those of the plain sync.  DESIGN.md 10c has the exact arithmetic and the suggested
+ * settings (polaris_amd/ctypes_api.py VARIANCE_DEFAULTS).  A field out of range is POLARIS_E_BAD_ARGUMENT: sigma_variance 0 or
+ * within [1e-6, 1e6], min_samples 1..64 (not looked at while off).  Set struct_size = sizeof(PolarisVarianceParams). */
+typedef struct PolarisVarianceParams {
+	uint32_t struct_size;       /* sizeof(PolarisVarianceParams) */
+	float    sigma_variance;    /* sigma_v of the luminance term: 0 = off (default) */
+	uint32_t min_samples;       /* pixels with fewer effective samples take the spatial estimate */
+} PolarisVarianceParams;
+int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams *p);
+
 /* frame_w*frame_h*4 bytes RGBA8 (pipeline.go:226-232). */
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes);
 
 /* Radiance-level read-back for parity tests (no reference counterpart): which = 0 trace
- * accumulator, 1 frame accumulator; n_floats = frame_w*frame_h*4 (float3 at stride 4). */
+ * accumulator, 1 frame accumulator; n_floats = frame_w*frame_h*4 (float3 at stride 4).  The .w of every pixel is the sum of the
+ * samples' squared luminance with the option "moments" on, and 0 otherwise. */
 int polaris_hip_read_accumulator(polaris_hip_tracer *h, int which, float *out, size_t n_floats);
 
 /* Test tap: generate + intersect the primary rays of one sample with camera seed `seed` and
@@ -410,6 +440,14 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
                                uint32_t block_y, uint32_t block_h, float weight, float exposure, const PolarisDenoiseParams *p,
                                float *denoised, uint8_t *rgba);
 
+/* Test entry of variance guidance on caller planes: acc (rgb | sum L^2, `samples` samples a pixel), guide and albedo are W x H float4
+ * planes; k_variance over the rows [block_y, block_y + block_h) into `variance`, then (p->iterations > 0) the variance-guided filter
+ * into `denoised` and its tone-map into rgba, or (iterations = 0) the plain tone-map of acc / samples -- the launches of a variance
+ * sync without temporal reuse.  The rows outside the request keep the bytes the caller passed in.  sigma_variance must be non-zero. */
+int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
+                                uint32_t block_y, uint32_t block_h, uint32_t samples, float exposure, const PolarisDenoiseParams *p,
+                                const PolarisVarianceParams *v, float *variance, float *denoised, uint8_t *rgba);
+
 /* Test entry of the temporal reprojection on caller planes: history (rgb | count), prev_guide, prev_albedo seen under the camera
  * (prev_eye, prev_frustum), and the current guide, albedo under (eye, frustum), all W x H float4 planes; the PRIOR plane of every
  * pixel into prior -- the launch of the first temporal sync after a set_camera.  Uses buffers of its own; no state of the tracer
@@ -466,7 +504,7 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * the wave-packet kernel), "intersect" (closest hit), "shade_first" / "shade_sort" /
  * "shade_plain" / "shade_wave" (one per shade kernel symbol), "scan", "occlusion", "fold" (the batch's NEE records into the
  * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
- * (polaris_hip_set_temporal). */
+ * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

@@ -296,6 +296,33 @@ func (tr *Tracer) SetTemporal(p TemporalParams) error {
 	return tr.check(C.polaris_hip_set_temporal(tr.handle, &c))
 }
 
+// VarianceParams configures variance-guided denoising (PolarisVarianceParams, include/polaris_hip.h; DESIGN.md section 10c).
+// SigmaVariance = 0 turns it off (the default); DefaultVariance holds the settings chosen on the CPU restatement.
+type VarianceParams struct {
+	SigmaVariance float32 // sigma_v of the variance-guided luminance term: 0 = off, else within [1e-6, 1e6]
+	MinSamples    uint32  // pixels with fewer effective samples take the spatial estimate, 1..64
+}
+
+var DefaultVariance = VarianceParams{SigmaVariance: 8, MinSamples: 8}
+
+// SetVariance turns variance guidance on or off: with it on the tracer keeps the samples' squared luminance beside the
+// accumulators (option "moments", set here first) and SyncFramebuffer filters by each pixel's variance estimate.  Turning it off
+// leaves "moments" on.
+func (tr *Tracer) SetVariance(p VarianceParams) error {
+	if p.SigmaVariance != 0 {
+		key := C.CString("moments")
+		defer C.free(unsafe.Pointer(key))
+		if err := tr.check(C.polaris_hip_set_option(tr.handle, key, 1)); err != nil {
+			return err
+		}
+	}
+	var c C.PolarisVarianceParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.sigma_variance = C.float(p.SigmaVariance)
+	c.min_samples = C.uint32_t(p.MinSamples)
+	return tr.check(C.polaris_hip_set_variance(tr.handle, &c))
+}
+
 // ReadFrameBuffer is what opencl.SaveFrameBuffer reads (tracer/opencl/pipeline.go:226-232).
 func (tr *Tracer) ReadFrameBuffer(pix []uint8) error {
 	if len(pix) == 0 {

@@ -34,6 +34,7 @@
 #include "scene_layout.h"
 #include "shading.h"
 #include "temporal.h"
+#include "variance.h"
 
 namespace pol {
 
@@ -1606,7 +1607,9 @@ __global__ __launch_bounds__(WG) void k_fold_nee(FoldArgs F, float4 *lsum) {
 	lsum[base + tid] = make_float4(acc[0][tid] + term.x, acc[1][tid] + term.y, acc[2][tid] + term.z, 0.0f);
 }
 
-// Batch epilogue: trace accumulator += per-path radiance, samples added in ascending order.
+// Batch epilogue: trace accumulator += per-path radiance, samples added in ascending order.  MOMENTS (tracer option "moments"):
+// acc.w += L_s^2 as well, L_s = va_lum of sample s (variance.h), in the same order; .xyz are the same either way.
+template <bool MOMENTS>
 __global__ __launch_bounds__(WG) void k_resolve(const float4 *lsum, float4 *acc, uint32_t K, uint32_t N, uint32_t Npad, uint32_t pixel0) {
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= N) return;
@@ -1614,17 +1617,20 @@ __global__ __launch_bounds__(WG) void k_resolve(const float4 *lsum, float4 *acc,
 	for (uint32_t s = 0; s < K; s++) {
 		const float4 l = lsum[(size_t)s * Npad + idx];
 		a.x += l.x; a.y += l.y; a.z += l.z;
+		if (MOMENTS) a.w += va_lum2(l.x, l.y, l.z);
 	}
 	acc[pixel0 + idx] = a;
 }
 
-// aggregateAccumulator, kernels/accumulator.cl:13-19 (rows of one block)
+// aggregateAccumulator, kernels/accumulator.cl:13-19 (rows of one block); MOMENTS: the sums of L^2 in .w too
+template <bool MOMENTS>
 __global__ __launch_bounds__(WG) void k_aggregate(const float4 *src, float4 *dst, uint32_t n) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= n) return;
 	float4 a = dst[i];
 	const float4 b = src[i];
 	a.x += b.x; a.y += b.y; a.z += b.z;
+	if (MOMENTS) a.w += b.w;
 	dst[i] = a;
 }
 
@@ -1770,9 +1776,12 @@ __global__ __launch_bounds__(WG) void k_denoise(const float4 *acc, float weight,
 // ------------------------------------------------------------------------------------------
 // PRIOR of every pixel of the frame (n = W * H): the current G-buffer (guide, albedo) under camera cur, projected into the
 // history camera hist (projectable) with its planes (hist rgb | count, hguide, halbedo).  Up to 2 + 4 x 3 float4 gathers a pixel.
+// M2 (variance guidance on): the history's VARIANCE plane hvar is gathered too, its M2 into PRIOR2 (h2 | 0 | 0 | m).
+template <bool M2>
 __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
                                                   const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
-                                                  uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior) {
+                                                  uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                  const float4 *hvar, float4 *prior2) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= W * H) return;
 	const float4 g = guide[i];
@@ -1782,10 +1791,12 @@ __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const floa
 		t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
 		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
 		t.leaf = halbedo[j].w;
+		if (M2) t.m2 = hvar[j].y;
 	};
-	float o[4];
-	tp_reproject(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o);
+	float o[4], o2[4];
+	tp_reproject<M2>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2);
 	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
+	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
 }
 
 // TEMPORAL plane over the rows [y0, y1): the frame accumulator blended with the PRIOR (n = accumulated + spp as a float,
@@ -1799,6 +1810,98 @@ __global__ __launch_bounds__(WG) void k_temporal(const float4 *acc, const float4
 	float o[4];
 	tp_combine(a, pr, n, weight, o);
 	out[i] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ------------------------------------------------------------------------------------------
+// Variance guidance (polaris_hip_set_variance).  Neither kernel touches an accumulator.  One thread per pixel, no
+// LDS; the arithmetic is variance.h's.
+// ------------------------------------------------------------------------------------------
+// The VARIANCE plane (M1 | M2 | n_eff | v) over the rows [y0, y1): the frame accumulator acc (rgb | sum L^2) with sync's n and
+// weight; with temporal reuse the mean is the TEMPORAL plane tp (else null) and prior2 (h2 | 0 | 0 | m, else null) the history's
+// M2.  `it` is dn_iter(0, ..., 0): the normal and depth terms of the spatial fallback.
+__global__ __launch_bounds__(WG) void k_variance(const float4 *acc, float n, float weight, const float4 *tp, const float4 *prior2,
+                                                 const float4 *guide, const float4 *albedo, float4 *out, uint32_t W, uint32_t y0, uint32_t y1,
+                                                 DnIter it, uint32_t min_samples) {
+	const uint32_t i = y0 * W + blockIdx.x * WG + threadIdx.x;
+	if (i >= y1 * W) return;
+	auto moments = [&](uint32_t j, float m[3]) {
+		const float4 a = acc[j];
+		float c[3];
+		if (tp) {
+			const float4 t = tp[j];
+			c[0] = t.x; c[1] = t.y; c[2] = t.z;
+		} else {
+			c[0] = a.x * weight; c[1] = a.y * weight; c[2] = a.z * weight;
+		}
+		float pm = 0.0f, h2 = 0.0f;
+		if (prior2) {
+			const float4 p = prior2[j];
+			h2 = p.x; pm = p.w;
+		}
+		va_moments(c, a.w, n, weight, pm, h2, m);
+	};
+	float mi[3];
+	moments(i, mi);
+	float v = 0.0f;
+	if (dn_filtered(albedo[i].w)) {
+		auto load = [&](uint32_t j, DnTap &t, float m[3]) -> bool {
+			if (!dn_filtered(albedo[j].w)) return false;
+			const float4 g = guide[j];
+			t.nx = g.x; t.ny = g.y; t.nz = g.z; t.t = g.w;
+			moments(j, m);
+			return true;
+		};
+		const float4 g = guide[i];
+		DnTap ci;
+		ci.nx = g.x; ci.ny = g.y; ci.nz = g.z; ci.t = g.w;
+		v = va_estimate(i % W, i / W, W, y0, y1, ci, mi, min_samples, it, load);
+	}
+	out[i] = make_float4(mi[0], mi[1], mi[2], v);
+}
+
+// One variance-guided a-trous iteration over the rows [y0, y1): k_denoise with va_step in place of dn_step (`it` has the luminance
+// term off).  r_in = null: iteration 0, the taps demodulate acc * weight and the VARIANCE plane's v on the fly; otherwise r_in holds
+// r^k | v^k.  last = 1: the DENOISED plane, remodulated rgb | the filtered variance remodulated (va_remod).  A pixel that is not
+// filtered passes c | 0 through.
+__global__ __launch_bounds__(WG) void k_denoise_variance(const float4 *acc, float weight, const float4 *var, const float4 *guide, const float4 *albedo,
+                                                         const float4 *r_in, float4 *out, uint32_t W, uint32_t y0, uint32_t y1, DnIter it,
+                                                         float sigma_v, int last) {
+	const uint32_t i = y0 * W + blockIdx.x * WG + threadIdx.x;
+	if (i >= y1 * W) return;
+	const float4 ai = albedo[i];
+	if (!dn_filtered(ai.w)) {
+		const float4 c4 = acc[i];
+		out[i] = make_float4(c4.x * weight, c4.y * weight, c4.z * weight, 0.0f);
+		return;
+	}
+	auto load = [&](uint32_t j, DnTap &t, float &v) -> bool {
+		const float4 aj = albedo[j];
+		if (!dn_filtered(aj.w)) return false;
+		const float4 g = guide[j];
+		t.nx = g.x; t.ny = g.y; t.nz = g.z; t.t = g.w;
+		if (r_in) {
+			const float4 r = r_in[j];
+			t.r = r.x; t.g = r.y; t.b = r.z;
+			v = r.w;
+		} else {
+			const float4 c = acc[j];
+			t.r = (c.x * weight) / dn_demod_albedo(aj.x); t.g = (c.y * weight) / dn_demod_albedo(aj.y); t.b = (c.z * weight) / dn_demod_albedo(aj.z);
+			const float a3[3] = {aj.x, aj.y, aj.z};
+			v = va_demod(var[j].w, a3);
+		}
+		return true;
+	};
+	DnTap ci;
+	float vi;
+	(void)load(i, ci, vi);
+	float r[4];
+	va_step(i % W, i / W, W, y0, y1, ci, vi, it, sigma_v, load, r);
+	if (last) {
+		const float a3[3] = {ai.x, ai.y, ai.z};
+		out[i] = make_float4(r[0] * dn_demod_albedo(ai.x), r[1] * dn_demod_albedo(ai.y), r[2] * dn_demod_albedo(ai.z), va_remod(r[3], a3));
+	} else {
+		out[i] = make_float4(r[0], r[1], r[2], r[3]);
+	}
 }
 
 } // namespace pol

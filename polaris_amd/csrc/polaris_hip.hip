@@ -131,6 +131,19 @@ struct polaris_hip_tracer {
 	bool tp_synced = false;      // a temporal sync ran under the current camera (tp_out and the G-buffer are this camera's)
 	bool tp_prior_valid = false; // tp_prior is the current history reprojected into the current camera with the current params
 
+	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
+	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
+	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
+	// set_camera swaps va_out <-> va_hist like the TEMPORAL plane, and k_reproject<true> gathers the history's M2 into tp_prior2
+	// (h2 | 0 | 0 | m); both go with free_temporal.
+	std::atomic<bool> opt_moments{false};
+	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
+	float4 *va_out = nullptr;                     // VARIANCE plane (M1 | M2 | n_eff | v)
+	bool va_valid = false;                        // a variance sync has written va_out (under the current camera with temporal reuse)
+	float4 *va_hist = nullptr, *tp_prior2 = nullptr;
+	bool va_synced = false;   // temporal: a variance sync ran under the current camera (va_out is this camera's, cleared at its first sync)
+	bool va_have_hist = false; // temporal: va_hist belongs to the history
+
 	// wavefront batch state: up to kMaxPipes pipelines (option "overlap", default 4; a Trace uses min(overlap, #batches) of
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
 	// bounces of batch i+1 on another stream
@@ -408,11 +421,18 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
 
 void free_temporal(polaris_hip_tracer *h) { // caller holds mu, every stream idle
-	for (float4 **p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo}) {
+	for (float4 **p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo, &h->va_hist, &h->tp_prior2}) {
 		if (*p) (void)hipFree(*p);
 		*p = nullptr;
 	}
 	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
+	h->va_synced = h->va_have_hist = false;
+}
+
+void free_variance(polaris_hip_tracer *h) { // caller holds mu, every stream idle
+	if (h->va_out) (void)hipFree(h->va_out);
+	h->va_out = nullptr;
+	h->va_valid = false;
 }
 
 void free_denoise(polaris_hip_tracer *h) { // caller holds mu, every stream idle
@@ -661,7 +681,8 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 		// batches resolve into the trace accumulator in sample order: wait for the previous batch's resolve
 		if (resolve_after) note(hipStreamWaitEvent(q, resolve_after, 0));
 		Timed t(h, "resolve", q);
-		hipLaunchKernelGGL(k_resolve, dim3(grid_for(N)), dim3(WG), 0, q, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W);
+		if (h->opt_moments) hipLaunchKernelGGL(k_resolve<true>, dim3(grid_for(N)), dim3(WG), 0, q, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W);
+		else hipLaunchKernelGGL(k_resolve<false>, dim3(grid_for(N)), dim3(WG), 0, q, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W);
 	}
 	note(hipEventRecord(P.done, q));
 	note(hipGetLastError()); // (launches through hipLaunchKernelGGL report here)
@@ -787,6 +808,7 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 		free_ring(h);
 		free_denoise(h);
 		free_temporal(h);
+		free_variance(h);
 		for (auto &e : h->ev_ipc_done)
 			if (e) { (void)hipEventDestroy(e); e = nullptr; }
 		{
@@ -836,6 +858,7 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	free_ring(h); // (an IPC export dies with the buffers: peers close, the tracer exports again)
 	free_denoise(h);
 	if (h->tp.max_history) free_temporal(h);
+	if (h->va.sigma_variance != 0.0f) free_variance(h);
 	if (h->frame_acc) (void)hipFree(h->frame_acc);
 	if (h->framebuffer) (void)hipFree(h->framebuffer);
 	h->frame_acc = nullptr;
@@ -875,7 +898,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	free_pool(h->scene_bufs);
 	h->have_scene = false;
 	h->gb_valid = false;
-	if (h->tp.max_history) h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false; // (the history saw the old scene)
+	if (h->tp.max_history) h->tp_have_hist = h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_have_hist = h->va_valid = false; // (the history saw the old scene)
 	int rc = 0;
 	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
 	rc |= dev_upload(h, h->scene_bufs, &pairs, L.pairs.data(), L.pairs.size());
@@ -983,8 +1006,11 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 			std::swap(h->gb_albedo, h->tp_halbedo);
 			h->tp_hcam = h->cam;
 			h->tp_have_hist = true;
+			// (the VARIANCE plane joins the history only if it was written under the same camera; else the history has no M2)
+			if (h->va_synced) std::swap(h->va_out, h->va_hist);
+			h->va_have_hist = h->va_synced;
 		}
-		h->tp_synced = h->tp_prior_valid = false;
+		h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
 	}
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
 	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
@@ -1006,7 +1032,14 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	if (!key) return fail(h, POLARIS_E_BAD_ARGUMENT, "option key is null");
 	const std::string k(key);
 	if (k == "samples_per_batch") h->opt_samples_per_batch = value < 0 ? 0 : value;
-	else if (k == "exact_accumulate") h->opt_exact = value != 0;
+	else if (k == "exact_accumulate") {
+		if (value != 0 && h->opt_moments) return fail(h, POLARIS_E_UNSUPPORTED, "exact_accumulate has no per-sample radiance: it cannot be combined with moments");
+		h->opt_exact = value != 0;
+	} else if (k == "moments") {
+		if (value != 0 && h->opt_exact) return fail(h, POLARIS_E_UNSUPPORTED, "moments need per-sample radiance: exact_accumulate cannot keep them");
+		if (value == 0 && h->va.sigma_variance != 0.0f) return fail(h, POLARIS_E_BAD_ARGUMENT, "moments cannot be turned off while variance guidance is on");
+		h->opt_moments = value != 0;
+	}
 	else if (k == "packet_primary") { h->opt_packet_primary = value < 0 ? -1 : (value != 0); if (value >= 0) h->packet_primary = value != 0; }
 	else if (k == "packet_shadow") h->opt_packet_shadow = (int)std::max<int64_t>(0, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
 	else if (k == "time_kernels") h->opt_time_kernels = value != 0;
@@ -1274,7 +1307,8 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 	}
 	{
 		Timed t(dst, "aggregate", q, true);
-		hipLaunchKernelGGL(k_aggregate, dim3(grid_for(n)), dim3(WG), 0, q, rows, dst->frame_acc + off, (uint32_t)n);
+		if (dst->opt_moments) hipLaunchKernelGGL(k_aggregate<true>, dim3(grid_for(n)), dim3(WG), 0, q, rows, dst->frame_acc + off, (uint32_t)n);
+		else hipLaunchKernelGGL(k_aggregate<false>, dim3(grid_for(n)), dim3(WG), 0, q, rows, dst->frame_acc + off, (uint32_t)n);
 	}
 	if (hipGetLastError() != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: kernel launch failed");
 	dst->merge_counts[branch]++;
@@ -1522,8 +1556,12 @@ int polaris_hip_merge_device(polaris_hip_tracer *dst, const void *device_rows, c
 	HIP_TRY(dst, hipSetDevice(dst->device));
 	const size_t off = (size_t)r->block_y * dst->W, n = (size_t)r->block_h * dst->W;
 	std::lock_guard<std::mutex> lk_merge(dst->merge_mu); // the frame accumulator is the merge stream's
-	hipLaunchKernelGGL(k_aggregate, dim3(grid_for(n)), dim3(WG), 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off,
-	                   (uint32_t)n);
+	if (dst->opt_moments)
+		hipLaunchKernelGGL(k_aggregate<true>, dim3(grid_for(n)), dim3(WG), 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off,
+		                   (uint32_t)n);
+	else
+		hipLaunchKernelGGL(k_aggregate<false>, dim3(grid_for(n)), dim3(WG), 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off,
+		                   (uint32_t)n);
 	HIP_TRY(dst, hipGetLastError());
 	dst->merge_counts[POLARIS_MERGE_DEVICE_STRIP]++;
 	HIP_TRY(dst, hipStreamSynchronize(dst->merge_stream)); // the caller owns device_rows: do not outlive it
@@ -1622,16 +1660,94 @@ TpCamera tp_camera(const float eye[3], const float fr[16]) {
 // The PRIOR plane of a W x H frame on stream q (caller holds mu): the history (hist, hguide, halbedo under hcam; hist = null: none)
 // reprojected onto the G-buffer (guide, albedo) under cam.  polaris_hip_sync_framebuffer and polaris_hip_reproject_planes both
 // launch it through here.
+// prior2 != null (variance guidance on): PRIOR2 too, from the history's VARIANCE plane hvar (null: the history has no M2, PRIOR2 = 0).
 hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *hist, const float4 *hguide, const float4 *halbedo, const TpCamera &hcam,
                       const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
-                      float4 *prior) {
+                      float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr) {
 	const size_t F = (size_t)W * H;
 	Timed t(h, "reproject", q);
+	if (prior2 && (!hist || !hvar || !tp_projectable(hcam) || p.max_history == 0)) {
+		if (hipError_t e = hipMemsetAsync(prior2, 0, F * sizeof(float4), q)) return e;
+		prior2 = nullptr; // (the PRIOR as without variance guidance)
+	}
 	if (!hist || !tp_projectable(hcam) || p.max_history == 0) return hipMemsetAsync(prior, 0, F * sizeof(float4), q); // no history anywhere: m = 0
-	if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject";
-	hipLaunchKernelGGL(k_reproject, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
-	                   p.normal_threshold, p.depth_threshold, prior);
+	if (prior2) {
+		if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject<true>";
+		hipLaunchKernelGGL(k_reproject<true>, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
+		                   p.normal_threshold, p.depth_threshold, prior, hvar, prior2);
+	} else {
+		if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject<false>";
+		hipLaunchKernelGGL(k_reproject<false>, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
+		                   p.normal_threshold, p.depth_threshold, prior, (const float4 *)nullptr, (float4 *)nullptr);
+	}
 	return hipGetLastError();
+}
+
+// The variance launches of a sync on stream q (caller holds mu): k_variance over the rows [y0, y1) into var (the frame accumulator acc
+// with sync's n and weight; with temporal reuse the TEMPORAL plane tp and PRIOR2 prior2, else both null), then, with p.iterations > 0,
+// the variance-guided filter through ping / pong into out and out's rows tone-mapped with weight 1; with p.iterations = 0 the tone-map
+// of the plain (or temporal) sync, unchanged.  polaris_hip_sync_framebuffer and polaris_hip_variance_planes both launch through here.
+void launch_variance(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, float nf, float weight, const float4 *tp, const float4 *prior2,
+                     const float4 *guide, const float4 *albedo, float4 *var, float4 *ping, float4 *pong, float4 *out, uchar4 *fb, uint32_t W,
+                     uint32_t y0, uint32_t y1, float exposure, const PolarisDenoiseParams &p, const PolarisVarianceParams &v) {
+	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
+	{
+		Timed t(h, "variance", q);
+		if (h->opt_time_kernels) h->timer_symbol["variance"] = "pol::k_variance";
+		const DnIter it0 = dn_iter(0, p.normal_power_log2, p.sigma_depth, 0.0f);
+		hipLaunchKernelGGL(k_variance, dim3(grid_for(n)), dim3(WG), 0, q, acc, nf, weight, tp, prior2, guide, albedo, var, W, y0, y1, it0, v.min_samples);
+	}
+	const float4 *c = tp ? tp : acc; // (the filter's and the tone-map's input: TEMPORAL with weight 1, or the accumulator)
+	const float cw = tp ? 1.0f : weight;
+	if (p.iterations == 0) {
+		Timed t(h, "tonemap", q);
+		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, c + off, fb + off, (uint32_t)n, cw, exposure);
+		return;
+	}
+	{
+		Timed t(h, "denoise_variance", q);
+		if (h->opt_time_kernels) h->timer_symbol["denoise_variance"] = "pol::k_denoise_variance";
+		const uint32_t K = p.iterations;
+		const float4 *in = nullptr;
+		for (uint32_t k = 0; k < K; k++) {
+			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
+			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, 0.0f);
+			hipLaunchKernelGGL(k_denoise_variance, dim3(grid_for(n)), dim3(WG), 0, q, c, cw, (const float4 *)var, guide, albedo, in, dst, W, y0, y1, it,
+			                   v.sigma_variance, k + 1 == K ? 1 : 0);
+			in = dst;
+		}
+	}
+	{
+		Timed t(h, "tonemap", q);
+		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
+	}
+}
+
+// polaris_hip_sync_framebuffer with variance guidance on and temporal reuse off (caller holds mu; request checked): G-buffer if
+// stale, then launch_variance over the request's rows.
+int sync_variance(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
+	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "variance guidance needs the camera (UpdateState CameraData)");
+	const size_t F = (size_t)h->W * h->H;
+	if (int rc = ensure_gbuffer(h)) return rc;
+	if (!h->va_out) {
+		HIP_TRY(h, hipMalloc((void **)&h->va_out, F * sizeof(float4)));
+		HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream));
+	}
+	if (h->dn.iterations) {
+		if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
+		if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
+		if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
+	}
+	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
+	const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
+	launch_variance(h, h->stream, h->frame_acc, nf, weight, nullptr, nullptr, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong, h->dn_out,
+	                h->framebuffer, h->W, r->block_y, r->block_y + r->block_h, r->exposure, h->dn, h->va);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	h->va_valid = true;
+	if (h->dn.iterations) h->dn_valid = true;
+	collect_timers(h);
+	return POLARIS_OK;
 }
 
 // polaris_hip_sync_framebuffer with temporal reuse on (caller holds mu; request checked): G-buffer if stale, TEMPORAL cleared at
@@ -1649,11 +1765,19 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 		if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
 		if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
 	}
+	const bool var = h->va.sigma_variance != 0.0f;
+	if (var) {
+		if (!h->va_out) HIP_TRY(h, hipMalloc((void **)&h->va_out, F * sizeof(float4)));
+		if (!h->tp_prior2) HIP_TRY(h, hipMalloc((void **)&h->tp_prior2, F * sizeof(float4)));
+		if (!h->va_synced) HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream)); // (as TEMPORAL: rows no sync reaches)
+		h->va_synced = true;
+	}
 	if (!h->tp_synced) HIP_TRY(h, hipMemsetAsync(h->tp_out, 0, F * sizeof(float4), h->stream)); // (rows no sync reaches: no history)
 	h->tp_synced = true;
 	if (!h->tp_prior_valid) {
 		HIP_TRY(h, launch_reproject(h, h->stream, h->tp_have_hist ? h->tp_hist : nullptr, h->tp_hguide, h->tp_halbedo, tp_camera(h->tp_hcam),
-		                            h->gb_guide, h->gb_albedo, tp_camera(h->cam), h->W, h->H, h->tp, h->tp_prior));
+		                            h->gb_guide, h->gb_albedo, tp_camera(h->cam), h->W, h->H, h->tp, h->tp_prior,
+		                            var && h->va_have_hist ? h->va_hist : nullptr, var ? h->tp_prior2 : nullptr));
 		h->tp_prior_valid = true;
 	}
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
@@ -1663,7 +1787,11 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 		const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
 		hipLaunchKernelGGL(k_temporal, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc, h->tp_prior, h->tp_out, h->W, y0, y1, nf, weight);
 	}
-	if (h->dn.iterations) {
+	if (var) {
+		const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
+		launch_variance(h, h->stream, h->frame_acc, nf, weight, h->tp_out, h->tp_prior2, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong,
+		                h->dn_out, h->framebuffer, h->W, y0, y1, r->exposure, h->dn, h->va);
+	} else if (h->dn.iterations) {
 		launch_denoise(h, h->stream, h->tp_out, 1.0f, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W, y0, y1,
 		               r->exposure, h->dn);
 	} else {
@@ -1674,6 +1802,7 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	if (h->dn.iterations) h->dn_valid = true;
+	if (var) h->va_valid = true;
 	collect_timers(h);
 	return POLARIS_OK;
 }
@@ -1716,12 +1845,37 @@ int polaris_hip_set_temporal(polaris_hip_tracer *h, const PolarisTemporalParams 
 	return POLARIS_OK;
 }
 
+int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisVarianceParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_variance: null params or struct_size != %zu", sizeof(PolarisVarianceParams));
+	if (va_check(p->sigma_variance, p->min_samples))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_variance: sigma_variance %g (0 or [%g, %g]), min_samples %u (1..%u)", (double)p->sigma_variance,
+		            (double)kDnSigmaMin, (double)kDnSigmaMax, p->min_samples, kVaMaxMinSamples);
+	const bool on = p->sigma_variance != 0.0f, was = h->va.sigma_variance != 0.0f;
+	if (on && !h->opt_moments) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_variance: variance guidance needs the option moments = 1 first");
+	if (!on && was) {
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every variance launch is on the main stream)
+		free_variance(h);
+		for (float4 **q : {&h->va_hist, &h->tp_prior2}) {
+			if (*q) (void)hipFree(*q);
+			*q = nullptr;
+		}
+		h->va_synced = h->va_have_hist = false;
+	}
+	if (on != was) h->tp_prior_valid = false; // (PRIOR2 is written, or no longer, by the next temporal sync's reprojection)
+	h->va = *p;
+	return POLARIS_OK;
+}
+
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	const size_t need = (size_t)h->W * h->H * 4;
-	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_PRIOR)
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2,3,4}", need);
+	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_PRIOR2)
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2,3,4,5,6}", need);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const float4 *src;
 	if (which == POLARIS_AOV_DENOISED) {
@@ -1730,6 +1884,12 @@ int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_
 	} else if (which == POLARIS_AOV_TEMPORAL || which == POLARIS_AOV_PRIOR) {
 		if (!h->tp_synced || !h->tp_prior_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no temporal sync under the current camera");
 		src = which == POLARIS_AOV_TEMPORAL ? h->tp_out : h->tp_prior;
+	} else if (which == POLARIS_AOV_VARIANCE) {
+		if (!h->va_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no variance sync%s", h->tp.max_history ? " under the current camera" : " since the last resize");
+		src = h->va_out;
+	} else if (which == POLARIS_AOV_PRIOR2) {
+		if (!h->va_valid || !h->tp.max_history || !h->tp_prior2) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no variance sync with temporal reuse under the current camera");
+		src = h->tp_prior2;
 	} else {
 		if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
@@ -1751,6 +1911,7 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
 	if (h->tp.max_history) return sync_temporal(h, r, weight);
+	if (h->va.sigma_variance != 0.0f) return sync_variance(h, r, weight);
 	if (h->dn.iterations) return sync_denoised(h, r, weight);
 	HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
 	{
@@ -2011,6 +2172,47 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
 	(void)hipFree(d);
 	if (e == hipSuccess) e = e2;
 	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "denoise_planes: %s", hipGetErrorString(e));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
+                                uint32_t block_y, uint32_t block_h, uint32_t samples, float exposure, const PolarisDenoiseParams *p,
+                                const PolarisVarianceParams *v, float *variance, float *denoised, uint8_t *rgba) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!acc || !guide || !albedo || !variance || !denoised || !rgba || !p || !v || p->struct_size != sizeof(PolarisDenoiseParams) ||
+	    v->struct_size != sizeof(PolarisVarianceParams) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H ||
+	    block_h > H - block_y || samples == 0 || dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance) ||
+	    v->sigma_variance == 0.0f || va_check(v->sigma_variance, v->min_samples))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "variance_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), samples %u (> 0), or "
+		            "params (sigma_variance [%g, %g], min_samples 1..%u)", W, H, block_y, block_h, samples, (double)kDnSigmaMin, (double)kDnSigmaMax,
+		            kVaMaxMinSamples);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
+	char *d = nullptr;
+	HIP_TRY(h, hipMalloc((void **)&d, 7 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
+	float4 *d_acc = (float4 *)d, *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_var = d_albedo + F, *d_ping = d_var + F, *d_pong = d_ping + F,
+	       *d_out = d_pong + F;
+	uchar4 *d_fb = (uchar4 *)(d_out + F);
+	hipError_t e = hipSuccess;
+	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_var, variance}, {d_out, denoised}};
+	for (const auto &c : in)
+		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) {
+		const float weight = (float)(1.0 / (float)samples); // (polaris_hip_sync_framebuffer's)
+		launch_variance(h, h->stream, d_acc, (float)samples, weight, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y,
+		                block_y + block_h, exposure, *p, *v);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(variance, d_var, plane, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream);
+	const hipError_t e2 = hipStreamSynchronize(h->stream);
+	(void)hipFree(d);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "variance_planes: %s", hipGetErrorString(e));
 	collect_timers(h);
 	return POLARIS_OK;
 }

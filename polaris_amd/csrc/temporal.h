@@ -74,8 +74,8 @@ PM_HD bool tp_project(const TpCamera &c, const float p[3], float &u, float &v, f
 	return true;
 }
 
-// One history tap as k_reproject gathers it.
-struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; };
+// One history tap as k_reproject gathers it (m2: the history's M2, gathered only by k_reproject<true>, variance.h).
+struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; float m2; };
 
 // The tap test: a history count > 0, finite history rgb, the same leaf word as pixel i, n_i . n_j >= normal_threshold and
 // |t_j - dist| <= depth_threshold * dist.
@@ -91,11 +91,14 @@ PM_HD bool tp_tap_ok(const TpTap &j, float leaf_i, float nx, float ny, float nz,
 // The PRIOR of pixel (gx, gy) of a W x H frame: guide_i / leaf_i of the current G-buffer, cur / hist the cameras (hist
 // projectable), load(j, tap) fills history tap j (row-major index).  out = h rgb | m; m = 0 (and h = 0) without history.
 // The taps are the 2 x 2 around (u W - 0.5, v H - 0.5) in the order (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1);
-// their bilinear weights are renormalised over the valid ones.
-template <class Load>
+// their bilinear weights are renormalised over the valid ones.  M2 (variance guidance with temporal reuse): the taps' m2 are
+// blended with the same weights into out2 = h2 | 0 | 0 | m (all 0 without history); M2 = false leaves out2 alone.
+template <bool M2 = false, class Load>
 PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const TpCamera &cur,
-                        const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4]) {
+                        const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4],
+                        float *out2 = nullptr) {
 	out[0] = out[1] = out[2] = out[3] = 0.0f;
+	if (M2) out2[0] = out2[1] = out2[2] = out2[3] = 0.0f;
 	if (!dn_filtered(leaf_i)) return;
 	float d[3];
 	tp_centre_ray(cur.tl, cur.tr, cur.bl, cur.br, gx, gy, 1.0f / (float)W, 1.0f / (float)H, d);
@@ -108,7 +111,7 @@ PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const 
 	const float fx0 = pm_floor(x), fy0 = pm_floor(y);
 	const float fx = x - fx0, fy = y - fy0;
 	const int x0 = (int)fx0, y0 = (int)fy0;
-	float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hc = 0.0f;
+	float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hc = 0.0f, h2 = 0.0f;
 	for (int k = 0; k < 4; k++) {
 		const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
 		if (xx < 0 || xx >= (int)W || yy < 0 || yy >= (int)H) continue;
@@ -121,6 +124,7 @@ PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const 
 		hg += w * j.g;
 		hb += w * j.b;
 		hc += w * j.count;
+		if (M2) h2 += w * j.m2;
 	}
 	if (!(sw > 0.0f)) return;
 	const float m = pm_min(hc / sw, (float)max_history);
@@ -129,6 +133,10 @@ PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const 
 	out[1] = hg / sw;
 	out[2] = hb / sw;
 	out[3] = m;
+	if (M2) {
+		out2[0] = h2 / sw;
+		out2[3] = m;
+	}
 }
 
 // The TEMPORAL pixel from the frame accumulator's a[4], the PRIOR's pr[4], n = accumulated_samples + samples_per_pixel as a float

@@ -155,7 +155,7 @@ class DenoiseParams(C.Structure):
 assert C.sizeof(DenoiseParams) == 20
 # the settings DESIGN.md section 10 chose on the CPU restatement (include/polaris_hip.h)
 DENOISE_DEFAULTS = {"iterations": 4, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_luminance": 4.0}
-AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED, AOV_TEMPORAL, AOV_PRIOR = 0, 1, 2, 3, 4
+AOV_GUIDE, AOV_ALBEDO, AOV_DENOISED, AOV_TEMPORAL, AOV_PRIOR, AOV_VARIANCE, AOV_PRIOR2 = 0, 1, 2, 3, 4, 5, 6
 
 
 class TemporalParams(C.Structure):
@@ -176,6 +176,26 @@ def temporal_params(max_history=32, normal_threshold=0.9, depth_threshold=0.1) -
     p = TemporalParams()
     p.max_history = int(max_history)
     p.normal_threshold, p.depth_threshold = float(normal_threshold), float(depth_threshold)
+    return p
+
+
+class VarianceParams(C.Structure):
+    """PolarisVarianceParams (include/polaris_hip.h): variance-guided denoising from per-pixel luminance moments."""
+    _fields_ = [("struct_size", C.c_uint32), ("sigma_variance", C.c_float), ("min_samples", C.c_uint32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(VarianceParams) == 12
+# the settings DESIGN.md section 10c chose on the CPU restatement (profiles/variance_quality.txt)
+VARIANCE_DEFAULTS = {"sigma_variance": 8.0, "min_samples": 8}
+
+
+def variance_params(sigma_variance=8.0, min_samples=8) -> VarianceParams:
+    p = VarianceParams()
+    p.sigma_variance, p.min_samples = float(sigma_variance), int(min_samples)
     return p
 
 # polaris_hip_selftest_builtins / polaris_oracle_builtins: the probed built-ins (enum PbFn, polaris_amd/csrc/builtin_probe.h)
@@ -275,7 +295,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_trace_slot", "polaris_hip_merge_slot", "polaris_hip_build_bvh", "polaris_hip_build_bvh_error",
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
-    "polaris_hip_set_temporal", "polaris_hip_reproject_planes",
+    "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
 ]
 
 _lib = None
@@ -376,6 +396,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_selftest_builtins.argtypes = [vp, u32, C.c_uint64, C.c_uint64, vp, vp]
     lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
     lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
+    lib.polaris_hip_set_variance.argtypes = [vp, C.POINTER(VarianceParams)]
+    lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),
+                                                C.POINTER(VarianceParams), vp, vp, vp]
     lib.polaris_hip_reproject_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(TemporalParams), vp]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)

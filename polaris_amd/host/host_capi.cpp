@@ -146,6 +146,17 @@ int polaris_host_renderer_set_temporal(void *h, const PolarisTemporalParams *p) 
 		if (int rc = polaris_hip_set_temporal(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// Variance guidance (polaris_hip_set_variance) on every tracer: the option "moments" on every tracer first (every block's
+// accumulator and every merge then carry the sums of L^2), then the params; turning it off leaves "moments" as it is.
+int polaris_host_renderer_set_variance(void *h, const PolarisVarianceParams *p) {
+	auto *box = static_cast<RendererBox *>(h);
+	if (p && p->sigma_variance != 0.0f)
+		for (auto *t : box->hips)
+			if (int rc = polaris_hip_set_option(t->Handle(), "moments", 1)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	for (auto *t : box->hips)
+		if (int rc = polaris_hip_set_variance(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	return 0;
+}
 // A camera move: the CameraData of every tracer, as the interactive renderer's UpdateState (renderer/opengl.go:294-301).
 int polaris_host_renderer_set_camera(void *h, const float eye[3], const float frustum[16]) {
 	auto *box = static_cast<RendererBox *>(h);

@@ -37,6 +37,12 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
         lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
+        lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
+        u32 = C.c_uint32
+        lib.polaris_host_variance.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams), C.POINTER(T.VarianceParams), vp]
+        lib.polaris_host_denoise_variance.argtypes = [vp, C.c_float, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams),
+                                                      C.POINTER(T.VarianceParams), vp]
+        lib.polaris_host_reproject_moments.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(T.TemporalParams), vp, vp]
         lib.polaris_host_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(T.TemporalParams), vp]
         lib.polaris_host_temporal_combine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         lib.polaris_host_camera_move.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.c_uint32, vp, vp, vp]
@@ -144,6 +150,12 @@ class Renderer:
         p = T.temporal_params(max_history, normal_threshold, depth_threshold)
         if self._lib.polaris_host_renderer_set_temporal(self._h, C.byref(p)):
             raise RuntimeError(f"set_temporal failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
+        """polaris_hip_set_variance on every tracer, after the option "moments" on every tracer (polaris_host_renderer_set_variance)."""
+        p = T.variance_params(sigma_variance, min_samples)
+        if self._lib.polaris_host_renderer_set_variance(self._h, C.byref(p)):
+            raise RuntimeError(f"set_variance failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
     def set_camera(self, eye, frustum) -> None:
         """A camera move: UpdateState(CameraData) on every tracer (DefaultRenderer::UpdateAll)."""
@@ -263,6 +275,70 @@ def temporal_combine(frame_acc, prior, accumulated_samples: int, samples_per_pix
     if rc:
         raise ValueError(f"temporal_combine: bad arguments (code {rc})")
     return res
+
+
+def _planes(name, *planes):
+    out = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+    H, W = out[0].shape[:2]
+    if any(a.shape != (H, W, 4) for a in out):
+        raise ValueError(f"{name}: the planes must be (H, W, 4) float32 of one size")
+    return out, H, W
+
+
+def variance(frame_acc, samples: int, guide, albedo, *, temporal=None, prior2=None, block_y: int = 0, block_h: int | None = None, out=None,
+             normal_power_log2: int = 5, sigma_depth: float = 0.1, sigma_variance: float = 8.0, min_samples: int = 8) -> np.ndarray:
+    """polaris_host_variance: the CPU restatement of k_variance (polaris_amd/host/variance.cpp).  frame_acc (rgb | sum L^2 of `samples`
+    samples), guide and albedo are (H, W, 4) float32; with temporal reuse the TEMPORAL plane and PRIOR2 are given too.  Returns the
+    VARIANCE plane (M1 | M2 | n_eff | v) -- `out` (a copy of it) with the request's rows written.  ValueError where refused."""
+    (acc, g, a), H, W = _planes("variance", frame_acc, guide, albedo)
+    tp = p2 = None
+    if temporal is not None or prior2 is not None:
+        (tp, p2), _, _ = _planes("variance", temporal, prior2)
+        if tp.shape != acc.shape:
+            raise ValueError("variance: temporal / prior2 must be (H, W, 4) like frame_acc")
+    res = np.zeros_like(acc) if out is None else np.array(out, dtype=np.float32, copy=True)
+    bh = H - block_y if block_h is None else block_h
+    p = T.denoise_params(1, normal_power_log2, sigma_depth, 0.0)
+    v = T.variance_params(sigma_variance, min_samples)
+    rc = load().polaris_host_variance(acc.ctypes.data, int(samples), None if tp is None else tp.ctypes.data, None if p2 is None else p2.ctypes.data,
+                                      g.ctypes.data, a.ctypes.data, W, H, int(block_y), int(bh), C.byref(p), C.byref(v), res.ctypes.data)
+    if rc:
+        raise ValueError(f"variance: bad arguments (code {rc})")
+    return res
+
+
+def denoise_variance(acc, weight: float, variance_plane, guide, albedo, *, block_y: int = 0, block_h: int | None = None, out=None,
+                     iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1, sigma_variance: float = 8.0,
+                     min_samples: int = 8) -> np.ndarray:
+    """polaris_host_denoise_variance: the CPU restatement of the variance-guided filter (polaris_amd/host/variance.cpp) over acc *
+    weight with the VARIANCE plane.  Returns the DENOISED plane (rgb | filtered variance) -- `out` (a copy) with the request's rows
+    written.  ValueError where refused."""
+    (c, vp, g, a), H, W = _planes("denoise_variance", acc, variance_plane, guide, albedo)
+    res = np.zeros_like(c) if out is None else np.array(out, dtype=np.float32, copy=True)
+    bh = H - block_y if block_h is None else block_h
+    p = T.denoise_params(iterations, normal_power_log2, sigma_depth, 0.0)
+    v = T.variance_params(sigma_variance, min_samples)
+    rc = load().polaris_host_denoise_variance(c.ctypes.data, float(weight), vp.ctypes.data, g.ctypes.data, a.ctypes.data, W, H, int(block_y),
+                                              int(bh), C.byref(p), C.byref(v), res.ctypes.data)
+    if rc:
+        raise ValueError(f"denoise_variance: bad arguments (code {rc})")
+    return res
+
+
+def reproject_moments(history, hvar, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *, max_history: int = 32,
+                      normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
+    """polaris_host_reproject_moments: reproject() plus the history VARIANCE plane's M2 -- returns (PRIOR, PRIOR2 = h2 | 0 | 0 | m)."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    (hist, hv, pg, pa, g, a), H, W = _planes("reproject_moments", history, hvar, prev_guide, prev_albedo, guide, albedo)
+    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+    prior, prior2 = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+    rc = load().polaris_host_reproject_moments(hist.ctypes.data, hv.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data,
+                                               g.ctypes.data, a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p), prior.ctypes.data,
+                                               prior2.ctypes.data)
+    if rc:
+        raise ValueError(f"reproject_moments: bad arguments (code {rc})")
+    return prior, prior2
 
 
 CAMERA_MOVES = {"up": 0, "down": 1, "left": 2, "right": 3, "forward": 4, "backward": 5}   # scene.CameraDirection (camera.go:12-19)

@@ -14,7 +14,11 @@ formulas of the reference's debug kernels, tracer/opencl/CL/kernels/debug.cl) an
 --frames N --move DIR:OFFSET renders N frames, each one render(accumulated=0) after a camera move (scene.Camera.Move, camera.go:76-97,
 DIR one of left, right, up, down, forward, backward), written as <out stem>_000.png, _001.png, ...: what the interactive renderer
 does while the user moves.  --temporal M reuses the last view's mean across the moves with max_history M (polaris_hip_set_temporal,
-the thresholds at their defaults)."""
+the thresholds at their defaults).
+
+--variance SIGMA guides the filter by each pixel's variance (polaris_hip_set_variance with sigma_variance SIGMA, min_samples at its
+default, the option moments on every tracer; 0 = off); with --aov-dir the VARIANCE plane (M1 | M2 | n_eff | v) is also written as
+variance.npy."""
 import argparse
 import os
 import sys
@@ -85,6 +89,7 @@ def main(argv=None):
     ap.add_argument("--devices", default="0", help="comma separated HIP device indices (a device may repeat)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--denoise", type=int, default=0, help="a-trous filter iterations at the frame sync (0 = off)")
+    ap.add_argument("--variance", type=float, default=0.0, help="sigma_variance of variance-guided denoising (0 = off)")
     ap.add_argument("--aov-dir", default=None, help="write normals.png, depth.png and albedo.png of the first-hit G-buffer here")
     ap.add_argument("--temporal", type=int, default=0, help="max_history of temporal reuse across camera moves (0 = off)")
     ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
@@ -107,6 +112,8 @@ def main(argv=None):
             r.set_denoise(iterations=a.denoise)
         if a.temporal:
             r.set_temporal(max_history=a.temporal)
+        if a.variance:
+            r.set_variance(sigma_variance=a.variance, min_samples=T.VARIANCE_DEFAULTS["min_samples"])
         if a.frames:
             for path, (rows, ms) in zip(frame_paths(a.out, a.frames), move_frames(r, sc, a.frames, a.move, a.width / a.height)):
                 r.save(path)
@@ -118,6 +125,8 @@ def main(argv=None):
             imgs = aov_images(r.read_aov(T.AOV_GUIDE), r.read_aov(T.AOV_ALBEDO))
             for name, img in imgs.items():
                 host_api.write_png(os.path.join(a.aov_dir, name + ".png"), img)
+            if a.variance:
+                np.save(os.path.join(a.aov_dir, "variance.npy"), r.read_aov(T.AOV_VARIANCE))
     finally:
         r.close()
     print(f"{a.scene}: {sc.vertices.shape[0] // 3} triangles, {len(sc.mesh_instances)} instances, {len(sc.material_nodes)} material nodes; "

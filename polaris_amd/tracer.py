@@ -158,9 +158,18 @@ class HipTracer:
         p = T.temporal_params(max_history, normal_threshold, depth_threshold)
         self._check(self._lib.polaris_hip_set_temporal(self._h, C.byref(p)), self._h)
 
+    def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
+        """Variance-guided denoising at every SyncFramebuffer (polaris_hip_set_variance): turns the option "moments" on first, then
+        sets the params; sigma_variance = 0 turns guidance off (the default) and leaves "moments" as it is."""
+        if sigma_variance != 0:
+            self.set_option("moments", 1)
+        p = T.variance_params(sigma_variance, min_samples)
+        self._check(self._lib.polaris_hip_set_variance(self._h, C.byref(p)), self._h)
+
     def read_aov(self, which: int) -> np.ndarray:
         """(H, W, 4) float32 plane of the denoiser: T.AOV_GUIDE (normal | hit distance), T.AOV_ALBEDO (albedo | leaf type bits)
-        or T.AOV_DENOISED (the filtered running mean of the last denoised sync)."""
+        or T.AOV_DENOISED (the filtered running mean of the last denoised sync); T.AOV_TEMPORAL / T.AOV_PRIOR (temporal reuse),
+        T.AOV_VARIANCE (M1 | M2 | n_eff | v) and T.AOV_PRIOR2 (variance guidance)."""
         self._commit()
         out = np.zeros((self._H, self._W, 4), dtype=np.float32)
         self._check(self._lib.polaris_hip_read_aov(self._h, int(which), out.ctypes.data, out.size), self._h)
@@ -237,6 +246,25 @@ class HipTracer:
                                                          int(bh), float(weight), float(exposure), C.byref(p), out.ctypes.data,
                                                          fb.ctypes.data), self._h)
         return out, fb
+
+    def variance_planes(self, acc, guide, albedo, *, samples: int, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None,
+                        variance=None, denoised=None, rgba=None, iterations: int = 4, normal_power_log2: int = 5, sigma_depth: float = 0.1,
+                        sigma_luminance: float = 4.0, sigma_variance: float = 8.0, min_samples: int = 8) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """polaris_hip_variance_planes: the launches of a variance sync on caller (H, W, 4) float32 planes (acc: rgb | sum L^2 of
+        `samples` samples).  Returns (VARIANCE, DENOISED, RGBA8); rows outside the request come back as passed (zeros by default)."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        acc, guide, albedo = f(acc), f(guide), f(albedo)
+        H, W = acc.shape[:2]
+        own = lambda a, dt: np.zeros((H, W, 4), dt) if a is None else np.array(a, dt, copy=True, order="C")  # noqa: E731
+        var, out, fb = own(variance, np.float32), own(denoised, np.float32), own(rgba, np.uint8)
+        assert guide.shape == albedo.shape == var.shape == out.shape == fb.shape == (H, W, 4)
+        p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
+        v = T.variance_params(sigma_variance, min_samples)
+        bh = H - block_y if block_h is None else block_h
+        self._check(self._lib.polaris_hip_variance_planes(self._h, acc.ctypes.data, guide.ctypes.data, albedo.ctypes.data, W, H, int(block_y),
+                                                          int(bh), int(samples), float(exposure), C.byref(p), C.byref(v), var.ctypes.data,
+                                                          out.ctypes.data, fb.ctypes.data), self._h)
+        return var, out, fb
 
     def reproject_planes(self, history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *,
                          max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
