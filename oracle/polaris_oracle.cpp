@@ -1122,7 +1122,8 @@ extern "C" int polaris_oracle_trace(const PolarisSceneView *sc, const float eye[
 	} else {
 		// CPU-baseline mode: samples are independent, so threads take whole samples with private
 		// buffers and a private accumulator strip; strips are added in thread order at the end
-		// (same paths, per-pixel sums re-associated like the GPU's batched mode).
+		// (same paths; the per-pixel sums are re-associated by whichever samples a thread happened to take -- within the RMSE
+		// bar, but NOT the GPU's batched mode, whose per-sample association is defined: tests/batched_oracle.py).
 		const size_t strip0 = (size_t)BY * W * 4, strip_n = (size_t)BH * W * 4;
 #pragma omp parallel
 		{

@@ -4,7 +4,9 @@ lights, odd frame sizes, partial row blocks, 1-6 bounces, any Russian-roulette t
 randomly drawn tracer options, against the CPU oracle.
 
 Bars: exact mode -- trace accumulator and every ray counter BIT-IDENTICAL to the oracle; default (batched) mode -- identical ray
-counters (=> identical paths) and per-pixel RMSE <= 1e-6 of the frame's brightest value (the batches' sums are associated differently).
+counters (=> identical paths), the block's rows BIT-IDENTICAL to the oracle's one-sample traces summed in ascending sample order
+(tests/batched_oracle.py: the association DESIGN.md section 2 defines), and per-pixel RMSE <= 1e-6 of the frame's brightest value
+against the oracle's reference order (the same terms, associated differently).
 The same seeds are checked oracle == compiled reference on the CPU (tests/test_oracle_vs_reference.py).
 """
 import os
@@ -13,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+from batched_oracle import per_sample_reference
 from conftest import bits, make_hip_tracer
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
@@ -65,6 +68,8 @@ def test_random_scenes_against_the_oracle(built, oracle, first, family):
 
         want, ws, _ = oracle.trace(sc, request(), seeds)
         assert not np.isnan(want[..., :3]).any(), seed      # (the generator's promise: NaN signs differ between hosts and are not fuzzed)
+        per_sample, ps = per_sample_reference(oracle, sc, request, seeds, spp, B)
+        assert counters(ps, B) == counters(ws, B), seed
         rng = np.random.default_rng(0xF00D + seed)
         opts = draw_options(rng)
         batched = dict(opts, samples_per_batch=int(rng.integers(1, spp + 1)), overlap=int(rng.integers(1, 4)))
@@ -84,3 +89,4 @@ def test_random_scenes_against_the_oracle(built, oracle, first, family):
                 scale = max(1.0, float(np.abs(want[by:by + bh, :, :3]).max()) / spp)
                 err = float(np.sqrt(np.mean((got[by:by + bh, :, :3] / spp - want[by:by + bh, :, :3] / spp) ** 2)))
                 assert err <= 1e-6 * scale, (what, err)
+                assert np.array_equal(bits(got[by:by + bh, :, :3]), bits(per_sample[by:by + bh, :, :3])), what

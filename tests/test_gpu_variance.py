@@ -13,6 +13,7 @@ import pytest
 
 import gbuffer_oracle as G
 import variance_oracle as VO
+from batched_oracle import per_sample_reference
 from conftest import bits, make_hip_tracer
 from polaris_amd import ctypes_api as T
 from test_gpu_denoise import sync, trace
@@ -87,9 +88,10 @@ def test_one_sample_is_the_square_of_its_luminance(built):
 
 
 @pytest.mark.parametrize("batch", [1, 3, 8])
-def test_per_sample_sum_in_ascending_order(built, batch):
+def test_per_sample_sum_in_ascending_order(built, oracle, batch):
     """Every sample's per-path radiance is added to the accumulator one by one in ascending k, whatever the batch size,
-    so the sum of L^2 of an 8 spp trace equals the float32 sum of lum(x_k)^2 of eight one-sample traces fed sample k's seeds."""
+    so the sum of L^2 of an 8 spp trace equals the float32 sum of lum(x_k)^2 of eight one-sample traces fed sample k's seeds -- HIP's
+    own one-sample traces, and the CPU oracle's (tests/batched_oracle.py), which no HIP kernel has touched."""
     from oracle import pybind as ob
     from polaris_amd import scenes
 
@@ -109,6 +111,9 @@ def test_per_sample_sum_in_ascending_order(built, batch):
     want = VO.moments_of_samples(xs)
     assert np.array_equal(bits(got[..., :3]), bits(want[..., :3]))
     assert np.array_equal(bits(got[..., 3]), bits(want[..., 3]))
+    per_sample, _ = per_sample_reference(oracle, sc, lambda: ob.make_request(W, H, spp=spp, bounces=5), scenes.make_seeds(spp, 5, base=7), spp, 5, moments=True)
+    assert np.array_equal(bits(got[..., :3]), bits(per_sample[..., :3]))
+    assert np.array_equal(bits(got[..., 3]), bits(per_sample[..., 3]))
 
 
 # ---- 4. merges --------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """A long run of the parity fuzz (GPU): seeds [first, last) of tests/tools/random_scenes.py, HIP (exact mode + a batched run, random
-tracer options) against the CPU oracle -- the loop of tests/test_gpu_fuzz_parity.py without pytest, reporting every seed that differs.
+tracer options) against the CPU oracle -- the loop of tests/test_gpu_fuzz_parity.py without pytest, reporting every seed that differs
+(the batched run: counters, RMSE against the reference order, and bit for bit against the per-sample sum of tests/batched_oracle.py).
     python tests/tools/fuzz_sweep.py 96 3000
     python tests/tools/fuzz_sweep.py 0 4096 ref      (CPU, build container: the oracle against the compiled reference instead)
     ... big / single                                  (random_case(seed, big=True / single=True))
@@ -15,6 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 
+from batched_oracle import per_sample_reference  # noqa: E402
 from conftest import bits, make_hip_tracer  # noqa: E402
 from oracle import pybind as ob  # noqa: E402
 from polaris_amd import scenes  # noqa: E402
@@ -88,6 +90,10 @@ def main():
         if np.isnan(want[..., :3]).any():
             print(f"seed {seed}: NaN in the oracle's frame (not compared)", flush=True)
             continue
+        per_sample, ps = per_sample_reference(oracle, sc, request, seeds, spp, B)
+        if counters(ps, B) != counters(ws, B):
+            bad.append(seed)
+            print(f"seed {seed} MISMATCH (oracle): one-sample traces' counters {counters(ps, B)} != {counters(ws, B)}; case {c}", flush=True)
         rng = np.random.default_rng(0xF00D + seed)
         opts = draw_options(rng)
         batched = dict(opts, samples_per_batch=int(rng.integers(1, spp + 1)), overlap=int(rng.integers(1, 4)))
@@ -114,6 +120,8 @@ def main():
                 err = float(np.sqrt(np.mean((got[by:by + bh, :, :3] / spp - want[by:by + bh, :, :3] / spp) ** 2)))
                 if err > 1e-6 * scale:
                     why = f"rmse {err:.3e} > 1e-6 x {scale:.3g}"
+                elif not np.array_equal(bits(got[by:by + bh, :, :3]), bits(per_sample[by:by + bh, :, :3])):
+                    why = f"{int((bits(got[by:by + bh, :, :3]) != bits(per_sample[by:by + bh, :, :3])).sum())} accumulator words differ from the per-sample sum"
             if why:
                 bad.append(seed)
                 print(f"seed {seed} MISMATCH ({'exact' if exact else 'batched'}): {why}; case {c}; options {options}", flush=True)
