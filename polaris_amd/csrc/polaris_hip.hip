@@ -25,6 +25,7 @@
 
 #include <unistd.h>
 
+#include "device_mem.h"
 #include "kernels.h"
 #include "polaris_hip.h"
 
@@ -41,10 +42,7 @@ std::atomic<uint64_t> g_error_seq{0};
 
 struct KernelTimer { double ms = 0.0; uint64_t launches = 0; };
 
-struct DevBuf {
-	void *p = nullptr;
-	size_t bytes = 0;
-};
+using DevPool = std::vector<DevArray<char>>; // buffers that live and die together (dev_alloc): the scene's, a pipeline's
 
 } // namespace
 
@@ -74,11 +72,12 @@ struct polaris_hip_tracer {
 
 	// frame-sized state (buffers.go:127-174)
 	uint32_t W = 0, H = 0;
-	float4 *trace_acc = nullptr, *frame_acc = nullptr; // trace_acc == ring[ring_pos]
-	uchar4 *framebuffer = nullptr;
+	float4 *trace_acc = nullptr; // == ring[ring_pos], which owns it
+	DevArray<float4> frame_acc;
+	DevArray<uchar4> framebuffer;
 	// The trace accumulator as a ring (polaris_hip_ipc_export): with depth > 1 every Trace writes the next slot, so a peer
 	// process may still read frame f's rows while frame f + 1 is traced.  Depth 1 = the reference's single buffer.
-	float4 *ring[POLARIS_IPC_MAX_DEPTH] = {};
+	DevArray<float4> ring[POLARIS_IPC_MAX_DEPTH];
 	uint32_t ring_depth = 1, ring_pos = 0;
 	// One inter-process event PER RING SLOT, recorded at the end of the Trace that wrote the slot (once exported).  A slot's event
 	// is re-recorded only when a Trace comes round to the slot again -- which the caller's protocol forbids while a peer may still
@@ -93,7 +92,7 @@ struct polaris_hip_tracer {
 
 	// scene (buffers.go:180-201), re-laid out by scene_layout.h
 	bool have_scene = false;
-	std::vector<DevBuf> scene_bufs;
+	DevPool scene_bufs;
 	BvhDev bvh{};
 	SceneDev scene{};
 	int max_stack = 0;
@@ -114,9 +113,9 @@ struct polaris_hip_tracer {
 	// is off: the G-buffer planes on first use (denoised sync or read_aov), the filter's three planes at the first denoised sync.
 	// All five are frame-sized float4 (80 B per pixel) and go with the frame buffers on resize.
 	PolarisDenoiseParams dn{sizeof(PolarisDenoiseParams), 0, 0, 0.0f, 0.0f};
-	float4 *gb_guide = nullptr, *gb_albedo = nullptr; // GUIDE / ALBEDO planes
+	DevArray<float4> gb_guide, gb_albedo;             // GUIDE / ALBEDO planes
 	bool gb_valid = false;                            // computed for the current scene, camera and frame size
-	float4 *dn_out = nullptr, *dn_ping = nullptr, *dn_pong = nullptr; // DENOISED plane, iteration buffers
+	DevArray<float4> dn_out, dn_ping, dn_pong;        // DENOISED plane, iteration buffers
 	bool dn_valid = false;                            // a denoised sync has written dn_out since the last resize
 
 	// temporal reuse across camera moves (polaris_hip_set_temporal; kernels.h k_reproject / k_temporal).  Nothing is allocated
@@ -124,8 +123,8 @@ struct polaris_hip_tracer {
 	// set_camera, which swaps the pointers (tp_out <-> tp_hist, gb_guide <-> tp_hguide, gb_albedo <-> tp_halbedo).  All five
 	// planes are frame-sized float4; resize frees them, upload_scene and max_history = 0 drop the history.
 	PolarisTemporalParams tp{sizeof(PolarisTemporalParams), 0, 0.0f, 0.0f};
-	float4 *tp_out = nullptr, *tp_prior = nullptr;                          // TEMPORAL / PRIOR planes
-	float4 *tp_hist = nullptr, *tp_hguide = nullptr, *tp_halbedo = nullptr; // the history
+	DevArray<float4> tp_out, tp_prior;               // TEMPORAL / PRIOR planes
+	DevArray<float4> tp_hist, tp_hguide, tp_halbedo; // the history
 	CameraArgs tp_hcam{};
 	bool tp_have_hist = false;
 	bool tp_synced = false;      // a temporal sync ran under the current camera (tp_out and the G-buffer are this camera's)
@@ -135,12 +134,12 @@ struct polaris_hip_tracer {
 	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
 	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
 	// set_camera swaps va_out <-> va_hist like the TEMPORAL plane, and k_reproject<true> gathers the history's M2 into tp_prior2
-	// (h2 | 0 | 0 | m); both go with free_temporal.
+	// (h2 | 0 | 0 | m); both go when either feature goes (free_moment_history).
 	std::atomic<bool> opt_moments{false};
 	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
-	float4 *va_out = nullptr;                     // VARIANCE plane (M1 | M2 | n_eff | v)
+	DevArray<float4> va_out;                      // VARIANCE plane (M1 | M2 | n_eff | v)
 	bool va_valid = false;                        // a variance sync has written va_out (under the current camera with temporal reuse)
-	float4 *va_hist = nullptr, *tp_prior2 = nullptr;
+	DevArray<float4> va_hist, tp_prior2;
 	bool va_synced = false;   // temporal: a variance sync ran under the current camera (va_out is this camera's, cleared at its first sync)
 	bool va_have_hist = false; // temporal: va_hist belongs to the history
 
@@ -157,19 +156,26 @@ struct polaris_hip_tracer {
 		uint8_t *vis[POLARIS_MAX_BOUNCES] = {};
 		uint32_t *cnt_occ_b[POLARIS_MAX_BOUNCES] = {};
 		uint32_t nee_bounces = 0; // how many of them are allocated
-		std::vector<DevBuf> bufs;
+		DevPool bufs;
 		hipEvent_t done = nullptr; // recorded after the pipe's last resolve
+		void release() { // forget everything the pipe owned (its stream must be idle)
+			bufs.clear();
+			st = Streams{};
+			slots = 0;
+			nee_bounces = 0;
+			for (auto &x : nee) x = nullptr;
+			for (auto &x : vis) x = nullptr;
+			for (auto &x : cnt_occ_b) x = nullptr;
+		}
 	};
 	static constexpr int kMaxPipes = 8;
 	Pipe pipe[kMaxPipes];
 	int opt_overlap = 4; // number of pipelines used (1 = no overlap)
-	uint32_t *d_seeds = nullptr;
-	size_t seeds_cap = 0;
-	unsigned long long *d_stats = nullptr;
-	float4 *d_cam_o = nullptr; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
+	DevArray<uint32_t> d_seeds; // grow-only
+	DevArray<unsigned long long> d_stats;
+	DevArray<float4> d_cam_o; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
 	int num_cus = 256;
-	void *staging = nullptr; // peer-merge staging strip
-	size_t staging_bytes = 0;
+	DevArray<float4> staging; // peer-merge staging strip (grow-only)
 	int opt_ipc_staged = 0;  // testing aid: peers opened from now on are merged through the staging strip (the path of a GPU without peer access)
 
 	// options
@@ -234,27 +240,20 @@ int fail(polaris_hip_tracer *h, int code, const char *fmt, ...) {
 	} while (0)
 
 template <typename T>
-int dev_alloc(polaris_hip_tracer *h, std::vector<DevBuf> &pool, T **out, size_t count) {
-	void *p = nullptr;
-	size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-	HIP_TRY(h, hipMalloc(&p, bytes));
-	pool.push_back({p, bytes});
-	*out = (T *)p;
+int dev_alloc(polaris_hip_tracer *h, DevPool &pool, T **out, size_t count) {
+	DevArray<char> a;
+	HIP_TRY(h, a.alloc(std::max<size_t>(count * sizeof(T), 16)));
+	*out = (T *)a.get();
+	pool.push_back(std::move(a));
 	return POLARIS_OK;
 }
 
 template <typename T>
-int dev_upload(polaris_hip_tracer *h, std::vector<DevBuf> &pool, T **out, const void *src, size_t count) {
+int dev_upload(polaris_hip_tracer *h, DevPool &pool, T **out, const void *src, size_t count) {
 	int rc = dev_alloc(h, pool, out, count);
 	if (rc) return rc;
 	if (count) HIP_TRY(h, hipMemcpyAsync(*out, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
 	return POLARIS_OK;
-}
-
-void free_pool(std::vector<DevBuf> &pool) {
-	for (auto &b : pool)
-		if (b.p) (void)hipFree(b.p);
-	pool.clear();
 }
 
 // Bracket a launch with events when time_kernels is on.
@@ -341,10 +340,7 @@ hipEvent_t reader_event(polaris_hip_tracer *src, int device) {
 }
 
 void free_ring(polaris_hip_tracer *h) { // caller holds mu + merge_mu, every stream idle
-	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) {
-		if (h->ring[i]) (void)hipFree(h->ring[i]);
-		h->ring[i] = nullptr;
-	}
+	for (auto &slot : h->ring) slot.reset();
 	h->trace_acc = nullptr;
 	h->ring_depth = 1;
 	h->ring_pos = 0;
@@ -367,13 +363,7 @@ int ensure_streams(polaris_hip_tracer *h, int p, size_t slots, bool want_inst, u
 	slots = std::max(slots, P.slots);
 	nee_bounces = std::max(nee_bounces, P.nee_bounces);
 	HIP_TRY(h, hipStreamSynchronize(P.q));
-	free_pool(P.bufs);
-	P.st = Streams{};
-	P.slots = 0;
-	P.nee_bounces = 0;
-	for (auto &q : P.nee) q = nullptr;
-	for (auto &q : P.vis) q = nullptr;
-	for (auto &q : P.cnt_occ_b) q = nullptr;
+	P.release();
 	const size_t wgs = slots / WG;
 	int rc = 0;
 	rc |= dev_alloc(h, P.bufs, &P.st.ray_o, slots);
@@ -400,7 +390,7 @@ int ensure_streams(polaris_hip_tracer *h, int p, size_t slots, bool want_inst, u
 		rc |= dev_alloc(h, P.bufs, &P.vis[b], slots);
 		rc |= dev_alloc(h, P.bufs, &P.cnt_occ_b[b], wgs);
 	}
-	if (rc) { free_pool(P.bufs); P.st = Streams{}; for (auto &q : P.nee) q = nullptr; for (auto &q : P.vis) q = nullptr; for (auto &q : P.cnt_occ_b) q = nullptr; return rc; }
+	if (rc) { P.release(); return rc; } // (nothing was queued on the stream since it was synchronised above)
 	P.slots = slots;
 	P.nee_bounces = nee_bounces;
 	return POLARIS_OK;
@@ -420,35 +410,48 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
 
-void free_temporal(polaris_hip_tracer *h) { // caller holds mu, every stream idle
-	for (float4 **p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo, &h->va_hist, &h->tp_prior2}) {
-		if (*p) (void)hipFree(*p);
-		*p = nullptr;
-	}
-	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
+// The free_* below: caller holds mu, every stream idle.  Every lazily allocated plane (ensure_plane) is reset by exactly one of them.
+void free_moment_history(polaris_hip_tracer *h) { // what exists only with temporal reuse AND variance guidance on: goes when either goes
+	h->va_hist.reset();
+	h->tp_prior2.reset();
 	h->va_synced = h->va_have_hist = false;
 }
 
-void free_variance(polaris_hip_tracer *h) { // caller holds mu, every stream idle
-	if (h->va_out) (void)hipFree(h->va_out);
-	h->va_out = nullptr;
+void free_temporal(polaris_hip_tracer *h) {
+	for (auto *p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo}) p->reset();
+	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
+	free_moment_history(h);
+}
+
+void free_variance(polaris_hip_tracer *h) {
+	h->va_out.reset();
 	h->va_valid = false;
 }
 
-void free_denoise(polaris_hip_tracer *h) { // caller holds mu, every stream idle
-	for (float4 **p : {&h->gb_guide, &h->gb_albedo, &h->dn_out, &h->dn_ping, &h->dn_pong}) {
-		if (*p) (void)hipFree(*p);
-		*p = nullptr;
-	}
+void free_denoise(polaris_hip_tracer *h) {
+	for (auto *p : {&h->gb_guide, &h->gb_albedo, &h->dn_out, &h->dn_ping, &h->dn_pong}) p->reset();
 	h->gb_valid = h->dn_valid = false;
+}
+
+// A frame-sized plane (F pixels) that exists from its first use on (caller holds mu).
+int ensure_plane(polaris_hip_tracer *h, DevArray<float4> &plane, size_t F) {
+	if (!plane) HIP_TRY(h, plane.alloc(F));
+	return POLARIS_OK;
+}
+
+// The filter's DENOISED plane and its two iteration buffers.
+int ensure_filter_planes(polaris_hip_tracer *h, size_t F) {
+	for (auto *p : {&h->dn_out, &h->dn_ping, &h->dn_pong})
+		if (int rc = ensure_plane(h, *p, F)) return rc;
+	return POLARIS_OK;
 }
 
 // The GUIDE / ALBEDO planes of the current scene, camera and frame size, computed if they are not (caller holds mu; checks done).
 int ensure_gbuffer(polaris_hip_tracer *h) {
 	if (h->gb_valid) return POLARIS_OK;
 	const size_t F = (size_t)h->W * h->H;
-	if (!h->gb_guide) HIP_TRY(h, hipMalloc((void **)&h->gb_guide, F * sizeof(float4)));
-	if (!h->gb_albedo) HIP_TRY(h, hipMalloc((void **)&h->gb_albedo, F * sizeof(float4)));
+	if (int rc = ensure_plane(h, h->gb_guide, F)) return rc;
+	if (int rc = ensure_plane(h, h->gb_albedo, F)) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
 	{
@@ -492,7 +495,8 @@ hipError_t launch_trace(polaris_hip_tracer *h, polaris_hip_tracer::Pipe &P, cons
 	Streams st = st_in;
 	uint32_t o_mask = ~0u;
 	if (camera && !ANY_HIT) { st.ray_o = h->d_cam_o; o_mask = 0u; }
-	void *args[] = {(void *)&st, (void *)&h->bvh, (void *)&chunks, (void *)&acc, (void *)&h->d_stats, (void *)&o_mask};
+	unsigned long long *stats = h->d_stats;
+	void *args[] = {(void *)&st, (void *)&h->bvh, (void *)&chunks, (void *)&acc, (void *)&stats, (void *)&o_mask};
 	return hipLaunchKernel(fn, dim3(grid), dim3(block), args, h->node_mode == kNodesLdsAll ? h->tiny_lds_bytes : 0, P.q);
 }
 
@@ -766,8 +770,8 @@ int polaris_hip_create(int device_index, polaris_hip_tracer **out) {
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->merge_stream, hipStreamNonBlocking);
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_merged, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipMalloc((void **)&h->d_stats, ST_COUNT * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMalloc((void **)&h->d_cam_o, sizeof(float4));
+	if (e == hipSuccess) e = h->d_stats.alloc(ST_COUNT);
+	if (e == hipSuccess) e = h->d_cam_o.alloc(1);
 	if (e == hipSuccess) {
 		hipDeviceProp_t p;
 		if (hipGetDeviceProperties(&p, device_index) == hipSuccess && p.multiProcessorCount > 0) h->num_cus = p.multiProcessorCount;
@@ -798,13 +802,13 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 		if (h->ev_merged) (void)hipEventDestroy(h->ev_merged);
 		for (auto e : h->event_pool) (void)hipEventDestroy(e);
 		for (auto &P : h->pipe) {
-			free_pool(P.bufs);
+			P.release();
 			if (P.done) (void)hipEventDestroy(P.done);
 		}
 		if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
 		for (int p = 1; p < polaris_hip_tracer::kMaxPipes; p++)
 			if (h->pipe[p].q) (void)hipStreamDestroy(h->pipe[p].q);
-		free_pool(h->scene_bufs);
+		h->scene_bufs.clear();
 		free_ring(h);
 		free_denoise(h);
 		free_temporal(h);
@@ -818,12 +822,13 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 			h->readers.clear();
 			h->reader_pool.clear();
 		}
-		if (h->frame_acc) (void)hipFree(h->frame_acc);
-		if (h->framebuffer) (void)hipFree(h->framebuffer);
-		if (h->d_seeds) (void)hipFree(h->d_seeds);
-		if (h->d_stats) (void)hipFree(h->d_stats);
-		if (h->d_cam_o) (void)hipFree(h->d_cam_o);
-		if (h->staging) (void)hipFree(h->staging);
+		// (here, under the locks and before the main stream goes -- not in `delete h` below)
+		h->frame_acc.reset();
+		h->framebuffer.reset();
+		h->d_seeds.reset();
+		h->d_stats.reset();
+		h->d_cam_o.reset();
+		h->staging.reset();
 		if (h->ev_start) (void)hipEventDestroy(h->ev_start);
 		if (h->ev_stop) (void)hipEventDestroy(h->ev_stop);
 		if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -859,16 +864,14 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	free_denoise(h);
 	if (h->tp.max_history) free_temporal(h);
 	if (h->va.sigma_variance != 0.0f) free_variance(h);
-	if (h->frame_acc) (void)hipFree(h->frame_acc);
-	if (h->framebuffer) (void)hipFree(h->framebuffer);
-	h->frame_acc = nullptr;
-	h->framebuffer = nullptr;
+	h->frame_acc.reset();
+	h->framebuffer.reset();
 	h->W = h->H = 0;
 	const size_t F = (size_t)frame_w * frame_h;
-	HIP_TRY(h, hipMalloc((void **)&h->ring[0], F * sizeof(float4)));
+	HIP_TRY(h, h->ring[0].alloc(F));
 	h->trace_acc = h->ring[0];
-	HIP_TRY(h, hipMalloc((void **)&h->frame_acc, F * sizeof(float4)));
-	HIP_TRY(h, hipMalloc((void **)&h->framebuffer, F * sizeof(uchar4)));
+	HIP_TRY(h, h->frame_acc.alloc(F));
+	HIP_TRY(h, h->framebuffer.alloc(F));
 	HIP_TRY(h, hipMemsetAsync(h->trace_acc, 0, F * sizeof(float4), h->stream));
 	HIP_TRY(h, hipMemsetAsync(h->frame_acc, 0, F * sizeof(float4), h->stream));
 	HIP_TRY(h, hipMemsetAsync(h->framebuffer, 0, F * sizeof(uchar4), h->stream));
@@ -895,7 +898,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	if (!err.empty()) return fail(h, POLARIS_E_BAD_SCENE, "%s", err.c_str());
 	HIP_TRY(h, hipSetDevice(h->device));
 	HIP_TRY(h, sync_all(h));
-	free_pool(h->scene_bufs);
+	h->scene_bufs.clear();
 	h->have_scene = false;
 	h->gb_valid = false;
 	if (h->tp.max_history) h->tp_have_hist = h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_have_hist = h->va_valid = false; // (the history saw the old scene)
@@ -948,7 +951,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	// the texture blob, padded: texels are fetched as the three dwords at their address whatever the format (shading.h, tex_fetch)
 	rc |= dev_alloc(h, h->scene_bufs, &tex_data, (size_t)sc->texture_data_bytes + 16);
 	if (!rc && sc->texture_data_bytes) HIP_TRY(h, hipMemcpyAsync(tex_data, sc->texture_data, sc->texture_data_bytes, hipMemcpyHostToDevice, h->stream));
-	if (rc) { free_pool(h->scene_bufs); return rc; }
+	if (rc) { h->scene_bufs.clear(); return rc; }
 	HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors in L die at return
 	h->bvh = BvhDev{pairs, (uint32_t)L.pairs.size(), leaves, tris, insts, L.root_ref, 0, InstRec{}, 0, 0};
 	if (L.root_ref < 0 && (((uint32_t)~L.root_ref) & 15u) == 0u && !(((uint32_t)~L.root_ref) & kBigLeafFlag)) { // the top-level tree is a single leaf ...
@@ -1128,16 +1131,10 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 		if (exact || h->opt_samples_per_batch > 0 || K == 1) return rc;
 		(void)hipGetLastError(); // out of memory: release every pipeline's buffers, halve the batch, try again
 		for (auto &P : h->pipe)
-			if (P.q && P.slots) { (void)hipStreamSynchronize(P.q); free_pool(P.bufs); P.st = Streams{}; P.slots = 0; P.nee_bounces = 0; for (auto &x : P.nee) x = nullptr; for (auto &x : P.vis) x = nullptr; for (auto &x : P.cnt_occ_b) x = nullptr; }
+			if (P.q && P.slots) { (void)hipStreamSynchronize(P.q); P.release(); }
 		K = (K + 1) / 2;
 	}
-	if (need_seeds > h->seeds_cap) {
-		if (h->d_seeds) (void)hipFree(h->d_seeds);
-		h->d_seeds = nullptr;
-		h->seeds_cap = 0;
-		HIP_TRY(h, hipMalloc((void **)&h->d_seeds, need_seeds * sizeof(uint32_t)));
-		h->seeds_cap = need_seeds;
-	}
+	HIP_TRY(h, h->d_seeds.reserve(need_seeds));
 	h->cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H); // resources.go:130-133
 	const size_t F = (size_t)h->W * h->H;
 	hipStream_t q = h->stream;
@@ -1273,19 +1270,14 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 	}
 	int branch = peer ? (peer->info.same_device == 1 ? POLARIS_MERGE_IPC_LOCAL : (peer->info.same_device == 0 ? POLARIS_MERGE_IPC_PEER : POLARIS_MERGE_IPC_UNKNOWN)) : POLARIS_MERGE_LOCAL;
 	auto need_staging = [&]() -> bool { // the merge stream's staging strip, big enough for this block (merges are serialised on the stream)
-		if (dst->staging_bytes >= n * sizeof(float4)) return true;
-		(void)hipStreamSynchronize(q);
-		if (dst->staging) (void)hipFree(dst->staging);
-		dst->staging = nullptr;
-		dst->staging_bytes = 0;
-		if (hipMalloc(&dst->staging, n * sizeof(float4)) != hipSuccess) return false;
-		dst->staging_bytes = n * sizeof(float4);
-		return true;
+		if (dst->staging.capacity() >= n) return true;
+		(void)hipStreamSynchronize(q); // (an earlier merge may still read the strip that goes)
+		return dst->staging.alloc(n) == hipSuccess;
 	};
 	if (peer && peer->info.staged) { // no peer access to the ring's GPU (or forced): the RUNTIME moves the rows, the kernel adds a local strip
 		if (!need_staging()) return fail_merge(POLARIS_E_DEVICE, "merge: out of device memory for the staging strip");
 		if (hipMemcpyAsync(dst->staging, rows, n * sizeof(float4), hipMemcpyDefault, q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge_ipc: hipMemcpyAsync from the peer's ring failed");
-		rows = (const float4 *)dst->staging;
+		rows = dst->staging;
 		branch = POLARIS_MERGE_IPC_STAGED;
 	}
 	if (!peer && src_device != dst->device) {
@@ -1302,7 +1294,7 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 			branch = POLARIS_MERGE_STAGED;
 			if (!need_staging()) return fail_merge(POLARIS_E_DEVICE, "merge: out of device memory for the staging strip");
 			if (hipMemcpyPeerAsync(dst->staging, dst->device, rows, src_device, n * sizeof(float4), q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipMemcpyPeerAsync failed");
-			rows = (const float4 *)dst->staging;
+			rows = dst->staging;
 		}
 	}
 	{
@@ -1368,11 +1360,10 @@ int polaris_hip_ipc_export(polaris_hip_tracer *h, uint32_t depth, PolarisIpcExpo
 	const size_t F = (size_t)h->W * h->H;
 	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) { // grow or shrink the ring to `depth` slots (slot 0 always exists)
 		if (i < depth && !h->ring[i]) {
-			HIP_TRY(h, hipMalloc((void **)&h->ring[i], F * sizeof(float4)));
+			HIP_TRY(h, h->ring[i].alloc(F));
 			HIP_TRY(h, hipMemsetAsync(h->ring[i], 0, F * sizeof(float4), h->stream));
-		} else if (i >= depth && h->ring[i]) {
-			(void)hipFree(h->ring[i]);
-			h->ring[i] = nullptr;
+		} else if (i >= depth) {
+			h->ring[i].reset();
 		}
 	}
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1635,9 +1626,7 @@ int sync_denoised(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "denoising needs the camera (UpdateState CameraData)");
 	const size_t F = (size_t)h->W * h->H;
 	if (int rc = ensure_gbuffer(h)) return rc;
-	if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
-	if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
-	if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
+	if (int rc = ensure_filter_planes(h, F)) return rc;
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
 	launch_denoise(h, h->stream, h->frame_acc, weight, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W,
 	               r->block_y, r->block_y + r->block_h, r->exposure, h->dn);
@@ -1730,14 +1719,11 @@ int sync_variance(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	const size_t F = (size_t)h->W * h->H;
 	if (int rc = ensure_gbuffer(h)) return rc;
 	if (!h->va_out) {
-		HIP_TRY(h, hipMalloc((void **)&h->va_out, F * sizeof(float4)));
+		if (int rc = ensure_plane(h, h->va_out, F)) return rc;
 		HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream));
 	}
-	if (h->dn.iterations) {
-		if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
-		if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
-		if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
-	}
+	if (h->dn.iterations)
+		if (int rc = ensure_filter_planes(h, F)) return rc;
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
 	const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
 	launch_variance(h, h->stream, h->frame_acc, nf, weight, nullptr, nullptr, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong, h->dn_out,
@@ -1758,17 +1744,14 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	const size_t F = (size_t)h->W * h->H, off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
 	const uint32_t y0 = r->block_y, y1 = r->block_y + r->block_h;
 	if (int rc = ensure_gbuffer(h)) return rc;
-	if (!h->tp_out) HIP_TRY(h, hipMalloc((void **)&h->tp_out, F * sizeof(float4)));
-	if (!h->tp_prior) HIP_TRY(h, hipMalloc((void **)&h->tp_prior, F * sizeof(float4)));
-	if (h->dn.iterations) {
-		if (!h->dn_out) HIP_TRY(h, hipMalloc((void **)&h->dn_out, F * sizeof(float4)));
-		if (!h->dn_ping) HIP_TRY(h, hipMalloc((void **)&h->dn_ping, F * sizeof(float4)));
-		if (!h->dn_pong) HIP_TRY(h, hipMalloc((void **)&h->dn_pong, F * sizeof(float4)));
-	}
+	if (int rc = ensure_plane(h, h->tp_out, F)) return rc;
+	if (int rc = ensure_plane(h, h->tp_prior, F)) return rc;
+	if (h->dn.iterations)
+		if (int rc = ensure_filter_planes(h, F)) return rc;
 	const bool var = h->va.sigma_variance != 0.0f;
 	if (var) {
-		if (!h->va_out) HIP_TRY(h, hipMalloc((void **)&h->va_out, F * sizeof(float4)));
-		if (!h->tp_prior2) HIP_TRY(h, hipMalloc((void **)&h->tp_prior2, F * sizeof(float4)));
+		if (int rc = ensure_plane(h, h->va_out, F)) return rc;
+		if (int rc = ensure_plane(h, h->tp_prior2, F)) return rc;
 		if (!h->va_synced) HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream)); // (as TEMPORAL: rows no sync reaches)
 		h->va_synced = true;
 	}
@@ -1859,11 +1842,7 @@ int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams 
 		HIP_TRY(h, hipSetDevice(h->device));
 		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every variance launch is on the main stream)
 		free_variance(h);
-		for (float4 **q : {&h->va_hist, &h->tp_prior2}) {
-			if (*q) (void)hipFree(*q);
-			*q = nullptr;
-		}
-		h->va_synced = h->va_have_hist = false;
+		free_moment_history(h);
 	}
 	if (on != was) h->tp_prior_valid = false; // (PRIOR2 is written, or no longer, by the next temporal sync's reprojection)
 	h->va = *p;
@@ -1962,19 +1941,17 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	Streams &st0 = h->pipe[0].st;
 	st0.hit12 = 0; // (the tap returns the hit distance: 16-byte records)
 	st0.o12 = 0;
-	if (h->seeds_cap < 1) {
-		HIP_TRY(h, hipMalloc((void **)&h->d_seeds, 64 * sizeof(uint32_t)));
-		h->seeds_cap = 64;
-	}
+	if (h->d_seeds.capacity() < 1) HIP_TRY(h, h->d_seeds.alloc(64));
 	h->cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
 	hipStream_t q = h->stream;
+	std::vector<float4> ro(N), rd(N), ht(N);
+	std::vector<int> inst(N);
+	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
 	hipLaunchKernelGGL(k_generate, dim3(Npad / WG), dim3(WG), 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
 	if (h->packet_primary) hipLaunchKernelGGL(k_trace_packet<false>, dim3(Npad / WG), dim3(WG), 0, q, st0, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
 	else hipLaunchKernelGGL(k_intersect, dim3(Npad / WG), dim3(WG), 0, q, st0, h->bvh);
 	HIP_TRY(h, hipGetLastError());
-	std::vector<float4> ro(N), rd(N), ht(N);
-	std::vector<int> inst(N);
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipMemcpyAsync(rd.data(), st0.ray_d, N * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipMemcpyAsync(ht.data(), st0.hit, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2013,24 +1990,19 @@ int polaris_hip_probe(polaris_hip_tracer *h, int kind, uint32_t index, uint32_t 
 	if (n == 0) return POLARIS_OK;
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t nin = (size_t)n * kProbeIn[kind], nout = (size_t)n * kProbeOut[kind];
-	float *d_in = nullptr, *d_out = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d_in, nin * sizeof(float)));
-	if (hipMalloc((void **)&d_out, nout * sizeof(float)) != hipSuccess) { (void)hipFree(d_in); return fail(h, POLARIS_E_DEVICE, "probe: out of device memory"); }
 	hipStream_t q = h->stream;
-	hipError_t e = hipMemcpyAsync(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice, q);
+	DevArray<float> d_in, d_out;
+	StreamDrain drain{q};
+	HIP_TRY(h, d_in.alloc(nin));
+	HIP_TRY(h, d_out.alloc(nout));
+	HIP_TRY(h, hipMemcpyAsync(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice, q));
 	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
 	                    h->scene.num_textures <= kLdsTextures;
-	if (e == hipSuccess) {
-		if (staged) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
-		else hipLaunchKernelGGL(k_probe<false>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost, q);
-	if (e == hipSuccess) e = hipStreamSynchronize(q);
-	else (void)hipStreamSynchronize(q);
-	(void)hipFree(d_in);
-	(void)hipFree(d_out);
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "probe: %s", hipGetErrorString(e));
+	if (staged) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
+	else hipLaunchKernelGGL(k_probe<false>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipMemcpyAsync(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost, q));
+	HIP_TRY(h, hipStreamSynchronize(q));
 	return POLARIS_OK;
 }
 
@@ -2052,30 +2024,26 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 	P.st.hit12 = 0; // (the probe returns the hit distance: 16-byte records)
 	P.st.o12 = 0;   // (... and takes arbitrary max distances)
 	hipStream_t q = P.q;
-	float *d_rays = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d_rays, (size_t)n * 8 * sizeof(float)));
-	hipError_t e = hipMemcpyAsync(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, q);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_probe_rays, dim3(wgs), dim3(WG), 0, q, P.st, d_rays, n, any_hit ? 1 : 0);
-		// the traversal kernel the options select for bounce rays (any_hit: shadow rays); packet_primary=1 sends closest-hit
-		// probes through the wave-packet kernel instead
-		if (any_hit) {
-			if (h->opt_packet_shadow > 0) hipLaunchKernelGGL(k_trace_packet<true>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats, h->cam.eye);
-			else if (h->opt_traversal) (void)launch_trace<true>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->occl_resident_per_cu)), wgs, P.st.lsum);
-			else hipLaunchKernelGGL(k_occlusion, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats);
-		} else {
-			if (h->opt_packet_primary == 1) hipLaunchKernelGGL(k_trace_packet<false>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
-			else if (h->opt_traversal) (void)launch_trace<false>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace_resident_per_cu)), wgs, nullptr);
-			else hipLaunchKernelGGL(k_intersect, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh);
-		}
-		e = hipGetLastError();
-	}
+	DevArray<float> d_rays;
 	std::vector<float4> res(n);
-	if (e == hipSuccess) e = hipMemcpyAsync(res.data(), any_hit ? P.st.lsum : P.st.hit, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, q);
-	const hipError_t e2 = hipStreamSynchronize(q);
-	(void)hipFree(d_rays);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "probe_intersect: %s", hipGetErrorString(e));
+	StreamDrain drain{q};
+	HIP_TRY(h, d_rays.alloc((size_t)n * 8));
+	HIP_TRY(h, hipMemcpyAsync(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, q));
+	hipLaunchKernelGGL(k_probe_rays, dim3(wgs), dim3(WG), 0, q, P.st, d_rays, n, any_hit ? 1 : 0);
+	// the traversal kernel the options select for bounce rays (any_hit: shadow rays); packet_primary=1 sends closest-hit
+	// probes through the wave-packet kernel instead
+	if (any_hit) {
+		if (h->opt_packet_shadow > 0) hipLaunchKernelGGL(k_trace_packet<true>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace<true>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->occl_resident_per_cu)), wgs, P.st.lsum);
+		else hipLaunchKernelGGL(k_occlusion, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats);
+	} else {
+		if (h->opt_packet_primary == 1) hipLaunchKernelGGL(k_trace_packet<false>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace<false>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace_resident_per_cu)), wgs, nullptr);
+		else hipLaunchKernelGGL(k_intersect, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh);
+	}
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipMemcpyAsync(res.data(), any_hit ? P.st.lsum : P.st.hit, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, q));
+	HIP_TRY(h, hipStreamSynchronize(q));
 	for (uint32_t i = 0; i < n; i++) {
 		if (any_hit) { hit[i] = res[i].x == 0.0f ? 1 : 0; continue; } // occluded rays leave their cell untouched
 		int t;
@@ -2093,18 +2061,15 @@ int polaris_hip_selftest_rcp(polaris_hip_tracer *h, float lo, float hi, uint64_t
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!mismatches_inside || !mismatches_outside) return fail(h, POLARIS_E_BAD_ARGUMENT, "selftest_rcp: null outputs");
 	HIP_TRY(h, hipSetDevice(h->device));
-	unsigned long long *d = nullptr, res[3] = {0, 0, 0};
-	HIP_TRY(h, hipMalloc((void **)&d, sizeof res));
-	hipError_t e = hipMemcpyAsync(d, res, sizeof res, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_rcp_sweep, dim3((uint32_t)h->num_cus * 32u), dim3(WG), 0, h->stream, lo, hi, d);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d, sizeof res, hipMemcpyDeviceToHost, h->stream);
-	const hipError_t e2 = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "selftest_rcp: %s", hipGetErrorString(e));
+	unsigned long long res[3] = {0, 0, 0};
+	DevArray<unsigned long long> d;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(3));
+	HIP_TRY(h, hipMemcpyAsync(d, res, sizeof res, hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(k_rcp_sweep, dim3((uint32_t)h->num_cus * 32u), dim3(WG), 0, h->stream, lo, hi, d);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipMemcpyAsync(res, d, sizeof res, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	*mismatches_inside = res[0];
 	*mismatches_outside = res[1];
 	if (sample) *sample = (uint32_t)res[2];
@@ -2122,22 +2087,18 @@ int polaris_hip_selftest_builtins(polaris_hip_tracer *h, uint32_t fn, uint64_t f
 		            (unsigned long long)(fn < PB_NUM_FN ? pb_inputs(fn) : 0), POLARIS_SELFTEST_MAX_RESULTS_LOG2);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t n_fp = fingerprints ? 2 * (size_t)((count + chunk - 1) / chunk) : 0, n_raw = results ? (size_t)count : 0;
-	char *d = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d, n_fp * sizeof(uint64_t) + n_raw * sizeof(uint32_t)));
-	unsigned long long *d_fp = n_fp ? (unsigned long long *)d : nullptr;
+	DevArray<char> d;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(n_fp * sizeof(uint64_t) + n_raw * sizeof(uint32_t)));
+	unsigned long long *d_fp = n_fp ? (unsigned long long *)d.get() : nullptr;
 	uint32_t *d_raw = n_raw ? (uint32_t *)(d + n_fp * sizeof(uint64_t)) : nullptr;
-	hipError_t e = n_fp ? hipMemsetAsync(d_fp, 0, n_fp * sizeof(uint64_t), h->stream) : hipSuccess;
-	if (e == hipSuccess) {
-		const uint64_t span = (uint64_t)WG * kSweepPerThread, blocks = (count + span - 1) / span; // <= 2^32 / 4096
-		hipLaunchKernelGGL(k_builtin_sweep, dim3((uint32_t)blocks), dim3(WG), 0, h->stream, fn, first, count, d_fp, d_raw);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && n_fp) e = hipMemcpyAsync(fingerprints, d_fp, n_fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess && n_raw) e = hipMemcpyAsync(results, d_raw, n_raw * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
-	const hipError_t e2 = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "selftest_builtins: %s", hipGetErrorString(e));
+	if (n_fp) HIP_TRY(h, hipMemsetAsync(d_fp, 0, n_fp * sizeof(uint64_t), h->stream));
+	const uint64_t span = (uint64_t)WG * kSweepPerThread, blocks = (count + span - 1) / span; // <= 2^32 / 4096
+	hipLaunchKernelGGL(k_builtin_sweep, dim3((uint32_t)blocks), dim3(WG), 0, h->stream, fn, first, count, d_fp, d_raw);
+	HIP_TRY(h, hipGetLastError());
+	if (n_fp) HIP_TRY(h, hipMemcpyAsync(fingerprints, d_fp, n_fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+	if (n_raw) HIP_TRY(h, hipMemcpyAsync(results, d_raw, n_raw * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	return POLARIS_OK;
 }
 
@@ -2153,25 +2114,19 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
 		            "(iterations 1..%u)", W, H, block_y, block_h, kDnMaxIterations);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	char *d = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d, 6 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
-	float4 *d_acc = (float4 *)d, *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_ping = d_albedo + F, *d_pong = d_ping + F, *d_out = d_pong + F;
+	DevArray<char> d;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(6 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
+	float4 *d_acc = (float4 *)d.get(), *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_ping = d_albedo + F, *d_pong = d_ping + F, *d_out = d_pong + F;
 	uchar4 *d_fb = (uchar4 *)(d_out + F);
-	hipError_t e = hipSuccess;
 	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_out, denoised}};
-	for (const auto &c : in)
-		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		launch_denoise(h, h->stream, d_acc, weight, d_guide, d_albedo, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure, *p);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream);
-	const hipError_t e2 = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "denoise_planes: %s", hipGetErrorString(e));
+	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream));
+	launch_denoise(h, h->stream, d_acc, weight, d_guide, d_albedo, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure, *p);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
 }
@@ -2190,29 +2145,23 @@ int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const f
 		            kVaMaxMinSamples);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	char *d = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d, 7 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
-	float4 *d_acc = (float4 *)d, *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_var = d_albedo + F, *d_ping = d_var + F, *d_pong = d_ping + F,
+	DevArray<char> d;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(7 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
+	float4 *d_acc = (float4 *)d.get(), *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_var = d_albedo + F, *d_ping = d_var + F, *d_pong = d_ping + F,
 	       *d_out = d_pong + F;
 	uchar4 *d_fb = (uchar4 *)(d_out + F);
-	hipError_t e = hipSuccess;
 	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_var, variance}, {d_out, denoised}};
-	for (const auto &c : in)
-		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		const float weight = (float)(1.0 / (float)samples); // (polaris_hip_sync_framebuffer's)
-		launch_variance(h, h->stream, d_acc, (float)samples, weight, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y,
-		                block_y + block_h, exposure, *p, *v);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(variance, d_var, plane, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream);
-	const hipError_t e2 = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "variance_planes: %s", hipGetErrorString(e));
+	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream));
+	const float weight = (float)(1.0 / (float)samples); // (polaris_hip_sync_framebuffer's)
+	launch_variance(h, h->stream, d_acc, (float)samples, weight, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y,
+	                block_y + block_h, exposure, *p, *v);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipMemcpyAsync(variance, d_var, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
 }
@@ -2230,24 +2179,18 @@ int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, co
 		            "normal_threshold [-1, 1], depth_threshold [0, %g])", W, H, kTpMaxHistory, (double)kTpMaxDepthThreshold);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	char *d = nullptr;
-	HIP_TRY(h, hipMalloc((void **)&d, 6 * plane));   // its own planes: no tracer state is read or written
-	float4 *d_hist = (float4 *)d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
+	DevArray<float4> d;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(6 * F));   // its own planes: no tracer state is read or written
+	float4 *d_hist = d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
 	       *d_prior = d_albedo + F;
-	hipError_t e = hipSuccess;
 	const std::pair<float4 *, const void *> in[] = {{d_hist, history}, {d_hguide, prev_guide}, {d_halbedo, prev_albedo}, {d_guide, guide},
 	                                                {d_albedo, albedo}};
-	for (const auto &c : in)
-		if (e == hipSuccess) e = hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		e = launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
-		                     W, H, *p, d_prior);
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream);
-	const hipError_t e2 = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(h, POLARIS_E_DEVICE, "reproject_planes: %s", hipGetErrorString(e));
+	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
+	                            W, H, *p, d_prior));
+	HIP_TRY(h, hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
 }

@@ -1,0 +1,160 @@
+"""Lifetimes of the handle's lazily allocated planes on the MI355X (polaris_amd/csrc/device_mem.h).
+
+One tracer is taken through feature toggles and resizes that allocate, free, swap and re-allocate every filter plane; after every
+sync its RGBA8 frame buffer, every AOV that can be read and the refusal of every AOV that cannot must equal, byte for byte, those
+of a second tracer that was configured directly for that state and saw none of the earlier toggles and resizes.  A plane that
+outlives its feature or frame size, is freed while in use, or is missed by a free_* shows as a difference (or a fault) here.
+
+Frames 24 x 16 and 40 x 12: 384 and 480 pixels, neither a multiple of the 256-thread workgroup."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from conftest import make_hip_tracer
+from polaris_amd import ctypes_api as T
+from test_gpu_denoise import sync, trace
+
+pytestmark = pytest.mark.gpu
+
+FRAME_A, FRAME_B = (24, 16), (40, 12)
+SPP, BOUNCES = 2, 2
+AOVS = {"guide": T.AOV_GUIDE, "albedo": T.AOV_ALBEDO, "denoised": T.AOV_DENOISED, "temporal": T.AOV_TEMPORAL, "prior": T.AOV_PRIOR,
+        "variance": T.AOV_VARIANCE, "prior2": T.AOV_PRIOR2}
+GBUFFER = {"guide", "albedo"}
+
+
+def scenes_pair():
+    """The Cornell box under the camera of frame A, and the same box with the eye moved (one scene for both frame sizes: a toggle
+    or a resize must not need a new camera)."""
+    from polaris_amd import scenes
+
+    sc0 = scenes.SCENES["cornell"](FRAME_A[0] / FRAME_A[1])
+    eye = (np.asarray(sc0.eye, np.float32) + np.array([0.02, 0.01, 0], np.float32)).astype(np.float32)
+    return sc0, dataclasses.replace(sc0, eye=eye)
+
+
+def set_camera(tr, sc):
+    from polaris_amd.tracer import ChangeType, UpdateMode
+
+    tr.UpdateState(UpdateMode.Synchronous, ChangeType.CameraData, sc)
+
+
+def resize(tr, frame):
+    from polaris_amd.tracer import ChangeType, UpdateMode
+
+    tr.UpdateState(UpdateMode.Synchronous, ChangeType.FrameDimensions, frame)
+
+
+def trace_sync(tr, frame, base):
+    trace(tr, *frame, SPP, base=base, bounces=BOUNCES)
+    sync(tr, *frame, SPP)
+
+
+def snapshot(tr):
+    """Frame-buffer bytes, and per AOV its bytes or its refusal (code and message)."""
+    from polaris_amd.tracer import TracerError
+
+    snap = {"framebuffer": tr.read_framebuffer().tobytes()}
+    for name, which in AOVS.items():
+        try:
+            snap[name] = tr.read_aov(which).tobytes()
+        except TracerError as e:
+            snap[name] = ("refused", e.code, str(e))
+    return snap
+
+
+def check(step, got, want, readable, frame):
+    """got == want byte for byte, exactly the AOVs in `readable` are planes of the frame's size, the others are refused alike."""
+    assert set(got) == set(want)
+    for name in got:
+        assert got[name] == want[name], (step, name)
+    for name in AOVS:
+        if name in readable:
+            assert isinstance(got[name], bytes) and len(got[name]) == frame[0] * frame[1] * 16, (step, name)
+        else:
+            assert got[name][:2] == ("refused", 2), (step, name, got[name])            # POLARIS_E_BAD_ARGUMENT
+    assert len(got["framebuffer"]) == frame[0] * frame[1] * 4 and any(got["framebuffer"]), step
+
+
+def fresh(sc, frame, *, variance=False, temporal=False):
+    tr = make_hip_tracer(sc, *frame)
+    tr.set_denoise(**T.DENOISE_DEFAULTS)
+    if variance:
+        tr.set_variance(**T.VARIANCE_DEFAULTS)
+    if temporal:
+        tr.set_temporal(**T.TEMPORAL_DEFAULTS)
+    return tr
+
+
+def fresh_snapshot(sc, frame, base, **features):
+    tr = fresh(sc, frame, **features)
+    try:
+        trace_sync(tr, frame, base)
+        return snapshot(tr)
+    finally:
+        tr.Close()
+
+
+def test_planes_follow_toggles_and_resizes(built):
+    sc0, sc1 = scenes_pair()
+    tr = make_hip_tracer(sc0, *FRAME_A)
+    ref = None
+    try:
+        tr.set_denoise(**T.DENOISE_DEFAULTS)                                         # 1. denoise on
+        trace_sync(tr, FRAME_A, 3)
+        check(1, snapshot(tr), fresh_snapshot(sc0, FRAME_A, 3), GBUFFER | {"denoised"}, FRAME_A)
+
+        tr.set_variance(**T.VARIANCE_DEFAULTS)                                       # 2. variance on
+        trace_sync(tr, FRAME_A, 4)
+        check(2, snapshot(tr), fresh_snapshot(sc0, FRAME_A, 4, variance=True), GBUFFER | {"denoised", "variance"}, FRAME_A)
+
+        tr.set_variance(0.0)                                                         # 3. variance off
+        resize(tr, FRAME_B)                                                          # 4. the second frame
+        tr.set_variance(**T.VARIANCE_DEFAULTS)                                       # 5. variance on
+        tr.set_temporal(**T.TEMPORAL_DEFAULTS)                                       # 6. temporal reuse on
+        trace_sync(tr, FRAME_B, 5)                                                   # 7.
+        # the reference of the two temporal syncs: the same two syncs around the same camera move (the resize dropped any older
+        # history, so this is the whole history)
+        ref = fresh(sc0, FRAME_B, variance=True, temporal=True)
+        trace_sync(ref, FRAME_B, 5)
+        check(7, snapshot(tr), snapshot(ref), set(AOVS), FRAME_B)
+
+        set_camera(tr, sc1)                                                          # 8. move the camera
+        trace_sync(tr, FRAME_B, 6)                                                   # 9.
+        set_camera(ref, sc1)
+        trace_sync(ref, FRAME_B, 6)
+        got = snapshot(tr)
+        check(9, got, snapshot(ref), set(AOVS), FRAME_B)
+        prior = np.frombuffer(got["prior"], np.float32).reshape(FRAME_B[1], FRAME_B[0], 4)
+        assert (prior[..., 3] > 0).mean() > 0.5                                     # (the history is in play: m > 0 on most pixels)
+
+        tr.set_temporal(0)                                                           # 10. temporal reuse off
+        trace_sync(tr, FRAME_B, 7)                                                   # 11.
+        check(11, snapshot(tr), fresh_snapshot(sc1, FRAME_B, 7, variance=True), GBUFFER | {"denoised", "variance"}, FRAME_B)
+
+        resize(tr, FRAME_A)                                                          # 12. back to the first frame
+        trace_sync(tr, FRAME_A, 8)                                                   # 13.
+        check(13, snapshot(tr), fresh_snapshot(sc1, FRAME_A, 8, variance=True), GBUFFER | {"denoised", "variance"}, FRAME_A)
+    finally:
+        tr.Close()
+        if ref is not None:
+            ref.Close()
+
+
+def test_destroy_with_every_plane_allocated(built):
+    """Three create / upload / denoised-variance-temporal sync / destroy cycles in a row.  The history planes exist only after a
+    camera move (set_camera swaps them in), hence the second sync; every cycle ends with all thirteen planes allocated."""
+    sc0, sc1 = scenes_pair()
+    snaps = []
+    for _ in range(3):
+        tr = fresh(sc0, FRAME_A, variance=True, temporal=True)
+        try:
+            trace_sync(tr, FRAME_A, 3)
+            set_camera(tr, sc1)
+            trace_sync(tr, FRAME_A, 4)
+            snaps.append(snapshot(tr))
+        finally:
+            tr.Close()
+    check("cycle", snaps[1], snaps[0], set(AOVS), FRAME_A)
+    check("cycle", snaps[2], snaps[0], set(AOVS), FRAME_A)
