@@ -1,0 +1,81 @@
+// kernel_table.h -- every kernel the host launches under a timer, named ONCE (host code only).
+//
+// A Variant is a kernel's function pointer, typed with the kernel family's own signature, next to the symbol the profiler prints
+// for it.  Both come from one spelling of the template-id (POLARIS_VARIANT): the string polaris_hip_kernel_symbol reports, by which
+// bench.py names its roofline objects, cannot disagree with the kernel that ran, and the compiler checks a launch through the
+// pointer against the kernel's parameter list.  The tables list exactly the instantiations the library holds.
+#pragma once
+
+#include <utility>
+
+#include "kernels.h"
+
+namespace pol {
+
+template <class... P>
+struct Variant {
+	void (*fn)(P...);
+	const char *symbol;
+	constexpr Variant(void (*f)(P...), const char *s) : fn(f), symbol(s) {}
+	const void *address() const { return reinterpret_cast<const void *>(fn); } // what the occupancy and attribute calls take
+	template <class... A> // (a launch's error is left for hipGetLastError / hipPeekAtLastError)
+	void enqueue(uint32_t grid, uint32_t block, uint32_t lds_bytes, hipStream_t q, A &&...a) const {
+		fn<<<dim3(grid), dim3(block), lds_bytes, q>>>(std::forward<A>(a)...);
+	}
+};
+// Spell EVERY template argument, defaults included, NODES as its number: that is how the profiler prints the symbol.
+#define POLARIS_VARIANT(...) Variant(&pol::__VA_ARGS__, "pol::" #__VA_ARGS__)
+static_assert(kNodesGlobal == 0 && kNodesLdsTop == 1 && kNodesLdsAll == 2, "the k_trace entries below spell NODES as a number");
+
+// k_trace<ANY_HIT, STACK, NODES, ONE>: [any hit][stack 16 / 24 / 32][node records global / LDS top]; tiny-scene mode: [any hit][general / ONE]
+using TraceVariant = decltype(POLARIS_VARIANT(k_trace<false, 16, 0, false>));
+const TraceVariant kTrace[2][3][2] = {
+	{{POLARIS_VARIANT(k_trace<false, 16, 0, false>), POLARIS_VARIANT(k_trace<false, 16, 1, false>)},
+	 {POLARIS_VARIANT(k_trace<false, 24, 0, false>), POLARIS_VARIANT(k_trace<false, 24, 1, false>)},
+	 {POLARIS_VARIANT(k_trace<false, 32, 0, false>), POLARIS_VARIANT(k_trace<false, 32, 1, false>)}},
+	{{POLARIS_VARIANT(k_trace<true, 16, 0, false>), POLARIS_VARIANT(k_trace<true, 16, 1, false>)},
+	 {POLARIS_VARIANT(k_trace<true, 24, 0, false>), POLARIS_VARIANT(k_trace<true, 24, 1, false>)},
+	 {POLARIS_VARIANT(k_trace<true, 32, 0, false>), POLARIS_VARIANT(k_trace<true, 32, 1, false>)}}};
+const TraceVariant kTraceTiny[2][2] = {{POLARIS_VARIANT(k_trace<false, 16, 2, false>), POLARIS_VARIANT(k_trace<false, 16, 2, true>)},
+                                       {POLARIS_VARIANT(k_trace<true, 16, 2, false>), POLARIS_VARIANT(k_trace<true, 16, 2, true>)}};
+// The k_trace variant of the uploaded scene with what its launch needs, resolved once per upload (polaris_hip.hip, select_trace).
+struct TraceLaunch {
+	const TraceVariant *v = nullptr;
+	int block = WG;          // workgroup size (kTinyBlock in the tiny-scene mode)
+	uint32_t lds_bytes = 0;  // dynamic LDS block of a workgroup (tiny-scene mode: stack rows + tree + triangle records, plan_tiny_lds)
+	int resident_per_cu = 6; // workgroups of it a CU holds at once (occupancy API)
+};
+
+// k_shade<LDS, SORT, FIRST>: [LDS tables][first / sort / plain], the order of the shade timers; k_shade_wave<LDS>: [LDS tables]
+using ShadeVariant = decltype(POLARIS_VARIANT(k_shade<false, false, true>));
+const ShadeVariant kShade[2][3] = {
+	{POLARIS_VARIANT(k_shade<false, false, true>), POLARIS_VARIANT(k_shade<false, true, false>), POLARIS_VARIANT(k_shade<false, false, false>)},
+	{POLARIS_VARIANT(k_shade<true, false, true>), POLARIS_VARIANT(k_shade<true, true, false>), POLARIS_VARIANT(k_shade<true, false, false>)}};
+using ShadeWaveVariant = decltype(POLARIS_VARIANT(k_shade_wave<false>));
+const ShadeWaveVariant kShadeWave[2] = {POLARIS_VARIANT(k_shade_wave<false>), POLARIS_VARIANT(k_shade_wave<true>)};
+
+// k_trace_packet<ANY_HIT, CAMERA>
+using PacketVariant = decltype(POLARIS_VARIANT(k_trace_packet<false, true>));
+enum { kPacketCamera, kPacketClosest, kPacketAnyHit };
+const PacketVariant kPacket[3] = {POLARIS_VARIANT(k_trace_packet<false, true>), POLARIS_VARIANT(k_trace_packet<false, false>),
+                                  POLARIS_VARIANT(k_trace_packet<true, false>)};
+
+// the kernels of two variants: [MOMENTS], [M2]
+const decltype(POLARIS_VARIANT(k_resolve<false>)) kResolve[2] = {POLARIS_VARIANT(k_resolve<false>), POLARIS_VARIANT(k_resolve<true>)};
+const decltype(POLARIS_VARIANT(k_aggregate<false>)) kAggregate[2] = {POLARIS_VARIANT(k_aggregate<false>), POLARIS_VARIANT(k_aggregate<true>)};
+const decltype(POLARIS_VARIANT(k_reproject<false>)) kReproject[2] = {POLARIS_VARIANT(k_reproject<false>), POLARIS_VARIANT(k_reproject<true>)};
+
+// the kernels of one variant (k_intersect / k_occlusion: the plain traversal, option traversal = 0)
+const auto kIntersect = POLARIS_VARIANT(k_intersect);
+const auto kOcclusion = POLARIS_VARIANT(k_occlusion);
+const auto kGenerate = POLARIS_VARIANT(k_generate);
+const auto kScan = POLARIS_VARIANT(k_scan);
+const auto kFoldNee = POLARIS_VARIANT(k_fold_nee);
+const auto kTonemap = POLARIS_VARIANT(k_tonemap);
+const auto kGbuffer = POLARIS_VARIANT(k_gbuffer);
+const auto kDenoise = POLARIS_VARIANT(k_denoise);
+const auto kTemporal = POLARIS_VARIANT(k_temporal);
+const auto kVariance = POLARIS_VARIANT(k_variance);
+const auto kDenoiseVariance = POLARIS_VARIANT(k_denoise_variance);
+
+} // namespace pol

@@ -26,7 +26,7 @@
 #include <unistd.h>
 
 #include "device_mem.h"
-#include "kernels.h"
+#include "kernel_table.h"
 #include "polaris_hip.h"
 
 using namespace pol;
@@ -99,10 +99,9 @@ struct polaris_hip_tracer {
 	int node_mode = kNodesGlobal; // where k_trace reads node records from (kernels.h NodeMode), resolved at upload
 	int opt_node_mode = -1;       // -1 = by scene size
 	uint32_t tex_bytes = 0; // size of the uploaded texture blob (without its padding)
-	int trace_resident_per_cu = 6, occl_resident_per_cu = 6; // workgroups of the selected k_trace<closest | any hit> variant a CU holds at once (occupancy API, at upload)
+	TraceLaunch trace[2];   // [any hit]: the scene's k_trace variant with its block size, dynamic LDS bytes and residency, resolved at upload (select_trace)
 	bool tiny_one = false;        // tiny-scene mode: the scene is one instance whose boxes all bound their subtrees (kernels.h k_trace, ONE); option tiny_one = 0 keeps the general variant
 	int opt_tiny_one = 1;
-	uint32_t tiny_lds_bytes = 0;  // tiny-scene mode: the dynamic LDS block of a k_trace workgroup (stack rows + tree + triangle records: plan_tiny_lds)
 	int opt_lds_tris = -1;        // tiny-scene mode: triangle records kept in LDS; -1 = as many as fit, 0 = none (A/B aid)
 
 	// camera (tracer.go:175-179)
@@ -204,7 +203,7 @@ struct polaris_hip_tracer {
 	std::vector<Pending> merge_pending; // launches on the merge stream (under merge_mu)
 	std::vector<hipEvent_t> event_pool;
 	std::map<std::string, KernelTimer> timers;
-	std::map<std::string, std::string> timer_symbol; // timer name -> the kernel symbol it last bracketed (polaris_hip_kernel_symbol)
+	std::map<std::string, const char *> timer_symbol; // timer name -> the kernel symbol it last bracketed (polaris_hip_kernel_symbol)
 	int last_shade_timer[POLARIS_MAX_BOUNCES] = {};            // per bounce of the last Trace: 0 shade_first, 1 shade_sort, 2 shade_plain, 3 shade_wave
 	uint64_t last_shade_counts[3 * POLARIS_MAX_BOUNCES] = {}; // per bounce of the last Trace: shaded hits, shaded misses, emitter hits
 	hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_fork = nullptr;
@@ -256,15 +255,16 @@ int dev_upload(polaris_hip_tracer *h, DevPool &pool, T **out, const void *src, s
 	return POLARIS_OK;
 }
 
-// Bracket a launch with events when time_kernels is on.
+// Bracket a launch with events when time_kernels is on (name = null: never), and note the symbol the timer brackets.
 struct Timed {
 	polaris_hip_tracer *h;
 	const char *name;
 	hipStream_t q;
 	bool on_merge; // a launch on the merge stream: the caller holds merge_mu (not mu), so the event pool is not touched
 	hipEvent_t a = nullptr, b = nullptr;
-	Timed(polaris_hip_tracer *h_, const char *n, hipStream_t q_ = nullptr, bool merge = false) : h(h_), name(n), q(q_ ? q_ : h_->stream), on_merge(merge) {
-		if (!h->opt_time_kernels) return;
+	Timed(polaris_hip_tracer *h_, const char *n, const char *symbol, hipStream_t q_, bool merge = false) : h(h_), name(n), q(q_), on_merge(merge) {
+		if (!h->opt_time_kernels || !name) return;
+		if (symbol) h->timer_symbol[name] = symbol; // (null: a bracket around no kernel, or one on the merge stream -- the map belongs to mu)
 		auto get = [&]() {
 			hipEvent_t e;
 			if (!on_merge && !h->event_pool.empty()) { e = h->event_pool.back(); h->event_pool.pop_back(); }
@@ -280,6 +280,14 @@ struct Timed {
 		(on_merge ? h->merge_pending : h->pending).push_back({name, a, b});
 	}
 };
+
+// THE launch of a kernel on stream q, bracketed by the named timer, which remembers the variant's symbol; returns the launch's error (also left for hipGetLastError).
+template <class... P, class... A>
+hipError_t launch(polaris_hip_tracer *h, const char *timer, hipStream_t q, const Variant<P...> &v, uint32_t grid, uint32_t block, uint32_t lds_bytes, A &&...a) {
+	Timed t(h, timer, v.symbol, q);
+	v.enqueue(grid, block, lds_bytes, q, std::forward<A>(a)...);
+	return hipPeekAtLastError();
+}
 
 void collect_timers(polaris_hip_tracer *h) { // caller holds mu; the main stream must be idle
 	auto take = [&](std::vector<polaris_hip_tracer::Pending> &list, bool may_be_running) {
@@ -454,50 +462,28 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 	if (int rc = ensure_plane(h, h->gb_albedo, F)) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
-	{
-		Timed t(h, "gbuffer");
-		if (h->opt_time_kernels) h->timer_symbol["gbuffer"] = "pol::k_gbuffer";
-		hipLaunchKernelGGL(k_gbuffer, dim3(grid_for(F)), dim3(WG), 0, h->stream, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo);
-	}
+	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo);
 	HIP_TRY(h, hipGetLastError());
 	h->gb_valid = true;
 	return POLARIS_OK;
 }
 
-// k_trace<ANY_HIT, STACK, NODES> of the uploaded scene: STACK from the exact depth the scene needs, NODES from its size
-// (kernels.h, NodeMode).  fn = the kernel (for the occupancy query), block = its workgroup size.
-template <bool ANY_HIT>
-const void *trace_kernel(polaris_hip_tracer *h, int *block) {
-	*block = h->node_mode == kNodesLdsAll ? kTinyBlock : WG;
-	if (h->node_mode == kNodesLdsAll) return h->tiny_one ? (const void *)k_trace<ANY_HIT, 16, kNodesLdsAll, true> : (const void *)k_trace<ANY_HIT, 16, kNodesLdsAll, false>;
-	const bool top = h->node_mode == kNodesLdsTop;
-	if (h->max_stack <= 16) return top ? (const void *)k_trace<ANY_HIT, 16, kNodesLdsTop> : (const void *)k_trace<ANY_HIT, 16, kNodesGlobal>;
-	if (h->max_stack <= 24) return top ? (const void *)k_trace<ANY_HIT, 24, kNodesLdsTop> : (const void *)k_trace<ANY_HIT, 24, kNodesGlobal>;
-	return top ? (const void *)k_trace<ANY_HIT, 32, kNodesLdsTop> : (const void *)k_trace<ANY_HIT, 32, kNodesGlobal>;
+// The scene's k_trace variants (closest hit, any hit) into the handle: STACK from the exact depth the scene needs, NODES from its
+// size (kernels.h, NodeMode), ONE in the tiny-scene mode; with the workgroup size.  plan_tiny_lds and trace_occupancy fill in the rest.
+void select_trace(polaris_hip_tracer *h) {
+	const bool tiny = h->node_mode == kNodesLdsAll;
+	for (int any = 0; any < 2; any++)
+		h->trace[any] = TraceLaunch{tiny ? &kTraceTiny[any][h->tiny_one] : &kTrace[any][h->max_stack <= 16 ? 0 : (h->max_stack <= 24 ? 1 : 2)][h->node_mode == kNodesLdsTop],
+		                            tiny ? kTinyBlock : WG, 0, 6};
 }
 
-// the symbol rocprofv3 prints for that kernel (bench.py names its roofline objects by it)
-template <bool ANY_HIT>
-std::string trace_symbol(polaris_hip_tracer *h) {
-	char buf[96];
-	const char *a = ANY_HIT ? "true" : "false";
-	if (h->node_mode == kNodesLdsAll) snprintf(buf, sizeof buf, "pol::k_trace<%s, 16, %d, %s>", a, (int)kNodesLdsAll, h->tiny_one ? "true" : "false");
-	else snprintf(buf, sizeof buf, "pol::k_trace<%s, %d, %d, false>", a, h->max_stack <= 16 ? 16 : (h->max_stack <= 24 ? 24 : 32), h->node_mode);
-	return buf;
-}
-
-// camera: the closest-hit launch of a batch's camera rays -- their common origin comes from the handle's one-record buffer
-// (kernels.h k_trace, o_mask), the origin stream is neither written nor read for them.
-template <bool ANY_HIT>
-hipError_t launch_trace(polaris_hip_tracer *h, polaris_hip_tracer::Pipe &P, const Streams &st_in, uint32_t grid, uint32_t chunks, float4 *acc, bool camera = false) {
-	int block = WG;
-	const void *fn = trace_kernel<ANY_HIT>(h, &block);
-	Streams st = st_in;
+// The scene's k_trace variant over `chunks` chunks of st on stream q, under `timer` (null: a probe's launch, untimed).  camera: the closest-hit launch of a batch's
+// camera rays -- their common origin comes from the handle's one-record buffer (kernels.h k_trace, o_mask), the origin stream is neither written nor read for them.
+hipError_t launch_trace(polaris_hip_tracer *h, const char *timer, bool any_hit, hipStream_t q, Streams st, uint32_t grid, uint32_t chunks, float4 *acc, bool camera = false) {
+	const TraceLaunch &T = h->trace[any_hit];
 	uint32_t o_mask = ~0u;
-	if (camera && !ANY_HIT) { st.ray_o = h->d_cam_o; o_mask = 0u; }
-	unsigned long long *stats = h->d_stats;
-	void *args[] = {(void *)&st, (void *)&h->bvh, (void *)&chunks, (void *)&acc, (void *)&stats, (void *)&o_mask};
-	return hipLaunchKernel(fn, dim3(grid), dim3(block), args, h->node_mode == kNodesLdsAll ? h->tiny_lds_bytes : 0, P.q);
+	if (camera && !any_hit) { st.ray_o = h->d_cam_o; o_mask = 0u; }
+	return launch(h, timer, q, *T.v, grid, (uint32_t)T.block, T.lds_bytes, st, h->bvh, chunks, acc, h->d_stats, o_mask);
 }
 
 // Tiny-scene mode: lay out the dynamic LDS block of a k_trace workgroup for the uploaded scene (kernels.h, k_trace) -- the stack
@@ -524,39 +510,67 @@ int plan_tiny_lds(polaris_hip_tracer *h, size_t n_slots) {
 	for (;;) {
 		h->bvh.tiny_stack_off = stack_off(tris);
 		h->bvh.lds_tris = tris;
-		h->tiny_lds_bytes = h->bvh.tiny_stack_off + rows * kRowBytes;
+		h->trace[0].lds_bytes = h->trace[1].lds_bytes = h->bvh.tiny_stack_off + rows * kRowBytes;
 		int worst = 8;
-		for (int any = 0; any < 2; any++) {
-			int block_unused = 0;
-			const void *fn = any ? trace_kernel<true>(h, &block_unused) : trace_kernel<false>(h, &block_unused);
+		for (const TraceLaunch &T : h->trace) {
 			// (the attribute belongs to the kernel, not to this handle: always the most any scene may ask for, so that handles
 			// with different scenes in one process do not lower it under each other)
-			HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(half - slack)));
+			HIP_TRY(h, hipFuncSetAttribute(T.v->address(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(half - slack)));
 			int n = 0;
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kTinyBlock, h->tiny_lds_bytes) != hipSuccess) { (void)hipGetLastError(); n = 2; } // (no answer: trust the arithmetic)
+			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, T.v->address(), T.block, T.lds_bytes) != hipSuccess) { (void)hipGetLastError(); n = 2; } // (no answer: trust the arithmetic)
 			worst = std::min(worst, n);
 		}
 		if (worst >= 2 || tris == 0) break;
 		tris = tris > 32 ? tris - 32 : 0; // the allocation granularity was coarser than assumed: give some back
 	}
-	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] tiny mode: %u stack rows at %u, %u pair records, %u of %zu triangle records in LDS (%u bytes per workgroup)\n", rows, h->bvh.tiny_stack_off, h->bvh.num_pairs, h->bvh.lds_tris, n_slots, h->tiny_lds_bytes);
+	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] tiny mode: %u stack rows at %u, %u pair records, %u of %zu triangle records in LDS (%u bytes per workgroup)\n", rows, h->bvh.tiny_stack_off, h->bvh.num_pairs, h->bvh.lds_tris, n_slots, h->trace[0].lds_bytes);
 	return POLARIS_OK;
 }
 
-// Resident workgroups per CU of the k_trace variant launch_trace<ANY_HIT> picks.
-template <bool ANY_HIT>
-int trace_occupancy(polaris_hip_tracer *h) {
-	int block = WG, n = 0;
-	const void *fn = trace_kernel<ANY_HIT>(h, &block);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, block, h->node_mode == kNodesLdsAll ? h->tiny_lds_bytes : 0) != hipSuccess || n < 1) n = h->node_mode == kNodesLdsAll ? 1 : (h->max_stack <= 24 ? 6 : 5);
-	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] k_trace<%d> node mode %d: %d resident workgroups of %d threads per CU\n", (int)ANY_HIT, h->node_mode, n, block);
+// Resident workgroups per CU of the scene's k_trace variant.
+int trace_occupancy(polaris_hip_tracer *h, bool any_hit) {
+	const TraceLaunch &T = h->trace[any_hit];
+	int n = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, T.v->address(), T.block, T.lds_bytes) != hipSuccess || n < 1) n = h->node_mode == kNodesLdsAll ? 1 : (h->max_stack <= 24 ? 6 : 5);
+	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] k_trace<%d> node mode %d: %d resident workgroups of %d threads per CU\n", (int)any_hit, h->node_mode, n, T.block);
 	return std::min(n, 8);
 }
 
-// One wavefront batch: K samples starting at sample s0, on pipeline p.
+// What one bounce of a Trace launches.  Every input is fixed per Trace (options, request) or per upload: planned once, before the batches.
+// isect_packet / occl_packet: the wave-packet kernel for the bounce's closest-hit / shadow rays; null: the scene's k_trace variant
+// (traversal = 1) or k_intersect / k_occlusion (traversal = 0).  Exactly one of shade / shade_wave is set.
+struct BouncePlan {
+	const PacketVariant *isect_packet = nullptr, *occl_packet = nullptr;
+	const ShadeVariant *shade = nullptr;
+	const ShadeWaveVariant *shade_wave = nullptr;
+	int shade_timer = 0; // index into kShadeTimer
+};
+// one timer per kernel symbol: shade_first = k_shade<.., FIRST> (camera rays), shade_sort = k_shade<.., SORT, ..> (bounce rays in
+// class order), shade_plain = k_shade<.., false, false>, shade_wave = k_shade_wave
+const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"};
+
+void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, BouncePlan *plan) {
+	// LDS-table variant of the shade kernels: only when all three tables fit (kernels.h, stage_scene)
+	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
+	                    h->scene.num_textures <= kLdsTextures;
+	for (uint32_t b = 0; b < r->num_bounces; b++) {
+		BouncePlan &pl = plan[b] = BouncePlan{};
+		if (b == 0 && h->packet_primary) pl.isect_packet = &kPacket[kPacketCamera];
+		if ((int)b < h->opt_packet_shadow) pl.occl_packet = &kPacket[kPacketAnyHit];
+		const bool wave = h->opt_shade_wave && b > 0 && (int)b >= (h->opt_shade_wave_from >= 0 ? h->opt_shade_wave_from : (int)r->min_bounces_for_rr + 1); // (never the first bounce: k_shade_wave reads the previous step's emit masks)
+		// bounce rays are shaded in the order of their material's shading class (kernels.h, k_shade SORT); camera rays are
+		// coherent as they come (64 neighbouring pixels per wave)
+		const bool sorted = b > 0 && h->scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
+		pl.shade_timer = wave ? 3 : (b == 0 ? 0 : (sorted ? 1 : 2));
+		if (wave) pl.shade_wave = &kShadeWave[staged];
+		else pl.shade = &kShade[staged][pl.shade_timer];
+	}
+}
+
+// One wavefront batch: K samples starting at sample s0, on pipeline p, by the Trace's plan.
 // Returns the first launch error of the batch (checked after every batch by the caller: a failed launch in batch 1 is reported
 // before batch 2 is queued behind it).
-hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest *r, uint32_t s0, uint32_t K, uint32_t N, uint32_t Npad,
+hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest *r, const BouncePlan *plan, uint32_t s0, uint32_t K, uint32_t N, uint32_t Npad,
                         bool exact, hipEvent_t resolve_after) {
 	hipError_t first_err = hipSuccess;
 	auto note = [&](hipError_t e) { if (first_err == hipSuccess && e != hipSuccess) first_err = e; };
@@ -566,28 +580,20 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	hipStream_t q = P.q;
 	P.st.hit12 = h->opt_hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
 	P.st.o12 = h->opt_o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
-	{
-		Timed t(h, "generate", q);
-		if (h->opt_time_kernels) h->timer_symbol["generate"] = "pol::k_generate";
-		hipLaunchKernelGGL(k_generate, dim3(wgs), dim3(WG), 0, q, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->W, r->block_y,
-		                   exact ? 0 : 1, (B > 0 && (h->packet_primary || h->opt_traversal)) ? 0 : 1); // (neither the wave-packet kernel nor k_trace's camera launch reads the origin stream)
-	}
+	note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->W, r->block_y,
+	            exact ? 0 : 1, (B > 0 && (h->packet_primary || h->opt_traversal)) ? 0 : 1)); // (neither the wave-packet kernel nor k_trace's camera launch reads the origin stream)
 	ShadeArgs A{};
 	A.seeds = h->d_seeds; A.seed_stride = stride; A.first_sample = s0;
 	A.N = N; A.Npad = Npad; A.W = h->W; A.blockY = r->block_y;
 	A.min_rr = r->min_bounces_for_rr;
 	A.exact = exact ? 1 : 0;
-	// LDS-table variant of the shade kernels: only when all three tables fit (kernels.h, stage_scene)
-	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
-	                    h->scene.num_textures <= kLdsTextures;
 	A.acc = exact ? h->trace_acc : P.st.lsum;
 	// persistent grid: chunks are dealt to workgroups statically, so a workgroup that is not resident
 	// from the start begins with its whole share still to do -- the grid must not exceed what the GPU
 	// holds at once (measured: 8 workgroups per CU where 6 fit cost the closest-hit kernel 12 %).  One
 	// batch at a time: exactly the resident capacity.  Several batches in flight: two thirds of it per
 	// launch (the launches share the CUs; measured flat to +5 % across the bench scenes).
-	// (LDS: 16-entry stack: 16 KB per
-	// workgroup -> 8 by LDS, VGPRs allow 7-8 waves/SIMD; 32-entry: 5)
+	// (LDS: 16-entry stack: 16 KB per workgroup -> 8 by LDS, VGPRs allow 7-8 waves/SIMD; 32-entry: 5)
 	auto grid_of = [&](int resident) {
 		uint32_t per_cu = (uint32_t)std::max(1, resident);
 		if (std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes) > 1 && !exact && per_cu > 2) per_cu = std::max(2u, per_cu * 2u / 3u);
@@ -602,94 +608,44 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 		if (h->opt_trace_grid > 0) return std::min<uint32_t>(wgs, (uint32_t)h->opt_trace_grid); // (A/B aid: an absolute persistent grid)
 		return std::min<uint32_t>(wgs, (uint32_t)h->num_cus * per_cu);
 	};
-	const uint32_t persistent = grid_of(h->trace_resident_per_cu), persistent_occl = grid_of(h->occl_resident_per_cu);
+	const uint32_t persistent = grid_of(h->trace[0].resident_per_cu), persistent_occl = grid_of(h->trace[1].resident_per_cu);
 	for (uint32_t b = 0; b < B; b++) {
+		const BouncePlan &pl = plan[b];
 		Streams S = P.st; // (in place: k_shade / k_shade_wave read a chunk's rays before they write into it)
 		if (!exact) { S.occ_e = P.nee[b]; S.vis = P.vis[b]; S.cnt_occ = P.cnt_occ_b[b]; } // this bounce's NEE records, visibility bytes and shadow-ray counts stay until k_fold_nee
 		float4 *const occl_acc = exact ? A.acc : nullptr;                // batched: unoccluded rays only mark their record (deferred)
-		{
-			Timed t(h, (b == 0 && h->packet_primary) ? "intersect_packet" : "intersect", q);
-			if (h->opt_time_kernels) {
-				if (b == 0 && h->packet_primary) h->timer_symbol["intersect_packet"] = "pol::k_trace_packet<false, true>";
-				else h->timer_symbol["intersect"] = h->opt_traversal ? trace_symbol<false>(h) : std::string("pol::k_intersect");
-			}
-			if (b == 0 && h->packet_primary)
-				hipLaunchKernelGGL((k_trace_packet<false, true>), dim3(wgs), dim3(WG), 0, q, S, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
-			else if (h->opt_traversal)
-				note(launch_trace<false>(h, P, S, persistent, wgs, nullptr, b == 0));
-			else
-				hipLaunchKernelGGL(k_intersect, dim3(wgs), dim3(WG), 0, q, S, h->bvh);
-		}
+		if (pl.isect_packet) note(launch(h, "intersect_packet", q, *pl.isect_packet, wgs, WG, 0, S, h->bvh, nullptr, h->d_stats, h->cam.eye));
+		else if (h->opt_traversal) note(launch_trace(h, "intersect", false, q, S, persistent, wgs, nullptr, b == 0));
+		else note(launch(h, "intersect", q, kIntersect, wgs, WG, 0, S, h->bvh));
 		A.bounce = b;
 		A.last_bounce = (b + 1 == B) ? 1 : 0;
 		A.emask_in = b == 0 ? nullptr : P.st.emask[(b + 1) & 1]; // the masks the previous step wrote
 		A.emask_out = P.st.emask[b & 1];
-		{
-			// one timer per kernel symbol: shade_first = k_shade<.., FIRST> (camera rays), shade_sort = k_shade<.., SORT, ..> (bounce
-			// rays in class order), shade_plain = k_shade<.., false, false>, shade_wave = k_shade_wave
-			const bool wave = h->opt_shade_wave && b > 0 && (int)b >= (h->opt_shade_wave_from >= 0 ? h->opt_shade_wave_from : (int)r->min_bounces_for_rr + 1); // (never the first bounce: k_shade_wave reads the previous step's emit masks)
-			// bounce rays are shaded in the order of their material's shading class (kernels.h, k_shade SORT); camera rays are
-			// coherent as they come (64 neighbouring pixels per wave)
-			const bool sorted = b > 0 && h->scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
-			const int which = wave ? 3 : (b == 0 ? 0 : (sorted ? 1 : 2));
-			static const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"};
-			h->last_shade_timer[b] = which;
-			Timed t(h, kShadeTimer[which], q);
-			if (h->opt_time_kernels) {
-				const char *l = staged ? "true" : "false";
-				char buf[64];
-				if (wave) snprintf(buf, sizeof buf, "pol::k_shade_wave<%s>", l);
-				else snprintf(buf, sizeof buf, "pol::k_shade<%s, %s, %s>", l, which == 1 ? "true" : "false", which == 0 ? "true" : "false");
-				h->timer_symbol[kShadeTimer[which]] = buf;
-			}
-			if (wave) {
-				// persistent waves pull groups of kSparseGroup chunks: no more workgroups than the GPU holds at once (4 per CU at
-				// the kernel's register count) nor than there are groups for their 4 waves
-				const uint32_t groups = (wgs + kSparseGroup - 1) / kSparseGroup;
-				const uint32_t grid = std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->opt_shade_wgs_per_cu)));
-				if (staged) hipLaunchKernelGGL(k_shade_wave<true>, dim3(grid), dim3(WG), 0, q, S, h->scene, A, wgs);
-				else hipLaunchKernelGGL(k_shade_wave<false>, dim3(grid), dim3(WG), 0, q, S, h->scene, A, wgs);
-			} else {
-				const void *fn;
-				if (b == 0) fn = staged ? (const void *)k_shade<true, false, true> : (const void *)k_shade<false, false, true>;
-				else if (sorted) fn = staged ? (const void *)k_shade<true, true, false> : (const void *)k_shade<false, true, false>;
-				else fn = staged ? (const void *)k_shade<true, false, false> : (const void *)k_shade<false, false, false>;
-				void *args[] = {(void *)&S, (void *)&h->scene, (void *)&A};
-				note(hipLaunchKernel(fn, dim3(wgs), dim3(WG), args, 0, q));
-			}
-		}
-		{
-			Timed t(h, "scan", q);
-			hipLaunchKernelGGL(k_scan, dim3(K), dim3(1024), 0, q, S, wgs_per_sample, b, A.last_bounce ? 0 : 1, h->d_stats);
-		}
-		{
-			Timed t(h, "occlusion", q);
-			if (h->opt_time_kernels) h->timer_symbol["occlusion"] = (int)b < h->opt_packet_shadow ? std::string("pol::k_trace_packet<true, false>") : (h->opt_traversal ? trace_symbol<true>(h) : std::string("pol::k_occlusion"));
-			if ((int)b < h->opt_packet_shadow)
-				hipLaunchKernelGGL(k_trace_packet<true>, dim3(wgs), dim3(WG), 0, q, S, h->bvh, occl_acc, h->d_stats, h->cam.eye);
-			else if (h->opt_traversal)
-				note(launch_trace<true>(h, P, S, persistent_occl, wgs, occl_acc));
-			else
-				hipLaunchKernelGGL(k_occlusion, dim3(wgs), dim3(WG), 0, q, S, h->bvh, occl_acc, h->d_stats);
-		}
+		if (pl.shade_wave) {
+			// persistent waves pull groups of kSparseGroup chunks: no more workgroups than the GPU holds at once (4 per CU at
+			// the kernel's register count) nor than there are groups for their 4 waves
+			const uint32_t groups = (wgs + kSparseGroup - 1) / kSparseGroup;
+			const uint32_t grid = std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->opt_shade_wgs_per_cu)));
+			note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade_wave, grid, WG, 0, S, h->scene, A, wgs));
+		} else note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade, wgs, WG, 0, S, h->scene, A));
+		note(launch(h, "scan", q, kScan, K, 1024, 0, S, wgs_per_sample, b, A.last_bounce ? 0 : 1, h->d_stats));
+		if (pl.occl_packet) note(launch(h, "occlusion", q, *pl.occl_packet, wgs, WG, 0, S, h->bvh, occl_acc, h->d_stats, h->cam.eye));
+		else if (h->opt_traversal) note(launch_trace(h, "occlusion", true, q, S, persistent_occl, wgs, occl_acc));
+		else note(launch(h, "occlusion", q, kOcclusion, wgs, WG, 0, S, h->bvh, occl_acc, h->d_stats));
 	}
 	if (!exact && B > 0) { // accumulateEmissiveSamples of the whole batch: the marked NEE records of every bounce into the per-path radiance
 		FoldArgs F{};
 		for (uint32_t b = 0; b < B; b++) { F.nee[b] = P.nee[b]; F.vis[b] = P.vis[b]; F.cnt[b] = P.cnt_occ_b[b]; }
 		F.bounces = B;
-		Timed t(h, "fold", q);
-		if (h->opt_time_kernels) h->timer_symbol["fold"] = "pol::k_fold_nee";
-		hipLaunchKernelGGL(k_fold_nee, dim3(wgs), dim3(WG), 0, q, F, P.st.lsum);
+		note(launch(h, "fold", q, kFoldNee, wgs, WG, 0, F, P.st.lsum));
 	}
 	if (!exact) {
 		// batches resolve into the trace accumulator in sample order: wait for the previous batch's resolve
 		if (resolve_after) note(hipStreamWaitEvent(q, resolve_after, 0));
-		Timed t(h, "resolve", q);
-		if (h->opt_moments) hipLaunchKernelGGL(k_resolve<true>, dim3(grid_for(N)), dim3(WG), 0, q, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W);
-		else hipLaunchKernelGGL(k_resolve<false>, dim3(grid_for(N)), dim3(WG), 0, q, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W);
+		note(launch(h, "resolve", q, kResolve[h->opt_moments], grid_for(N), WG, 0, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W));
 	}
 	note(hipEventRecord(P.done, q));
-	note(hipGetLastError()); // (launches through hipLaunchKernelGGL report here)
+	note(hipGetLastError()); // (whatever a launch left)
 	return first_err;
 }
 
@@ -985,14 +941,14 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	                     L.big_leaves == 0 && L.max_stack <= 16;
 	h->node_mode = tiny_ok ? kNodesLdsAll : (L.pairs.size() <= (size_t)(POLARIS_LDS_TOP_MAX_PAIRS) ? kNodesLdsTop : kNodesGlobal);
 	if (h->opt_node_mode >= 0 && (h->opt_node_mode != kNodesLdsAll || tiny_ok)) h->node_mode = h->opt_node_mode;
-	h->tiny_lds_bytes = 0;
 	h->tiny_one = h->node_mode == kNodesLdsAll && h->opt_tiny_one && h->bvh.root_is_instance && L.unbounded_boxes == 0;
+	select_trace(h);
 	if (h->node_mode == kNodesLdsAll) {
 		if (int prc = plan_tiny_lds(h, L.tris.size())) return prc;
 		if (h->opt_packet_primary < 0 && h->bvh.lds_tris > 0) h->packet_primary = false;
 	}
-	h->trace_resident_per_cu = trace_occupancy<false>(h);
-	h->occl_resident_per_cu = trace_occupancy<true>(h);
+	h->trace[0].resident_per_cu = trace_occupancy(h, false);
+	h->trace[1].resident_per_cu = trace_occupancy(h, true);
 	h->have_scene = true;
 	return POLARIS_OK;
 }
@@ -1172,10 +1128,13 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 		polaris_hip_tracer *h; int n; bool armed = true;
 		~DrainOnError() { if (armed) for (int p = 0; p < n; p++) (void)hipStreamSynchronize(h->pipe[p].q); }
 	} drain{h, n_pipes};
+	BouncePlan plan[POLARIS_MAX_BOUNCES];
+	plan_bounces(h, r, plan);
+	for (uint32_t b = 0; b < B && spp; b++) h->last_shade_timer[b] = plan[b].shade_timer;
 	uint32_t bi = 0;
 	for (uint32_t s0 = 0; s0 < spp; s0 += K, bi++) {
 		const int p = (int)(bi % (uint32_t)n_pipes), prev = (int)((bi + (uint32_t)n_pipes - 1) % (uint32_t)n_pipes);
-		HIP_TRY(h, launch_batch(h, p, r, s0, std::min(K, spp - s0), N, Npad, exact, (n_pipes > 1 && bi > 0) ? h->pipe[prev].done : nullptr));
+		HIP_TRY(h, launch_batch(h, p, r, plan, s0, std::min(K, spp - s0), N, Npad, exact, (n_pipes > 1 && bi > 0) ? h->pipe[prev].done : nullptr));
 	}
 	for (int p = 1; p < n_pipes; p++) HIP_TRY(h, hipStreamWaitEvent(q, h->pipe[p].done, 0)); // join
 	HIP_TRY(h, hipGetLastError());
@@ -1298,9 +1257,8 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 		}
 	}
 	{
-		Timed t(dst, "aggregate", q, true);
-		if (dst->opt_moments) hipLaunchKernelGGL(k_aggregate<true>, dim3(grid_for(n)), dim3(WG), 0, q, rows, dst->frame_acc + off, (uint32_t)n);
-		else hipLaunchKernelGGL(k_aggregate<false>, dim3(grid_for(n)), dim3(WG), 0, q, rows, dst->frame_acc + off, (uint32_t)n);
+		Timed t(dst, "aggregate", nullptr, q, true);
+		kAggregate[dst->opt_moments].enqueue(grid_for(n), WG, 0, q, rows, dst->frame_acc + off, (uint32_t)n);
 	}
 	if (hipGetLastError() != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: kernel launch failed");
 	dst->merge_counts[branch]++;
@@ -1547,12 +1505,7 @@ int polaris_hip_merge_device(polaris_hip_tracer *dst, const void *device_rows, c
 	HIP_TRY(dst, hipSetDevice(dst->device));
 	const size_t off = (size_t)r->block_y * dst->W, n = (size_t)r->block_h * dst->W;
 	std::lock_guard<std::mutex> lk_merge(dst->merge_mu); // the frame accumulator is the merge stream's
-	if (dst->opt_moments)
-		hipLaunchKernelGGL(k_aggregate<true>, dim3(grid_for(n)), dim3(WG), 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off,
-		                   (uint32_t)n);
-	else
-		hipLaunchKernelGGL(k_aggregate<false>, dim3(grid_for(n)), dim3(WG), 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off,
-		                   (uint32_t)n);
+	kAggregate[dst->opt_moments].enqueue(grid_for(n), WG, 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off, (uint32_t)n);
 	HIP_TRY(dst, hipGetLastError());
 	dst->merge_counts[POLARIS_MERGE_DEVICE_STRIP]++;
 	HIP_TRY(dst, hipStreamSynchronize(dst->merge_stream)); // the caller owns device_rows: do not outlive it
@@ -1603,21 +1556,17 @@ void launch_denoise(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, flo
                     const PolarisDenoiseParams &p) {
 	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
 	{
-		Timed t(h, "denoise", q);
-		if (h->opt_time_kernels) h->timer_symbol["denoise"] = "pol::k_denoise";
+		Timed t(h, "denoise", kDenoise.symbol, q); // (one bracket around the K iterations)
 		const uint32_t K = p.iterations;
 		const float4 *in = nullptr;
 		for (uint32_t k = 0; k < K; k++) {
 			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
 			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, p.sigma_luminance);
-			hipLaunchKernelGGL(k_denoise, dim3(grid_for(n)), dim3(WG), 0, q, acc, weight, guide, albedo, in, dst, W, y0, y1, it, k + 1 == K ? 1 : 0);
+			kDenoise.enqueue(grid_for(n), WG, 0, q, acc, weight, guide, albedo, in, dst, W, y0, y1, it, k + 1 == K ? 1 : 0);
 			in = dst;
 		}
 	}
-	{
-		Timed t(h, "tonemap", q);
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
-	}
+	(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
 }
 
 // polaris_hip_sync_framebuffer with denoising on (caller holds mu; request checked): G-buffer if stale, K filter iterations over
@@ -1654,21 +1603,14 @@ hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *
                       const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
                       float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr) {
 	const size_t F = (size_t)W * H;
-	Timed t(h, "reproject", q);
-	if (prior2 && (!hist || !hvar || !tp_projectable(hcam) || p.max_history == 0)) {
+	const bool none = !hist || !tp_projectable(hcam) || p.max_history == 0; // no history anywhere: m = 0
+	const bool m2 = prior2 && hvar && !none;                                // (else the PRIOR as without variance guidance, PRIOR2 = 0)
+	Timed t(h, "reproject", none ? nullptr : kReproject[m2].symbol, q);
+	if (prior2 && !m2)
 		if (hipError_t e = hipMemsetAsync(prior2, 0, F * sizeof(float4), q)) return e;
-		prior2 = nullptr; // (the PRIOR as without variance guidance)
-	}
-	if (!hist || !tp_projectable(hcam) || p.max_history == 0) return hipMemsetAsync(prior, 0, F * sizeof(float4), q); // no history anywhere: m = 0
-	if (prior2) {
-		if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject<true>";
-		hipLaunchKernelGGL(k_reproject<true>, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
-		                   p.normal_threshold, p.depth_threshold, prior, hvar, prior2);
-	} else {
-		if (h->opt_time_kernels) h->timer_symbol["reproject"] = "pol::k_reproject<false>";
-		hipLaunchKernelGGL(k_reproject<false>, dim3(grid_for(F)), dim3(WG), 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history,
-		                   p.normal_threshold, p.depth_threshold, prior, (const float4 *)nullptr, (float4 *)nullptr);
-	}
+	if (none) return hipMemsetAsync(prior, 0, F * sizeof(float4), q);
+	kReproject[m2].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold, p.depth_threshold,
+	                       prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr);
 	return hipGetLastError();
 }
 
@@ -1680,36 +1622,25 @@ void launch_variance(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, fl
                      const float4 *guide, const float4 *albedo, float4 *var, float4 *ping, float4 *pong, float4 *out, uchar4 *fb, uint32_t W,
                      uint32_t y0, uint32_t y1, float exposure, const PolarisDenoiseParams &p, const PolarisVarianceParams &v) {
 	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
-	{
-		Timed t(h, "variance", q);
-		if (h->opt_time_kernels) h->timer_symbol["variance"] = "pol::k_variance";
-		const DnIter it0 = dn_iter(0, p.normal_power_log2, p.sigma_depth, 0.0f);
-		hipLaunchKernelGGL(k_variance, dim3(grid_for(n)), dim3(WG), 0, q, acc, nf, weight, tp, prior2, guide, albedo, var, W, y0, y1, it0, v.min_samples);
-	}
+	(void)launch(h, "variance", q, kVariance, grid_for(n), WG, 0, acc, nf, weight, tp, prior2, guide, albedo, var, W, y0, y1, dn_iter(0, p.normal_power_log2, p.sigma_depth, 0.0f), v.min_samples);
 	const float4 *c = tp ? tp : acc; // (the filter's and the tone-map's input: TEMPORAL with weight 1, or the accumulator)
 	const float cw = tp ? 1.0f : weight;
 	if (p.iterations == 0) {
-		Timed t(h, "tonemap", q);
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, c + off, fb + off, (uint32_t)n, cw, exposure);
+		(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, c + off, fb + off, (uint32_t)n, cw, exposure);
 		return;
 	}
 	{
-		Timed t(h, "denoise_variance", q);
-		if (h->opt_time_kernels) h->timer_symbol["denoise_variance"] = "pol::k_denoise_variance";
+		Timed t(h, "denoise_variance", kDenoiseVariance.symbol, q); // (one bracket around the K iterations)
 		const uint32_t K = p.iterations;
 		const float4 *in = nullptr;
 		for (uint32_t k = 0; k < K; k++) {
 			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
 			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, 0.0f);
-			hipLaunchKernelGGL(k_denoise_variance, dim3(grid_for(n)), dim3(WG), 0, q, c, cw, (const float4 *)var, guide, albedo, in, dst, W, y0, y1, it,
-			                   v.sigma_variance, k + 1 == K ? 1 : 0);
+			kDenoiseVariance.enqueue(grid_for(n), WG, 0, q, c, cw, var, guide, albedo, in, dst, W, y0, y1, it, v.sigma_variance, k + 1 == K ? 1 : 0);
 			in = dst;
 		}
 	}
-	{
-		Timed t(h, "tonemap", q);
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, q, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
-	}
+	(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
 }
 
 // polaris_hip_sync_framebuffer with variance guidance on and temporal reuse off (caller holds mu; request checked): G-buffer if
@@ -1764,24 +1695,15 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 		h->tp_prior_valid = true;
 	}
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	{
-		Timed t(h, "temporal");
-		if (h->opt_time_kernels) h->timer_symbol["temporal"] = "pol::k_temporal";
-		const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
-		hipLaunchKernelGGL(k_temporal, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc, h->tp_prior, h->tp_out, h->W, y0, y1, nf, weight);
-	}
+	const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
+	(void)launch(h, "temporal", h->stream, kTemporal, grid_for(n), WG, 0, h->frame_acc, h->tp_prior, h->tp_out, h->W, y0, y1, nf, weight);
 	if (var) {
-		const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
 		launch_variance(h, h->stream, h->frame_acc, nf, weight, h->tp_out, h->tp_prior2, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong,
 		                h->dn_out, h->framebuffer, h->W, y0, y1, r->exposure, h->dn, h->va);
 	} else if (h->dn.iterations) {
 		launch_denoise(h, h->stream, h->tp_out, 1.0f, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W, y0, y1,
 		               r->exposure, h->dn);
-	} else {
-		Timed t(h, "tonemap");
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->tp_out + off, h->framebuffer + off, (uint32_t)n, 1.0f,
-		                   r->exposure);
-	}
+	} else (void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->tp_out + off, h->framebuffer + off, (uint32_t)n, 1.0f, r->exposure);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	if (h->dn.iterations) h->dn_valid = true;
@@ -1893,11 +1815,7 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	if (h->va.sigma_variance != 0.0f) return sync_variance(h, r, weight);
 	if (h->dn.iterations) return sync_denoised(h, r, weight);
 	HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
-	{
-		Timed t(h, "tonemap");
-		hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(WG), 0, h->stream, h->frame_acc + off, h->framebuffer + off, (uint32_t)n,
-		                   weight, r->exposure);
-	}
+	(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->frame_acc + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
@@ -1948,9 +1866,9 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	std::vector<int> inst(N);
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
-	hipLaunchKernelGGL(k_generate, dim3(Npad / WG), dim3(WG), 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
-	if (h->packet_primary) hipLaunchKernelGGL(k_trace_packet<false>, dim3(Npad / WG), dim3(WG), 0, q, st0, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
-	else hipLaunchKernelGGL(k_intersect, dim3(Npad / WG), dim3(WG), 0, q, st0, h->bvh);
+	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
+	if (h->packet_primary) kPacket[kPacketClosest].enqueue(Npad / WG, WG, 0, q, st0, h->bvh, nullptr, h->d_stats, h->cam.eye);
+	else kIntersect.enqueue(Npad / WG, WG, 0, q, st0, h->bvh);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipMemcpyAsync(rd.data(), st0.ray_d, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2033,13 +1951,13 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 	// the traversal kernel the options select for bounce rays (any_hit: shadow rays); packet_primary=1 sends closest-hit
 	// probes through the wave-packet kernel instead
 	if (any_hit) {
-		if (h->opt_packet_shadow > 0) hipLaunchKernelGGL(k_trace_packet<true>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace<true>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->occl_resident_per_cu)), wgs, P.st.lsum);
-		else hipLaunchKernelGGL(k_occlusion, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, P.st.lsum, h->d_stats);
+		if (h->opt_packet_shadow > 0) kPacket[kPacketAnyHit].enqueue(wgs, WG, 0, q, P.st, h->bvh, P.st.lsum, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace(h, nullptr, true, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace[1].resident_per_cu)), wgs, P.st.lsum);
+		else kOcclusion.enqueue(wgs, WG, 0, q, P.st, h->bvh, P.st.lsum, h->d_stats);
 	} else {
-		if (h->opt_packet_primary == 1) hipLaunchKernelGGL(k_trace_packet<false>, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh, (float4 *)nullptr, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace<false>(h, P, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace_resident_per_cu)), wgs, nullptr);
-		else hipLaunchKernelGGL(k_intersect, dim3(wgs), dim3(WG), 0, q, P.st, h->bvh);
+		if (h->opt_packet_primary == 1) kPacket[kPacketClosest].enqueue(wgs, WG, 0, q, P.st, h->bvh, nullptr, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace(h, nullptr, false, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace[0].resident_per_cu)), wgs, nullptr);
+		else kIntersect.enqueue(wgs, WG, 0, q, P.st, h->bvh);
 	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(res.data(), any_hit ? P.st.lsum : P.st.hit, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2200,7 +2118,7 @@ int polaris_hip_kernel_symbol(polaris_hip_tracer *h, const char *kernel, char sy
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!kernel || !symbol) return fail(h, POLARIS_E_BAD_ARGUMENT, "kernel_symbol: null argument");
 	auto it = h->timer_symbol.find(kernel);
-	snprintf(symbol, 128, "%s", it == h->timer_symbol.end() ? "" : it->second.c_str());
+	snprintf(symbol, 128, "%s", it == h->timer_symbol.end() ? "" : it->second);
 	return POLARIS_OK;
 }
 
