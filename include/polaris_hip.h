@@ -100,7 +100,13 @@ const char *polaris_hip_last_error(polaris_hip_tracer *h);
 /* (Re)allocate every frame-sized buffer; clears the frame accumulator. */
 int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h);
 
-/* Validate, re-lay-out for traversal and upload the scene.  Everything is copied. */
+/* Validate, re-lay-out for traversal and upload the scene.  Everything is copied.  With temporal reuse on, the history is dropped
+ * (it saw the old scene) -- unless the option "object_motion" is in effect: then the upload is to the history what a set_camera is
+ * (the planes of a temporal sync under the old scene become the history, with the old scene's instance table), and the history is
+ * kept if the new scene is compatible with it: the same num_mesh_instances, the same mesh_index per instance and the same
+ * num_triangles.  Only inv_transform may differ between compatible scenes as far as the library can tell: vertex and material edits
+ * under an unchanged topology are the caller's responsibility (upload such a scene with the option off, or drop the history with
+ * polaris_hip_set_temporal(max_history = 0) first). */
 int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *scene);
 
 /* eye[3]; frustum[16] = corner rays TL, TR, BL, BR as float4 (scene.Camera.Frustrum). */
@@ -125,6 +131,17 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *                        polaris_hip_set_variance); .rgb are the same bit for bit.  Default 0.  POLARIS_E_UNSUPPORTED together
  *                        with "exact_accumulate" = 1 (in either order: that mode has no per-sample radiance); 0 is
  *                        POLARIS_E_BAD_ARGUMENT while variance guidance is on
+ *   "object_motion"      0 (default) or 1: temporal reuse (polaris_hip_set_temporal) survives an upload_scene that only moves mesh
+ *                        instances.  The first-hit G-buffer gains an INSTANCE plane (polaris_hip_read_instance_plane), the history
+ *                        carries the instance table it was seen with, and the reprojection takes a first hit of instance k back
+ *                        through inverse(inv_transform_history[k]) . inv_transform_now[k] before it projects it into the history
+ *                        camera; a history tap must show the same instance.  In effect only while max_history > 0.
+ *                        The tracer keeps a host copy of the scene's instance table (mesh_index, inv_transform, num_triangles)
+ *                        from every upload_scene made with the option on.  Turned on after the scene, it takes the matrices
+ *                        from the uploaded instance records: camera moves reuse the history at once, but the first upload_scene
+ *                        after that still drops it (the old scene's mesh indices were not kept); set it before the scene.
+ *                        Changing it drops the history and invalidates the G-buffer.  It never changes an accumulator or a
+ *                        counter; off, no device memory is allocated and no kernel launched for it
  *   "overlap"            batches in flight on separate streams (1-8, default 4)
  *   "max_leaf_tris"      applies to the NEXT upload_scene: triangle leaves with more triangles
  *                        than this are subdivided where a surface-area split pays (default -1:
@@ -456,6 +473,23 @@ int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, co
                                  const float prev_eye[3], const float prev_frustum[16], const float *guide, const float *albedo,
                                  const float eye[3], const float frustum[16], uint32_t W, uint32_t H, const PolarisTemporalParams *p,
                                  float *prior);
+
+/* polaris_hip_reproject_planes with object motion (option "object_motion"): also the two INSTANCE planes (W x H words as
+ * polaris_hip_read_instance_plane returns them; a word >= n_instances gives its pixel no history), the inv_transform tables of the
+ * n_instances (1..2^20) mesh instances the history and the current frame were seen with (16 floats each, column major, as
+ * PolarisMeshInstance) and, optionally, the history's VARIANCE plane with PRIOR2 as its output (both NULL or neither) -- the launch
+ * of the first temporal sync after an upload_scene that moved instances.  Uses buffers of its own; no state of the tracer is read or
+ * changed. */
+int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                        const uint32_t *prev_instance, const float prev_eye[3], const float prev_frustum[16], const float *guide,
+                                        const float *albedo, const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t W,
+                                        uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
+                                        const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2);
+
+/* The INSTANCE plane of the first-hit G-buffer (option "object_motion"): per pixel the mesh-instance index of the hit POLARIS_AOV_GUIDE
+ * describes, 0xFFFFFFFF for a miss (where GUIDE's t is FLT_MAX); n >= frame_w * frame_h words.  Errors as polaris_hip_read_aov of
+ * POLARIS_AOV_GUIDE; POLARIS_E_BAD_ARGUMENT with the option off, or without effect because temporal reuse is off. */
+int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n);
 
 /*
  * BVH construction on the device -- an ALTERNATIVE producer of the scene's two-level BVH (the stretch; the

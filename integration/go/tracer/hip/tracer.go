@@ -296,6 +296,19 @@ func (tr *Tracer) SetTemporal(p TemporalParams) error {
 	return tr.check(C.polaris_hip_set_temporal(tr.handle, &c))
 }
 
+// SetObjectMotion turns the option "object_motion" on or off: with it on (and temporal reuse on) the history survives an
+// UpdateState(SceneData) that only moves mesh instances -- same instances, same meshes, same triangle count -- and is reprojected
+// through each instance's motion (DESIGN.md section 10d).  Changing it drops the history.
+func (tr *Tracer) SetObjectMotion(on bool) error {
+	key := C.CString("object_motion")
+	defer C.free(unsafe.Pointer(key))
+	var v C.int64_t
+	if on {
+		v = 1
+	}
+	return tr.check(C.polaris_hip_set_option(tr.handle, key, v))
+}
+
 // VarianceParams configures variance-guided denoising (PolarisVarianceParams, include/polaris_hip.h; DESIGN.md section 10c).
 // SigmaVariance = 0 turns it off (the default); DefaultVariance holds the settings chosen on the CPU restatement.
 type VarianceParams struct {

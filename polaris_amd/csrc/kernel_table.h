@@ -60,10 +60,12 @@ enum { kPacketCamera, kPacketClosest, kPacketAnyHit };
 const PacketVariant kPacket[3] = {POLARIS_VARIANT(k_trace_packet<false, true>), POLARIS_VARIANT(k_trace_packet<false, false>),
                                   POLARIS_VARIANT(k_trace_packet<true, false>)};
 
-// the kernels of two variants: [MOMENTS], [M2]
+// the kernels of two variants: [MOMENTS]; k_reproject<M2, MOTION>: [M2][MOTION]
 const decltype(POLARIS_VARIANT(k_resolve<false>)) kResolve[2] = {POLARIS_VARIANT(k_resolve<false>), POLARIS_VARIANT(k_resolve<true>)};
 const decltype(POLARIS_VARIANT(k_aggregate<false>)) kAggregate[2] = {POLARIS_VARIANT(k_aggregate<false>), POLARIS_VARIANT(k_aggregate<true>)};
-const decltype(POLARIS_VARIANT(k_reproject<false>)) kReproject[2] = {POLARIS_VARIANT(k_reproject<false>), POLARIS_VARIANT(k_reproject<true>)};
+const decltype(POLARIS_VARIANT(k_reproject<false, false>)) kReproject[2][2] = {
+	{POLARIS_VARIANT(k_reproject<false, false>), POLARIS_VARIANT(k_reproject<false, true>)},
+	{POLARIS_VARIANT(k_reproject<true, false>), POLARIS_VARIANT(k_reproject<true, true>)}};
 
 // the kernels of one variant (k_intersect / k_occlusion: the plain traversal, option traversal = 0)
 const auto kIntersect = POLARIS_VARIANT(k_intersect);

@@ -1691,7 +1691,9 @@ __global__ __launch_bounds__(WG) void k_builtin_sweep(uint32_t fn, uint64_t firs
 // hit, bit for bit), surfaceInit as in shade_ray, and the material-tree walk of the reference's debug normal kernel (PRNG state
 // (p, p), no path flags).  GUIDE = n after bump / normal maps | t (miss: 0, 0, 0, FLT_MAX); ALBEDO = clamp(tint * kcol, 0, 1)
 // for diffuse and (rough) conductor leaves, 1 for the other leaves | the leaf type's bits (miss: 1, 1, 1 | -1).
-__global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo) {
+// inst (option "object_motion"; null: not written): the INSTANCE plane, the first hit's mesh-instance index (miss: 0xFFFFFFFF).
+__global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                uint32_t *inst) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
@@ -1706,8 +1708,10 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 	if (h.tri < 0) {
 		guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
 		albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
+		if (inst) inst[idx] = kTpNoInstance;
 		return;
 	}
+	if (inst) inst[idx] = (uint32_t)h.inst; // (traverse enters the one instance of a root_is_instance scene through its leaf reference too)
 	const int tri = h.tri & (int)((1u << S.tri_bits) - 1u); // (the shading class rides above the index)
 	// surfaceInit, util/surface.cl:12-33 (as shade_ray)
 	const float bu = h.u, bv = h.v, bw = 1.0f - (bu + bv);
@@ -1777,11 +1781,15 @@ __global__ __launch_bounds__(WG) void k_denoise(const float4 *acc, float weight,
 // PRIOR of every pixel of the frame (n = W * H): the current G-buffer (guide, albedo) under camera cur, projected into the
 // history camera hist (projectable) with its planes (hist rgb | count, hguide, halbedo).  Up to 2 + 4 x 3 float4 gathers a pixel.
 // M2 (variance guidance on): the history's VARIANCE plane hvar is gathered too, its M2 into PRIOR2 (h2 | 0 | 0 | m).
-template <bool M2>
+// MOTION (option "object_motion"): the two INSTANCE planes (inst current, hinst the history's: one more word per tap) and the
+// motion table (four float4 per instance, temporal.h tp_motion_table; n_inst entries) -- at most four float4 of it per pixel, by
+// plain global loads: the instance index is nearly wave-uniform.  The variants without MOTION read none of the three.
+template <bool M2, bool MOTION>
 __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
                                                   const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
                                                   uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
-                                                  const float4 *hvar, float4 *prior2) {
+                                                  const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                  const float4 *motion, uint32_t n_inst) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= W * H) return;
 	const float4 g = guide[i];
@@ -1792,9 +1800,24 @@ __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const floa
 		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
 		t.leaf = halbedo[j].w;
 		if (M2) t.m2 = hvar[j].y;
+		if (MOTION) t.inst = hinst[j];
 	};
 	float o[4], o2[4];
-	tp_reproject<M2>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2);
+	if constexpr (MOTION) {
+		auto entry = [&](uint32_t k, float *D) -> uint32_t { // (k < n_inst: tp_reproject checks)
+			const float4 *e = motion + 4 * (size_t)k;
+			const uint32_t flag = pm_f2u(e[3].x);
+			if (flag == kTpMoved) {
+				const float4 r0 = e[0], r1 = e[1], r2 = e[2];
+				D[0] = r0.x; D[1] = r0.y; D[2] = r0.z; D[3] = r0.w;
+				D[4] = r1.x; D[5] = r1.y; D[6] = r1.z; D[7] = r1.w;
+				D[8] = r2.x; D[9] = r2.y; D[10] = r2.z; D[11] = r2.w;
+			}
+			return flag;
+		};
+		tp_reproject<M2, true>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2, inst[i],
+		                       n_inst, entry);
+	} else tp_reproject<M2>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2);
 	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
 	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
 }

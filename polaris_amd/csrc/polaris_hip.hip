@@ -129,6 +129,29 @@ struct polaris_hip_tracer {
 	bool tp_synced = false;      // a temporal sync ran under the current camera (tp_out and the G-buffer are this camera's)
 	bool tp_prior_valid = false; // tp_prior is the current history reprojected into the current camera with the current params
 
+	// temporal reuse across moving instances (option "object_motion").  In effect (motion_on) only with temporal
+	// reuse on; no device memory below is allocated otherwise.  The INSTANCE plane (one word per pixel, k_gbuffer) is swapped into
+	// the history like the G-buffer planes, and the history carries the instance table it was seen with; upload_scene keeps a
+	// history whose table is compatible with the new scene's.  The current scene's table is a host copy made by an upload with the
+	// option on (68 bytes an instance).  When the option is turned on after the scene, the matrices are read back from the device's
+	// instance records; the mesh indices are not there, so such a table is compatible with nothing: camera moves reuse the history
+	// at once, the first upload after it drops the history as without the option, and from that upload on the table is complete.
+	struct InstTable {
+		std::vector<uint32_t> mesh_index;
+		std::vector<float> inv; // 16 floats of inv_transform per instance
+		uint32_t num_triangles = 0;
+		bool topology_known = false; // mesh_index and num_triangles are the scene's
+		bool compatible(const InstTable &o) const {
+			return topology_known && o.topology_known && mesh_index == o.mesh_index && num_triangles == o.num_triangles;
+		}
+	};
+	uint32_t num_insts = 0; // mesh instances of the uploaded scene (the length of bvh.insts)
+	int opt_object_motion = 0;
+	InstTable mo_cur, mo_hist;           // the current scene's instance table, the history's
+	DevArray<uint32_t> gb_inst, tp_hinst; // INSTANCE plane, the history's
+	DevArray<float4> mo_table;           // motion table of the last PRIOR (temporal.h tp_motion_table), grow-only until free_temporal
+	std::vector<float> mo_table_host;
+
 	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
 	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
 	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
@@ -428,6 +451,9 @@ void free_moment_history(polaris_hip_tracer *h) { // what exists only with tempo
 void free_temporal(polaris_hip_tracer *h) {
 	for (auto *p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo}) p->reset();
 	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
+	h->gb_inst.reset(); // (written only with temporal reuse on: ensure_gbuffer recomputes the G-buffer when it is wanted and missing)
+	h->tp_hinst.reset();
+	h->mo_table.reset();
 	free_moment_history(h);
 }
 
@@ -442,7 +468,8 @@ void free_denoise(polaris_hip_tracer *h) {
 }
 
 // A frame-sized plane (F pixels) that exists from its first use on (caller holds mu).
-int ensure_plane(polaris_hip_tracer *h, DevArray<float4> &plane, size_t F) {
+template <class T>
+int ensure_plane(polaris_hip_tracer *h, DevArray<T> &plane, size_t F) {
 	if (!plane) HIP_TRY(h, plane.alloc(F));
 	return POLARIS_OK;
 }
@@ -454,18 +481,45 @@ int ensure_filter_planes(polaris_hip_tracer *h, size_t F) {
 	return POLARIS_OK;
 }
 
-// The GUIDE / ALBEDO planes of the current scene, camera and frame size, computed if they are not (caller holds mu; checks done).
+// Object motion is in effect: the option is on and temporal reuse is on.
+bool motion_on(const polaris_hip_tracer *h) { return h->opt_object_motion && h->tp.max_history; }
+
+// The GUIDE / ALBEDO planes of the current scene, camera and frame size (with object motion the INSTANCE plane too), computed if
+// they are not (caller holds mu; checks done).
 int ensure_gbuffer(polaris_hip_tracer *h) {
-	if (h->gb_valid) return POLARIS_OK;
+	const bool want_inst = motion_on(h);
+	if (h->gb_valid && (!want_inst || h->gb_inst)) return POLARIS_OK;
 	const size_t F = (size_t)h->W * h->H;
 	if (int rc = ensure_plane(h, h->gb_guide, F)) return rc;
 	if (int rc = ensure_plane(h, h->gb_albedo, F)) return rc;
+	if (want_inst)
+		if (int rc = ensure_plane(h, h->gb_inst, F)) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
-	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo);
+	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo,
+	             want_inst ? h->gb_inst.get() : nullptr);
 	HIP_TRY(h, hipGetLastError());
 	h->gb_valid = true;
 	return POLARIS_OK;
+}
+
+// The last temporal sync's planes under the current camera (and, with object motion, the current scene's instance table) become
+// the history; no sync under them: the older history stays.  set_camera and, with object motion, upload_scene call it before they
+// change what the planes were seen with (caller holds mu, temporal reuse on).
+void capture_history(polaris_hip_tracer *h) {
+	if (!h->tp_synced) return;
+	std::swap(h->tp_out, h->tp_hist);
+	std::swap(h->gb_guide, h->tp_hguide);
+	std::swap(h->gb_albedo, h->tp_halbedo);
+	h->tp_hcam = h->cam;
+	h->tp_have_hist = true;
+	if (motion_on(h)) {
+		std::swap(h->gb_inst, h->tp_hinst);
+		h->mo_hist = h->mo_cur;
+	}
+	// (the VARIANCE plane joins the history only if it was written under the same camera; else the history has no M2)
+	if (h->va_synced) std::swap(h->va_out, h->va_hist);
+	h->va_have_hist = h->va_synced;
 }
 
 // The scene's k_trace variants (closest hit, any hit) into the handle: STACK from the exact depth the scene needs, NODES from its
@@ -857,7 +911,32 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	h->scene_bufs.clear();
 	h->have_scene = false;
 	h->gb_valid = false;
-	if (h->tp.max_history) h->tp_have_hist = h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_have_hist = h->va_valid = false; // (the history saw the old scene)
+	{
+		// With object motion the upload is to the history what a camera move is: the planes synced under the old scene join it, and it
+		// survives if the new scene has the same instances of the same meshes (temporal.h: k_reproject carries a hit back through the
+		// two tables).  Otherwise the history saw the old scene and goes.
+		bool keep = false;
+		polaris_hip_tracer::InstTable next;
+		if (h->opt_object_motion) {
+			next.num_triangles = sc->num_triangles;
+			next.topology_known = true;
+			next.mesh_index.resize(sc->num_mesh_instances);
+			next.inv.resize((size_t)sc->num_mesh_instances * 16);
+			for (uint32_t i = 0; i < sc->num_mesh_instances; i++) {
+				next.mesh_index[i] = sc->mesh_instances[i].mesh_index;
+				memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
+			}
+		}
+		if (motion_on(h)) {
+			capture_history(h);
+			keep = h->tp_have_hist && h->mo_hist.compatible(next);
+		}
+		if (h->tp.max_history) {
+			if (!keep) h->tp_have_hist = h->va_have_hist = false;
+			h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
+		}
+		h->mo_cur = std::move(next);
+	}
 	int rc = 0;
 	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
 	rc |= dev_upload(h, h->scene_bufs, &pairs, L.pairs.data(), L.pairs.size());
@@ -924,6 +1003,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	h->scene = SceneDev{vertices, normals, uvs, mat_index, nodes, emissives, tex_meta, tex_data, sc->num_emissives,
 	                    sc->scene_diffuse_mat_index, sc->num_material_nodes, sc->num_textures, light_geo, sc->num_emissives ? pm_rcp((float)(int)sc->num_emissives) : 0.0f, L.tri_bits};
 	h->max_stack = L.max_stack;
+	h->num_insts = (uint32_t)L.insts.size();
 	h->tex_bytes = sc->texture_data_bytes;
 	// camera rays: the wave-packet kernel where a packet stays together AND the tree is small -- one instance, up to 32 K
 	// triangles.  Since the per-ray kernel's instruction diet the two are level on the tiny scenes (headline 11.37 /
@@ -958,17 +1038,7 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
 	if (h->tp.max_history) {
-		// the last temporal sync's planes under the old camera become the history (no sync under it: the older history stays)
-		if (h->tp_synced) {
-			std::swap(h->tp_out, h->tp_hist);
-			std::swap(h->gb_guide, h->tp_hguide);
-			std::swap(h->gb_albedo, h->tp_halbedo);
-			h->tp_hcam = h->cam;
-			h->tp_have_hist = true;
-			// (the VARIANCE plane joins the history only if it was written under the same camera; else the history has no M2)
-			if (h->va_synced) std::swap(h->va_out, h->va_hist);
-			h->va_have_hist = h->va_synced;
-		}
+		capture_history(h); // the last temporal sync's planes under the old camera become the history
 		h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
 	}
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
@@ -1017,6 +1087,38 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "hit12") h->opt_hit12 = value != 0;
 	else if (k == "o12") h->opt_o12 = value != 0;
 	else if (k == "lds_tris") h->opt_lds_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
+	else if (k == "object_motion") {
+		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "object_motion is 0 or 1");
+		if ((int)value != h->opt_object_motion) { // the history (with or without an INSTANCE plane) and the G-buffer go with the old setting
+			h->opt_object_motion = (int)value;
+			h->tp_have_hist = h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_have_hist = h->va_valid = false;
+			h->gb_valid = false;
+			h->mo_hist = polaris_hip_tracer::InstTable();
+			h->mo_cur = polaris_hip_tracer::InstTable(); // (kept with the option on only)
+			if (value && h->have_scene) {
+				// the scene was uploaded with the option off: its matrices come back from the device's instance records (rows 0-2 of
+				// inv_transform, all the traversal and the motion table use); the mesh indices do not (InstTable::topology_known)
+				std::vector<InstH> recs(h->num_insts);
+				HIP_TRY(h, hipSetDevice(h->device));
+				HIP_TRY(h, hipStreamSynchronize(h->stream));
+				HIP_TRY(h, hipMemcpy(recs.data(), h->bvh.insts, recs.size() * sizeof(InstH), hipMemcpyDeviceToHost));
+				h->mo_cur.mesh_index.assign(h->num_insts, 0u);
+				h->mo_cur.inv.assign((size_t)h->num_insts * 16, 0.0f);
+				for (uint32_t i = 0; i < h->num_insts; i++) {
+					float *m = h->mo_cur.inv.data() + 16 * (size_t)i; // column major: m[4 * c + r]
+					for (int c = 0; c < 4; c++) { m[4 * c + 0] = recs[i].r0[c]; m[4 * c + 1] = recs[i].r1[c]; m[4 * c + 2] = recs[i].r2[c]; }
+					m[15] = 1.0f;
+				}
+			}
+			if (!value && (h->gb_inst || h->tp_hinst || h->mo_table)) { // what exists only with the option on goes with it
+				HIP_TRY(h, hipSetDevice(h->device));
+				HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every launch that uses them is on the main stream)
+				h->gb_inst.reset();
+				h->tp_hinst.reset();
+				h->mo_table.reset();
+			}
+		}
+	}
 	else if (k == "max_leaf_tris") h->opt_max_leaf_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
 	else return fail(h, POLARIS_E_BAD_ARGUMENT, "unknown option '%s'", key);
 	return POLARIS_OK;
@@ -1599,18 +1701,22 @@ TpCamera tp_camera(const float eye[3], const float fr[16]) {
 // reprojected onto the G-buffer (guide, albedo) under cam.  polaris_hip_sync_framebuffer and polaris_hip_reproject_planes both
 // launch it through here.
 // prior2 != null (variance guidance on): PRIOR2 too, from the history's VARIANCE plane hvar (null: the history has no M2, PRIOR2 = 0).
+// mo != null (object motion): the two INSTANCE planes and the motion table of the instances between the history and now.
+struct MotionArgs { const uint32_t *inst, *hinst; const float4 *table; uint32_t n_inst; };
 hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *hist, const float4 *hguide, const float4 *halbedo, const TpCamera &hcam,
                       const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
-                      float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr) {
+                      float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr, const MotionArgs *mo = nullptr) {
 	const size_t F = (size_t)W * H;
 	const bool none = !hist || !tp_projectable(hcam) || p.max_history == 0; // no history anywhere: m = 0
 	const bool m2 = prior2 && hvar && !none;                                // (else the PRIOR as without variance guidance, PRIOR2 = 0)
-	Timed t(h, "reproject", none ? nullptr : kReproject[m2].symbol, q);
+	const auto &variant = kReproject[m2][mo != nullptr];
+	Timed t(h, "reproject", none ? nullptr : variant.symbol, q);
 	if (prior2 && !m2)
 		if (hipError_t e = hipMemsetAsync(prior2, 0, F * sizeof(float4), q)) return e;
 	if (none) return hipMemsetAsync(prior, 0, F * sizeof(float4), q);
-	kReproject[m2].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold, p.depth_threshold,
-	                       prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr);
+	variant.enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold, p.depth_threshold,
+	                prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo ? mo->inst : nullptr, mo ? mo->hinst : nullptr, mo ? mo->table : nullptr,
+	                mo ? mo->n_inst : 0u);
 	return hipGetLastError();
 }
 
@@ -1689,9 +1795,21 @@ int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float wei
 	if (!h->tp_synced) HIP_TRY(h, hipMemsetAsync(h->tp_out, 0, F * sizeof(float4), h->stream)); // (rows no sync reaches: no history)
 	h->tp_synced = true;
 	if (!h->tp_prior_valid) {
+		MotionArgs mo{};
+		const bool motion = motion_on(h) && h->tp_have_hist; // (a history kept with object motion on has an INSTANCE plane and a table of the scene's size)
+		if (motion && (h->mo_hist.inv.size() != h->mo_cur.inv.size() || h->mo_cur.mesh_index.empty() || !h->tp_hinst || !h->gb_inst))
+			return fail(h, POLARIS_E_DEVICE, "temporal sync: the history's instance table does not fit the scene's"); // (cannot happen: upload_scene drops such a history)
+		if (motion) {
+			const uint32_t n_inst = (uint32_t)h->mo_cur.mesh_index.size();
+			h->mo_table_host.resize((size_t)n_inst * 16);
+			tp_motion_table(n_inst, h->mo_hist.inv.data(), h->mo_cur.inv.data(), h->mo_table_host.data());
+			HIP_TRY(h, h->mo_table.reserve((size_t)n_inst * 4)); // (the main stream is idle: every temporal sync ends with its synchronisation)
+			HIP_TRY(h, hipMemcpyAsync(h->mo_table, h->mo_table_host.data(), h->mo_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+			mo = MotionArgs{h->gb_inst, h->tp_hinst, h->mo_table, n_inst};
+		}
 		HIP_TRY(h, launch_reproject(h, h->stream, h->tp_have_hist ? h->tp_hist : nullptr, h->tp_hguide, h->tp_halbedo, tp_camera(h->tp_hcam),
 		                            h->gb_guide, h->gb_albedo, tp_camera(h->cam), h->W, h->H, h->tp, h->tp_prior,
-		                            var && h->va_have_hist ? h->va_hist : nullptr, var ? h->tp_prior2 : nullptr));
+		                            var && h->va_have_hist ? h->va_hist : nullptr, var ? h->tp_prior2 : nullptr, motion ? &mo : nullptr));
 		h->tp_prior_valid = true;
 	}
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
@@ -2108,6 +2226,67 @@ int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, co
 	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
 	                            W, H, *p, d_prior));
 	HIP_TRY(h, hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                        const uint32_t *prev_instance, const float prev_eye[3], const float prev_frustum[16], const float *guide,
+                                        const float *albedo, const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t W,
+                                        uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
+                                        const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!history || !prev_guide || !prev_albedo || !prev_instance || !prev_eye || !prev_frustum || !guide || !albedo || !instance || !eye || !frustum ||
+	    !prev_inv_transforms || !inv_transforms || !prior || !p || p->struct_size != sizeof(PolarisTemporalParams) || W == 0 || H == 0 ||
+	    (uint64_t)W * H > (1ull << 26) || n_instances == 0 || n_instances > kTpMaxInstances || (history_variance == nullptr) != (prior2 == nullptr) ||
+	    tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_motion_planes: null argument, frame %ux%u (1..2^26 pixels), %u instances (1..%u), "
+		            "history_variance without prior2 (or the reverse), or params (max_history 0..%u, normal_threshold [-1, 1], depth_threshold [0, %g])",
+		            W, H, n_instances, kTpMaxInstances, kTpMaxHistory, (double)kTpMaxDepthThreshold);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
+	std::vector<float> table((size_t)n_instances * 16);
+	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
+	DevArray<float4> d, d_table;
+	DevArray<uint32_t> d_words;
+	StreamDrain drain{h->stream};
+	HIP_TRY(h, d.alloc(8 * F));   // its own planes: no tracer state is read or written
+	HIP_TRY(h, d_words.alloc(2 * F));
+	HIP_TRY(h, d_table.alloc((size_t)n_instances * 4));
+	float4 *d_hist = d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
+	       *d_prior = d_albedo + F, *d_hvar = d_prior + F, *d_prior2 = d_hvar + F;
+	uint32_t *d_hinst = d_words, *d_inst = d_hinst + F;
+	const std::pair<float4 *, const void *> in[] = {{d_hist, history}, {d_hguide, prev_guide}, {d_halbedo, prev_albedo}, {d_guide, guide},
+	                                                {d_albedo, albedo}, {d_hvar, history_variance}};
+	for (const auto &c : in)
+		if (c.second) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(d_hinst, prev_instance, F * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(d_inst, instance, F * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+	const MotionArgs mo{d_inst, d_hinst, d_table, n_instances};
+	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
+	                            W, H, *p, d_prior, history_variance ? d_hvar : nullptr, prior2 ? d_prior2 : nullptr, &mo));
+	HIP_TRY(h, hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream));
+	if (prior2) HIP_TRY(h, hipMemcpyAsync(prior2, d_prior2, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const size_t need = (size_t)h->W * h->H;
+	if (!out || n < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: need %zu words", need);
+	if (!h->opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
+	HIP_TRY(h, hipSetDevice(h->device));
+	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: camera not set");
+	if (!motion_on(h)) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
+	if (int rc = ensure_gbuffer(h)) return rc;
+	HIP_TRY(h, hipMemcpyAsync(out, h->gb_inst, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;

@@ -9,9 +9,13 @@
 // with.  For a filtered pixel i of the current G-buffer the first hit p = eye + t_i d_i is projected into the history camera, and
 // the 2 x 2 history pixels around it that saw the same surface give the PRIOR (h rgb | m, m = 0: no history).  The TEMPORAL plane
 // then blends the running mean with it: (acc + m h) / (n + m).
+// With the option "object_motion"  the history also carries an INSTANCE plane and the instance table it was seen
+// with, and p is first taken to where its instance stood then (tp_motion_matrix on the host, tp_reproject<*, true>).
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "denoise.h"
 #include "polaris_math.h"
@@ -74,8 +78,70 @@ PM_HD bool tp_project(const TpCamera &c, const float p[3], float &u, float &v, f
 	return true;
 }
 
-// One history tap as k_reproject gathers it (m2: the history's M2, gathered only by k_reproject<true>, variance.h).
-struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; float m2; };
+// One history tap as k_reproject gathers it (m2: the history's M2, gathered only by k_reproject<true, *>, variance.h; inst: the
+// history's INSTANCE word, gathered only by k_reproject<*, true>).
+struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; float m2; uint32_t inst; };
+
+// Object motion (option "object_motion"): what became of mesh instance k between the history and now, one entry of
+// the motion table per instance.  STATIC: the instance has not moved, p as without the option.  MOVED: a first hit p of the
+// current frame lay at D p when the history was seen (D the affine 3 x 4, rows r0, r1, r2).  INVALID: no history for its pixels.
+enum : uint32_t { kTpStatic = 0, kTpMoved = 1, kTpInvalid = 2 };
+constexpr uint32_t kTpNoInstance = 0xFFFFFFFFu; // the INSTANCE word of a miss
+constexpr uint32_t kTpMaxInstances = 1u << 20;   // of polaris_hip_reproject_motion_planes / polaris_host_reproject_motion
+struct TpNoMotion {}; // (tp_reproject<*, false> never calls its motion argument)
+
+// ---- host only (plain functions: no device code is generated for them) ----
+// The motion table's entry of one instance from its two inv_transform (PolarisMeshInstance: column major, world -> mesh; the
+// affine rows 0-2 are what the traversal uses): STATIC when the two are byte-equal, else D = inverse(Inv_hist) . Inv_cur in double
+// precision (cofactor inversion of the upper 3 x 3), rounded to float once at the end.  INVALID when either upper 3 x 3 has a
+// determinant of 0 or a non-finite one, or an entry of D is not finite after rounding.  D is the identity for STATIC, 0 for INVALID.
+// Host only: the library (where the PRIOR is computed) and the CPU restatement both call it.
+inline uint32_t tp_motion_matrix(const float inv_hist[16], const float inv_cur[16], float D[12]) {
+	for (int k = 0; k < 12; k++) D[k] = 0.0f;
+	if (memcmp(inv_hist, inv_cur, 16 * sizeof(float)) == 0) {
+		D[0] = D[5] = D[10] = 1.0f;
+		return kTpStatic;
+	}
+	double a[3][3], c[3][3], dt[3];
+	for (int r = 0; r < 3; r++) {
+		for (int k = 0; k < 3; k++) { a[r][k] = (double)inv_hist[4 * k + r]; c[r][k] = (double)inv_cur[4 * k + r]; }
+		dt[r] = (double)inv_cur[12 + r] - (double)inv_hist[12 + r];
+	}
+	auto det3 = [](const double m[3][3], double co[3]) {
+		co[0] = m[1][1] * m[2][2] - m[1][2] * m[2][1];
+		co[1] = m[1][2] * m[2][0] - m[1][0] * m[2][2];
+		co[2] = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+		return m[0][0] * co[0] + m[0][1] * co[1] + m[0][2] * co[2];
+	};
+	double co[3], cc[3];
+	const double det = det3(a, co), det_cur = det3(c, cc);
+	if (!(det != 0.0) || !isfinite(det) || !(det_cur != 0.0) || !isfinite(det_cur)) return kTpInvalid;
+	const double inv[3][3] = {
+		{co[0] / det, (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det, (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det},
+		{co[1] / det, (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det, (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det},
+		{co[2] / det, (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det, (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det}};
+	bool finite = true;
+	for (int r = 0; r < 3; r++) {
+		for (int k = 0; k < 3; k++) D[4 * r + k] = (float)((inv[r][0] * c[0][k] + inv[r][1] * c[1][k]) + inv[r][2] * c[2][k]);
+		D[4 * r + 3] = (float)((inv[r][0] * dt[0] + inv[r][1] * dt[1]) + inv[r][2] * dt[2]);
+		for (int k = 0; k < 4; k++) finite = finite && isfinite(D[4 * r + k]);
+	}
+	if (!finite) {
+		for (int k = 0; k < 12; k++) D[k] = 0.0f;
+		return kTpInvalid;
+	}
+	return kTpMoved;
+}
+
+// The motion table as it is uploaded, four float4 per instance: rows r0, r1, r2 of D, then the flag word (bits of .x) | 0 | 0 | 0.
+inline void tp_motion_table(uint32_t n_instances, const float *inv_hist, const float *inv_cur, float *table) {
+	for (uint32_t k = 0; k < n_instances; k++) {
+		float *e = table + 16 * (size_t)k;
+		const uint32_t flag = tp_motion_matrix(inv_hist + 16 * (size_t)k, inv_cur + 16 * (size_t)k, e);
+		memcpy(e + 12, &flag, sizeof flag);
+		e[13] = e[14] = e[15] = 0.0f;
+	}
+}
 
 // The tap test: a history count > 0, finite history rgb, the same leaf word as pixel i, n_i . n_j >= normal_threshold and
 // |t_j - dist| <= depth_threshold * dist.
@@ -93,17 +159,32 @@ PM_HD bool tp_tap_ok(const TpTap &j, float leaf_i, float nx, float ny, float nz,
 // The taps are the 2 x 2 around (u W - 0.5, v H - 0.5) in the order (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1);
 // their bilinear weights are renormalised over the valid ones.  M2 (variance guidance with temporal reuse): the taps' m2 are
 // blended with the same weights into out2 = h2 | 0 | 0 | m (all 0 without history); M2 = false leaves out2 alone.
-template <bool M2 = false, class Load>
+// MOTION (option "object_motion"): inst_i is the pixel's INSTANCE word and motion(k, D) gives instance k's motion table entry, the
+// flag returned and, for MOVED, D's twelve floats filled in (k < n_inst; a word outside the table gives no history).  INVALID:
+// m = 0.  MOVED: p becomes D p, each row ((r.x px + r.y py) + r.z pz) + r.w, before the projection, so the depth test sees
+// |D p - eye'|.  A tap must also carry the INSTANCE word inst_i.  MOTION = false reads neither.
+template <bool M2 = false, bool MOTION = false, class Load, class Motion = TpNoMotion>
 PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const TpCamera &cur,
                         const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4],
-                        float *out2 = nullptr) {
+                        float *out2 = nullptr, uint32_t inst_i = 0, uint32_t n_inst = 0, Motion motion = Motion()) {
 	out[0] = out[1] = out[2] = out[3] = 0.0f;
 	if (M2) out2[0] = out2[1] = out2[2] = out2[3] = 0.0f;
 	if (!dn_filtered(leaf_i)) return;
 	float d[3];
 	tp_centre_ray(cur.tl, cur.tr, cur.bl, cur.br, gx, gy, 1.0f / (float)W, 1.0f / (float)H, d);
 	const float t = guide_i[3];
-	const float p[3] = {cur.eye[0] + t * d[0], cur.eye[1] + t * d[1], cur.eye[2] + t * d[2]};
+	float p[3] = {cur.eye[0] + t * d[0], cur.eye[1] + t * d[1], cur.eye[2] + t * d[2]};
+	if constexpr (MOTION) {
+		if (inst_i >= n_inst) return;
+		float D[12];
+		const uint32_t flag = motion(inst_i, D);
+		if (flag == kTpMoved) {
+			const float px = p[0], py = p[1], pz = p[2];
+			p[0] = ((D[0] * px + D[1] * py) + D[2] * pz) + D[3];
+			p[1] = ((D[4] * px + D[5] * py) + D[6] * pz) + D[7];
+			p[2] = ((D[8] * px + D[9] * py) + D[10] * pz) + D[11];
+		} else if (flag != kTpStatic) return;
+	}
 	float u, v, dist;
 	if (!tp_project(hist, p, u, v, dist)) return;
 	const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
@@ -118,6 +199,7 @@ PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const 
 		const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
 		TpTap j;
 		load((uint32_t)yy * W + (uint32_t)xx, j);
+		if (MOTION && j.inst != inst_i) continue;
 		if (!tp_tap_ok(j, leaf_i, guide_i[0], guide_i[1], guide_i[2], dist, normal_threshold, depth_threshold)) continue;
 		sw += w;
 		hr += w * j.r;

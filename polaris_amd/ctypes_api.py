@@ -296,6 +296,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
+    "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
 ]
 
 _lib = None
@@ -400,6 +401,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),
                                                 C.POINTER(VarianceParams), vp, vp, vp]
     lib.polaris_hip_reproject_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(TemporalParams), vp]
+    lib.polaris_hip_reproject_motion_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp,
+                                                        C.POINTER(TemporalParams), vp, vp, vp]
+    lib.polaris_hip_read_instance_plane.argtypes = [vp, vp, C.c_size_t]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

@@ -141,7 +141,7 @@ int polaris_host_reproject_moments(const float *history, const float *hvar, cons
 	const bool ok = tp_projectable(hcam) && p->max_history != 0;
 	auto load = [&](uint32_t j, TpTap &t) {
 		const float *c = history + 4 * (size_t)j, *n = prev_guide + 4 * (size_t)j;
-		t = TpTap{c[0], c[1], c[2], c[3], n[0], n[1], n[2], n[3], prev_albedo[4 * (size_t)j + 3], hvar[4 * (size_t)j + 1]};
+		t = TpTap{c[0], c[1], c[2], c[3], n[0], n[1], n[2], n[3], prev_albedo[4 * (size_t)j + 3], hvar[4 * (size_t)j + 1], 0u};
 	};
 	for (size_t i = 0; i < F; i++) {
 		float *o = prior + 4 * i, *o2 = prior2 + 4 * i;

@@ -44,6 +44,9 @@ def load() -> C.CDLL:
                                                       C.POINTER(T.VarianceParams), vp]
         lib.polaris_host_reproject_moments.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(T.TemporalParams), vp, vp]
         lib.polaris_host_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(T.TemporalParams), vp]
+        lib.polaris_host_reproject_motion.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(T.TemporalParams),
+                                                      vp, vp, vp]
+        lib.polaris_host_motion_matrix.argtypes = [vp, vp, C.POINTER(u32), vp]
         lib.polaris_host_temporal_combine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         lib.polaris_host_camera_move.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.c_uint32, vp, vp, vp]
         lib.polaris_host_denoise.argtypes = [vp, C.c_float, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -151,6 +154,11 @@ class Renderer:
         if self._lib.polaris_host_renderer_set_temporal(self._h, C.byref(p)):
             raise RuntimeError(f"set_temporal failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
+    def set_object_motion(self, on: bool = True) -> None:
+        """The option "object_motion" on every tracer (temporal reuse across moving mesh instances); only the primary syncs,
+        so only the primary's history is ever used."""
+        self.set_option("object_motion", 1 if on else 0)
+
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """polaris_hip_set_variance on every tracer, after the option "moments" on every tracer (polaris_host_renderer_set_variance)."""
         p = T.variance_params(sigma_variance, min_samples)
@@ -257,6 +265,51 @@ def reproject(history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, a
     if rc:
         raise ValueError(f"reproject: bad arguments (code {rc})")
     return out
+
+
+MOTION_STATIC, MOTION_MOVED, MOTION_INVALID = 0, 1, 2
+
+
+def motion_matrix(inv_hist, inv_cur) -> tuple[int, np.ndarray]:
+    """tp_motion_matrix (polaris_amd/csrc/temporal.h), the function the library builds its motion table with: (flag, D (3, 4) float32)
+    of one mesh instance from its two inv_transform (16 floats, column major): MOTION_STATIC when they are byte-equal, MOTION_MOVED
+    with D = inverse(Inv_hist) . Inv_cur, or MOTION_INVALID."""
+    a = np.ascontiguousarray(inv_hist, dtype=np.float32).reshape(16)
+    b = np.ascontiguousarray(inv_cur, dtype=np.float32).reshape(16)
+    flag, D = C.c_uint32(), np.zeros((3, 4), np.float32)
+    if load().polaris_host_motion_matrix(a.ctypes.data, b.ctypes.data, C.byref(flag), D.ctypes.data):
+        raise ValueError("motion_matrix: bad arguments")
+    return int(flag.value), D
+
+
+def reproject_motion(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
+                     prev_inv_transforms, inv_transforms, *, history_variance=None, max_history: int = 32, normal_threshold: float = 0.9,
+                     depth_threshold: float = 0.1):
+    """polaris_host_reproject_motion: reproject() with object motion -- the two (H, W) uint32 INSTANCE planes and the two (n, 16)
+    inv_transform tables the history and the current frame were seen with.  Returns the PRIOR plane, or (PRIOR, PRIOR2) when the
+    history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
+    (hist, pg, pa, g, a), H, W = _planes("reproject_motion", history, prev_guide, prev_albedo, guide, albedo)
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
+    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+    pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
+    pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
+    if pi.shape != (H, W) or ci.shape != (H, W) or pt.shape != ct.shape:
+        raise ValueError("reproject_motion: the INSTANCE planes must be (H, W), the two tables (n, 16)")
+    hv = None
+    if history_variance is not None:
+        (hv,), _, _ = _planes("reproject_motion", history_variance)
+        if hv.shape != hist.shape:
+            raise ValueError("reproject_motion: history_variance must be (H, W, 4) like the history")
+    out = np.zeros((H, W, 4), np.float32)
+    out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+    rc = load().polaris_host_reproject_motion(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data,
+                                              g.ctypes.data, a.ctypes.data, ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct),
+                                              pt.ctypes.data, ct.ctypes.data, C.byref(p), None if hv is None else hv.ctypes.data,
+                                              out.ctypes.data, None if out2 is None else out2.ctypes.data)
+    if rc:
+        raise ValueError(f"reproject_motion: bad arguments (code {rc})")
+    return out if out2 is None else (out, out2)
 
 
 def temporal_combine(frame_acc, prior, accumulated_samples: int, samples_per_pixel: int, *, block_y: int = 0, block_h: int | None = None,

@@ -475,7 +475,7 @@ def checker_rgba8(n=64, cells=8, a=(230, 230, 230), b=(60, 60, 70)):
     return img
 
 
-def cornell_box(variant="layered", aspect=1.0, compiler="numpy") -> Scene:
+def cornell_box(variant="layered", aspect=1.0, compiler="numpy", world=None) -> Scene:
     """Cornell box from the classic measured geometry (dimensions of the Cornell Program of
     Computer Graphics data set, scaled by 1/555 so the box spans ~[0,1]^3).
 
@@ -484,6 +484,8 @@ def cornell_box(variant="layered", aspect=1.0, compiler="numpy") -> Scene:
     mix(diffuse, roughConductor, 0.5), the short block is replaced by a dielectric sphere over a
     rough-dielectric pedestal, the floor carries an RGBA8 checker texture, the back wall a
     bump-mapped diffuse -- every BxDF family and the MIS / RR machinery is exercised.
+
+    world: the 4 x 4 matrix of the scene's one mesh instance (default: the identity); the camera does not follow it.
     """
     s = 1.0 / 555.0
     mt = MaterialTable()
@@ -522,14 +524,15 @@ def cornell_box(variant="layered", aspect=1.0, compiler="numpy") -> Scene:
     else:
         parts.append(box((130 * s, 0, 65 * s), (130 * s + 165 * s, 165 * s, 65 * s + 165 * s), white, rot_y=0.29))
     mesh = merge(parts)
+    world = np.eye(4) if world is None else np.asarray(world, np.float64)
     if compiler == "reference":
         # the C++ restatement of the reference's own compiler (bvh_builder.go SAH on up to 1024
         # candidate planes per axis, leaves of <= 10 triangles): the BVH `polaris render` would upload
         from . import host_api
 
-        sc = host_api.compile_scene([mesh], [(0, np.eye(4))], mt, min_leaf=10, name=f"cornell-{variant}-refbvh")
+        sc = host_api.compile_scene([mesh], [(0, world)], mt, min_leaf=10, name=f"cornell-{variant}-refbvh")
     else:
-        sc = compile_scene([mesh], [(0, np.eye(4))], mt, name=f"cornell-{variant}")
+        sc = compile_scene([mesh], [(0, world)], mt, name=f"cornell-{variant}")
     sc.set_camera(eye=(278 * s, 273 * s, -800 * s), look=(278 * s, 273 * s, 0), fov=0.6911, aspect=aspect)
     return sc
 
@@ -610,6 +613,37 @@ def transformed_instances(aspect=1.0) -> Scene:
     ]
     sc = compile_scene([cube, ball, panel, ground], insts, mt, scene_diffuse=bg, name="transformed-instances")
     sc.set_camera(eye=(0, 2.4, 6.0), look=(0, 0.8, 0), fov=0.75, aspect=aspect)
+    return sc
+
+
+def moving_instances(step=0, aspect=1.0) -> Scene:
+    """The Cornell-diffuse box as three mesh instances, two of them moving with `step` (temporal reuse across object motion,
+    DESIGN.md 10d): instance 0 the room with its light (static), instance 1 the tall block rotated by 0.05 rad per step about the
+    vertical axis through its centre, instance 2 the short block shifted by +0.03 in x per step.  Every step has the same meshes,
+    instances and triangles: only inv_transform differs.  Camera: cornell_box's."""
+    s = 1.0 / 555.0
+    mt = MaterialTable()
+    white = mt.diffuse((0.725, 0.71, 0.68))
+    red = mt.diffuse((0.63, 0.065, 0.05))
+    green = mt.diffuse((0.14, 0.45, 0.091))
+    light = mt.emissive((17.0, 12.0, 4.0), 1.0)
+    X, Y, Z = 556.0 * s, 548.8 * s, 559.2 * s
+    room = merge([
+        quad((X, 0, 0), (0, 0, 0), (0, 0, Z), (X, 0, Z), white),
+        quad((X, Y, 0), (X, Y, Z), (0, Y, Z), (0, Y, 0), white),
+        quad((X, 0, Z), (0, 0, Z), (0, Y, Z), (X, Y, Z), white),
+        quad((0, 0, Z), (0, 0, 0), (0, Y, 0), (0, Y, Z), green),
+        quad((X, 0, 0), (X, 0, Z), (X, Y, Z), (X, Y, 0), red),
+        quad((343 * s, Y - 1e-3, 227 * s), (343 * s, Y - 1e-3, 332 * s), (213 * s, Y - 1e-3, 332 * s), (213 * s, Y - 1e-3, 227 * s), light),
+    ])
+    tall = box((265 * s, 0, 296 * s), (265 * s + 165 * s, 330 * s, 296 * s + 165 * s), white, rot_y=-0.29)
+    short = box((130 * s, 0, 65 * s), (130 * s + 165 * s, 165 * s, 65 * s + 165 * s), white, rot_y=0.29)
+    c = np.array([(265 + 82.5) * s, 0.0, (296 + 82.5) * s])
+    insts = [(0, np.eye(4)),
+             (1, translation(c) @ rotation_y(0.05 * step) @ translation(-c)),
+             (2, translation((0.03 * step, 0, 0)))]
+    sc = compile_scene([room, tall, short], insts, mt, name=f"moving-instances-{step}")
+    sc.set_camera(eye=(278 * s, 273 * s, -800 * s), look=(278 * s, 273 * s, 0), fov=0.6911, aspect=aspect)
     return sc
 
 

@@ -282,6 +282,38 @@ class HipTracer:
                                                            out.ctypes.data), self._h)
         return out
 
+    def reproject_motion_planes(self, history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye,
+                                frustum, prev_inv_transforms, inv_transforms, *, history_variance=None, max_history: int = 32,
+                                normal_threshold: float = 0.9, depth_threshold: float = 0.1):
+        """polaris_hip_reproject_motion_planes: reproject_planes with object motion -- the two (H, W) uint32 INSTANCE planes and the two
+        (n, 16) inv_transform tables (column major, as MESH_INSTANCE) the history and the current frame were seen with.  Returns the
+        PRIOR plane, or (PRIOR, PRIOR2) when the history's VARIANCE plane is given."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
+        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+        H, W = g.shape[:2]
+        pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
+        pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
+        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4) and pi.shape == ci.shape == (H, W) and pt.shape == ct.shape
+        hv = None if history_variance is None else f(history_variance)
+        assert hv is None or hv.shape == (H, W, 4)
+        out = np.zeros((H, W, 4), np.float32)
+        out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
+        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+        self._check(self._lib.polaris_hip_reproject_motion_planes(
+            self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data, a.ctypes.data,
+            ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct), pt.ctypes.data, ct.ctypes.data, C.byref(p),
+            None if hv is None else hv.ctypes.data, out.ctypes.data, None if out2 is None else out2.ctypes.data), self._h)
+        return out if out2 is None else (out, out2)
+
+    def read_instance_plane(self) -> np.ndarray:
+        """(H, W) uint32 INSTANCE plane of the first-hit G-buffer (polaris_hip_read_instance_plane; option "object_motion" with temporal
+        reuse on): the mesh-instance index of every pixel's first hit, 0xFFFFFFFF for a miss."""
+        self._commit()
+        out = np.zeros((self._H, self._W), dtype=np.uint32)
+        self._check(self._lib.polaris_hip_read_instance_plane(self._h, out.ctypes.data, out.size), self._h)
+        return out
+
     def kernel_ms(self, name: str) -> tuple[float, int]:
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._lib.polaris_hip_kernel_ms(self._h, name.encode(), C.byref(ms), C.byref(n)), self._h)
