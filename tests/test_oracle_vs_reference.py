@@ -182,6 +182,37 @@ def test_emissive_probes_bit_exact(oracle, ref_pm):
                 assert same_bits(a, b), (name, e)
 
 
+@pytest.mark.parametrize("family", ["lattice", "relief", "doubled", "coincident", "epsilon"])
+def test_tie_scenes_bit_exact(oracle, ref_pm, family):
+    """Scenes and rays on which traversal order decides the answer (tests/tools/tie_scenes.py: exact ties of two to six triangles and
+    across instances, rays in box-face planes whose hits the reference drops tree-dependently, the strict comparisons against
+    INTERSECTION_EPSILON and maxDist, zero-area triangles): closest hits -- flags, (instance, triangle), bits of (w, u, v, t) -- and
+    any-hit flags of the restatement equal the compiled reference's, also with maxDist at, one ulp below and one ulp above each hit.
+    The same inputs run every HIP traversal kernel against the oracle (tests/test_gpu_ties.py)."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+    import tie_scenes as TS
+
+    compared = 0
+    for tag in TS.FAMILIES[family]:
+        sc, rays = TS.case(tag)
+        hit, wuvt, it = oracle.intersect(sc, rays, any_hit=False)
+        occ, _, _ = oracle.intersect(sc, rays, any_hit=True)
+        assert 0 < (hit != 0).sum() < len(rays), tag
+        r_hit, r_wuvt, r_it = ref_pm.intersect(sc, rays, any_hit=False)
+        assert same_bits(r_hit, hit) and same_bits(r_it, it) and same_bits(r_wuvt, wuvt), tag
+        assert same_bits(ref_pm.intersect(sc, rays, any_hit=True)[0], occ), tag
+        for key, r in TS.shadow_variants(rays, hit, wuvt[:, 3]).items():
+            assert same_bits(ref_pm.intersect(sc, r, any_hit=True)[0], oracle.intersect(sc, r, any_hit=True)[0]), (tag, key)
+            s_hit, s_wuvt, s_it = oracle.intersect(sc, r, any_hit=False)
+            q_hit, q_wuvt, q_it = ref_pm.intersect(sc, r, any_hit=False)
+            assert same_bits(q_hit, s_hit) and same_bits(q_it, s_it) and same_bits(q_wuvt, s_wuvt), (tag, key)
+        compared += 1
+    assert compared == len(TS.FAMILIES[family]) >= 3
+
+
 @pytest.mark.parametrize("name", SCENES)
 def test_libm_build_agrees_pixel_by_pixel(oracle, ref_libm, name):
     """The same reference kernels with glibc's libm behind sin / cos / atan / atan2 / acos / pow / sqrt instead of

@@ -170,6 +170,44 @@ def test_layout_traversal_equals_the_reference_query_on_random_rays(harness, ora
             assert cnt[6] == 0
 
 
+def _tie_cases():
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import tie_scenes as TS
+
+    return TS
+
+
+@pytest.mark.parametrize("tag", _tie_cases().CASES)
+def test_layout_traversal_breaks_exact_ties_as_the_reference_query_does(harness, oracle, tag):
+    """The scenes and rays of tests/tools/tie_scenes.py -- exact ties of up to six triangles and across instances, rays lying in
+    box-face planes (0 * inf = NaN in the slab test), the strict comparisons against INTERSECTION_EPSILON and maxDist -- through the
+    kernels' traversal rules over the layout the upload makes (its irank / trank assignment compiled for the host), for
+    max_leaf_tris 0 / 1 / 2 / 4: hit flags, instance, triangle and the bits of t, u, v equal the oracle's; any-hit flags too, also
+    with maxDist at, one ulp below and one ulp above each hit."""
+    TS = _tie_cases()
+    sc, rays = TS.case(tag)
+    h, wuvt, it = oracle.intersect(sc, rays)
+    ha, _, _ = oracle.intersect(sc, rays, any_hit=True)
+    hm = h != 0
+    assert 0 < hm.sum() < len(rays)
+    shadows = [(key, r, oracle.intersect(sc, r, any_hit=True)[0], oracle.intersect(sc, r)[0]) for key, r in TS.shadow_variants(rays, h, wuvt[:, 3]).items()]
+    for max_leaf in (0, 1, 2, 4):
+        got, _ = traverse(harness, sc, rays, max_leaf)
+        what = (tag, max_leaf)
+        assert np.array_equal(got[:, 5] != 0, hm), (what, int(((got[:, 5] != 0) != hm).sum()))
+        bad = np.nonzero((got[hm][:, [1, 0]] != it[hm]).any(axis=1))[0]
+        assert len(bad) == 0, (what, len(bad), rays[hm][bad[0]], got[hm][bad[0]], it[hm][bad[0]])
+        assert np.array_equal(got[hm][:, 2], wuvt[hm][:, 3].view(np.int32)), what
+        assert np.array_equal(got[hm][:, 3:5], wuvt[hm][:, 1:3].view(np.int32)), what
+        got_any, _ = traverse(harness, sc, rays, max_leaf, any_hit=True)
+        assert np.array_equal(got_any[:, 5] != 0, ha != 0), what
+        for key, r, occ, closest in shadows:
+            assert np.array_equal(traverse(harness, sc, r, max_leaf, any_hit=True)[0][:, 5] != 0, occ != 0), (what, key)
+            assert np.array_equal(traverse(harness, sc, r, max_leaf)[0][:, 5] != 0, closest != 0), (what, key)
+
+
 def face_rays(sc, rng, n):
     """Rays that sit exactly ON box faces and run exactly parallel to them: origins take coordinates of BVH box bounds (node
     mins / maxes are vertex coordinates, so these are also the planes of axis-aligned walls), directions have one or two
