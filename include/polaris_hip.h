@@ -142,6 +142,10 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *                        after that still drops it (the old scene's mesh indices were not kept); set it before the scene.
  *                        Changing it drops the history and invalidates the G-buffer.  It never changes an accumulator or a
  *                        counter; off, no device memory is allocated and no kernel launched for it
+ *   "instance_update"    0 (default) or 1, applies to the NEXT upload_scene: the upload keeps what polaris_hip_update_instances
+ *                        needs (the top-level tree as a refit schedule, the triangle list of every mesh, host copies of the
+ *                        emissive list and the packed light geometry).  Off, an upload keeps nothing extra: every
+ *                        code path, allocation and launch is what it is without the option
  *   "overlap"            batches in flight on separate streams (1-8, default 4)
  *   "max_leaf_tris"      applies to the NEXT upload_scene: triangle leaves with more triangles
  *                        than this are subdivided where a surface-area split pays (default -1:
@@ -492,6 +496,51 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
 int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n);
 
 /*
+ * Move mesh instances in place (no reference counterpart: the reference uploads the whole scene, tracer.go:166-173).
+ * Synchronous, under the handle's mutex, behind every stream of the handle, like an upload.  Afterwards the tracer behaves bit for
+ * bit as if polaris_hip_upload_scene had been given the uploaded scene's arrays with three substitutions:
+ *   - mesh_instances[i].inv_transform = inv_transforms[i];
+ *   - emissives = the new list (NULL: unchanged).  Only `transform` and `area` of an entry may differ from the uploaded list;
+ *   - the top-level BVH nodes REFIT: a top-level leaf takes instance_boxes[i] verbatim (also a box that does not bound its
+ *     instance: the scene reader's translation-only boxes survive), a top-level inner node the component-wise minimum / maximum of
+ *     its two children (fmin / fmax of finite values; where +0 meets -0, the left child's).
+ * Topology, child order, mesh trees, triangle records and everything else stay as uploaded.  The library recomputes what a full
+ * upload derives from these: the Inst records, the boxes and cull factors of the top-level pair records (the exact world extent
+ * of every instance's mesh, on the device), the padding of the boxes leaf subdivision added (it depends on the matrices and the
+ * world box: every update RE-PADS those boxes, and no move is refused for the padding's sake), the light geometry derived from
+ * `transform` and `area`.
+ * One deviation: build_layout bounds an instance by the eight corners of its mesh's box once a scene needs more than 32 M / 3
+ * vertex transforms, the update always by all vertices, so above that cap a cull factor may be 1.001 where a full upload has
+ * +inf -- only ever where culling is legal; results are the same.
+ * To the temporal history the call is what an upload_scene is: with "object_motion" in effect the planes synced under the old
+ * matrices join the history and it is kept (instances and meshes are the same); without, the history is dropped.  The G-buffer is
+ * invalidated.
+ * A failing HIP call (POLARIS_E_DEVICE) after the arguments were accepted leaves the scene as a failed upload_scene does: upload again.
+ * Refusals leave the tracer's state unchanged: POLARIS_E_NO_SCENE_DATA before an upload; POLARIS_E_UNSUPPORTED when the scene was
+ * uploaded with "instance_update" off; POLARIS_E_BAD_ARGUMENT for a wrong struct_size, a wrong instance count, null pointers, or an
+ * emissive list whose count or per-entry type / tri_index / mat_node_index differs from the uploaded one; POLARIS_E_BAD_SCENE for a
+ * matrix entry not finite or beyond 2^30 (the upload's own rule) and for a box that is not finite or has min > max.
+ */
+typedef struct PolarisInstanceUpdate {
+	uint32_t struct_size;             /* = sizeof(PolarisInstanceUpdate) */
+	uint32_t num_mesh_instances;      /* must equal the uploaded scene's */
+	const float *inv_transforms;      /* [NI][16], column major, as PolarisMeshInstance.inv_transform */
+	const float *instance_boxes;      /* [NI][6] world-space min.xyz, max.xyz: the scene reader's boxes, as in PolarisBvhBuildInput */
+	const PolarisEmissive *emissives; /* NULL = unchanged; else [num_emissives] */
+	uint32_t num_emissives;
+} PolarisInstanceUpdate;
+int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpdate *u);
+
+/* Test tap (no reference counterpart): the device's pair records (POLARIS_REC_PAIRS: 64 bytes each, scene_layout.h PairNodeH) or
+ * instance records (POLARIS_REC_INSTS: 64 bytes each, InstH) of the uploaded scene, copied back; POLARIS_REC_COUNTS: four uint64_t,
+ * the number of pair records, of instance records, of device allocations the scene owns and the bytes in them (what the option
+ * "instance_update" adds shows here, exactly; free device memory is everybody's).  n_bytes must be at least the size of what is asked for. */
+#define POLARIS_REC_PAIRS 0
+#define POLARIS_REC_INSTS 1
+#define POLARIS_REC_COUNTS 2
+int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, size_t n_bytes);
+
+/*
  * BVH construction on the device -- an ALTERNATIVE producer of the scene's two-level BVH (the stretch; the
  * reference's own builder, asset/compiler/bvh/bvh_builder.go:100-308, scores ~1024 / (depth + 1) candidate planes per axis with
  * one goroutine each and is restated for the CPU in polaris_amd/host/scene_compiler.cpp).  Two algorithms (`algorithm`):
@@ -538,7 +587,8 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * the wave-packet kernel), "intersect" (closest hit), "shade_first" / "shade_sort" /
  * "shade_plain" / "shade_wave" (one per shade kernel symbol), "scan", "occlusion", "fold" (the batch's NEE records into the
  * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
- * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance). */
+ * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance), "instance_extent",
+ * "repad" and "refit_top" (polaris_hip_update_instances). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

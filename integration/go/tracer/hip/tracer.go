@@ -18,6 +18,7 @@ import (
 	"errors"
 	"fmt"
 	"math/rand"
+	"runtime"
 	"sync"
 	"time"
 	"unsafe"
@@ -307,6 +308,47 @@ func (tr *Tracer) SetObjectMotion(on bool) error {
 		v = 1
 	}
 	return tr.check(C.polaris_hip_set_option(tr.handle, key, v))
+}
+
+// SetInstanceUpdate turns the option "instance_update" on or off for the NEXT UpdateState(SceneData): with it on the upload keeps
+// what UpdateInstances needs (DESIGN.md section 10e).
+func (tr *Tracer) SetInstanceUpdate(on bool) error {
+	key := C.CString("instance_update")
+	defer C.free(unsafe.Pointer(key))
+	var v C.int64_t
+	if on {
+		v = 1
+	}
+	return tr.check(C.polaris_hip_set_option(tr.handle, key, v))
+}
+
+// UpdateInstances moves the uploaded scene's mesh instances in place (polaris_hip_update_instances; DESIGN.md section 10e):
+// invTransforms holds 16 floats per instance (column major, as scene.MeshInstance.Transform), boxes 6 floats per instance (world-space
+// min.xyz, max.xyz, the scene reader's boxes), emissives the scene's emissive list with new Transform / Area values or nil to keep
+// the uploaded ones.  Afterwards the tracer behaves as if the scene had been uploaded with these and its top-level BVH refit.  The
+// scene must have been uploaded after SetInstanceUpdate(true); a refusal leaves the tracer as it was.  The slices are only read
+// during the call (cgo rule: nothing the caller owns is retained).
+func (tr *Tracer) UpdateInstances(invTransforms []float32, boxes []float32, emissives []scene.EmissivePrimitive) error {
+	tr.Lock()
+	defer tr.Unlock()
+	if len(invTransforms)%16 != 0 || len(boxes) != len(invTransforms)/16*6 || len(invTransforms) == 0 {
+		return fmt.Errorf("hip tracer (%s): UpdateInstances wants 16 matrix floats and 6 box floats per instance", tr.dev.Name)
+	}
+	// c is Go memory that holds Go pointers: the cgo rules allow passing &c only while what it points to is pinned
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	var c C.PolarisInstanceUpdate
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.num_mesh_instances = C.uint32_t(len(invTransforms) / 16)
+	pin.Pin(&invTransforms[0])
+	pin.Pin(&boxes[0])
+	c.inv_transforms = (*C.float)(unsafe.Pointer(&invTransforms[0]))
+	c.instance_boxes = (*C.float)(unsafe.Pointer(&boxes[0]))
+	if n := len(emissives); n > 0 {
+		pin.Pin(&emissives[0])
+		c.emissives, c.num_emissives = (*C.PolarisEmissive)(unsafe.Pointer(&emissives[0])), C.uint32_t(n)
+	}
+	return tr.check(C.polaris_hip_update_instances(tr.handle, &c))
 }
 
 // VarianceParams configures variance-guided denoising (PolarisVarianceParams, include/polaris_hip.h; DESIGN.md section 10c).

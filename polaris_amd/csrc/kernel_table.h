@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "kernels.h"
+#include "instance_update.h"
 
 namespace pol {
 
@@ -19,8 +20,8 @@ struct Variant {
 	constexpr Variant(void (*f)(P...), const char *s) : fn(f), symbol(s) {}
 	const void *address() const { return reinterpret_cast<const void *>(fn); } // what the occupancy and attribute calls take
 	template <class... A> // (a launch's error is left for hipGetLastError / hipPeekAtLastError)
-	void enqueue(uint32_t grid, uint32_t block, uint32_t lds_bytes, hipStream_t q, A &&...a) const {
-		fn<<<dim3(grid), dim3(block), lds_bytes, q>>>(std::forward<A>(a)...);
+	void enqueue(dim3 grid, uint32_t block, uint32_t lds_bytes, hipStream_t q, A &&...a) const { // (grid: a count, or a dim3)
+		fn<<<grid, dim3(block), lds_bytes, q>>>(std::forward<A>(a)...);
 	}
 };
 // Spell EVERY template argument, defaults included, NODES as its number: that is how the profiler prints the symbol.
@@ -79,5 +80,9 @@ const auto kDenoise = POLARIS_VARIANT(k_denoise);
 const auto kTemporal = POLARIS_VARIANT(k_temporal);
 const auto kVariance = POLARIS_VARIANT(k_variance);
 const auto kDenoiseVariance = POLARIS_VARIANT(k_denoise_variance);
+// polaris_hip_update_instances (instance_update.h)
+const auto kInstanceExtent = POLARIS_VARIANT(k_instance_extent);
+const auto kRepad = POLARIS_VARIANT(k_repad);
+const auto kRefitTop = POLARIS_VARIANT(k_refit_top);
 
 } // namespace pol

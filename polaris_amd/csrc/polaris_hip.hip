@@ -152,6 +152,23 @@ struct polaris_hip_tracer {
 	DevArray<float4> mo_table;           // motion table of the last PRIOR (temporal.h tp_motion_table), grow-only until free_temporal
 	std::vector<float> mo_table_host;
 
+	// moving instances in place (option "instance_update", polaris_hip_update_instances).  With the option on an upload
+	// keeps the update plan (scene_layout.h UpdatePlan; its device copies and the kernels' scratch live in scene_bufs and go with the
+	// scene) and host copies of the emissive list and the packed light geometry.  Off, `upd` stays empty and nothing is allocated.
+	int opt_instance_update = 0; // next upload
+	struct InstanceUpdateState {
+		bool on = false; // the uploaded scene has a plan
+		UpdatePlan plan;
+		std::vector<PolarisEmissive> emissives;
+		std::vector<float> light_geo;
+		PairNode *pairs = nullptr; InstRec *insts = nullptr; // the scene's records, writable
+		PolarisEmissive *d_emissives = nullptr; float *d_light_geo = nullptr;
+		UpdateNode *nodes = nullptr; uint32_t *level_first = nullptr, *tri_list = nullptr; uint2 *inst_range = nullptr;
+		PaddedBox *padded = nullptr; float *pads = nullptr;
+		UpdateBox *scratch = nullptr; InstUpdateRec *recs = nullptr; float *partial = nullptr;
+		uint32_t chunks = 1, chunk_tris = kExtentChunkTris; // k_instance_extent: chunks per instance, triangles per chunk
+	} upd;
+
 	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
 	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
 	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
@@ -306,7 +323,7 @@ struct Timed {
 
 // THE launch of a kernel on stream q, bracketed by the named timer, which remembers the variant's symbol; returns the launch's error (also left for hipGetLastError).
 template <class... P, class... A>
-hipError_t launch(polaris_hip_tracer *h, const char *timer, hipStream_t q, const Variant<P...> &v, uint32_t grid, uint32_t block, uint32_t lds_bytes, A &&...a) {
+hipError_t launch(polaris_hip_tracer *h, const char *timer, hipStream_t q, const Variant<P...> &v, dim3 grid, uint32_t block, uint32_t lds_bytes, A &&...a) {
 	Timed t(h, timer, v.symbol, q);
 	v.enqueue(grid, block, lds_bytes, q, std::forward<A>(a)...);
 	return hipPeekAtLastError();
@@ -520,6 +537,29 @@ void capture_history(polaris_hip_tracer *h) {
 	// (the VARIANCE plane joins the history only if it was written under the same camera; else the history has no M2)
 	if (h->va_synced) std::swap(h->va_out, h->va_hist);
 	h->va_have_hist = h->va_synced;
+}
+
+// The floats of an area light's packed record (shading.h, SceneT::light_geo) that depend on the emissive's transform and area; g[0..29]
+// hold the light's triangle.  upload_scene and update_instances share it.
+void derive_light_geo(const PolarisEmissive &em, float *g) {
+	// what areaLightGetPdf (emissive_sampler.cl:117-173) and areaLightGetSample (:96) derive from the light alone, with the
+	// kernels' own operations in the kernels' order (this file is compiled without FMA contraction; polaris_math.h is
+	// bit-identical on the host): v0, v1 - v0, v2 - v0 through mul4x1 (util/transform.cl:9-16), normalize(cross(e1, e2)), 1 / area
+	const float *m = em.transform;
+	auto xform = [&](const float p[3], float out[3]) {
+		out[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
+		out[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
+		out[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
+	};
+	const float v0[3] = {g[0], g[1], g[2]};
+	const float d1[3] = {g[4] - v0[0], g[5] - v0[1], g[6] - v0[2]}, d2[3] = {g[8] - v0[0], g[9] - v0[1], g[10] - v0[2]};
+	float tv0[3], te1[3], te2[3];
+	xform(v0, tv0); xform(d1, te1); xform(d2, te2);
+	const float cx = te1[1] * te2[2] - te1[2] * te2[1], cy = te1[2] * te2[0] - te1[0] * te2[2], cz = te1[0] * te2[1] - te1[1] * te2[0];
+	const float inv_len = 1.0f / pm_sqrt(cx * cx + cy * cy + cz * cz);
+	for (int k = 0; k < 3; k++) { g[32 + k] = tv0[k]; g[36 + k] = te1[k]; g[40 + k] = te2[k]; }
+	g[44] = cx * inv_len; g[45] = cy * inv_len; g[46] = cz * inv_len;
+	g[30] = 1.0f / em.area;
 }
 
 // The scene's k_trace variants (closest hit, any hit) into the handle: STACK from the exact depth the scene needs, NODES from its
@@ -896,6 +936,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!sc) return fail(h, POLARIS_E_BAD_ARGUMENT, "scene view is null");
 	SceneLayout L;
+	L.want_update_plan = h->opt_instance_update != 0;
 	// Defaults by scene size (measured): small scenes live in L2/LDS and are bound by
 	// instruction issue -> small leaves and packet traversal of camera rays pay; scenes far larger than
 	// the caches are bound by node fetches -> fewer, fuller leaves and one ray per lane.
@@ -903,12 +944,14 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	std::string err = build_layout(*sc, L, max_leaf);
 	if (err == "@retry-without-subdivision") { // the deeper tree would not fit the traversal stack
 		L = SceneLayout();
+		L.want_update_plan = h->opt_instance_update != 0;
 		err = build_layout(*sc, L, 0);
 	}
 	if (!err.empty()) return fail(h, POLARIS_E_BAD_SCENE, "%s", err.c_str());
 	HIP_TRY(h, hipSetDevice(h->device));
 	HIP_TRY(h, sync_all(h));
 	h->scene_bufs.clear();
+	h->upd = polaris_hip_tracer::InstanceUpdateState();
 	h->have_scene = false;
 	h->gb_valid = false;
 	{
@@ -955,24 +998,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 			for (int k = 0; k < 3; k++) { g[4 * v + k] = sc->vertices[4 * (off + v) + k]; g[12 + 4 * v + k] = sc->normals[4 * (off + v) + k]; }
 			g[24 + 2 * v] = sc->uvs[2 * (off + v)]; g[25 + 2 * v] = sc->uvs[2 * (off + v) + 1];
 		}
-		// what areaLightGetPdf (emissive_sampler.cl:117-173) and areaLightGetSample (:96) derive from the light alone, with the
-		// kernels' own operations in the kernels' order (this file is compiled without FMA contraction; polaris_math.h is
-		// bit-identical on the host): v0, v1 - v0, v2 - v0 through mul4x1 (util/transform.cl:9-16), normalize(cross(e1, e2)), 1 / area
-		const float *m = sc->emissives[e].transform;
-		auto xform = [&](const float p[3], float out[3]) {
-			out[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
-			out[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
-			out[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
-		};
-		const float v0[3] = {g[0], g[1], g[2]};
-		const float d1[3] = {g[4] - v0[0], g[5] - v0[1], g[6] - v0[2]}, d2[3] = {g[8] - v0[0], g[9] - v0[1], g[10] - v0[2]};
-		float tv0[3], te1[3], te2[3];
-		xform(v0, tv0); xform(d1, te1); xform(d2, te2);
-		const float cx = te1[1] * te2[2] - te1[2] * te2[1], cy = te1[2] * te2[0] - te1[0] * te2[2], cz = te1[0] * te2[1] - te1[1] * te2[0];
-		const float inv_len = 1.0f / pm_sqrt(cx * cx + cy * cy + cz * cz);
-		for (int k = 0; k < 3; k++) { g[32 + k] = tv0[k]; g[36 + k] = te1[k]; g[40 + k] = te2[k]; }
-		g[44] = cx * inv_len; g[45] = cy * inv_len; g[46] = cz * inv_len;
-		g[30] = 1.0f / sc->emissives[e].area;
+		derive_light_geo(sc->emissives[e], g);
 	}
 	const size_t nv = (size_t)sc->num_triangles * 3;
 	rc |= dev_upload(h, h->scene_bufs, &vertices, sc->vertices, nv);
@@ -985,6 +1011,30 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	rc |= dev_upload(h, h->scene_bufs, &light_geo, geo.data(), geo.size());
 	// the texture blob, padded: texels are fetched as the three dwords at their address whatever the format (shading.h, tex_fetch)
 	rc |= dev_alloc(h, h->scene_bufs, &tex_data, (size_t)sc->texture_data_bytes + 16);
+	polaris_hip_tracer::InstanceUpdateState U;
+	std::vector<uint2> inst_range;
+	if (L.want_update_plan) { // the update plan's device copies and the scratch of its kernels (instance_update.h)
+		const UpdatePlan &P = L.plan;
+		const uint32_t NI = sc->num_mesh_instances;
+		uint32_t longest = 1;
+		inst_range.resize(NI);
+		for (uint32_t i = 0; i < NI; i++) {
+			const uint32_t m = P.mesh_of_inst[i];
+			inst_range[i] = make_uint2(P.tri_first[m], P.tri_first[m + 1] - P.tri_first[m]);
+			longest = std::max(longest, inst_range[i].y);
+		}
+		U.chunks = std::max(1u, std::min(std::min((longest + kExtentChunkTris - 1) / kExtentChunkTris, kExtentMaxChunks), (1u << 22) / NI));
+		U.chunk_tris = (longest + U.chunks - 1) / U.chunks;
+		rc |= dev_upload(h, h->scene_bufs, &U.nodes, P.nodes.data(), P.nodes.size());
+		rc |= dev_upload(h, h->scene_bufs, &U.level_first, P.level_first.data(), P.level_first.size());
+		rc |= dev_upload(h, h->scene_bufs, &U.tri_list, P.tri_list.data(), P.tri_list.size());
+		rc |= dev_upload(h, h->scene_bufs, &U.inst_range, inst_range.data(), inst_range.size());
+		rc |= dev_upload(h, h->scene_bufs, &U.padded, P.padded.data(), P.padded.size());
+		rc |= dev_alloc(h, h->scene_bufs, &U.pads, P.mesh_box.size());
+		rc |= dev_alloc(h, h->scene_bufs, &U.scratch, P.nodes.size());
+		rc |= dev_alloc(h, h->scene_bufs, &U.recs, (size_t)NI);
+		rc |= dev_alloc(h, h->scene_bufs, &U.partial, (size_t)NI * U.chunks * 6);
+	}
 	if (!rc && sc->texture_data_bytes) HIP_TRY(h, hipMemcpyAsync(tex_data, sc->texture_data, sc->texture_data_bytes, hipMemcpyHostToDevice, h->stream));
 	if (rc) { h->scene_bufs.clear(); return rc; }
 	HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors in L die at return
@@ -1002,6 +1052,14 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	}
 	h->scene = SceneDev{vertices, normals, uvs, mat_index, nodes, emissives, tex_meta, tex_data, sc->num_emissives,
 	                    sc->scene_diffuse_mat_index, sc->num_material_nodes, sc->num_textures, light_geo, sc->num_emissives ? pm_rcp((float)(int)sc->num_emissives) : 0.0f, L.tri_bits};
+	if (L.want_update_plan) {
+		U.on = true;
+		U.pairs = pairs; U.insts = insts; U.d_emissives = emissives; U.d_light_geo = light_geo;
+		U.plan = std::move(L.plan);
+		U.emissives.assign(sc->emissives, sc->emissives + sc->num_emissives);
+		U.light_geo = std::move(geo);
+		h->upd = std::move(U);
+	}
 	h->max_stack = L.max_stack;
 	h->num_insts = (uint32_t)L.insts.size();
 	h->tex_bytes = sc->texture_data_bytes;
@@ -1030,6 +1088,94 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	h->trace[0].resident_per_cu = trace_occupancy(h, false);
 	h->trace[1].resident_per_cu = trace_occupancy(h, true);
 	h->have_scene = true;
+	return POLARIS_OK;
+}
+
+// Move the uploaded scene's mesh instances in place (include/polaris_hip.h; instance_update.h has the arithmetic).
+int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpdate *u) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
+	std::string msg;
+	if (int st = check_instance_update(u, h->have_scene, U.on, h->num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
+	const uint32_t NI = h->num_insts;
+	std::vector<InstUpdateRec> recs;
+	std::vector<float> pads;
+	if (int st = prepare_instance_update(U.plan, NI, u->inv_transforms, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str());
+	std::vector<float> geo;
+	if (u->emissives) { // the floats of the packed light records that depend on transform and area
+		geo = U.light_geo;
+		for (uint32_t e = 0; e < u->num_emissives; e++)
+			if (u->emissives[e].type == POLARIS_EMISSIVE_AREA) derive_light_geo(u->emissives[e], geo.data() + (size_t)e * kLightGeoFloats);
+	}
+	// ---- accepted: from here on the state changes ----
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, sync_all(h));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	h->gb_valid = false;
+	{
+		// to the temporal history the update is what an upload_scene is (see there): with object motion the planes synced under the old
+		// matrices join the history, which stays -- instances and meshes are the same; without, the history saw the old scene and goes
+		bool keep = false;
+		polaris_hip_tracer::InstTable next = h->mo_cur;
+		if (h->opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
+		if (motion_on(h)) {
+			capture_history(h);
+			keep = h->tp_have_hist && h->mo_hist.compatible(next);
+		}
+		if (h->tp.max_history) {
+			if (!keep) h->tp_have_hist = h->va_have_hist = false;
+			h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
+		}
+		h->mo_cur = std::move(next);
+	}
+	hipStream_t q = h->stream;
+	const UpdatePlan &P = U.plan;
+	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
+	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	if (u->emissives && u->num_emissives) {
+		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, u->emissives, (size_t)u->num_emissives * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
+		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	}
+	(void)launch(h, "instance_extent", q, kInstanceExtent, dim3(U.chunks, std::min(NI, 65535u)), kExtentBlock, 0, h->scene.vertices, U.tri_list, U.inst_range, U.recs, NI,
+	             U.chunk_tris, U.partial);
+	if (!P.padded.empty())
+		(void)launch(h, "repad", q, kRepad, ((uint32_t)P.padded.size() + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, U.padded, (uint32_t)P.padded.size(), U.pads, U.pairs);
+	const RefitArgs A{U.nodes, U.level_first, U.scratch, U.pairs, U.insts, U.recs, U.partial, U.chunks};
+	const uint32_t levels = (uint32_t)P.level_first.size() - 1;
+	if (P.nodes.size() <= kRefitOneGroupNodes) (void)launch(h, "refit_top", q, kRefitTop, 1, kRefitBlock, 0, A, 0u, levels);
+	else
+		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
+			(void)launch(h, "refit_top", q, kRefitTop, (P.level_first[l + 1] - P.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(q)); // (recs, pads and geo die at return)
+	collect_timers(h);
+	if (h->bvh.root_is_instance) { // the one instance's record travels in the kernel arguments
+		const InstUpdateRec &R = recs[((uint32_t)~h->bvh.root_ref) >> 4];
+		h->bvh.root_inst.r0 = make_float4(R.r0[0], R.r0[1], R.r0[2], R.r0[3]);
+		h->bvh.root_inst.r1 = make_float4(R.r1[0], R.r1[1], R.r1[2], R.r1[3]);
+		h->bvh.root_inst.r2 = make_float4(R.r2[0], R.r2[1], R.r2[2], R.r2[3]);
+	}
+	if (u->emissives) {
+		U.emissives.assign(u->emissives, u->emissives + u->num_emissives);
+		U.light_geo = std::move(geo);
+	}
+	return POLARIS_OK;
+}
+
+int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, size_t n_bytes) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (which != POLARIS_REC_PAIRS && which != POLARIS_REC_INSTS && which != POLARIS_REC_COUNTS) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: unknown record kind %d", which);
+	uint64_t counts[4] = {h->bvh.num_pairs, h->num_insts, h->scene_bufs.size(), 0};
+	for (const DevArray<char> &b : h->scene_bufs) counts[3] += b.capacity();
+	const size_t need = which == POLARIS_REC_COUNTS ? sizeof counts : (size_t)counts[which] * 64;
+	if (!out || n_bytes < need) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: need %zu bytes", need);
+	if (which == POLARIS_REC_COUNTS) { memcpy(out, counts, sizeof counts); return POLARIS_OK; }
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	HIP_TRY(h, hipMemcpy(out, which == POLARIS_REC_PAIRS ? (const void *)h->bvh.pairs : (const void *)h->bvh.insts, need, hipMemcpyDeviceToHost));
 	return POLARIS_OK;
 }
 
@@ -1118,6 +1264,10 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 				h->mo_table.reset();
 			}
 		}
+	}
+	else if (k == "instance_update") { // next upload
+		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "instance_update is 0 or 1");
+		h->opt_instance_update = (int)value;
 	}
 	else if (k == "max_leaf_tris") h->opt_max_leaf_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
 	else return fail(h, POLARIS_E_BAD_ARGUMENT, "unknown option '%s'", key);

@@ -55,6 +55,80 @@ constexpr int kTraversalStack = 32; // entries per ray, == BVH_MAX_STACK_SIZE (i
 
 constexpr uint32_t kBigLeafFlag = 1u << 30; // leaf code: count nibble 0 and this bit = "look the triangle range up in LeafInfo[node]"
 
+#if defined(__HIPCC__)
+#define POL_HD __host__ __device__
+#else
+#define POL_HD
+#endif
+
+// What polaris_hip_update_instances needs beside the uploaded records: the top-level tree as a refit schedule, the
+// triangles of every mesh, and the terms of the leaf-subdivision padding.  Filled by build_layout when want_update_plan is set.
+struct UpdateNode {
+	int32_t kid0, kid1;   // inner node: its children as plan indices; instance leaf: kid0 = the mesh instance, kid1 = -1
+	int32_t pair;         // inner node: index of its pair record AFTER the breadth-first renumbering; leaf: -1
+	int32_t parent_side;  // parent's plan index << 1 | side of the parent's record (0 = lo0/hi0, 1 = lo1/hi1); -1 for the root
+};
+struct PaddedBox {
+	int32_t pair;        // the pair record (after the renumbering) that holds the box ...
+	uint32_t side_mesh;  // ... side (bit 0: 0 = lo0/hi0, 1 = lo1/hi1) | index of its mesh << 1
+	float lo[3], hi[3];  // exact bounds of its triangles: the record holds lo - pad, hi + pad (subdivision_pad, largest over the mesh's instances)
+};
+struct UpdatePlan {
+	std::vector<UpdateNode> nodes;      // deepest level first, the nodes of a level contiguous: children come before their parent
+	std::vector<uint32_t> level_first;  // [levels + 1]: level l is nodes[level_first[l] .. level_first[l + 1])
+	std::vector<uint32_t> mesh_of_inst; // [NI]: index of the instance's mesh in the arrays below (one entry per distinct mesh root)
+	std::vector<uint32_t> tri_first;    // [meshes + 1]: mesh m owns tri_list[tri_first[m] .. tri_first[m + 1])
+	std::vector<uint32_t> tri_list;     // scene triangle indices below each mesh root (the mesh_tris walk without its work cap)
+	std::vector<PolarisBvhNode> mesh_box; // [meshes]: the mesh root's node (its box is a term of the padding)
+	std::vector<PaddedBox> padded;      // every box leaf subdivision added: where it is held, and what it is before the padding
+};
+
+// Padding of the boxes leaf subdivision adds below the mesh root `rb` for an instance with inverse matrix m (column major) in a
+// scene whose world box is `world`: 2^-13 of the scene's extent in the mesh's object space (build_layout).
+inline float subdivision_pad(const float *m, const PolarisBvhNode &world, const PolarisBvhNode &rb) {
+	float ext = 0.0f;
+	for (int corner = 0; corner < 8; corner++) {
+		const float w[3] = {corner & 1 ? world.max[0] : world.min[0], corner & 2 ? world.max[1] : world.min[1],
+		                    corner & 4 ? world.max[2] : world.min[2]};
+		for (int r = 0; r < 3; r++) {
+			const float v = std::fabs(m[r] * w[0] + m[4 + r] * w[1] + m[8 + r] * w[2] + m[12 + r]);
+			if (!(v <= ext)) ext = v; // also takes NaN
+		}
+	}
+	for (int k = 0; k < 3; k++) { ext = std::fmax(ext, std::fabs(rb.min[k])); ext = std::fmax(ext, std::fabs(rb.max[k])); }
+	float pad = ext * (1.0f / 8192.0f);
+	if (!(pad <= 1e30f)) pad = 1e30f;
+	return pad;
+}
+
+// Forward (object -> world) matrix of an instance, row major in double, from its stored inverse (column major); false: singular.
+inline bool invert_instance_matrix(const float *a, double *o) {
+	double m[4][8];
+	for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { m[r][c] = a[4 * c + r]; m[r][4 + c] = r == c; }
+	for (int c = 0; c < 4; c++) {
+		int piv = c;
+		for (int r = c + 1; r < 4; r++) if (std::fabs(m[r][c]) > std::fabs(m[piv][c])) piv = r;
+		if (!(std::fabs(m[piv][c]) > 0.0)) return false;
+		for (int k = 0; k < 8; k++) std::swap(m[c][k], m[piv][k]);
+		const double d = m[c][c];
+		for (int k = 0; k < 8; k++) m[c][k] /= d;
+		for (int r = 0; r < 4; r++) if (r != c) { const double f = m[r][c]; for (int k = 0; k < 8; k++) m[r][k] -= f * m[c][k]; }
+	}
+	for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) o[4 * r + c] = m[r][4 + c]; // row major
+	return true;
+}
+
+// Does the box [bmin, bmax] contain the content [clo, chi]?  A few ulps of tolerance: the extent of an instance is recomputed
+// through the forward matrix in double, the host rounded its own way (far inside the 1.001 cull margin either way).
+POL_HD inline bool box_bounds_content(const float *bmin, const float *bmax, const float *clo, const float *chi) {
+	bool inside = true;
+	for (int k = 0; k < 3; k++) {
+		const float tol = 9.6e-7f * fmaxf(fmaxf(fabsf(clo[k]), fabsf(chi[k])), chi[k] - clo[k]) + 1e-30f;
+		if (!(bmin[k] - tol <= clo[k] && chi[k] <= bmax[k] + tol)) inside = false;
+	}
+	return inside;
+}
+
 struct SceneLayout {
 	std::vector<PairNodeH> pairs;   // inner nodes only, in breadth-first order (the first kLdsTopNodes are staged in LDS)
 	std::vector<LeafInfoH> leaves;  // indexed by node id (only leaves meaningful; the kernels read it for leaves of > 15 triangles only)
@@ -68,6 +142,8 @@ struct SceneLayout {
 	// triangles, else 31 = no class).  The traversal kernels hand the word through to the hit record untouched; k_shade
 	// sorts a workgroup's rays by the class and masks it off.
 	uint32_t tri_bits = 31;
+	bool want_update_plan = false;  // set by the caller: build_layout also fills `plan` (option instance_update)
+	UpdatePlan plan;
 };
 
 // Shading class of every material node = which BxDF leaves and texture operators the tree rooted at it can reach.  k_shade
@@ -322,30 +398,22 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 
 	// ---- optional subdivision of big leaves ---------------------------------------------------
 	bool subdivided = false;
+	std::vector<float> root_pad; // per mesh root: padding of the boxes added below it
+	struct AddedBox { int32_t node, root; float lo[3], hi[3]; };
+	std::vector<AddedBox> added_boxes;                     // (for the update plan) the boxes subdivision adds, unpadded
+	std::vector<std::pair<int32_t, int>> added_parent;     // added node (index - NN) -> the node whose children it is one of, side
 	if (max_leaf_tris > 0) {
 		// extent of the scene in each mesh's object space -> padding of the added boxes
-		std::vector<float> root_pad(NN, 0.0f);
+		root_pad.assign(NN, 0.0f);
 		const PolarisBvhNode &world = sc.bvh_nodes[0];
 		for (uint32_t i = 0; i < NI; i++) {
 			const PolarisMeshInstance &mi = sc.mesh_instances[i];
-			const float *m = mi.inv_transform; // column major: m[4*c + r]
-			float ext = 0.0f;
-			for (int corner = 0; corner < 8; corner++) {
-				const float w[3] = {corner & 1 ? world.max[0] : world.min[0], corner & 2 ? world.max[1] : world.min[1],
-				                    corner & 4 ? world.max[2] : world.min[2]};
-				for (int r = 0; r < 3; r++) {
-					const float v = std::fabs(m[r] * w[0] + m[4 + r] * w[1] + m[8 + r] * w[2] + m[12 + r]);
-					if (!(v <= ext)) ext = v; // also takes NaN
-				}
-			}
-			const PolarisBvhNode &rb = sc.bvh_nodes[mi.bvh_root];
-			for (int k = 0; k < 3; k++) { ext = std::fmax(ext, std::fabs(rb.min[k])); ext = std::fmax(ext, std::fabs(rb.max[k])); }
-			float pad = ext * (1.0f / 8192.0f);
-			if (!(pad <= 1e30f)) pad = 1e30f;
+			const float pad = subdivision_pad(mi.inv_transform, world, sc.bvh_nodes[mi.bvh_root]);
 			if (pad > root_pad[mi.bvh_root]) root_pad[mi.bvh_root] = pad;
 		}
 		struct Range { int32_t node; uint32_t lo, hi; };
 		std::vector<Range> work;
+		added_parent.clear();
 		for (uint32_t idx = 0; idx < NN; idx++) {
 			if (leaf_root[idx] < 0) continue;
 			const PolarisBvhNode src = sc.bvh_nodes[idx];
@@ -376,8 +444,10 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 					}
 				}
 				PolarisBvhNode &nd = nodes[rg.node];
-				if (rg.node != (int32_t)idx) // the reference's own leaf keeps the reference's box
+				if (rg.node != (int32_t)idx) { // the reference's own leaf keeps the reference's box
 					for (int k = 0; k < 3; k++) { nd.min[k] = bmin[k] - pad; nd.max[k] = bmax[k] + pad; }
+					if (out.want_update_plan) added_boxes.push_back({rg.node, leaf_root[idx], {bmin[0], bmin[1], bmin[2]}, {bmax[0], bmax[1], bmax[2]}});
+				}
 				// surface-area sweep over the three axes (triangles sorted by centroid): split where
 				// area(L)*|L| + area(R)*|R| is smallest, and only if that beats testing all of them
 				int best_axis = -1;
@@ -423,6 +493,8 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 				nodes.push_back(PolarisBvhNode{});
 				nodes[rg.node].ldata = l;
 				nodes[rg.node].rdata = l + 1;
+				added_parent.push_back({rg.node, 0});
+				added_parent.push_back({rg.node, 1});
 				work.push_back({l, rg.lo, mid});
 				work.push_back({l + 1, mid, rg.hi});
 			}
@@ -475,21 +547,7 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 		auto grow = [](Box &b, const float *p) { for (int k = 0; k < 3; k++) { b.lo[k] = std::fmin(b.lo[k], p[k]); b.hi[k] = std::fmax(b.hi[k], p[k]); } };
 		auto merge = [&](Box &b, const Box &c) { grow(b, c.lo); grow(b, c.hi); };
 		// forward (object -> world) matrices, in double: the stored ones are the inverses
-		auto invert = [](const float *a, double *o) {
-			double m[4][8];
-			for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { m[r][c] = a[4 * c + r]; m[r][4 + c] = r == c; }
-			for (int c = 0; c < 4; c++) {
-				int piv = c;
-				for (int r = c + 1; r < 4; r++) if (std::fabs(m[r][c]) > std::fabs(m[piv][c])) piv = r;
-				if (!(std::fabs(m[piv][c]) > 0.0)) return false;
-				for (int k = 0; k < 8; k++) std::swap(m[c][k], m[piv][k]);
-				const double d = m[c][c];
-				for (int k = 0; k < 8; k++) m[c][k] /= d;
-				for (int r = 0; r < 4; r++) if (r != c) { const double f = m[r][c]; for (int k = 0; k < 8; k++) m[r][k] -= f * m[c][k]; }
-			}
-			for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) o[4 * r + c] = m[r][4 + c]; // row major
-			return true;
-		};
+		auto invert = invert_instance_matrix;
 		// scene triangles below a mesh root (cached); empty when transforming them for every instance of the
 		// mesh would be too much work (more than ~32 M vertex transforms per upload)
 		std::vector<uint32_t> inst_count(n_nodes, 0);
@@ -583,13 +641,7 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 		auto cull_factor = [&](int32_t child) {
 			const PolarisBvhNode &n = nodes[child];
 			const Box &c = content[child];
-			bool inside = true;
-			for (int k = 0; k < 3; k++) {
-				// a few ulps: the extent of an instance is recomputed here through the forward matrix in
-				// double, the host rounded its own way (far inside the 1.001 cull margin either way)
-				const float tol = 9.6e-7f * std::fmax(std::fmax(std::fabs(c.lo[k]), std::fabs(c.hi[k])), c.hi[k] - c.lo[k]) + 1e-30f;
-				if (!(n.min[k] - tol <= c.lo[k] && c.hi[k] <= n.max[k] + tol)) inside = false;
-			}
+			const bool inside = box_bounds_content(n.min, n.max, c.lo, c.hi);
 			return inside ? kCullMargin : std::numeric_limits<float>::infinity();
 		};
 		for (uint32_t idx = 0; idx < n_nodes; idx++) {
@@ -648,6 +700,71 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 		if (out.pairs.empty()) out.pairs.push_back(PairNodeH{}); // never an empty device array
 		out.root_ref = remap(out.root_ref);
 		for (uint32_t i = 0; i < NI; i++) out.insts[i].root_ref = remap(out.insts[i].root_ref);
+
+		// ---- the update plan (polaris_hip_update_instances) ---------------------------------------
+		out.plan = UpdatePlan();
+		if (out.want_update_plan) {
+			UpdatePlan &P = out.plan;
+			// top-level nodes with their depth, parents before children; then levels, deepest first
+			struct Top { int32_t node, parent; int depth, side; };
+			std::vector<Top> top{{0, -1, 0, 0}};
+			int deepest = 0;
+			for (size_t k = 0; k < top.size(); k++) {
+				const Top t = top[k];
+				const PolarisBvhNode &n = nodes[t.node];
+				deepest = std::max(deepest, t.depth);
+				if (is_leaf(n)) continue;
+				top.push_back({n.ldata, (int32_t)k, t.depth + 1, 0});
+				top.push_back({n.rdata, (int32_t)k, t.depth + 1, 1});
+			}
+			std::vector<uint32_t> plan_of(top.size());
+			P.level_first.push_back(0);
+			for (int d = deepest; d >= 0; d--) {
+				for (size_t k = 0; k < top.size(); k++)
+					if (top[k].depth == d) { plan_of[k] = (uint32_t)P.nodes.size(); P.nodes.push_back(UpdateNode{-1, -1, -1, -1}); }
+				P.level_first.push_back((uint32_t)P.nodes.size());
+			}
+			for (size_t k = 0; k < top.size(); k++) {
+				const PolarisBvhNode &n = nodes[top[k].node];
+				UpdateNode &u = P.nodes[plan_of[k]];
+				if (is_leaf(n)) u.kid0 = (int32_t)(uint32_t)(-(int64_t)n.ldata);
+				else u.pair = new_id[top[k].node];
+				if (top[k].parent >= 0) {
+					UpdateNode &up = P.nodes[plan_of[top[k].parent]];
+					(top[k].side ? up.kid1 : up.kid0) = (int32_t)plan_of[k];
+					u.parent_side = (int32_t)(plan_of[top[k].parent] << 1 | (uint32_t)top[k].side);
+				}
+			}
+			// the triangles of every distinct mesh root, and the padding its added boxes got
+			std::vector<int32_t> mesh_id(n_nodes, -1);
+			P.mesh_of_inst.resize(NI);
+			P.tri_first.push_back(0);
+			for (uint32_t i = 0; i < NI; i++) {
+				const uint32_t root = sc.mesh_instances[i].bvh_root;
+				if (mesh_id[root] < 0) {
+					mesh_id[root] = (int32_t)P.mesh_box.size();
+					P.mesh_box.push_back(sc.bvh_nodes[root]);
+					std::vector<int32_t> stack{(int32_t)root};
+					while (!stack.empty()) {
+						const PolarisBvhNode &m = nodes[stack.back()];
+						stack.pop_back();
+						if (is_leaf(m)) {
+							const uint32_t f0 = (uint32_t)(-(int64_t)m.ldata);
+							for (uint32_t q = f0; q < f0 + (uint32_t)m.rdata; q++) P.tri_list.push_back(slot_src[q]);
+						} else { stack.push_back(m.rdata); stack.push_back(m.ldata); }
+					}
+					P.tri_first.push_back((uint32_t)P.tri_list.size());
+				}
+				P.mesh_of_inst[i] = (uint32_t)mesh_id[root];
+			}
+			if (subdivided)
+				for (const AddedBox &a : added_boxes) {
+					const std::pair<int32_t, int> &par = added_parent[(size_t)a.node - NN];
+					if (new_id[par.first] < 0 || mesh_id[a.root] < 0) continue; // (below a leaf no instance reaches)
+					P.padded.push_back(PaddedBox{new_id[par.first], (uint32_t)par.second | (uint32_t)mesh_id[a.root] << 1,
+					                             {a.lo[0], a.lo[1], a.lo[2]}, {a.hi[0], a.hi[1], a.hi[2]}});
+				}
+		}
 	}
 
 	// ---- small scenes: triangle slots in the order of how often a ray reaches their leaf ------------------------------------------

@@ -261,6 +261,42 @@ class BvhBuildInput(C.Structure):
 BVH_SAH, BVH_LBVH = 0, 1   # PolarisBvhBuildInput.algorithm
 
 
+class InstanceUpdate(C.Structure):
+    """PolarisInstanceUpdate (include/polaris_hip.h): what polaris_hip_update_instances moves the uploaded scene's instances to."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_mesh_instances", C.c_uint32),
+        ("inv_transforms", C.c_void_p), ("instance_boxes", C.c_void_p),
+        ("emissives", C.c_void_p), ("num_emissives", C.c_uint32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(InstanceUpdate) == 40
+REC_PAIRS, REC_INSTS, REC_COUNTS = 0, 1, 2   # polaris_hip_read_scene_records
+PAIR_RECORD = np.dtype([("lo0", "<f4", 3), ("ref0", "<i4"), ("hi0", "<f4", 3), ("cull0", "<f4"),
+                        ("lo1", "<f4", 3), ("ref1", "<i4"), ("hi1", "<f4", 3), ("cull1", "<f4")])
+INST_RECORD = np.dtype([("r0", "<f4", 4), ("r1", "<f4", 4), ("r2", "<f4", 4), ("root_ref", "<i4"), ("rank", "<u4"), ("pad", "<u4", 2)])
+assert PAIR_RECORD.itemsize == 64 and INST_RECORD.itemsize == 64
+
+
+def instance_update(inv, boxes, emissives=None):
+    """An InstanceUpdate over the given arrays, and the arrays it borrows (keep them alive while it is used)."""
+    inv = np.ascontiguousarray(inv, dtype=np.float32).reshape(-1, 16)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    u = InstanceUpdate()
+    u.num_mesh_instances = len(inv)
+    u.inv_transforms, u.instance_boxes = inv.ctypes.data, boxes.ctypes.data
+    keep = [inv, boxes]
+    if emissives is not None:
+        em = np.ascontiguousarray(emissives, dtype=EMISSIVE)
+        u.emissives, u.num_emissives = (em.ctypes.data if em.size else None), len(em)
+        keep.append(em)
+    return u, keep
+
+
 def _ptr(a):
     return None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
 
@@ -297,6 +333,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
+    "polaris_hip_update_instances", "polaris_hip_read_scene_records",
 ]
 
 _lib = None
@@ -404,6 +441,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_reproject_motion_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp,
                                                         C.POINTER(TemporalParams), vp, vp, vp]
     lib.polaris_hip_read_instance_plane.argtypes = [vp, vp, C.c_size_t]
+    lib.polaris_hip_update_instances.argtypes = [vp, C.POINTER(InstanceUpdate)]
+    lib.polaris_hip_read_scene_records.argtypes = [vp, i32, vp, C.c_size_t]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

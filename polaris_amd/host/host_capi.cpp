@@ -132,6 +132,22 @@ int polaris_host_renderer_set_option(void *h, const char *key, int64_t value) {
 		if (int rc = polaris_hip_set_option(t->Handle(), key, value)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// A new scene: UpdateState(SceneData) on every tracer.  (An option that applies to the NEXT upload -- "instance_update" -- is set
+// with polaris_host_renderer_set_option first; the constructor's own upload came before any option.)
+int polaris_host_renderer_upload_scene(void *h, const PolarisSceneView *scene) {
+	auto *box = static_cast<RendererBox *>(h);
+	if (!scene) return POLARIS_E_BAD_ARGUMENT;
+	if (Error e = box->r->UpdateAll(tracer::ChangeType::SceneData, scene)) { box->error = e.msg; return e.code; }
+	return 0;
+}
+// Moving the scene's mesh instances in place (polaris_hip_update_instances) on every tracer, as set_option: every
+// tracer holds the whole scene.  The tracers must have been given the option "instance_update" before the scene.
+int polaris_host_renderer_update_instances(void *h, const PolarisInstanceUpdate *u) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (Error e = t->UpdateInstances(u)) { box->error = e.msg; return e.code; }
+	return 0;
+}
 // Denoising (polaris_hip_set_denoise) on every tracer, as set_option; only the primary's SyncFramebuffer runs, so only it filters.
 int polaris_host_renderer_set_denoise(void *h, const PolarisDenoiseParams *p) {
 	auto *box = static_cast<RendererBox *>(h);

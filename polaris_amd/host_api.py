@@ -34,6 +34,8 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_push_seeds.argtypes = [vp, C.c_uint32, vp, C.c_size_t]
         lib.polaris_host_renderer_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         lib.polaris_host_renderer_set_denoise.argtypes = [vp, C.POINTER(T.DenoiseParams)]
+        lib.polaris_host_renderer_update_instances.argtypes = [vp, C.POINTER(T.InstanceUpdate)]
+        lib.polaris_host_renderer_upload_scene.argtypes = [vp, C.POINTER(T.SceneView)]
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
         lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
@@ -158,6 +160,22 @@ class Renderer:
         """The option "object_motion" on every tracer (temporal reuse across moving mesh instances); only the primary syncs,
         so only the primary's history is ever used."""
         self.set_option("object_motion", 1 if on else 0)
+
+    def upload_scene(self, scene) -> None:
+        """A new scene: UpdateState(SceneData) on every tracer.  Options that apply to the next upload ("instance_update") take
+        effect here; the constructor's upload came before any option."""
+        self._scene, self._view = scene, T.scene_view(scene)
+        if self._lib.polaris_host_renderer_upload_scene(self._h, C.byref(self._view)):
+            raise RuntimeError(f"upload_scene failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def update_instances(self, inv, boxes, emissives=None) -> None:
+        """polaris_hip_update_instances on every tracer: move the scene's mesh instances in place.  Arguments as
+        HipTracer.update_instances; the scene must have been uploaded with the option on: set_option("instance_update", 1), then
+        upload_scene (the constructor's upload came before any option)."""
+        u, keep = T.instance_update(inv, boxes, emissives)
+        if self._lib.polaris_host_renderer_update_instances(self._h, C.byref(u)):
+            raise RuntimeError(f"update_instances failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+        del keep
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """polaris_hip_set_variance on every tracer, after the option "moments" on every tracer (polaris_host_renderer_set_variance)."""

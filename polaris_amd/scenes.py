@@ -588,11 +588,12 @@ def scaling(sx, sy, sz):
     return np.diag([sx, sy, sz, 1.0])
 
 
-def transformed_instances(aspect=1.0) -> Scene:
+def transformed_instances(aspect=1.0, turn=0.0) -> Scene:
     """Instances with rotation and NON-UNIFORM SCALE, one of them carrying an emissive triangle
     pair: exercises the ray transform on instance entry / exit (intersect.cl:239-252, 330-335), the
     comparison of hit distances across differently scaled instance spaces and reference quirk
-    a-9(4) (emissive normals and pdf edges go through the point transform of the INVERSE matrix)."""
+    a-9(4) (emissive normals and pdf edges go through the point transform of the INVERSE matrix).
+    turn: extra rotation (rad, about the vertical) of the first cube and of the light panel (a moved step of the same scene)."""
     mt = MaterialTable()
     a = mt.diffuse((0.7, 0.5, 0.2))
     b = mt.mix(mt.diffuse((0.2, 0.4, 0.7)), mt.conductor((0.9, 0.9, 0.9)), 0.5)
@@ -605,11 +606,11 @@ def transformed_instances(aspect=1.0) -> Scene:
     ground = quad((-6, 0, -6), (-6, 0, 6), (6, 0, 6), (6, 0, -6), floor)
     insts = [
         (3, np.eye(4)),
-        (0, translation((-1.5, 0.8, 0)) @ rotation_y(0.6) @ scaling(1.0, 1.6, 0.7)),
+        (0, translation((-1.5, 0.8, 0)) @ rotation_y(0.6 + turn) @ scaling(1.0, 1.6, 0.7)),
         (0, translation((1.4, 0.4, -0.8)) @ rotation_y(-1.1) @ scaling(0.8, 0.8, 0.8)),
         (1, translation((0.1, 0.9, 0.6)) @ scaling(1.8, 0.9, 1.2)),
         (1, translation((-0.4, 0.35, 2.0)) @ rotation_y(2.0) @ scaling(0.7, 0.7, 0.7)),
-        (2, translation((0.0, 3.5, 0.0)) @ rotation_y(0.4) @ scaling(2.5, 1.0, 1.5)),
+        (2, translation((0.0, 3.5, 0.0)) @ rotation_y(0.4 + turn) @ scaling(2.5, 1.0, 1.5)),
     ]
     sc = compile_scene([cube, ball, panel, ground], insts, mt, scene_diffuse=bg, name="transformed-instances")
     sc.set_camera(eye=(0, 2.4, 6.0), look=(0, 0.8, 0), fov=0.75, aspect=aspect)
@@ -645,6 +646,105 @@ def moving_instances(step=0, aspect=1.0) -> Scene:
     sc = compile_scene([room, tall, short], insts, mt, name=f"moving-instances-{step}")
     sc.set_camera(eye=(278 * s, 273 * s, -800 * s), look=(278 * s, 273 * s, 0), fov=0.6911, aspect=aspect)
     return sc
+
+
+def rotation_axis(axis, a):
+    """Rotation by a rad about `axis` (Rodrigues)."""
+    x, y, z = _normalize(np.asarray(axis, dtype=np.float64))
+    K = np.array([[0, -z, y], [z, 0, -x], [-y, x, 0]])
+    m = np.eye(4)
+    m[:3, :3] = np.eye(3) + math.sin(a) * K + (1 - math.cos(a)) * (K @ K)
+    return m
+
+
+def instance_swarm(n=150, seed=11, step=0, aspect=1.0) -> Scene:
+    """n mesh instances: a ground quad, a light panel, and n - 2 cubes and small spheres (alternating: every mesh is shared) with
+    seeded random rotations and NON-UNIFORM scales, drifting and turning with `step`.  Every step has the same meshes, instances
+    and triangles; the top-level tree is rebuilt per step (scenes.refit_instances)."""
+    assert n >= 3
+    rng = np.random.default_rng(seed)
+    mt = MaterialTable()
+    a = mt.diffuse((0.7, 0.5, 0.2))
+    b = mt.diffuse((0.2, 0.4, 0.7))
+    floor = mt.diffuse((0.6, 0.6, 0.6))
+    light = mt.emissive((6, 6, 5), 1.5)
+    bg = mt.diffuse((0.2, 0.25, 0.35))
+    cube = box((-0.5, -0.5, -0.5), (0.5, 0.5, 0.5), a)
+    ball = uv_sphere((0, 0, 0), 0.5, b, n_lat=6, n_lon=8)
+    panel = merge([quad((-0.5, 0, -0.5), (0.5, 0, -0.5), (0.5, 0, 0.5), (-0.5, 0, 0.5), light)])
+    ground = quad((-9, 0, -9), (-9, 0, 9), (9, 0, 9), (9, 0, -9), floor)
+    insts = [(3, np.eye(4)), (2, translation((0.0, 6.0, 0.0)) @ scaling(6.0, 1.0, 6.0))]
+    for i in range(n - 2):
+        pos = rng.uniform((-7, 0.4, -7), (7, 3.0, 7))
+        vel = rng.normal(scale=0.05, size=3)
+        axis = rng.normal(size=3)
+        ang, rate = rng.uniform(0, 2 * math.pi), rng.normal(scale=0.1)
+        sc3 = rng.uniform(0.3, 1.2, size=3)
+        insts.append((i % 2, translation(pos + step * vel) @ rotation_axis(axis, ang + step * rate) @ scaling(*sc3)))
+    sc = compile_scene([cube, ball, panel, ground], insts, mt, scene_diffuse=bg, name=f"swarm-{n}-{step}")
+    sc.set_camera(eye=(0, 5.0, 14.0), look=(0, 1.0, 0), fov=0.75, aspect=aspect)
+    return sc
+
+
+def _top_level_nodes(scene: Scene):
+    """Indices and depths of the top-level BVH nodes (node 0 down to the instance leaves), parents before children."""
+    nodes = scene.bvh_nodes
+    idx, depth = [0], [0]
+    k = 0
+    while k < len(idx):
+        n = nodes[idx[k]]
+        if n["ldata"] > 0:
+            idx += [int(n["ldata"]), int(n["rdata"])]
+            depth += [depth[k] + 1] * 2
+        k += 1
+    return np.array(idx, dtype=np.int64), np.array(depth, dtype=np.int64)
+
+
+def instance_boxes(scene: Scene) -> np.ndarray:
+    """(NI, 6) f32: min.xyz, max.xyz of every mesh instance as the scene's top-level leaves hold them (the scene reader's boxes)."""
+    idx, _ = _top_level_nodes(scene)
+    top = scene.bvh_nodes[idx]
+    leaves = top[top["ldata"] <= 0]
+    out = np.zeros((len(scene.mesh_instances), 6), dtype=F32)
+    inst = -leaves["ldata"].astype(np.int64)
+    out[inst, :3] = leaves["min"]
+    out[inst, 3:] = leaves["max"]
+    return out
+
+
+def instance_update_args(scene: Scene):
+    """(inv_transforms (NI, 16), instance_boxes (NI, 6), emissives) of a scene: what HipTracer.update_instances takes to move an
+    uploaded scene's instances to where they are in `scene` (polaris_hip_update_instances)."""
+    return (np.ascontiguousarray(scene.mesh_instances["inv_transform"], dtype=F32).copy(), instance_boxes(scene), scene.emissives.copy())
+
+
+def refit_instances(base: Scene, moved: Scene) -> Scene:
+    """`moved`'s instance matrices and emissives on `base`'s top-level topology, the top-level boxes refit: a leaf takes moved's box
+    of its instance verbatim, an inner node the component-wise minimum / maximum of its two children (where +0 meets -0, the left
+    child's).  compile_scene rebuilds the top-level tree for every step of an animation, so two steps may differ in topology; this
+    is the scene polaris_hip_update_instances makes of an uploaded `base`.  Everything else is base's."""
+    assert len(base.mesh_instances) == len(moved.mesh_instances) and len(base.emissives) == len(moved.emissives)
+    assert np.array_equal(base.mesh_instances["mesh_index"], moved.mesh_instances["mesh_index"])
+    nodes = base.bvh_nodes.copy()
+    idx, depth = _top_level_nodes(base)
+    boxes = instance_boxes(moved)
+    leaf = idx[nodes["ldata"][idx] <= 0]
+    inst = -nodes["ldata"][leaf].astype(np.int64)
+    nodes["min"][leaf] = boxes[inst, :3]
+    nodes["max"][leaf] = boxes[inst, 3:]
+    for d in range(int(depth.max()), -1, -1):   # deepest level first: a level's children are all done
+        lvl = idx[depth == d]
+        inner = lvl[nodes["ldata"][lvl] > 0]
+        l, r = nodes["ldata"][inner], nodes["rdata"][inner]
+        nodes["min"][inner] = np.where(nodes["min"][r] < nodes["min"][l], nodes["min"][r], nodes["min"][l])
+        nodes["max"][inner] = np.where(nodes["max"][r] > nodes["max"][l], nodes["max"][r], nodes["max"][l])
+    inst_tab = base.mesh_instances.copy()
+    inst_tab["inv_transform"] = moved.mesh_instances["inv_transform"]
+    return Scene(bvh_nodes=nodes, mesh_instances=inst_tab, material_nodes=base.material_nodes, emissives=moved.emissives.copy(),
+                 texture_data=base.texture_data, texture_meta=base.texture_meta, vertices=base.vertices, normals=base.normals,
+                 uvs=base.uvs, material_index=base.material_index, scene_diffuse_mat_index=base.scene_diffuse_mat_index,
+                 scene_emissive_mat_index=base.scene_emissive_mat_index, eye=base.eye.copy(), frustum=base.frustum.copy(),
+                 name=f"{base.name}-refit-{moved.name}", bvh_max_depth=base.bvh_max_depth)
 
 
 def textured_materials_scene(aspect=1.0) -> Scene:

@@ -314,6 +314,32 @@ class HipTracer:
         self._check(self._lib.polaris_hip_read_instance_plane(self._h, out.ctypes.data, out.size), self._h)
         return out
 
+    def update_instances(self, inv, boxes, emissives=None) -> None:
+        """Move the uploaded scene's mesh instances in place (polaris_hip_update_instances): inv (NI, 16) column-major
+        inverse matrices, boxes (NI, 6) world-space min.xyz, max.xyz, emissives the scene's emissive array with new transform / area
+        (None: unchanged) -- scenes.instance_update_args(scene) makes the triple.  The scene must have been uploaded with the option
+        "instance_update" on.  Queued state changes are committed first, as by Trace."""
+        self._commit()
+        u, keep = T.instance_update(inv, boxes, emissives)
+        self._check(self._lib.polaris_hip_update_instances(self._h, C.byref(u)), self._h)
+        del keep
+
+    def read_scene_records(self) -> tuple[np.ndarray, np.ndarray]:
+        """(pair records, instance records) of the uploaded scene as the device holds them (polaris_hip_read_scene_records; test tap):
+        arrays of ctypes_api.PAIR_RECORD and INST_RECORD."""
+        self._commit()
+        counts = self.scene_counts()
+        pairs, insts = np.zeros(int(counts[0]), T.PAIR_RECORD), np.zeros(int(counts[1]), T.INST_RECORD)
+        self._check(self._lib.polaris_hip_read_scene_records(self._h, T.REC_PAIRS, pairs.ctypes.data, max(pairs.nbytes, 1)), self._h)
+        self._check(self._lib.polaris_hip_read_scene_records(self._h, T.REC_INSTS, insts.ctypes.data, max(insts.nbytes, 1)), self._h)
+        return pairs, insts
+
+    def scene_counts(self) -> tuple[int, int, int, int]:
+        """(pair records, instance records, device allocations the scene owns, bytes in them): POLARIS_REC_COUNTS."""
+        counts = np.zeros(4, np.uint64)
+        self._check(self._lib.polaris_hip_read_scene_records(self._h, T.REC_COUNTS, counts.ctypes.data, counts.nbytes), self._h)
+        return tuple(int(v) for v in counts)
+
     def kernel_ms(self, name: str) -> tuple[float, int]:
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._lib.polaris_hip_kernel_ms(self._h, name.encode(), C.byref(ms), C.byref(n)), self._h)
