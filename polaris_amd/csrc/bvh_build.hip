@@ -44,6 +44,7 @@
 
 #include <rocprim/rocprim.hpp> // (after <cstring>: its texture iterator calls memset unqualified)
 
+#include "device_mem.h"
 #include "polaris_hip.h"
 
 namespace {
@@ -791,9 +792,8 @@ int polaris_hip_build_bvh(int device, const PolarisBvhBuildInput *in, PolarisBvh
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_build_error = "build_bvh: no such HIP device"; return POLARIS_E_NO_DEVICE; }
 	BUILD_TRY(hipSetDevice(device));
-	hipStream_t q = nullptr;
-	BUILD_TRY(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-	struct StreamGuard { hipStream_t q; ~StreamGuard() { (void)hipStreamDestroy(q); } } guard{q};
+	pol::DevStream q;
+	BUILD_TRY(q.create(hipStreamCreateWithFlags, hipStreamNonBlocking));
 	const bool sah = in->algorithm != POLARIS_BVH_LBVH;
 	Scratch S;
 	SahScratch H;
@@ -837,10 +837,9 @@ int polaris_hip_build_bvh(int device, const PolarisBvhBuildInput *in, PolarisBvh
 	}
 	BUILD_TRY(hipMemcpyAsync(d_verts, in->vertices, (size_t)in->num_triangles * 3 * sizeof(float4), hipMemcpyHostToDevice, q));
 	BUILD_TRY(hipStreamSynchronize(q)); // (the upload is not part of the build time: a scene's vertices are on the device anyway)
-	hipEvent_t e0, e1;
-	BUILD_TRY(hipEventCreate(&e0));
-	BUILD_TRY(hipEventCreate(&e1));
-	struct EventGuard { hipEvent_t a, b; ~EventGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eguard{e0, e1};
+	pol::DevEvent e0, e1;
+	BUILD_TRY(e0.create(hipEventCreate));
+	BUILD_TRY(e1.create(hipEventCreate));
 	BUILD_TRY(hipEventRecord(e0, q));
 	// top-level tree first (node 0 is the scene's root): one instance per leaf (compiler.go:88-103)
 	static_assert(sizeof(Box) == 24, "instance boxes arrive as 6 floats");

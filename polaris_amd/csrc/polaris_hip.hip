@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -46,11 +47,14 @@ using DevPool = std::vector<DevArray<char>>; // buffers that live and die togeth
 
 } // namespace
 
+// Every stream, event and device allocation of the handle is a member that owns it (device_mem.h), so `delete h` releases
+// them all and a new one needs no line in polaris_hip_destroy, which only makes every stream idle first.  The members'
+// destruction order (the reverse of their declaration) means nothing: with every stream idle no handle depends on another.
 struct polaris_hip_tracer {
 	int device = 0;
 	char pci_bus_id[32] = {}; // which GPU `device` is (device indices are per process); "" if the runtime does not say
 	uint64_t merge_counts[POLARIS_MERGE_BRANCHES] = {}; // which branch every merge onto this tracer took (under merge_mu; polaris_hip_merge_counts)
-	hipStream_t stream = nullptr;
+	hipStream_t stream = nullptr; // the main stream: an alias of pipe[0].q, which owns it
 	std::mutex mu;
 	std::string error;
 	// The frame accumulator belongs to the MERGE stream: the Reset stage, MergeOutput and merge_device run there, under
@@ -58,9 +62,9 @@ struct polaris_hip_tracer {
 	// primary overlaps the primary's own Trace (Exec1DNoWait, tracer/opencl/resources.go:119; renderer/default.go:188-191
 	// calls it from the secondaries' goroutines).  SyncFramebuffer makes the main stream wait for the merges queued so far.
 	// Lock order: mu, then merge_mu.  W / H / frame_acc are written under both and may be read under either.
-	hipStream_t merge_stream = nullptr;
+	DevStream merge_stream;
 	std::mutex merge_mu;
-	hipEvent_t ev_merged = nullptr;
+	DevEvent ev_merged;
 	// Reset epoch: how many times a Trace with accumulated_samples == 0 (or reset_frame) has got as far as queueing the clear
 	// of the frame accumulator -- or has failed before it could.  A host that merges from other threads waits for the
 	// primary's epoch to advance before it queues this frame's merges (polaris_hip_wait_reset), instead of for the
@@ -83,10 +87,10 @@ struct polaris_hip_tracer {
 	// is re-recorded only when a Trace comes round to the slot again -- which the caller's protocol forbids while a peer may still
 	// read it -- so a peer's wait on slot s's event names exactly the Trace whose rows it is about to read (round 4 had ONE event
 	// re-recorded by every Trace: a primary merging frame f while the peer was already in Trace f + 1 waited for whichever it got).
-	hipEvent_t ev_ipc_done[POLARIS_IPC_MAX_DEPTH] = {};
+	DevEvent ev_ipc_done[POLARIS_IPC_MAX_DEPTH];
 	// Events recorded by OTHER handles' merge streams behind their reads of this handle's trace accumulator
 	// (polaris_hip_merge with dst != src): this handle's next Trace waits for them before it clears the rows.
-	struct Reader { hipEvent_t ev; int device; };
+	struct Reader { DevEvent ev; int device; };
 	std::mutex readers_mu;
 	std::vector<Reader> readers, reader_pool;
 
@@ -186,7 +190,7 @@ struct polaris_hip_tracer {
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
 	// bounces of batch i+1 on another stream
 	struct Pipe {
-		hipStream_t q = nullptr;
+		DevStream q; // (pipe[0].q is the main stream)
 		size_t slots = 0; // capacity in slots
 		Streams st{};
 		// batched mode: one NEE record array (occ_e) and one shadow-ray count array (cnt_occ) PER BOUNCE, kept until k_fold_nee has
@@ -196,7 +200,7 @@ struct polaris_hip_tracer {
 		uint32_t *cnt_occ_b[POLARIS_MAX_BOUNCES] = {};
 		uint32_t nee_bounces = 0; // how many of them are allocated
 		DevPool bufs;
-		hipEvent_t done = nullptr; // recorded after the pipe's last resolve
+		DevEvent done; // recorded after the pipe's last resolve
 		void release() { // forget everything the pipe owned (its stream must be idle)
 			bufs.clear();
 			st = Streams{};
@@ -238,24 +242,25 @@ struct polaris_hip_tracer {
 	int opt_traversal = 1; // 1 = persistent waves with lane refill (k_trace), 0 = one ray per lane (k_intersect/k_occlusion)
 
 	// per-kernel timing (option time_kernels)
-	struct Pending { const char *name; hipEvent_t a, b; };
+	struct Pending { const char *name; DevEvent a, b; };
 	std::vector<Pending> pending;
 	std::vector<Pending> merge_pending; // launches on the merge stream (under merge_mu)
-	std::vector<hipEvent_t> event_pool;
+	std::vector<DevEvent> event_pool;
 	std::map<std::string, KernelTimer> timers;
 	std::map<std::string, const char *> timer_symbol; // timer name -> the kernel symbol it last bracketed (polaris_hip_kernel_symbol)
 	int last_shade_timer[POLARIS_MAX_BOUNCES] = {};            // per bounce of the last Trace: 0 shade_first, 1 shade_sort, 2 shade_plain, 3 shade_wave
 	uint64_t last_shade_counts[3 * POLARIS_MAX_BOUNCES] = {}; // per bounce of the last Trace: shaded hits, shaded misses, emitter hits
-	hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_fork = nullptr;
+	DevEvent ev_start, ev_stop, ev_fork;
 };
 
 // Another process's trace accumulator ring, opened through HIP IPC on `owner`'s device.
 struct polaris_hip_peer {
 	polaris_hip_tracer *owner = nullptr;
 	uint32_t depth = 0, W = 0, H = 0;
-	void *mem[POLARIS_IPC_MAX_DEPTH] = {};
-	hipEvent_t ev[POLARIS_IPC_MAX_DEPTH] = {}; // per slot: the peer's "the Trace that wrote this slot is done" event (null: the exporter had none)
+	IpcMapping mem[POLARIS_IPC_MAX_DEPTH];
+	DevEvent ev[POLARIS_IPC_MAX_DEPTH];        // per slot: the peer's "the Trace that wrote this slot is done" event (null: the exporter had none)
 	PolarisPeerInfo info{};                    // what the mapping is (polaris_hip_peer_info); info.same_device picks the merge branch counted
+	void drop_events() { for (auto &e : ev) e.reset(); } // under owner->merge_mu once the peer is published
 };
 
 
@@ -301,14 +306,14 @@ struct Timed {
 	const char *name;
 	hipStream_t q;
 	bool on_merge; // a launch on the merge stream: the caller holds merge_mu (not mu), so the event pool is not touched
-	hipEvent_t a = nullptr, b = nullptr;
+	DevEvent a, b;
 	Timed(polaris_hip_tracer *h_, const char *n, const char *symbol, hipStream_t q_, bool merge = false) : h(h_), name(n), q(q_), on_merge(merge) {
 		if (!h->opt_time_kernels || !name) return;
 		if (symbol) h->timer_symbol[name] = symbol; // (null: a bracket around no kernel, or one on the merge stream -- the map belongs to mu)
 		auto get = [&]() {
-			hipEvent_t e;
-			if (!on_merge && !h->event_pool.empty()) { e = h->event_pool.back(); h->event_pool.pop_back(); }
-			else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+			DevEvent e;
+			if (!on_merge && !h->event_pool.empty()) { e = std::move(h->event_pool.back()); h->event_pool.pop_back(); }
+			else (void)e.create(hipEventCreate);
 			return e;
 		};
 		a = get(); b = get();
@@ -317,7 +322,7 @@ struct Timed {
 	~Timed() {
 		if (!a || !b) return;
 		(void)hipEventRecord(b, q);
-		(on_merge ? h->merge_pending : h->pending).push_back({name, a, b});
+		(on_merge ? h->merge_pending : h->pending).push_back({name, std::move(a), std::move(b)});
 	}
 };
 
@@ -335,14 +340,14 @@ void collect_timers(polaris_hip_tracer *h) { // caller holds mu; the main stream
 		for (auto &p : list) {
 			float ms = 0.0f;
 			const hipError_t e = hipEventElapsedTime(&ms, p.a, p.b);
-			if (e == hipErrorNotReady && may_be_running) { (void)hipGetLastError(); keep.push_back(p); continue; }
+			if (e == hipErrorNotReady && may_be_running) { (void)hipGetLastError(); keep.push_back(std::move(p)); continue; }
 			if (e == hipSuccess) {
 				auto &t = h->timers[p.name];
 				t.ms += ms;
 				t.launches++;
 			}
-			h->event_pool.push_back(p.a);
-			h->event_pool.push_back(p.b);
+			h->event_pool.push_back(std::move(p.a));
+			h->event_pool.push_back(std::move(p.b));
 		}
 		list.swap(keep);
 	};
@@ -367,23 +372,23 @@ hipError_t wait_readers(polaris_hip_tracer *h, hipStream_t q) {
 	for (auto &r : h->readers) {
 		const hipError_t e = hipStreamWaitEvent(q, r.ev, 0);
 		if (first == hipSuccess) first = e;
-		h->reader_pool.push_back(r);
+		h->reader_pool.push_back(std::move(r));
 	}
 	h->readers.clear();
 	return first;
 }
 
 // An event on `device` (the current device) for a read of src's trace accumulator; recorded by the caller, then handed to src.
-hipEvent_t reader_event(polaris_hip_tracer *src, int device) {
+DevEvent reader_event(polaris_hip_tracer *src, int device) {
 	std::lock_guard<std::mutex> lk(src->readers_mu);
 	for (size_t i = 0; i < src->reader_pool.size(); i++)
 		if (src->reader_pool[i].device == device) {
-			hipEvent_t e = src->reader_pool[i].ev;
+			DevEvent e = std::move(src->reader_pool[i].ev);
 			src->reader_pool.erase(src->reader_pool.begin() + (long)i);
 			return e;
 		}
-	hipEvent_t e = nullptr;
-	if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+	DevEvent e;
+	if (e.create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError();
 	return e;
 }
 
@@ -813,24 +818,23 @@ int polaris_hip_create(int device_index, polaris_hip_tracer **out) {
 	h->device = device_index;
 	if (hipDeviceGetPCIBusId(h->pci_bus_id, (int)sizeof h->pci_bus_id, device_index) != hipSuccess) { (void)hipGetLastError(); h->pci_bus_id[0] = 0; }
 	hipError_t e = hipSetDevice(device_index);
-	if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-	h->pipe[0].q = h->stream;
-	for (int p = 1; p < polaris_hip_tracer::kMaxPipes && e == hipSuccess; p++) e = hipStreamCreateWithFlags(&h->pipe[p].q, hipStreamNonBlocking);
-	for (int p = 0; p < polaris_hip_tracer::kMaxPipes && e == hipSuccess; p++) e = hipEventCreateWithFlags(&h->pipe[p].done, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->merge_stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_merged, hipEventDisableTiming);
+	for (int p = 0; p < polaris_hip_tracer::kMaxPipes && e == hipSuccess; p++) e = h->pipe[p].q.create(hipStreamCreateWithFlags, hipStreamNonBlocking);
+	h->stream = h->pipe[0].q;
+	for (int p = 0; p < polaris_hip_tracer::kMaxPipes && e == hipSuccess; p++) e = h->pipe[p].done.create(hipEventCreateWithFlags, hipEventDisableTiming);
+	if (e == hipSuccess) e = h->ev_fork.create(hipEventCreateWithFlags, hipEventDisableTiming);
+	if (e == hipSuccess) e = h->merge_stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking);
+	if (e == hipSuccess) e = h->ev_merged.create(hipEventCreateWithFlags, hipEventDisableTiming);
 	if (e == hipSuccess) e = h->d_stats.alloc(ST_COUNT);
 	if (e == hipSuccess) e = h->d_cam_o.alloc(1);
 	if (e == hipSuccess) {
 		hipDeviceProp_t p;
 		if (hipGetDeviceProperties(&p, device_index) == hipSuccess && p.multiProcessorCount > 0) h->num_cus = p.multiProcessorCount;
 	}
-	if (e == hipSuccess) e = hipEventCreate(&h->ev_start);
-	if (e == hipSuccess) e = hipEventCreate(&h->ev_stop);
+	if (e == hipSuccess) e = h->ev_start.create(hipEventCreate);
+	if (e == hipSuccess) e = h->ev_stop.create(hipEventCreate);
 	if (e != hipSuccess) {
 		fail(nullptr, POLARIS_E_DEVICE, "creating tracer on device %d: %s", device_index, hipGetErrorString(e));
-		delete h;
+		delete h; // (releases whatever was created before the failure)
 		return POLARIS_E_DEVICE;
 	}
 	*out = h;
@@ -847,42 +851,12 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 			if (h->pipe[p].q) (void)hipStreamSynchronize(h->pipe[p].q);
 		if (h->merge_stream) (void)hipStreamSynchronize(h->merge_stream);
 		collect_timers(h);
-		std::lock_guard<std::mutex> lk_merge(h->merge_mu);
-		if (h->merge_stream) (void)hipStreamDestroy(h->merge_stream);
-		if (h->ev_merged) (void)hipEventDestroy(h->ev_merged);
-		for (auto e : h->event_pool) (void)hipEventDestroy(e);
-		for (auto &P : h->pipe) {
-			P.release();
-			if (P.done) (void)hipEventDestroy(P.done);
-		}
-		if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-		for (int p = 1; p < polaris_hip_tracer::kMaxPipes; p++)
-			if (h->pipe[p].q) (void)hipStreamDestroy(h->pipe[p].q);
-		h->scene_bufs.clear();
-		free_ring(h);
-		free_denoise(h);
-		free_temporal(h);
-		free_variance(h);
-		for (auto &e : h->ev_ipc_done)
-			if (e) { (void)hipEventDestroy(e); e = nullptr; }
-		{
-			std::lock_guard<std::mutex> lk_r(h->readers_mu);
-			for (auto &r : h->readers) (void)hipEventDestroy(r.ev);
-			for (auto &r : h->reader_pool) (void)hipEventDestroy(r.ev);
-			h->readers.clear();
-			h->reader_pool.clear();
-		}
-		// (here, under the locks and before the main stream goes -- not in `delete h` below)
-		h->frame_acc.reset();
-		h->framebuffer.reset();
-		h->d_seeds.reset();
-		h->d_stats.reset();
-		h->d_cam_o.reset();
-		h->staging.reset();
-		if (h->ev_start) (void)hipEventDestroy(h->ev_start);
-		if (h->ev_stop) (void)hipEventDestroy(h->ev_stop);
-		if (h->stream) (void)hipStreamDestroy(h->stream);
+		std::lock_guard<std::mutex> lk_merge(h->merge_mu); // (a merge queued by another thread has left its critical section)
 	}
+	// The members release themselves, outside the locks (they are members too) and in no particular order.  Releasing "under the
+	// locks and before the main stream goes", as this function once did by hand, was no constraint: a caller that destroys a handle
+	// has no other call on it in flight, so the locks above only wait for one that is returning; and with every stream idle neither
+	// hipFree nor the destruction of an event or stream depends on the main stream, or on each other.
 	delete h;
 }
 
@@ -1455,7 +1429,7 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 	if (peer) {
 		if (peer->owner != dst) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge_ipc: the peer was opened by another tracer");
 		if (slot < 0 || (uint32_t)slot >= peer->depth) bad_slot = true;
-		else src_acc = (const float4 *)peer->mem[slot];
+		else src_acc = (const float4 *)peer->mem[slot].get();
 		src_w = peer->W; src_h = peer->H;
 	}
 	if (bad_slot) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge: ring slot out of range");
@@ -1474,8 +1448,7 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 		// its rows are complete.  A runtime that refuses to wait for another process's / another device's event must not cost the frame:
 		// drop the peer's events (the wait is not retried) and go on with the host-side ordering alone.
 		(void)hipGetLastError();
-		for (auto &e : peer->ev)
-			if (e) { (void)hipEventDestroy(e); e = nullptr; }
+		peer->drop_events();
 		(void)hipGetLastError();
 		if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] merge_ipc: hipStreamWaitEvent on the peer's inter-process event failed; continuing with the host-side ordering\n");
 	}
@@ -1519,14 +1492,13 @@ static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_
 	// (merge_slot): with a ring of depth 1 that slot IS what the next Trace clears, and with a deeper ring the wait is for a
 	// kernel of microseconds.
 	if (src && src != dst) {
-		hipEvent_t e = reader_event(src, dst->device);
+		DevEvent e = reader_event(src, dst->device);
 		if (!e || hipEventRecord(e, q) != hipSuccess) { // cannot fence on the device: finish the read now
 			(void)hipGetLastError();
-			if (e) (void)hipEventDestroy(e);
 			if (hipStreamSynchronize(q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipStreamSynchronize failed");
 		} else {
 			std::lock_guard<std::mutex> lk_r(src->readers_mu);
-			src->readers.push_back({e, dst->device});
+			src->readers.push_back({std::move(e), dst->device});
 		}
 	}
 	return POLARIS_OK; // asynchronous like Exec1DNoWait (resources.go:119); completed by sync_framebuffer
@@ -1595,13 +1567,11 @@ int polaris_hip_ipc_export(polaris_hip_tracer *h, uint32_t depth, PolarisIpcExpo
 	bool events = true;
 	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) {
 		if (i >= depth) {
-			if (h->ev_ipc_done[i]) { (void)hipEventDestroy(h->ev_ipc_done[i]); h->ev_ipc_done[i] = nullptr; }
+			h->ev_ipc_done[i].reset();
 			continue;
 		}
-		if (!h->ev_ipc_done[i]) {
-			hipEvent_t e = nullptr;
-			if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventInterprocess) == hipSuccess) h->ev_ipc_done[i] = e;
-			else { (void)hipGetLastError(); events = false; break; }
+		if (!h->ev_ipc_done[i] && h->ev_ipc_done[i].create(hipEventCreateWithFlags, hipEventDisableTiming | hipEventInterprocess) != hipSuccess) {
+			(void)hipGetLastError(); events = false; break;
 		}
 		hipIpcEventHandle_t eh;
 		if (hipEventRecord(h->ev_ipc_done[i], h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
@@ -1609,8 +1579,7 @@ int polaris_hip_ipc_export(polaris_hip_tracer *h, uint32_t depth, PolarisIpcExpo
 		else { (void)hipGetLastError(); events = false; break; }
 	}
 	if (!events) {
-		for (auto &e : h->ev_ipc_done)
-			if (e) { (void)hipEventDestroy(e); e = nullptr; }
+		for (auto &e : h->ev_ipc_done) e.reset();
 		memset(out->event, 0, sizeof out->event);
 	}
 	out->has_event = events ? 1 : 0;
@@ -1627,7 +1596,7 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 	if (x->frame_w != dst->W || x->frame_h != dst->H || dst->W == 0) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_open: the peer's frame %ux%u does not match the tracer's %ux%u", x->frame_w, x->frame_h, dst->W, dst->H);
 	if (x->pid == (uint32_t)getpid()) return fail(dst, POLARIS_E_UNSUPPORTED, "ipc_open: the export comes from this process (HIP cannot open its own IPC handle): use polaris_hip_merge / polaris_hip_merge_slot");
 	HIP_TRY(dst, hipSetDevice(dst->device));
-	polaris_hip_peer *p = new polaris_hip_peer();
+	std::unique_ptr<polaris_hip_peer> p(new polaris_hip_peer()); // (a failure below closes what was opened)
 	p->owner = dst; p->depth = x->depth; p->W = x->frame_w; p->H = x->frame_h;
 	{ // what the mapping is: the exporter's GPU by bus id, as this process sees it
 		PolarisPeerInfo &I = p->info;
@@ -1651,27 +1620,18 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 		//   the ring is on another GPU this process cannot even SEE (a per-rank visibility mask): refuse, the caller has its strip fallback;
 		//   the ring is on a visible GPU without peer access: merges go through the staging strip (a runtime copy, then the add).
 		if (I.same_device == 0 && I.local_device < 0) {
-			delete p;
 			return fail(dst, POLARIS_E_UNSUPPORTED, "ipc_open: the peer's ring lives on GPU %s, which is not visible to this process (device visibility mask?): "
 			            "a peer mapping cannot be verified; use a transport that does not need one", I.pci_bus_id);
 		}
 		I.staged = (dst->opt_ipc_staged || (I.same_device == 0 && I.can_access_peer == 0)) ? 1 : 0;
 	}
-	auto undo = [&]() {
-		for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++)
-			if (p->mem[i]) (void)hipIpcCloseMemHandle(p->mem[i]);
-		for (auto &e : p->ev)
-			if (e) (void)hipEventDestroy(e);
-		delete p;
-		(void)hipGetLastError();
-	};
 	for (uint32_t i = 0; i < x->depth; i++) {
 		hipIpcMemHandle_t mh;
 		memcpy(&mh, x->mem[i], 64);
-		const hipError_t e = hipIpcOpenMemHandle(&p->mem[i], mh, hipIpcMemLazyEnablePeerAccess);
+		const hipError_t e = p->mem[i].create(hipIpcOpenMemHandle, mh, hipIpcMemLazyEnablePeerAccess);
 		if (e != hipSuccess) {
-			p->mem[i] = nullptr;
-			undo();
+			p.reset();
+			(void)hipGetLastError();
 			return fail(dst, POLARIS_E_UNSUPPORTED, "ipc_open: hipIpcOpenMemHandle (slot %u, peer pid %u device %d): %s", i, x->pid, x->device, hipGetErrorString(e));
 		}
 	}
@@ -1679,10 +1639,9 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 		for (uint32_t i = 0; i < x->depth; i++) {
 			hipIpcEventHandle_t eh;
 			memcpy(&eh, x->event[i], 64);
-			if (hipIpcOpenEventHandle(&p->ev[i], eh) != hipSuccess) { // all or none
+			if (p->ev[i].create(hipIpcOpenEventHandle, eh) != hipSuccess) { // all or none
 				(void)hipGetLastError();
-				p->ev[i] = nullptr;
-				for (uint32_t j = 0; j < i; j++) { (void)hipEventDestroy(p->ev[j]); p->ev[j] = nullptr; }
+				p->drop_events();
 				break;
 			}
 		}
@@ -1695,14 +1654,13 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 		for (uint32_t i = 0; i < x->depth && visible; i++) visible = hipEventQuery(p->ev[i]) == hipSuccess;
 		if (!visible) {
 			(void)hipGetLastError();
-			for (auto &e : p->ev)
-				if (e) { (void)hipEventDestroy(e); e = nullptr; }
+			p->drop_events();
 			(void)hipGetLastError();
 			if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] ipc_open: the peer's inter-process events do not read complete here; merging on the host-side ordering alone\n");
 		}
 	}
 	p->info.has_events = p->ev[0] ? 1u : 0u;
-	*out = p;
+	*out = p.release();
 	return POLARIS_OK;
 }
 
@@ -1728,12 +1686,8 @@ int polaris_hip_ipc_close(polaris_hip_tracer *dst, polaris_hip_peer *p) {
 	std::lock_guard<std::mutex> lk(dst->merge_mu);
 	(void)hipSetDevice(dst->device);
 	(void)hipStreamSynchronize(dst->merge_stream); // a merge may still be reading the mapping
-	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++)
-		if (p->mem[i]) (void)hipIpcCloseMemHandle(p->mem[i]);
-	for (auto &e : p->ev)
-		if (e) (void)hipEventDestroy(e);
-	(void)hipGetLastError();
 	delete p;
+	(void)hipGetLastError();
 	return POLARIS_OK;
 }
 

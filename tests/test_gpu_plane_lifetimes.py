@@ -5,7 +5,10 @@ sync its RGBA8 frame buffer, every AOV that can be read and the refusal of every
 of a second tracer that was configured directly for that state and saw none of the earlier toggles and resizes.  A plane that
 outlives its feature or frame size, is freed while in use, or is missed by a free_* shows as a difference (or a fault) here.
 
-Frames 24 x 16 and 40 x 12: 384 and 480 pixels, neither a multiple of the 256-thread workgroup."""
+Frames 24 x 16 and 40 x 12: 384 and 480 pixels, neither a multiple of the 256-thread workgroup.
+
+The last two tests do the same for the handle's streams, events and inter-process events (DevStream / DevEvent in device_mem.h):
+every kind is live when the handle is destroyed, and the ring of exported events shrinks and grows.  Every call in them succeeds."""
 import dataclasses
 
 import numpy as np
@@ -158,3 +161,70 @@ def test_destroy_with_every_plane_allocated(built):
             tr.Close()
     check("cycle", snaps[1], snaps[0], set(AOVS), FRAME_A)
     check("cycle", snaps[2], snaps[0], set(AOVS), FRAME_A)
+
+
+# ---- streams and events: every kind live, then released ---------------------------------------------------------------------
+HANDLE_SPP = 4
+
+
+def request(accumulated=0, spp=HANDLE_SPP):
+    from oracle import pybind as ob
+
+    return ob.make_request(*FRAME_A, spp=spp, bounces=BOUNCES, accumulated=accumulated)
+
+
+def seeds(base):
+    from polaris_amd import scenes
+
+    return scenes.make_seeds(HANDLE_SPP, BOUNCES, base=base)
+
+
+def test_destroy_with_every_kind_of_event_and_stream_live(built):
+    """Two tracers with kernel timing on and four one-sample batches on four pipelines (the timer events cycle through the pool);
+    `a` exports a ring of three (its inter-process events), merges `b` (one of a's merge-stream events enters b's reader list, moves
+    to b's pool at b's next Trace and is taken out again by the next merge) and itself.  Three such cycles, closed in either order,
+    give the same bytes."""
+    sc0, _ = scenes_pair()
+    req = request()
+    snaps = []
+    for cycle in range(3):
+        a = make_hip_tracer(sc0, *FRAME_A, time_kernels=1, overlap=4, samples_per_batch=1)
+        b = make_hip_tracer(sc0, *FRAME_A, time_kernels=1, overlap=4, samples_per_batch=1)
+        try:
+            a.ipc_export(3)
+            a.Trace(req, seeds(3))
+            b.Trace(req, seeds(4))
+            a.MergeOutput(b, req)
+            a.MergeOutput(a, req)
+            b.Trace(req, seeds(5))
+            a.MergeOutput(b, req)
+            a.SyncFramebuffer(request(spp=3 * HANDLE_SPP))
+            snaps.append({"framebuffer": a.read_framebuffer().tobytes(), "a.trace": a.read_accumulator(0).tobytes(),
+                          "a.frame": a.read_accumulator(1).tobytes(), "b.trace": b.read_accumulator(0).tobytes()})
+            assert a.kernel_ms("generate")[1] > 0
+        finally:
+            for tr in ((a, b) if cycle % 2 == 0 else (b, a)):
+                tr.Close()
+    assert any(snaps[0]["framebuffer"]) and any(snaps[0]["a.frame"])
+    assert snaps[1] == snaps[0] and snaps[2] == snaps[0]
+
+
+def test_exported_ring_shrinks_and_grows(built):
+    """ipc_export(3), (1), (4) on one tracer with Traces in between: after every Trace its trace accumulator equals that of a plain
+    tracer given the same seeds, and the three exports agree on whether they carry events."""
+    sc0, _ = scenes_pair()
+    req = request()
+    tr, plain = make_hip_tracer(sc0, *FRAME_A), make_hip_tracer(sc0, *FRAME_A)
+    try:
+        has_event = []
+        for depth, bases in ((3, (11, 12, 13)), (1, (14,)), (4, (15,))):
+            has_event.append(int(T.IpcExport.from_buffer_copy(tr.ipc_export(depth)).has_event))
+            for base in bases:
+                tr.Trace(req, seeds(base))
+                plain.Trace(req, seeds(base))
+                got = tr.read_accumulator(0)
+                assert got.any() and got.tobytes() == plain.read_accumulator(0).tobytes(), (depth, base)
+        assert has_event[1] == has_event[0] and has_event[2] == has_event[0]
+    finally:
+        tr.Close()
+        plain.Close()
