@@ -151,6 +151,11 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *                        than this are subdivided where a surface-area split pays (default -1:
  *                        2 up to 32 K triangles, 4 above; 0 = keep the caller's leaves).  Never
  *                        changes a result: DESIGN.md 2 (HBM data layout)
+ *   "shade_prefilter"    1 (default): the shade kernels retire, before they shade a hit, the rays whose whole effect is a count --
+ *                        a ray that left a scene without a background, and a ray that Russian roulette rejects on a hit whose
+ *                        material cannot end in an emitter (the roulette reads only the carried throughput and the ray's third
+ *                        PRNG draw).  0: every ray goes through the full shading code (k_shade_wave still queues them).  Never
+ *                        changes an accumulator or a counter: it exists for the A/B and the equality tests
  *   further A/B switches of the kernels ("traversal", "node_mode", "packet_shadow", "shade_wave",
  *   "shade_wave_from", "shade_sort", "shade_wgs_per_cu", "stage_lds", "trace_wgs_per_cu", "trace_grid", "hit12", "o12", "ipc_staged"): see
  *   DESIGN.md 3.  Apart from "exact_accumulate" (the order of the float sums) no option changes a

@@ -14,6 +14,9 @@
 //                      verbatim, folds its instance's partial extents and writes Inst.r0..r2; an inner node takes the union
 //                      of its children's boxes and contents and writes both children's lo / hi and cull factors into its pair record.
 //
+// The triangle records are not touched, so neither are the shading classes that ride in their `orig` words, and the material
+// table does not change: SceneT::emit_classes (the classes that can end in an emitter, scene_layout.h) stays what the upload set.
+//
 // The per-node arithmetic (refit_leaf, refit_inner) is __host__ __device__: host_refit below is the same code on the CPU, and
 // tests/tools/instance_update_check.cpp shows it byte-equal to build_layout of the refit scene.
 //

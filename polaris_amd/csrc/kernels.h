@@ -129,6 +129,9 @@ __device__ __forceinline__ float4 load_hit(const Streams &st, size_t slot) {
 	if (st.hit12) { const float *h = reinterpret_cast<const float *>(st.hit) + 3 * slot; return make_float4(h[0], h[1], 0.0f, h[2]); }
 	return st.hit[slot];
 }
+__device__ __forceinline__ float load_hit_word(const Streams &st, size_t slot) { // the record's last word alone (triangle | class, < 0 = miss)
+	return st.hit12 ? reinterpret_cast<const float *>(st.hit)[3 * slot + 2] : reinterpret_cast<const float *>(st.hit)[4 * slot + 3];
+}
 
 // device-side counters of one Trace call (mirrors PolarisTraceStats, all uint64)
 // (shaded hits / misses / emitter hits are kept per bounce: the totals of PolarisTraceStats are their sums, and bench.py prices
@@ -972,6 +975,7 @@ struct ShadeArgs {
 	uint32_t bounce, min_rr;
 	int last_bounce;   // no closest-hit query follows (pipeline.go:203): do not emit indirect rays
 	int exact;         // accumulate into acc[pixelIndex] (trace accumulator) instead of lsum[path slot]
+	int prefilter;     // retire the rays that only count before shade_ray (shade_fate; option shade_prefilter)
 	float4 *acc;       // trace accumulator (exact) or lsum (batched)
 	const uint32_t *emask_in; // emit masks of the previous shade step (null at bounce 0: canonical index = slot index)
 	uint32_t *emask_out;      // ... of this one
@@ -1107,6 +1111,32 @@ __device__ __forceinline__ void shade_ray(const SceneT<LDS> &S, const ShadeArgs 
 	}
 }
 
+// What can be said of a ray BEFORE its hit is shaded, from the carried throughput, the hit's last word and the ray's PRNG
+// position alone.  Russian roulette (pt_integrator.cl:113-125) reads only the throughput and the third draw of
+// Rng{seed, gid_ref}, and a ray it rejects has one way left to change the result: radiance, if it struck the front of an
+// emitter (:101-107, tested before the roulette).  Where the hit's shading class cannot end in an emissive leaf
+// (SceneT::emit_classes) the rejected ray's whole effect is one counted hit; a ray that left the scene with no background to
+// shade has none at all.  The shade kernels retire both kinds here -- no vertices, no material walk, no texel -- and keep them
+// out of the class sort and the wave passes.  The roulette is written with exactly the operations of shade_ray, which is
+// unchanged: a live ray draws its samples again there (nothing is carried across the sort), and the reject for an INVALID
+// leaf, which needs the walk, stays there too.  Scenes without classes have every bit set: only their escaped rays retire.
+enum ShadeFate : uint32_t { kFateLive = 0, kFateEscaped = 1, kFateRejected = 2 }; // (rejected: counts one hit)
+// (`gid_ref` is a callable: the ray's position costs a canonical index, wanted only where the roulette is really played)
+template <bool LDS, class GidRef>
+__device__ __forceinline__ uint32_t shade_fate(const SceneT<LDS> &S, const ShadeArgs &A, uint32_t seed, GidRef gid_ref, float4 t4, float hit_w) {
+	const int tri_word = fbits(hit_w);
+	if (tri_word < 0) return S.bg_node < 0 ? kFateEscaped : kFateLive;
+	if (A.bounce < A.min_rr) return kFateLive;
+	if ((S.emit_classes >> min((uint32_t)tri_word >> S.tri_bits, 15u)) & 1u) return kFateLive;
+	Rng rng = {seed, gid_ref()};
+	rng_next(rng);
+	rng_next(rng);
+	const f2 sample2 = rng_next(rng);
+	const f3 thr = xyz(t4);
+	const float p = pm_max(pm_min(0.5f, 0.2126f * thr.x + 0.7152f * thr.y + 0.0722f * thr.z), 0.01f);
+	return p < sample2.x ? kFateRejected : kFateLive;
+}
+
 constexpr uint32_t kLdsMatNodes = 64, kLdsLights = 16, kLdsTextures = 16;
 
 // Material nodes, emissive records and texture metadata are tiny tables that EVERY ray walks
@@ -1132,7 +1162,7 @@ __device__ __forceinline__ SceneT<LDS> stage_scene(const SceneDev &Sg, ShadeLds 
 	SceneT<LDS> S;
 	S.vertices = Sg.vertices; S.normals = Sg.normals; S.uvs = Sg.uvs; S.mat_index = Sg.mat_index; S.tex_data = Sg.tex_data;
 	S.num_emissives = Sg.num_emissives; S.bg_node = Sg.bg_node; S.num_nodes = Sg.num_nodes; S.num_textures = Sg.num_textures;
-	S.tri_bits = Sg.tri_bits; S.sel_pdf = Sg.sel_pdf;
+	S.tri_bits = Sg.tri_bits; S.sel_pdf = Sg.sel_pdf; S.emit_classes = Sg.emit_classes;
 	if constexpr (LDS) { // the host launches this variant only when all three tables fit
 		const uint32_t tid = threadIdx.x;
 		const bool has_n = tid < Sg.num_nodes * 4, has_l = tid < Sg.num_emissives * 5, has_t = tid < Sg.num_textures;
@@ -1188,6 +1218,12 @@ __device__ __forceinline__ uint32_t canonical_index(const uint32_t (&mask)[8], u
 // per-wave ballots, the 64 (class, wave) counts scanned by every wave with shuffles, the rays (already in registers)
 // moved to their lane through LDS -- no memory round trip is added.  Most waves then run ONE short path and retire early.
 //
+// PREFILTER (ShadeArgs::prefilter, shade_fate above): a ray that only counts never reaches shade_ray.  SORT evaluates the
+// predicate per live lane after the staging barrier; a retired lane posts its hit by one ballot per wave and keeps the "no ray"
+// key, so it takes no part in the counting sort or the LDS exchange, and the rays to shade are the total of the (class, wave)
+// scan, not the chunk's count: at the roulette bounce a chunk's ~150 live rays leave ~25, one wave instead of three, and the
+// other waves go straight to the publishing step.  The unsorted variants do not compact: a retired lane skips shade_ray.
+//
 // In-place safety: a chunk's input streams (ray_d, thr, hit) are overwritten by its own outputs.  Every wave's inputs are
 // in registers before the workgroup's last barrier (SORT: the exchange barrier; otherwise the staging barrier, in front
 // of which every wave waits for its loads), and no wave stores before that barrier.
@@ -1240,11 +1276,22 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHAD
 	// in-place safety without SORT: this wave's rays are in registers before the staging barrier (the empty asm consumes them)
 	const SceneT<LDS> S = stage_scene<LDS>(Sg, lds, [&]() { if (!SORT) asm volatile("" ::"v"(d4.w), "v"(t4.w), "v"(h4.w)); });
 	const unsigned long long below = (1ull << lane) - 1ull;
+	uint32_t todo_rays = cnt; // rays of the chunk that go through shade_ray
 	if (SORT) {
 		uint32_t key = 16; // no ray
+		bool counted = false;
 		if (tid < cnt) {
 			const int w = fbits(h4.w);
 			key = w < 0 ? 0u : min((uint32_t)w >> S.tri_bits, 15u);
+			if (A.prefilter) { // a ray that only counts takes no part in the sort: it keeps the "no ray" key
+				const uint32_t fate = shade_fate(S, A, seed, [&]() { return pfx0 + canonical_index(pmask, (uint32_t)fbits(t4.w)); }, t4, h4.w);
+				if (fate != kFateLive) key = 16;
+				counted = fate == kFateRejected;
+			}
+		}
+		if (A.prefilter) {
+			const unsigned long long mc = __ballot(counted);
+			if (lane == 0 && mc) atomicAdd(&s_tot[2], (uint32_t)__popcll(mc));
 		}
 		if (lane < 16) s_cnt[wave][lane] = 0; // (LDS operations of one wave execute in order)
 		uint32_t rank_in = 0;
@@ -1266,17 +1313,24 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHAD
 			if ((int)lane >= d) incl += up;
 		}
 		const uint32_t dest = __shfl(incl - mine, (int)((key & 15u) * 4 + wave)) + rank_in;
+		todo_rays = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63); // (== cnt without the prefilter)
 		if (key < 16) { x_d[dest] = d4; x_t[dest] = t4; x_h[dest] = h4; }
 		__syncthreads();
-		if (tid < cnt) { d4 = x_d[tid]; t4 = x_t[tid]; h4 = x_h[tid]; }
+		if (tid < todo_rays) { d4 = x_d[tid]; t4 = x_t[tid]; h4 = x_h[tid]; }
 	}
-	if (wave * 64 < cnt) { // (uniform per wave)
+	if (wave * 64 < todo_rays) { // (uniform per wave; a wave the prefilter left nothing goes straight to the publishing step)
 		ShadeOut R;
 		R.emit_ind = false;
 		R.hit = R.miss = R.emit = 0;
 		uint32_t canon = 0;
-		if (tid < cnt) {
-			canon = FIRST ? tid : canonical_index(pmask, (uint32_t)fbits(t4.w));
+		bool shade = tid < todo_rays;
+		if (shade) canon = FIRST ? tid : canonical_index(pmask, (uint32_t)fbits(t4.w));
+		if (!SORT && shade && A.prefilter) { // no compaction here: a ray that only counts skips shade_ray and posts its count
+			const uint32_t fate = shade_fate(S, A, seed, [&]() { return pfx0 + canon; }, t4, h4.w);
+			shade = fate == kFateLive;
+			R.hit = fate == kFateRejected ? 1u : 0u;
+		}
+		if (shade) {
 			shade_ray(S, A, s, seed, pfx0 + canon, d4, t4, h4, R, [&](float4 oo, float4 od, float4 oe) {
 				// the lanes that get here emit a shadow ray: one of them reserves their slots, all store at once
 				const unsigned long long m = __ballot(true);
@@ -1330,9 +1384,24 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHAD
 // (round 1 walked one chunk per pass: 11 % of the lanes of a VALU instruction were live).  Every lane knows its ray's
 // chunk (its sample, seed, reference position and emit mask are per lane); outputs go to the ray's own chunk through
 // per-chunk LDS counters (same canonical-order protocol as k_shade; never the first bounce).
-// In-place safety: a chunk's rays are read in slot order, a pass's reads precede its writes (program order of one wave),
-// and a chunk never holds more emitted rays than rays already read from it.
+// Two stages per wave (ShadeArgs::prefilter): after Russian roulette about five rays in six only count (shade_fate), so
+// a pass formed from whatever is live would again run shade_ray with a sixth of its lanes.
+//   1. SCREEN: the group's live rays 64 at a time, in (chunk, slot) order -- only the throughput, the hit's last word and the
+//      chunk's emit mask are loaded.  A ray that only counts posts its hit and is done; a survivor's descriptor (chunk in
+//      group, slot, canonical index) is appended to the wave's LDS queue, by ballot rank, so the queue keeps that order.
+//   2. SHADE: whenever the queue holds 64 descriptors, and once more at the end of the group, the OLDEST 64 are taken and
+//      their rays loaded and put through shade_ray: full passes of survivors, whichever chunks of the group they are from.
+// The queue is a ring of kWaveQueue entries per wave: at most 63 are left after a shade pass and a screen pass adds at
+// most 64.  (With the option off every ray is a survivor and takes the same way.)
+// In-place safety: survivors are shaded in ascending (chunk, slot) order, and the m-th ray shaded from a chunk sits at slot
+// >= m - 1.  Emitted rays fill the chunk from slot 0 and are no more than the rays already shaded from it, so a write of
+// the pass that shades that m-th ray lands on a slot <= m - 1: never beyond the rays of its own pass, whose loads precede
+// its stores (program order of one wave), and so never on a slot that is still queued or still to be screened -- those all
+// lie further on in the same order.  (A retired ray's slot may be overwritten: nothing reads it again.)
 constexpr int kSparseGroup = 8;
+constexpr uint32_t kWaveQueue = 128;
+static_assert(kWaveQueue >= 127 && (kWaveQueue & (kWaveQueue - 1)) == 0, "63 descriptors left by a shade pass + 64 of a screen pass; a ring indexed by masking");
+static_assert(kSparseGroup <= 256 && WG <= 256, "a descriptor is chunk in group << 16 | slot << 8 | canonical index");
 template <bool LDS>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4))) // (fits 128 VGPRs without a spill: 4 waves per SIMD instead of 3)
 void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
@@ -1341,11 +1410,13 @@ void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
 	__shared__ uint32_t wg_cursor;
 	__shared__ uint32_t w_emit[4][G][8]; // per wave and chunk of its group: the emit mask
 	__shared__ uint32_t w_cnt[4][G][3];  // ... indirect rays, shadow rays, event counters (hits | misses << 10 | emitter hits << 20)
+	__shared__ uint32_t w_queue[4][kWaveQueue]; // per wave: the survivors' descriptors, oldest first from q_head
 	if (threadIdx.x == 0) wg_cursor = 0;
 	for (uint32_t i = threadIdx.x; i < 4 * G * 8; i += WG) (&w_emit[0][0][0])[i] = 0;
 	for (uint32_t i = threadIdx.x; i < 4 * G * 3; i += WG) (&w_cnt[0][0][0])[i] = 0;
 	const SceneT<LDS> S = stage_scene<LDS>(Sg, lds); // (ends in the __syncthreads that also publishes the LDS words above)
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const unsigned long long below = (1ull << lane) - 1ull;
 	const uint32_t wgs_per_sample = A.Npad / WG;
 	const uint32_t num_groups = (num_chunks + G - 1) / G;
 	for (;;) {
@@ -1364,30 +1435,28 @@ void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
 		}
 		const uint32_t excl = incl - my_cnt;
 		const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, G - 1);
-		for (uint32_t j = 0; j < total; j += 64) {
-			const uint32_t r = j + lane; // the group's r-th live ray
-			const bool live = r < total;
-			uint32_t k = 0, first = 0; // its chunk within the group, and the rays of the group before that chunk
-#pragma unroll
-			for (int q = 1; q < G; q++) {
-				const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)excl, q);
-				if (r >= e) { k = q; first = e; }
-			}
+		uint32_t q_head = 0, q_tail = 0; // descriptors taken from / appended to the wave's queue so far (uniform)
+		// ---- stage 2: the oldest (up to) 64 survivors through shade_ray ---------------------------------
+		auto shade_pass = [&]() {
+			const uint32_t n = min(q_tail - q_head, 64u);
+			const bool live = lane < n;
+			// (the descriptors were written by other lanes of this wave: LDS operations of one wave execute in order, and the
+			// fences keep the compiler from moving the loads over the stores)
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			const uint32_t desc = live ? w_queue[wave][(q_head + lane) & (kWaveQueue - 1)] : 0u;
+			q_head += n;
+			const uint32_t k = desc >> 16, idx = (desc >> 8) & 255u, canon = desc & 255u;
+			const uint32_t chunk = chunk0 + k;
+			const size_t base = (size_t)chunk * WG;
 			ShadeOut R;
 			R.emit_ind = false;
 			R.hit = R.miss = R.emit = 0;
-			uint32_t canon = 0;
-			const uint32_t chunk = chunk0 + k;
-			const size_t base = (size_t)chunk * WG;
 			if (live) {
-				const uint32_t idx = r - first;
-				const float4 t4 = st.thr[base + idx];
-				const uint4 m0 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2], m1 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2 + 1];
-				const uint32_t pmask[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-				canon = canonical_index(pmask, (uint32_t)fbits(t4.w));
 				const uint32_t s = chunk / wgs_per_sample;
 				const uint32_t seed = A.seeds[(size_t)(A.first_sample + s) * A.seed_stride + 1 + A.bounce];
-				shade_ray(S, A, s, seed, st.pfx[chunk] + canon, st.ray_d[base + idx], t4, load_hit(st, base + idx), R, [&](float4 oo, float4 od, float4 oe) {
+				shade_ray(S, A, s, seed, st.pfx[chunk] + canon, st.ray_d[base + idx], st.thr[base + idx], load_hit(st, base + idx), R, [&](float4 oo, float4 od, float4 oe) {
 					const size_t d = base + atomicAdd(&w_cnt[wave][k][1], 1u); // (shadow rays have no order to keep)
 					st.occ_o[d] = oo; st.occ_d[d] = od; st.occ_e[d] = oe;
 				});
@@ -1399,7 +1468,40 @@ void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
 				store_ray_o(st, d, R.ro); st.ray_d[d] = R.rd; st.thr[d] = R.thr;
 			}
 			if (live && (R.hit | R.miss | R.emit) != 0) atomicAdd(&w_cnt[wave][k][2], R.hit | (R.miss << 10) | (R.emit << 20));
+		};
+		// ---- stage 1: screen the group's live rays, 64 at a time ---------------------------------------
+		for (uint32_t j = 0; j < total; j += 64) {
+			const uint32_t r = j + lane; // the group's r-th live ray
+			uint32_t k = 0, first = 0; // its chunk within the group, and the rays of the group before that chunk
+#pragma unroll
+			for (int q = 1; q < G; q++) {
+				const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)excl, q);
+				if (r >= e) { k = q; first = e; }
+			}
+			bool keep = false;
+			uint32_t desc = 0;
+			if (r < total) {
+				const uint32_t chunk = chunk0 + k, idx = r - first;
+				const size_t base = (size_t)chunk * WG;
+				const float4 t4 = st.thr[base + idx];
+				const uint4 m0 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2], m1 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2 + 1];
+				const uint32_t pmask[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+				const uint32_t canon = canonical_index(pmask, (uint32_t)fbits(t4.w));
+				uint32_t fate = kFateLive;
+				if (A.prefilter) {
+					const uint32_t seed = A.seeds[(size_t)(A.first_sample + chunk / wgs_per_sample) * A.seed_stride + 1 + A.bounce];
+					fate = shade_fate(S, A, seed, [&]() { return st.pfx[chunk] + canon; }, t4, load_hit_word(st, base + idx));
+				}
+				if (fate == kFateRejected) atomicAdd(&w_cnt[wave][k][2], 1u); // one hit
+				keep = fate == kFateLive;
+				desc = k << 16 | idx << 8 | canon;
+			}
+			const unsigned long long mk = __ballot(keep);
+			if (keep) w_queue[wave][(q_tail + (uint32_t)__popcll(mk & below)) & (kWaveQueue - 1)] = desc;
+			q_tail += (uint32_t)__popcll(mk);
+			if (q_tail - q_head >= 64u) shade_pass();
 		}
+		if (q_tail != q_head) shade_pass();
 		// publish the group's chunks (LDS operations of one wave execute in order: the atomics above are done) and clear the wave's words
 		if (lane < (uint32_t)G && chunk0 + lane < num_chunks) {
 			st.cnt_ray[chunk0 + lane] = w_cnt[wave][lane][0];

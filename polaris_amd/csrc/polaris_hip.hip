@@ -236,6 +236,7 @@ struct polaris_hip_tracer {
 	int opt_shade_wgs_per_cu = 4;
 	int opt_shade_wave_from = -1; // first bounce shaded by k_shade_wave; -1 = the bounce AFTER Russian roulette starts thinning the
 	                              // chunks (min_bounces_for_rr + 1: the RR bounce itself still shades dense chunks); earlier bounces use k_shade
+	int opt_shade_prefilter = 1; // the shade kernels retire rays that only count -- escaped, or rejected by Russian roulette off an emitter -- before shade_ray (kernels.h, shade_fate)
 	int opt_shade_sort = -1; // first bounce whose rays k_shade groups by shading class; -1 = default (1), POLARIS_MAX_BOUNCES = never
 	int opt_hit12 = 1;     // 12-byte hit records inside a Trace (A/B aid: 0 = 16)
 	int opt_o12 = 1;       // 12-byte origins of the closest-hit rays inside a Trace (A/B aid: 0 = 16)
@@ -686,6 +687,7 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	A.N = N; A.Npad = Npad; A.W = h->W; A.blockY = r->block_y;
 	A.min_rr = r->min_bounces_for_rr;
 	A.exact = exact ? 1 : 0;
+	A.prefilter = h->opt_shade_prefilter ? 1 : 0;
 	A.acc = exact ? h->trace_acc : P.st.lsum;
 	// persistent grid: chunks are dealt to workgroups statically, so a workgroup that is not resident
 	// from the start begins with its whole share still to do -- the grid must not exceed what the GPU
@@ -1025,7 +1027,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 		}
 	}
 	h->scene = SceneDev{vertices, normals, uvs, mat_index, nodes, emissives, tex_meta, tex_data, sc->num_emissives,
-	                    sc->scene_diffuse_mat_index, sc->num_material_nodes, sc->num_textures, light_geo, sc->num_emissives ? pm_rcp((float)(int)sc->num_emissives) : 0.0f, L.tri_bits};
+	                    sc->scene_diffuse_mat_index, sc->num_material_nodes, sc->num_textures, light_geo, sc->num_emissives ? pm_rcp((float)(int)sc->num_emissives) : 0.0f, L.tri_bits, L.emit_classes};
 	if (L.want_update_plan) {
 		U.on = true;
 		U.pairs = pairs; U.insts = insts; U.d_emissives = emissives; U.d_light_geo = light_geo;
@@ -1198,6 +1200,7 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "shade_wave_from") h->opt_shade_wave_from = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
 	else if (k == "shade_wgs_per_cu") h->opt_shade_wgs_per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(value, 64));
 	else if (k == "stage_lds") h->opt_stage_lds = value != 0;
+	else if (k == "shade_prefilter") h->opt_shade_prefilter = value != 0;
 	else if (k == "shade_sort") h->opt_shade_sort = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
 	else if (k == "ipc_staged") h->opt_ipc_staged = value != 0;
 	else if (k == "overlap") h->opt_overlap = (int)std::max<int64_t>(1, std::min<int64_t>(value, polaris_hip_tracer::kMaxPipes));

@@ -142,6 +142,8 @@ struct SceneLayout {
 	// triangles, else 31 = no class).  The traversal kernels hand the word through to the hit record untouched; k_shade
 	// sorts a workgroup's rays by the class and masks it off.
 	uint32_t tri_bits = 31;
+	// bit c: a hit of shading class c may end in an emissive leaf (emitting_classes below); all ones when hits carry no class
+	uint32_t emit_classes = 0xFFFFu;
 	bool want_update_plan = false;  // set by the caller: build_layout also fills `plan` (option instance_update)
 	UpdatePlan plan;
 };
@@ -196,6 +198,40 @@ inline void shading_classes(const PolarisSceneView &sc, std::vector<uint8_t> &cl
 		const size_t k = (size_t)(std::lower_bound(distinct.begin(), distinct.end(), reach[i]) - distinct.begin());
 		cls[i] = (uint8_t)std::min<size_t>(1 + k, 15);
 	}
+}
+
+// Which shading classes can end in an emitter: bit c of the result is set when the material walk from ANY node of class c can
+// arrive at an emissive leaf.  The shade kernels retire a ray that Russian roulette rejects before they touch its hit record,
+// which is only right when the hit cannot add radiance (kernels.h, shade_fate): a clear bit is that promise, so every doubt sets
+// it.  Reachability is taken over the child edges the device walk follows (select_material: left, and right for the two mixes), to
+// a fixed point and from the leaves up -- the reach sets above stop at a node that is still on their walk, so for a tree with a
+// cycle they may lack a leaf the 64-step device walk does get to; here a cycle is walked like any other edge.  An invalid leaf or a
+// child out of range ends the path without a contribution and sets nothing.  Class 15 is the OR of every set that shares it.
+inline uint32_t emitting_classes(const PolarisSceneView &sc, const std::vector<uint8_t> &cls) {
+	const uint32_t n = sc.num_material_nodes;
+	std::vector<std::vector<uint32_t>> parents(n);
+	std::vector<uint8_t> emits(n, 0);
+	std::vector<uint32_t> todo;
+	for (uint32_t i = 0; i < n; i++) {
+		const PolarisMaterialNode &m = sc.material_nodes[i];
+		if (m.type < POLARIS_MAT_OP_MIX) {
+			if (m.type == POLARIS_BXDF_EMISSIVE) { emits[i] = 1; todo.push_back(i); }
+			continue;
+		}
+		if (m.type > POLARIS_MAT_OP_DISPERSE) continue; // unknown operator: the walk ends there
+		if (m.left_child < n) parents[m.left_child].push_back(i);
+		if ((m.type == POLARIS_MAT_OP_MIX || m.type == POLARIS_MAT_OP_MIX_MAP) && (uint32_t)m.right_child < n) parents[(uint32_t)m.right_child].push_back(i);
+	}
+	while (!todo.empty()) {
+		const uint32_t i = todo.back();
+		todo.pop_back();
+		for (uint32_t p : parents[i])
+			if (!emits[p]) { emits[p] = 1; todo.push_back(p); }
+	}
+	uint32_t mask = 0;
+	for (uint32_t i = 0; i < n; i++)
+		if (emits[i]) mask |= 1u << (cls[i] & 15u);
+	return mask;
 }
 
 
@@ -813,6 +849,7 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 	std::vector<uint8_t> node_class;
 	shading_classes(sc, node_class);
 	out.tri_bits = NT <= (1u << 24) ? 24 : 31;
+	out.emit_classes = out.tri_bits < 31 ? emitting_classes(sc, node_class) : 0xFFFFu;
 	out.tris.assign(n_slots, TriH{});
 	for (uint32_t s = 0; s < n_slots; s++) {
 		const uint32_t t = slot_src[s];

@@ -88,6 +88,8 @@ template <bool LDS> struct SceneT {
 	float sel_pdf; // 1 / number of emissives (emissiveSelect, emissive_sampler.cl:226-237)
 	// a hit record's last word = scene triangle index | shading class << tri_bits (scene_layout.h; 31 = scenes too big to carry a class)
 	uint32_t tri_bits;
+	// bit c: a hit of shading class c may end in an emissive leaf (scene_layout.h, emitting_classes); all ones without classes
+	uint32_t emit_classes;
 };
 constexpr uint32_t kLightGeoFloats = 48;
 typedef SceneT<false> SceneDev; // what the host fills in
