@@ -156,6 +156,10 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *                        material cannot end in an emitter (the roulette reads only the carried throughput and the ray's third
  *                        PRNG draw).  0: every ray goes through the full shading code (k_shade_wave still queues them).  Never
  *                        changes an accumulator or a counter: it exists for the A/B and the equality tests
+ *   "shade_wave_from"    first bounce shaded by k_shade_wave (persistent waves over groups of 8 chunks); never bounce 0.  -1 (default):
+ *                        min_bounces_for_rr + 1 -- or min_bounces_for_rr, the bounce where Russian roulette starts, when
+ *                        "shade_prefilter" is on, some shading class of the scene cannot emit and a full batch of the Trace holds at
+ *                        least 8 such groups per compute unit.  Never changes an accumulator or a counter
  *   further A/B switches of the kernels ("traversal", "node_mode", "packet_shadow", "shade_wave",
  *   "shade_wave_from", "shade_sort", "shade_wgs_per_cu", "stage_lds", "trace_wgs_per_cu", "trace_grid", "hit12", "o12", "ipc_staged"): see
  *   DESIGN.md 3.  Apart from "exact_accumulate" (the order of the float sums) no option changes a

@@ -234,8 +234,9 @@ struct polaris_hip_tracer {
 	int opt_stage_lds = 1;    // k_shade stages material nodes / lights / texture metadata in LDS when they fit
 	int opt_shade_wave = 1;   // 1 = persistent wave-per-chunk shading (k_shade_wave), 0 = one workgroup per chunk (k_shade)
 	int opt_shade_wgs_per_cu = 4;
-	int opt_shade_wave_from = -1; // first bounce shaded by k_shade_wave; -1 = the bounce AFTER Russian roulette starts thinning the
-	                              // chunks (min_bounces_for_rr + 1: the RR bounce itself still shades dense chunks); earlier bounces use k_shade
+	int opt_shade_wave_from = -1; // first bounce shaded by k_shade_wave; -1 = automatic (plan_bounces): the bounce AFTER Russian roulette
+	                              // starts thinning the chunks (min_bounces_for_rr + 1), or the roulette bounce itself where the prefilter
+	                              // thins its chunks and the launch is large; earlier bounces use k_shade
 	int opt_shade_prefilter = 1; // the shade kernels retire rays that only count -- escaped, or rejected by Russian roulette off an emitter -- before shade_ray (kernels.h, shade_fate)
 	int opt_shade_sort = -1; // first bounce whose rays k_shade groups by shading class; -1 = default (1), POLARIS_MAX_BOUNCES = never
 	int opt_hit12 = 1;     // 12-byte hit records inside a Trace (A/B aid: 0 = 16)
@@ -645,19 +646,35 @@ struct BouncePlan {
 	const ShadeWaveVariant *shade_wave = nullptr;
 	int shade_timer = 0; // index into kShadeTimer
 };
+// Automatic shade_wave_from: a full batch must hold this many groups of kSparseGroup chunks per CU for k_shade_wave to take the roulette
+// bounce itself (profiles/shade_sparse_ab.txt).
+constexpr uint32_t kWaveRouletteGroupsPerCu = 8;
 // one timer per kernel symbol: shade_first = k_shade<.., FIRST> (camera rays), shade_sort = k_shade<.., SORT, ..> (bounce rays in
 // class order), shade_plain = k_shade<.., false, false>, shade_wave = k_shade_wave
 const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"};
 
-void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, BouncePlan *plan) {
+// `batch_chunks`: the chunks of one full batch of the Trace (the size of its shade launches).
+void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, uint32_t batch_chunks, BouncePlan *plan) {
 	// LDS-table variant of the shade kernels: only when all three tables fit (kernels.h, stage_scene)
 	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
 	                    h->scene.num_textures <= kLdsTextures;
+	// First bounce of k_shade_wave.  The bounce where Russian roulette starts still finds the chunks as the previous bounce left them;
+	// only with the prefilter (shade_fate retires the rays roulette rejects, where some shading class cannot emit: otherwise nothing is
+	// retired) does a chunk of that bounce hold a sixth of its rays, and k_shade still pays a workgroup's latency chain per chunk.
+	// k_shade_wave screens and shades them a group at a time -- on launches large enough to keep its persistent grid busy: smaller
+	// ones (a row block of a multi-GPU frame, the frames of the tests) keep the plan they had.
+	int wave_from = h->opt_shade_wave_from;
+	if (wave_from < 0) {
+		wave_from = (int)r->min_bounces_for_rr + 1;
+		const uint64_t groups = ((uint64_t)batch_chunks + kSparseGroup - 1) / kSparseGroup;
+		if (h->opt_shade_prefilter && (h->scene.emit_classes & 0xFFFFu) != 0xFFFFu && groups >= (uint64_t)kWaveRouletteGroupsPerCu * (uint64_t)h->num_cus)
+			wave_from = (int)r->min_bounces_for_rr;
+	}
 	for (uint32_t b = 0; b < r->num_bounces; b++) {
 		BouncePlan &pl = plan[b] = BouncePlan{};
 		if (b == 0 && h->packet_primary) pl.isect_packet = &kPacket[kPacketCamera];
 		if ((int)b < h->opt_packet_shadow) pl.occl_packet = &kPacket[kPacketAnyHit];
-		const bool wave = h->opt_shade_wave && b > 0 && (int)b >= (h->opt_shade_wave_from >= 0 ? h->opt_shade_wave_from : (int)r->min_bounces_for_rr + 1); // (never the first bounce: k_shade_wave reads the previous step's emit masks)
+		const bool wave = h->opt_shade_wave && b > 0 && (int)b >= wave_from; // (never the first bounce: k_shade_wave reads the previous step's emit masks)
 		// bounce rays are shaded in the order of their material's shading class (kernels.h, k_shade SORT); camera rays are
 		// coherent as they come (64 neighbouring pixels per wave)
 		const bool sorted = b > 0 && h->scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
@@ -1358,7 +1375,7 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 		~DrainOnError() { if (armed) for (int p = 0; p < n; p++) (void)hipStreamSynchronize(h->pipe[p].q); }
 	} drain{h, n_pipes};
 	BouncePlan plan[POLARIS_MAX_BOUNCES];
-	plan_bounces(h, r, plan);
+	plan_bounces(h, r, K * (Npad / WG), plan);
 	for (uint32_t b = 0; b < B && spp; b++) h->last_shade_timer[b] = plan[b].shade_timer;
 	uint32_t bi = 0;
 	for (uint32_t s0 = 0; s0 < spp; s0 += K, bi++) {

@@ -10,6 +10,7 @@
 #     --patch reorder           + -DPOLARIS_EXP_REORDER        the coherence-reorder experiment (scripts/wave_lines.py; closed: EXPERIMENTS.md)
 #     --patch timing_inexact    + -DPOLARIS_TIMING_FMA_SLAB / -DPOLARIS_TIMING_CONTRACT_MT   TIMING-ONLY inexact arithmetic (profiles/r06_price_of_exactness.txt)
 #     --patch tiny_lds_transposed  [-DPOLARIS_AB_B128]        the tiny mode's pair records transposed in LDS (closed: profiles/r06_tiny_lds_layout_ab.txt)
+#     --patch shade_sparse      (options shade_sparse, shade_sparse_from; [-DPOLARIS_SPARSE_SHADE_GROUP=16] [-DPOLARIS_SPARSE_SORT=0])   k_shade_sparse: the roulette bounces by chunk group (closed: profiles/shade_sparse_ab.txt; kept as shade_sparse.diff)
 #     --patch trace_spill       (option trace_spill=1)         16 stack entries in LDS + a global overflow column: 8 workgroups per CU (closed: profiles/r06_occupancy_curve.txt)
 # (the three combine: apply them in the order reorder, profile_loops, profile_prologue -- scripts/wave_lines.py needs the first two.)
 # Only the tracer's translation unit is rebuilt, from a patched COPY of polaris_amd/csrc in a temporary directory; the device BVH
@@ -25,7 +26,8 @@ SRC=$(mktemp -d /tmp/polaris_variant.XXXXXX)
 trap 'rm -rf "$SRC"' EXIT
 cp "$ROOT"/polaris_amd/csrc/*.h "$ROOT"/polaris_amd/csrc/*.hip "$SRC"/
 for p in "${patches[@]}"; do
-  (cd "$SRC" && patch -s -p1 < "$ROOT/polaris_amd/csrc/experiments/$p.patch") || { echo "build_variant.sh: experiments/$p.patch does not apply" >&2; exit 1; }
+  pf="$ROOT/polaris_amd/csrc/experiments/$p.patch"; [ -f "$pf" ] || pf="$ROOT/polaris_amd/csrc/experiments/$p.diff"
+  (cd "$SRC" && patch -s -p1 < "$pf") || { echo "build_variant.sh: experiments/$(basename "$pf") does not apply" >&2; exit 1; }
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -fno-slp-vectorize -Wall -Wno-unused-function \
