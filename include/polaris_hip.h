@@ -45,7 +45,8 @@ extern "C" {
  * default for a zero-initialised caller changed from the linear BVH to the binned-SAH builder.  5: + device_identity / can_access_peer /
  * peer_info / merge_counts (which GPU a tracer really runs on, and which branch every merge took: what a multi-GPU bench line needs to prove
  * itself); PolarisIpcExport carries the exporting GPU's PCI bus id (544 -> 576 bytes); PolarisBvhBuildInput LEADS with `struct_size`
- * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end. */
+ * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end.  Still 5: + update_instances,
+ * + update_vertices / PolarisVertexUpdate (additions only: older callers keep working). */
 #define POLARIS_HIP_ABI_VERSION 5
 
 /* status codes (0 = ok).  The first three mirror tracer/opencl/errors.go sentinels. */
@@ -146,6 +147,10 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
  *                        needs (the top-level tree as a refit schedule, the triangle list of every mesh, host copies of the
  *                        emissive list and the packed light geometry).  Off, an upload keeps nothing extra: every
  *                        code path, allocation and launch is what it is without the option
+ *   "vertex_update"      0 (default) or 1, applies to the NEXT upload_scene: the upload keeps everything "instance_update" keeps (so
+ *                        polaris_hip_update_instances is accepted too) plus what polaris_hip_update_vertices needs: the slot -> scene
+ *                        triangle map and the mesh trees as a refit schedule.  Off, an upload allocates, copies
+ *                        and launches exactly what it does without the option
  *   "overlap"            batches in flight on separate streams (1-8, default 4)
  *   "max_leaf_tris"      applies to the NEXT upload_scene: triangle leaves with more triangles
  *                        than this are subdivided where a surface-area split pays (default -1:
@@ -540,6 +545,48 @@ typedef struct PolarisInstanceUpdate {
 } PolarisInstanceUpdate;
 int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpdate *u);
 
+/* Deform the uploaded scene's meshes in place (no reference counterpart).  The scene must have been uploaded with the
+ * option "vertex_update" on.  Synchronous, under the handle's mutex, behind every stream, like an upload.  Afterwards the tracer
+ * behaves -- accumulators, counters, probes, taps, G-buffer planes -- bit for bit as a fresh tracer does after polaris_hip_upload_scene
+ * of the uploaded scene's arrays with these substitutions:
+ *   - vertices = the new ones; normals = the new ones (NULL: unchanged);
+ *   - the mesh BVH nodes (every node below a mesh root, the root included) REFIT on the unchanged topology: a triangle leaf takes the
+ *     exact bounds of its triangles' vertices, an inner node the union of its two children.  Minimum and maximum are b < a ? b : a
+ *     and b > a ? b : a with a the running value, folded over the leaf's triangles in its own order, of each v0, v1, v2; for an inner
+ *     node the left child before the right.  Where +0 meets -0 the earlier operand stays;
+ *   - mesh_instances[i].inv_transform = inv_transforms[i] (NULL: unchanged);
+ *   - the top-level nodes refit as polaris_hip_update_instances defines, from instance_boxes;
+ *   - emissives = the new list (NULL: unchanged).  Only `transform` and `area` of an entry may differ from the uploaded one: the
+ *     area of an area light changes when its triangle deforms, and the caller supplies it.
+ * Two things do not follow the deformation, and neither can change a result.  The topology leaf subdivision ADDED below the caller's
+ * leaves was chosen from the uploaded vertices and is kept; its boxes become the exact bounds of the triangles below them with the
+ * padding a full upload would compute now, so they still only cull inside a leaf of the caller's tree (a full upload of the refit
+ * scene may split its leaves differently: with max_leaf_tris != 0 the records are not comparable byte for byte, the results are).
+ * And the slot order of a scene of at most 2 046 slots (it follows the leaf areas at upload) and the kernel selection (node mode,
+ * tiny_one, packet use) stay as uploaded.
+ * To the temporal history the call is a scene it never saw: the history is dropped, with "object_motion" on or off, and the G-buffer
+ * is invalidated.
+ * A failing HIP call (POLARIS_E_DEVICE) after the arguments were accepted leaves the scene as a failed upload_scene does: upload again.
+ * Refusals are decided on the host before anything is touched and leave the tracer's state unchanged: POLARIS_E_NO_SCENE_DATA before
+ * an upload; POLARIS_E_UNSUPPORTED when the scene was uploaded with "vertex_update" off, or when no mesh plan could be kept (two mesh
+ * roots share a subtree: the message names the node); POLARIS_E_BAD_ARGUMENT for a wrong struct_size, wrong counts, null vertices or
+ * instance_boxes, or an emissive list whose count or per-entry type / tri_index / mat_node_index differs from the uploaded one;
+ * POLARIS_E_BAD_SCENE for a vertex coordinate not finite or beyond 2^40, a matrix entry not finite or beyond 2^30 (the upload's own
+ * rules and texts) and for a box that is not finite or has min > max.
+ */
+typedef struct PolarisVertexUpdate {
+	uint32_t struct_size;             /* = sizeof(PolarisVertexUpdate) */
+	uint32_t num_triangles;           /* must equal the uploaded scene's */
+	const float *vertices;            /* [3 NT][4], as PolarisSceneView.vertices */
+	const float *normals;             /* NULL = unchanged; else [3 NT][4] */
+	uint32_t num_mesh_instances;      /* must equal the uploaded scene's */
+	const float *instance_boxes;      /* [NI][6]: the scene reader's world boxes for the deformed meshes */
+	const float *inv_transforms;      /* NULL = unchanged; else [NI][16] column major */
+	const PolarisEmissive *emissives; /* NULL = unchanged; else [num_emissives] */
+	uint32_t num_emissives;
+} PolarisVertexUpdate;
+int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate *u);
+
 /* Test tap (no reference counterpart): the device's pair records (POLARIS_REC_PAIRS: 64 bytes each, scene_layout.h PairNodeH) or
  * instance records (POLARIS_REC_INSTS: 64 bytes each, InstH) of the uploaded scene, copied back; POLARIS_REC_COUNTS: four uint64_t,
  * the number of pair records, of instance records, of device allocations the scene owns and the bytes in them (what the option
@@ -597,7 +644,8 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * "shade_plain" / "shade_wave" (one per shade kernel symbol), "scan", "occlusion", "fold" (the batch's NEE records into the
  * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
  * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance), "instance_extent",
- * "repad" and "refit_top" (polaris_hip_update_instances). */
+ * "repad" and "refit_top" (polaris_hip_update_instances), "tri_records" and "refit_mesh" (polaris_hip_update_vertices, which runs the
+ * former three as well). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

@@ -351,6 +351,59 @@ func (tr *Tracer) UpdateInstances(invTransforms []float32, boxes []float32, emis
 	return tr.check(C.polaris_hip_update_instances(tr.handle, &c))
 }
 
+// SetVertexUpdate turns the option "vertex_update" on or off for the NEXT UpdateState(SceneData): with it on the upload keeps what
+// UpdateVertices needs, and what UpdateInstances needs too (DESIGN.md section 10f).
+func (tr *Tracer) SetVertexUpdate(on bool) error {
+	key := C.CString("vertex_update")
+	defer C.free(unsafe.Pointer(key))
+	var v C.int64_t
+	if on {
+		v = 1
+	}
+	return tr.check(C.polaris_hip_set_option(tr.handle, key, v))
+}
+
+// UpdateVertices deforms the uploaded scene's meshes in place (polaris_hip_update_vertices; DESIGN.md section 10f): vertices holds 4
+// floats per vertex, three vertices per triangle, as the scene's vertex list; boxes 6 floats per instance (world-space min.xyz,
+// max.xyz of the deformed instances); normals as vertices, or nil to keep the uploaded ones; invTransforms 16 floats per instance, or
+// nil to keep the current matrices; emissives the scene's emissive list with new Transform / Area values, or nil to keep the current
+// ones.  Afterwards the tracer behaves as if the scene had been uploaded with these and its mesh and top-level BVHs refit.  The scene
+// must have been uploaded after SetVertexUpdate(true); a refusal leaves the tracer as it was.  The slices are only read during the
+// call (cgo rule: nothing the caller owns is retained).
+func (tr *Tracer) UpdateVertices(vertices []float32, boxes []float32, normals []float32, invTransforms []float32, emissives []scene.EmissivePrimitive) error {
+	tr.Lock()
+	defer tr.Unlock()
+	if len(vertices) == 0 || len(vertices)%12 != 0 || len(boxes) == 0 || len(boxes)%6 != 0 {
+		return fmt.Errorf("hip tracer (%s): UpdateVertices wants 12 vertex floats per triangle and 6 box floats per instance", tr.dev.Name)
+	}
+	if (normals != nil && len(normals) != len(vertices)) || (invTransforms != nil && len(invTransforms) != len(boxes)/6*16) {
+		return fmt.Errorf("hip tracer (%s): UpdateVertices wants as many normals as vertices and 16 matrix floats per instance", tr.dev.Name)
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	var c C.PolarisVertexUpdate
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.num_triangles = C.uint32_t(len(vertices) / 12)
+	c.num_mesh_instances = C.uint32_t(len(boxes) / 6)
+	pin.Pin(&vertices[0])
+	pin.Pin(&boxes[0])
+	c.vertices = (*C.float)(unsafe.Pointer(&vertices[0]))
+	c.instance_boxes = (*C.float)(unsafe.Pointer(&boxes[0]))
+	if len(normals) > 0 {
+		pin.Pin(&normals[0])
+		c.normals = (*C.float)(unsafe.Pointer(&normals[0]))
+	}
+	if len(invTransforms) > 0 {
+		pin.Pin(&invTransforms[0])
+		c.inv_transforms = (*C.float)(unsafe.Pointer(&invTransforms[0]))
+	}
+	if n := len(emissives); n > 0 {
+		pin.Pin(&emissives[0])
+		c.emissives, c.num_emissives = (*C.PolarisEmissive)(unsafe.Pointer(&emissives[0])), C.uint32_t(n)
+	}
+	return tr.check(C.polaris_hip_update_vertices(tr.handle, &c))
+}
+
 // VarianceParams configures variance-guided denoising (PolarisVarianceParams, include/polaris_hip.h; DESIGN.md section 10c).
 // SigmaVariance = 0 turns it off (the default); DefaultVariance holds the settings chosen on the CPU restatement.
 type VarianceParams struct {

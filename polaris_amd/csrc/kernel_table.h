@@ -10,6 +10,7 @@
 
 #include "kernels.h"
 #include "instance_update.h"
+#include "vertex_update.h"
 
 namespace pol {
 
@@ -84,5 +85,8 @@ const auto kDenoiseVariance = POLARIS_VARIANT(k_denoise_variance);
 const auto kInstanceExtent = POLARIS_VARIANT(k_instance_extent);
 const auto kRepad = POLARIS_VARIANT(k_repad);
 const auto kRefitTop = POLARIS_VARIANT(k_refit_top);
+// polaris_hip_update_vertices (vertex_update.h)
+const auto kTriRecords = POLARIS_VARIANT(k_tri_records);
+const auto kRefitMesh = POLARIS_VARIANT(k_refit_mesh);
 
 } // namespace pol

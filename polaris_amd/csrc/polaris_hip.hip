@@ -173,6 +173,19 @@ struct polaris_hip_tracer {
 		uint32_t chunks = 1, chunk_tris = kExtentChunkTris; // k_instance_extent: chunks per instance, triangles per chunk
 	} upd;
 
+	// deforming meshes in place (option "vertex_update", polaris_hip_update_vertices).  With the option on an upload keeps
+	// everything the instance update keeps (`upd`, whose plan carries the mesh plan: scene_layout.h MeshPlan) plus the device copies
+	// below, in scene_bufs like the rest, and a host copy of the current instance matrices.  Off, `vup` stays empty.
+	int opt_vertex_update = 0; // next upload
+	struct VertexUpdateState {
+		bool on = false; // the scene was uploaded with the option on (the mesh plan itself may still have been refused: upd.plan.mesh)
+		std::vector<float> inv; // [NI][16]: the current inverse matrices (upload, update_instances and update_vertices keep it current)
+		uint32_t num_triangles = 0, num_slots = 0;
+		float4 *vertices = nullptr, *normals = nullptr; TriRec *tris = nullptr; // the scene's arrays, writable
+		uint32_t *slot_src = nullptr, *level_first = nullptr; MeshPlanNode *nodes = nullptr;
+		float4 *scratch = nullptr, *mesh_box = nullptr;
+	} vup;
+
 	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
 	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
 	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
@@ -930,6 +943,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	if (!sc) return fail(h, POLARIS_E_BAD_ARGUMENT, "scene view is null");
 	SceneLayout L;
 	L.want_update_plan = h->opt_instance_update != 0;
+	L.want_mesh_plan = h->opt_vertex_update != 0;
 	// Defaults by scene size (measured): small scenes live in L2/LDS and are bound by
 	// instruction issue -> small leaves and packet traversal of camera rays pay; scenes far larger than
 	// the caches are bound by node fetches -> fewer, fuller leaves and one ray per lane.
@@ -938,6 +952,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	if (err == "@retry-without-subdivision") { // the deeper tree would not fit the traversal stack
 		L = SceneLayout();
 		L.want_update_plan = h->opt_instance_update != 0;
+		L.want_mesh_plan = h->opt_vertex_update != 0;
 		err = build_layout(*sc, L, 0);
 	}
 	if (!err.empty()) return fail(h, POLARIS_E_BAD_SCENE, "%s", err.c_str());
@@ -945,6 +960,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	HIP_TRY(h, sync_all(h));
 	h->scene_bufs.clear();
 	h->upd = polaris_hip_tracer::InstanceUpdateState();
+	h->vup = polaris_hip_tracer::VertexUpdateState();
 	h->have_scene = false;
 	h->gb_valid = false;
 	{
@@ -1028,6 +1044,15 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 		rc |= dev_alloc(h, h->scene_bufs, &U.recs, (size_t)NI);
 		rc |= dev_alloc(h, h->scene_bufs, &U.partial, (size_t)NI * U.chunks * 6);
 	}
+	polaris_hip_tracer::VertexUpdateState V;
+	if (L.want_mesh_plan && L.plan.mesh.on) { // the mesh plan's device copies and the scratch of its kernel (vertex_update.h)
+		const MeshPlan &M = L.plan.mesh;
+		rc |= dev_upload(h, h->scene_bufs, &V.slot_src, M.slot_src.data(), M.slot_src.size());
+		rc |= dev_upload(h, h->scene_bufs, &V.nodes, M.nodes.data(), M.nodes.size());
+		rc |= dev_upload(h, h->scene_bufs, &V.level_first, M.level_first.data(), M.level_first.size());
+		rc |= dev_alloc(h, h->scene_bufs, &V.scratch, 2 * M.nodes.size());
+		rc |= dev_alloc(h, h->scene_bufs, &V.mesh_box, 2 * M.root.size());
+	}
 	if (!rc && sc->texture_data_bytes) HIP_TRY(h, hipMemcpyAsync(tex_data, sc->texture_data, sc->texture_data_bytes, hipMemcpyHostToDevice, h->stream));
 	if (rc) { h->scene_bufs.clear(); return rc; }
 	HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors in L die at return
@@ -1052,6 +1077,15 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 		U.emissives.assign(sc->emissives, sc->emissives + sc->num_emissives);
 		U.light_geo = std::move(geo);
 		h->upd = std::move(U);
+	}
+	if (L.want_mesh_plan) {
+		V.on = true;
+		V.vertices = vertices; V.normals = normals; V.tris = tris;
+		V.num_triangles = sc->num_triangles;
+		V.num_slots = (uint32_t)L.tris.size();
+		V.inv.resize((size_t)sc->num_mesh_instances * 16);
+		for (uint32_t i = 0; i < sc->num_mesh_instances; i++) memcpy(V.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
+		h->vup = std::move(V);
 	}
 	h->max_stack = L.max_stack;
 	h->num_insts = (uint32_t)L.insts.size();
@@ -1082,6 +1116,25 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	h->trace[1].resident_per_cu = trace_occupancy(h, true);
 	h->have_scene = true;
 	return POLARIS_OK;
+}
+
+// The three launches of an instance update on stream q: the world extent of every instance's mesh, the padding of the boxes leaf
+// subdivision added, the top-level refit.  The per-instance records and the paddings are on the device (U.recs, U.pads); errors are
+// left for hipGetLastError.  update_instances and update_vertices share it.
+void launch_instance_refit(polaris_hip_tracer *h, hipStream_t q) {
+	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
+	const UpdatePlan &P = U.plan;
+	const uint32_t NI = h->num_insts;
+	(void)launch(h, "instance_extent", q, kInstanceExtent, dim3(U.chunks, std::min(NI, 65535u)), kExtentBlock, 0, h->scene.vertices, U.tri_list, U.inst_range, U.recs, NI,
+	             U.chunk_tris, U.partial);
+	if (!P.padded.empty())
+		(void)launch(h, "repad", q, kRepad, ((uint32_t)P.padded.size() + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, U.padded, (uint32_t)P.padded.size(), U.pads, U.pairs);
+	const RefitArgs A{U.nodes, U.level_first, U.scratch, U.pairs, U.insts, U.recs, U.partial, U.chunks};
+	const uint32_t levels = (uint32_t)P.level_first.size() - 1;
+	if (P.nodes.size() <= kRefitOneGroupNodes) (void)launch(h, "refit_top", q, kRefitTop, 1, kRefitBlock, 0, A, 0u, levels);
+	else
+		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
+			(void)launch(h, "refit_top", q, kRefitTop, (P.level_first[l + 1] - P.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
 }
 
 // Move the uploaded scene's mesh instances in place (include/polaris_hip.h; instance_update.h has the arithmetic).
@@ -1122,24 +1175,15 @@ int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpd
 		}
 		h->mo_cur = std::move(next);
 	}
+	if (h->vup.on) h->vup.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
 	hipStream_t q = h->stream;
-	const UpdatePlan &P = U.plan;
 	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
 	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
 	if (u->emissives && u->num_emissives) {
 		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, u->emissives, (size_t)u->num_emissives * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
 		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
 	}
-	(void)launch(h, "instance_extent", q, kInstanceExtent, dim3(U.chunks, std::min(NI, 65535u)), kExtentBlock, 0, h->scene.vertices, U.tri_list, U.inst_range, U.recs, NI,
-	             U.chunk_tris, U.partial);
-	if (!P.padded.empty())
-		(void)launch(h, "repad", q, kRepad, ((uint32_t)P.padded.size() + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, U.padded, (uint32_t)P.padded.size(), U.pads, U.pairs);
-	const RefitArgs A{U.nodes, U.level_first, U.scratch, U.pairs, U.insts, U.recs, U.partial, U.chunks};
-	const uint32_t levels = (uint32_t)P.level_first.size() - 1;
-	if (P.nodes.size() <= kRefitOneGroupNodes) (void)launch(h, "refit_top", q, kRefitTop, 1, kRefitBlock, 0, A, 0u, levels);
-	else
-		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
-			(void)launch(h, "refit_top", q, kRefitTop, (P.level_first[l + 1] - P.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
+	launch_instance_refit(h, q);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(q)); // (recs, pads and geo die at return)
 	collect_timers(h);
@@ -1153,6 +1197,92 @@ int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpd
 		U.emissives.assign(u->emissives, u->emissives + u->num_emissives);
 		U.light_geo = std::move(geo);
 	}
+	return POLARIS_OK;
+}
+
+// Deform the uploaded scene's meshes in place (include/polaris_hip.h; vertex_update.h has the arithmetic).
+int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate *u) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
+	polaris_hip_tracer::VertexUpdateState &V = h->vup;
+	std::string msg;
+	if (int st = check_vertex_update(u, h->have_scene, V.on, U.plan.mesh, V.num_triangles, h->num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
+	const uint32_t NI = h->num_insts, NT = V.num_triangles;
+	if (int st = check_vertex_magnitudes(u->vertices, NT, msg)) return fail(h, st, "%s", msg.c_str());
+	const float *inv = u->inv_transforms ? u->inv_transforms : V.inv.data();
+	std::vector<InstUpdateRec> recs;
+	std::vector<float> pads;
+	// (matrices and boxes are judged now; the records and paddings are made again below, once the deformed meshes' boxes are known)
+	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str());
+	// the packed light records: the triangle of every area light from the new arrays, then what derives from transform and area
+	const PolarisEmissive *ems = u->emissives ? u->emissives : U.emissives.data();
+	std::vector<float> geo = U.light_geo;
+	for (size_t e = 0; e < U.emissives.size(); e++) {
+		if (ems[e].type != POLARIS_EMISSIVE_AREA) continue;
+		const size_t off = (size_t)ems[e].tri_index * 3;
+		float *g = geo.data() + e * kLightGeoFloats;
+		for (int v = 0; v < 3; v++)
+			for (int k = 0; k < 3; k++) {
+				g[4 * v + k] = u->vertices[4 * (off + v) + k];
+				if (u->normals) g[12 + 4 * v + k] = u->normals[4 * (off + v) + k];
+			}
+		derive_light_geo(ems[e], g);
+	}
+	// ---- accepted: from here on the state changes ----
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, sync_all(h));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	h->have_scene = false; // (a failing call below leaves the scene as a failed upload does)
+	h->gb_valid = false;
+	if (h->tp.max_history) { // the history never saw this scene
+		h->tp_have_hist = h->va_have_hist = false;
+		h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
+	}
+	if (h->opt_object_motion && u->inv_transforms && h->mo_cur.inv.size() == (size_t)NI * 16) h->mo_cur.inv.assign(inv, inv + (size_t)NI * 16);
+	hipStream_t q = h->stream;
+	UpdatePlan &P = U.plan;
+	const MeshPlan &M = P.mesh;
+	const size_t nv = (size_t)NT * 3;
+	HIP_TRY(h, hipMemcpyAsync(V.vertices, u->vertices, nv * sizeof(float4), hipMemcpyHostToDevice, q));
+	if (u->normals) HIP_TRY(h, hipMemcpyAsync(V.normals, u->normals, nv * sizeof(float4), hipMemcpyHostToDevice, q));
+	(void)launch(h, "tri_records", q, kTriRecords, (V.num_slots + kTriRecordBlock - 1) / kTriRecordBlock, kTriRecordBlock, 0, V.vertices, V.slot_src, V.num_slots, V.tris);
+	const MeshRefitArgs A{V.nodes, V.level_first, V.slot_src, V.vertices, V.scratch, U.pairs, U.padded, V.mesh_box};
+	const uint32_t levels = (uint32_t)M.level_first.size() - 1;
+	if (M.nodes.size() <= kMeshRefitOneGroupNodes) (void)launch(h, "refit_mesh", q, kRefitMesh, 1, kRefitBlock, 0, A, 0u, levels);
+	else
+		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
+			(void)launch(h, "refit_mesh", q, kRefitMesh, (M.level_first[l + 1] - M.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
+	HIP_TRY(h, hipGetLastError());
+	// the deformed meshes' root boxes come back: a term of the padding of the boxes leaf subdivision added (subdivision_pad)
+	std::vector<float> boxes(8 * M.root.size());
+	HIP_TRY(h, hipMemcpyAsync(boxes.data(), V.mesh_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, q));
+	HIP_TRY(h, hipStreamSynchronize(q));
+	for (size_t m = 0; m < M.root.size(); m++) {
+		memcpy(P.mesh_box[m].min, boxes.data() + 8 * m, 12);
+		memcpy(P.mesh_box[m].max, boxes.data() + 8 * m + 4, 12);
+	}
+	if (int st = prepare_instance_update(P, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
+	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
+	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	if (!U.emissives.empty()) {
+		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, ems, U.emissives.size() * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
+		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	}
+	launch_instance_refit(h, q);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(q)); // (recs, pads and geo die at return)
+	collect_timers(h);
+	if (h->bvh.root_is_instance) { // the one instance's record travels in the kernel arguments
+		const InstUpdateRec &R = recs[((uint32_t)~h->bvh.root_ref) >> 4];
+		h->bvh.root_inst.r0 = make_float4(R.r0[0], R.r0[1], R.r0[2], R.r0[3]);
+		h->bvh.root_inst.r1 = make_float4(R.r1[0], R.r1[1], R.r1[2], R.r1[3]);
+		h->bvh.root_inst.r2 = make_float4(R.r2[0], R.r2[1], R.r2[2], R.r2[3]);
+	}
+	if (u->inv_transforms) V.inv.assign(inv, inv + (size_t)NI * 16);
+	if (u->emissives) U.emissives.assign(u->emissives, u->emissives + u->num_emissives);
+	U.light_geo = std::move(geo);
+	h->have_scene = true;
 	return POLARIS_OK;
 }
 
@@ -1262,6 +1392,10 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "instance_update") { // next upload
 		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "instance_update is 0 or 1");
 		h->opt_instance_update = (int)value;
+	}
+	else if (k == "vertex_update") { // next upload
+		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "vertex_update is 0 or 1");
+		h->opt_vertex_update = (int)value;
 	}
 	else if (k == "max_leaf_tris") h->opt_max_leaf_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
 	else return fail(h, POLARIS_E_BAD_ARGUMENT, "unknown option '%s'", key);

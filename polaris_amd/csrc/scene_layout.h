@@ -73,7 +73,30 @@ struct PaddedBox {
 	uint32_t side_mesh;  // ... side (bit 0: 0 = lo0/hi0, 1 = lo1/hi1) | index of its mesh << 1
 	float lo[3], hi[3];  // exact bounds of its triangles: the record holds lo - pad, hi + pad (subdivision_pad, largest over the mesh's instances)
 };
+// What polaris_hip_update_vertices needs on top of that: every node of the mesh trees the kernels traverse -- the
+// nodes leaf subdivision added included -- as a refit schedule.  Filled by build_layout when want_mesh_plan is set.
+struct MeshPlanNode {
+	int32_t a, b;        // inner node: its two children as plan indices; leaf: a = its first triangle slot as the kernels see it, b = -1
+	uint32_t count;      // leaf: its triangles (big leaves too: what LeafInfo holds); inner node: 0 -- except a leaf of the caller's tree that
+	                     // leaf subdivision split (b >= 0): the caller's count, its bounds are the fold of the scene triangles
+	                     // [first_tri, first_tri + count) in the caller's order (the slots below it were sorted), not the union of its children
+	int32_t pair_side;   // where its box is held: pair record (after the renumbering) << 1 | side; -1: a mesh root, no record holds its box
+	int32_t padded;      // its entry of UpdatePlan::padded if leaf subdivision added it, else -1
+	uint32_t mesh;       // index of its mesh (UpdatePlan::mesh_box)
+	uint32_t node;       // the caller's node index; >= num_bvh_nodes: an added node
+	uint32_t first_tri;  // a split leaf of the caller's tree: its first scene triangle
+};
+static_assert(sizeof(MeshPlanNode) == 32, "layout");
+struct MeshPlan {
+	bool on = false;                     // the plan below is filled
+	std::string refused;                 // why it is not: a node that two mesh trees share (the upload succeeds, update_vertices is refused)
+	std::vector<uint32_t> slot_src;      // [slots]: triangle slot -> scene triangle, the final order (after the tiny-scene reorder)
+	std::vector<MeshPlanNode> nodes;     // by height, leaves first, the nodes of a level contiguous: children come before their parent
+	std::vector<uint32_t> level_first;   // [levels + 1]
+	std::vector<uint32_t> root;          // [meshes]: plan index of the mesh's root
+};
 struct UpdatePlan {
+	MeshPlan mesh;                      // (option vertex_update)
 	std::vector<UpdateNode> nodes;      // deepest level first, the nodes of a level contiguous: children come before their parent
 	std::vector<uint32_t> level_first;  // [levels + 1]: level l is nodes[level_first[l] .. level_first[l + 1])
 	std::vector<uint32_t> mesh_of_inst; // [NI]: index of the instance's mesh in the arrays below (one entry per distinct mesh root)
@@ -145,6 +168,7 @@ struct SceneLayout {
 	// bit c: a hit of shading class c may end in an emissive leaf (emitting_classes below); all ones when hits carry no class
 	uint32_t emit_classes = 0xFFFFu;
 	bool want_update_plan = false;  // set by the caller: build_layout also fills `plan` (option instance_update)
+	bool want_mesh_plan = false;    // set by the caller: build_layout also fills `plan.mesh`, and `plan` with it (option vertex_update)
 	UpdatePlan plan;
 };
 
@@ -259,6 +283,7 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 	if (sc.num_material_nodes == 0 || !sc.material_nodes) return "scene has no material nodes";
 	if (sc.num_emissives && !sc.emissives) return "emissive list pointer is null";
 	if (sc.num_textures && (!sc.texture_meta || !sc.texture_data)) return "texture pointers are null";
+	if (out.want_mesh_plan) out.want_update_plan = true;
 
 	// ---- magnitudes ------------------------------------------------------------------------
 	// The triangle tests take 1 / det from v_rcp_f32 + one Newton step, which equals the correctly rounded quotient for
@@ -800,6 +825,78 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 					P.padded.push_back(PaddedBox{new_id[par.first], (uint32_t)par.second | (uint32_t)mesh_id[a.root] << 1,
 					                             {a.lo[0], a.lo[1], a.lo[2]}, {a.hi[0], a.hi[1], a.hi[2]}});
 				}
+			// ---- the mesh plan (polaris_hip_update_vertices) --------------------------------------------
+			if (out.want_mesh_plan) {
+				MeshPlan &M = P.mesh;
+				std::vector<int32_t> padded_of(n_nodes > NN ? n_nodes - NN : 0, -1); // added node -> its entry of P.padded
+				if (subdivided) {
+					int32_t at = 0;
+					for (const AddedBox &a : added_boxes) {
+						const std::pair<int32_t, int> &par = added_parent[(size_t)a.node - NN];
+						if (new_id[par.first] < 0 || mesh_id[a.root] < 0) continue;
+						padded_of[(size_t)a.node - NN] = at++;
+					}
+				}
+				// every mesh tree in pre-order (a parent before its children), then by height
+				struct Seen { int32_t node, parent; int side; uint32_t mesh; };
+				std::vector<Seen> pre;
+				std::vector<uint8_t> reached(n_nodes, 0);
+				std::vector<uint32_t> root_at(P.mesh_box.size(), 0);
+				std::vector<uint8_t> walked(P.mesh_box.size(), 0);
+				for (uint32_t i = 0; i < NI && M.refused.empty(); i++) {
+					const uint32_t root = sc.mesh_instances[i].bvh_root, m = (uint32_t)mesh_id[root];
+					if (walked[m]) continue; // (a mesh shared by instances: one walk)
+					walked[m] = 1;
+					root_at[m] = (uint32_t)pre.size();
+					std::vector<Seen> stack{{(int32_t)root, -1, 0, m}};
+					while (!stack.empty()) {
+						const Seen s = stack.back();
+						stack.pop_back();
+						if (reached[s.node]) { M.refused = "BVH node " + std::to_string(s.node) + " is shared by two mesh trees"; break; }
+						reached[s.node] = 1;
+						const PolarisBvhNode &n = nodes[s.node];
+						if (!is_leaf(n)) {
+							stack.push_back({n.rdata, (int32_t)pre.size(), 1, m});
+							stack.push_back({n.ldata, (int32_t)pre.size(), 0, m});
+						}
+						pre.push_back(s);
+					}
+				}
+				if (M.refused.empty()) {
+					std::vector<int> height(pre.size(), 0);
+					int tallest = 0;
+					for (size_t k = pre.size(); k-- > 0;) { // (children come after their parent)
+						if (pre[k].parent >= 0) height[pre[k].parent] = std::max(height[pre[k].parent], height[k] + 1);
+						tallest = std::max(tallest, height[k]);
+					}
+					std::vector<uint32_t> count(tallest + 2, 0), plan_of(pre.size());
+					for (size_t k = 0; k < pre.size(); k++) count[height[k] + 1]++;
+					for (int l = 0; l <= tallest; l++) count[l + 1] += count[l];
+					M.level_first.assign(count.begin(), count.end());
+					for (size_t k = 0; k < pre.size(); k++) plan_of[k] = count[height[k]]++;
+					M.nodes.assign(pre.size(), MeshPlanNode{-1, -1, 0, -1, -1, 0, 0, 0});
+					for (size_t k = 0; k < pre.size(); k++) {
+						MeshPlanNode &u = M.nodes[plan_of[k]];
+						const PolarisBvhNode &n = nodes[pre[k].node];
+						u.mesh = pre[k].mesh;
+						u.node = (uint32_t)pre[k].node;
+						if (is_leaf(n)) { u.a = (int32_t)(uint32_t)(-(int64_t)n.ldata); u.count = (uint32_t)n.rdata; }
+						else if ((uint32_t)pre[k].node < NN && is_leaf(sc.bvh_nodes[pre[k].node])) { // split by leaf subdivision
+							u.first_tri = (uint32_t)(-(int64_t)sc.bvh_nodes[pre[k].node].ldata);
+							u.count = (uint32_t)sc.bvh_nodes[pre[k].node].rdata;
+						}
+						if ((uint32_t)pre[k].node >= NN) u.padded = padded_of[(size_t)pre[k].node - NN];
+						if (pre[k].parent >= 0) {
+							MeshPlanNode &up = M.nodes[plan_of[pre[k].parent]];
+							(pre[k].side ? up.b : up.a) = (int32_t)plan_of[k];
+							u.pair_side = (int32_t)((uint32_t)new_id[pre[pre[k].parent].node] << 1 | (uint32_t)pre[k].side);
+						}
+					}
+					M.root.resize(P.mesh_box.size());
+					for (size_t m = 0; m < M.root.size(); m++) M.root[m] = plan_of[root_at[m]];
+					M.on = true;
+				}
+			}
 		}
 	}
 
@@ -843,8 +940,11 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 			out.root_ref = moved(out.root_ref);
 			for (uint32_t i = 0; i < NI; i++) out.insts[i].root_ref = moved(out.insts[i].root_ref);
 			slot_src.swap(new_src);
+			for (MeshPlanNode &u : out.plan.mesh.nodes) // (the mesh plan names a leaf by its first slot)
+				if (u.count && u.b < 0) u.a = (int32_t)new_first[(uint32_t)u.a];
 		}
 	}
+	if (out.plan.mesh.on) out.plan.mesh.slot_src = slot_src;
 
 	std::vector<uint8_t> node_class;
 	shading_classes(sc, node_class);

@@ -297,6 +297,48 @@ def instance_update(inv, boxes, emissives=None):
     return u, keep
 
 
+class VertexUpdate(C.Structure):
+    """PolarisVertexUpdate (include/polaris_hip.h): what polaris_hip_update_vertices deforms the uploaded scene's meshes to."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_triangles", C.c_uint32),
+        ("vertices", C.c_void_p), ("normals", C.c_void_p),
+        ("num_mesh_instances", C.c_uint32), ("instance_boxes", C.c_void_p), ("inv_transforms", C.c_void_p),
+        ("emissives", C.c_void_p), ("num_emissives", C.c_uint32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(VertexUpdate) == 64
+
+
+def vertex_update(vertices, boxes, normals=None, inv=None, emissives=None):
+    """A VertexUpdate over the given arrays, and the arrays it borrows (keep them alive while it is used)."""
+    vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    u = VertexUpdate()
+    u.num_triangles, u.num_mesh_instances = len(vertices) // 3, len(boxes)
+    u.vertices, u.instance_boxes = vertices.ctypes.data, boxes.ctypes.data
+    keep = [vertices, boxes]
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 4)
+        assert len(normals) == len(vertices)
+        u.normals = normals.ctypes.data
+        keep.append(normals)
+    if inv is not None:
+        inv = np.ascontiguousarray(inv, dtype=np.float32).reshape(-1, 16)
+        assert len(inv) == len(boxes)
+        u.inv_transforms = inv.ctypes.data
+        keep.append(inv)
+    if emissives is not None:
+        em = np.ascontiguousarray(emissives, dtype=EMISSIVE)
+        u.emissives, u.num_emissives = (em.ctypes.data if em.size else None), len(em)
+        keep.append(em)
+    return u, keep
+
+
 def _ptr(a):
     return None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
 
@@ -333,7 +375,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
-    "polaris_hip_update_instances", "polaris_hip_read_scene_records",
+    "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
 ]
 
 _lib = None
@@ -443,6 +485,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_read_instance_plane.argtypes = [vp, vp, C.c_size_t]
     lib.polaris_hip_update_instances.argtypes = [vp, C.POINTER(InstanceUpdate)]
     lib.polaris_hip_read_scene_records.argtypes = [vp, i32, vp, C.c_size_t]
+    lib.polaris_hip_update_vertices.argtypes = [vp, C.POINTER(VertexUpdate)]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

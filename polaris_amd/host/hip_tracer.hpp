@@ -60,6 +60,15 @@ public:
 		const char *m = polaris_hip_last_error(h_);
 		return Error{rc, std::string("hip tracer: ") + (m ? m : "update_instances failed")};
 	}
+	// Deform the uploaded scene's meshes in place (polaris_hip_update_vertices; the scene must have been uploaded with the option
+	// "vertex_update" on).  Synchronous; a refusal leaves the tracer as it was.
+	Error UpdateVertices(const PolarisVertexUpdate *u) {
+		if (!h_) return Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: UpdateVertices on a closed tracer"};
+		const int rc = polaris_hip_update_vertices(h_, u);
+		if (rc == POLARIS_OK) return Error::Nil();
+		const char *m = polaris_hip_last_error(h_);
+		return Error{rc, std::string("hip tracer: ") + (m ? m : "update_vertices failed")};
+	}
 	void ResetFrame() { if (h_) (void)polaris_hip_reset_frame(h_); } // the Reset stage on its own (also advances the epoch)
 	const PolarisTraceStats &LastTraceStats() const { return last_; }
 	polaris_hip_tracer *Handle() const { return h_; }

@@ -148,6 +148,14 @@ int polaris_host_renderer_update_instances(void *h, const PolarisInstanceUpdate 
 		if (Error e = t->UpdateInstances(u)) { box->error = e.msg; return e.code; }
 	return 0;
 }
+// Deforming the scene's meshes in place (polaris_hip_update_vertices) on every tracer, as update_instances.  The
+// tracers must have been given the option "vertex_update" before the scene.
+int polaris_host_renderer_update_vertices(void *h, const PolarisVertexUpdate *u) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (Error e = t->UpdateVertices(u)) { box->error = e.msg; return e.code; }
+	return 0;
+}
 // Denoising (polaris_hip_set_denoise) on every tracer, as set_option; only the primary's SyncFramebuffer runs, so only it filters.
 int polaris_host_renderer_set_denoise(void *h, const PolarisDenoiseParams *p) {
 	auto *box = static_cast<RendererBox *>(h);

@@ -35,6 +35,7 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         lib.polaris_host_renderer_set_denoise.argtypes = [vp, C.POINTER(T.DenoiseParams)]
         lib.polaris_host_renderer_update_instances.argtypes = [vp, C.POINTER(T.InstanceUpdate)]
+        lib.polaris_host_renderer_update_vertices.argtypes = [vp, C.POINTER(T.VertexUpdate)]
         lib.polaris_host_renderer_upload_scene.argtypes = [vp, C.POINTER(T.SceneView)]
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
@@ -175,6 +176,15 @@ class Renderer:
         u, keep = T.instance_update(inv, boxes, emissives)
         if self._lib.polaris_host_renderer_update_instances(self._h, C.byref(u)):
             raise RuntimeError(f"update_instances failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+        del keep
+
+    def update_vertices(self, vertices, boxes, normals=None, inv=None, emissives=None) -> None:
+        """polaris_hip_update_vertices on every tracer: deform the scene's meshes in place.  Arguments as
+        HipTracer.update_vertices; the scene must have been uploaded with the option on: set_option("vertex_update", 1), then
+        upload_scene (the constructor's upload came before any option)."""
+        u, keep = T.vertex_update(vertices, boxes, normals, inv, emissives)
+        if self._lib.polaris_host_renderer_update_vertices(self._h, C.byref(u)):
+            raise RuntimeError(f"update_vertices failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
         del keep
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:

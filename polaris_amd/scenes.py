@@ -747,6 +747,92 @@ def refit_instances(base: Scene, moved: Scene) -> Scene:
                  name=f"{base.name}-refit-{moved.name}", bvh_max_depth=base.bvh_max_depth)
 
 
+def _mesh_tree_nodes(scene: Scene, root: int):
+    """Indices and depths of the nodes of the mesh BVH below `root` (the root included), parents before children."""
+    nodes = scene.bvh_nodes
+    idx, depth = [np.array([root], dtype=np.int64)], [np.zeros(1, dtype=np.int64)]
+    while True:
+        cur = idx[-1]
+        inner = cur[nodes["ldata"][cur] > 0]
+        if not len(inner):
+            break
+        idx.append(np.stack([nodes["ldata"][inner], nodes["rdata"][inner]], axis=1).reshape(-1).astype(np.int64))
+        depth.append(np.full(len(idx[-1]), depth[-1][0] + 1, dtype=np.int64))
+    return np.concatenate(idx), np.concatenate(depth)
+
+
+def _fold_leaf_bounds(vertices, first, count):
+    """min / max over the vertices of the triangles [first, first + count) of every leaf, folded in order (triangle by triangle, of
+    each v0, v1, v2) with b < a ? b : a / b > a ? b : a, a the running value: where +0 meets -0 the earlier operand stays."""
+    v = vertices[:, :3]
+    lo = v[3 * first].copy()
+    hi = lo.copy()
+    for j in range(1, 3 * int(count.max())):
+        live = (j < 3 * count)[:, None]
+        b = v[np.where(j < 3 * count, 3 * first + j, 0)]
+        lo = np.where(live & (b < lo), b, lo)
+        hi = np.where(live & (b > hi), b, hi)
+    return lo, hi
+
+
+def refit_vertices(base: Scene, vertices, normals=None, moved: Scene | None = None) -> Scene:
+    """`base` deformed: the scene polaris_hip_update_vertices makes of an uploaded `base`.  vertices (3 NT, 4) replace
+    base's, normals too where given.  Every mesh BVH node is refit on base's topology: a triangle leaf takes the exact bounds of its
+    triangles' vertices (_fold_leaf_bounds), an inner node the union of its children, left before right, by the same rule.  `moved`
+    (None: base) supplies the instance matrices and the emissives' transforms.  The instance boxes are the world minimum / maximum of
+    the deformed mesh through the forward matrix, area emissives get 0.5 |cross| of the deformed triangle (both as compile_scene
+    computes them), and the top level goes through refit_instances."""
+    vertices = np.ascontiguousarray(vertices, dtype=F32).reshape(-1, 4)
+    assert vertices.shape == base.vertices.shape
+    normals = base.normals if normals is None else np.ascontiguousarray(normals, dtype=F32).reshape(-1, 4)
+    assert normals.shape == base.normals.shape
+    src = base if moved is None else moved
+    assert len(src.mesh_instances) == len(base.mesh_instances) and len(src.emissives) == len(base.emissives)
+    nodes = base.bvh_nodes.copy()
+    inst_tab = base.mesh_instances.copy()
+    inst_tab["inv_transform"] = src.mesh_instances["inv_transform"]
+    mesh_verts = {}
+    for root in dict.fromkeys(int(r) for r in base.mesh_instances["bvh_root"]):
+        idx, depth = _mesh_tree_nodes(base, root)
+        leaf = idx[nodes["ldata"][idx] <= 0]
+        first, count = -nodes["ldata"][leaf].astype(np.int64), nodes["rdata"][leaf].astype(np.int64)
+        nodes["min"][leaf], nodes["max"][leaf] = _fold_leaf_bounds(vertices, first, count)
+        for d in range(int(depth.max()), -1, -1):
+            lvl = idx[depth == d]
+            inner = lvl[nodes["ldata"][lvl] > 0]
+            l, r = nodes["ldata"][inner], nodes["rdata"][inner]
+            nodes["min"][inner] = np.where(nodes["min"][r] < nodes["min"][l], nodes["min"][r], nodes["min"][l])
+            nodes["max"][inner] = np.where(nodes["max"][r] > nodes["max"][l], nodes["max"][r], nodes["max"][l])
+        tri = np.concatenate([np.arange(f, f + c) for f, c in zip(first, count)])
+        mesh_verts[root] = vertices[(3 * tri[:, None] + np.arange(3)).reshape(-1), :3].astype(np.float64)
+    top, _ = _top_level_nodes(base)
+    for n in top[nodes["ldata"][top] <= 0]:
+        i = -int(nodes["ldata"][n])
+        xf = np.linalg.inv(inst_tab["inv_transform"][i].reshape(4, 4).T.astype(np.float64))
+        w = mesh_verts[int(inst_tab["bvh_root"][i])] @ xf[:3, :3].T + xf[:3, 3]
+        nodes["min"][n], nodes["max"][n] = w.min(0).astype(F32), w.max(0).astype(F32)
+    ems = src.emissives.copy()
+    for e in range(len(ems)):
+        if ems["type"][e] == T.EMISSIVE_AREA:
+            p = vertices[3 * int(ems["tri_index"][e]):3 * int(ems["tri_index"][e]) + 3, :3].astype(np.float64)
+            ems["area"][e] = F32(0.5 * np.linalg.norm(np.cross(p[2] - p[0], p[2] - p[1])))
+    mid = Scene(bvh_nodes=nodes, mesh_instances=inst_tab, material_nodes=base.material_nodes, emissives=ems,
+                texture_data=base.texture_data, texture_meta=base.texture_meta, vertices=vertices, normals=normals,
+                uvs=base.uvs, material_index=base.material_index, scene_diffuse_mat_index=base.scene_diffuse_mat_index,
+                scene_emissive_mat_index=base.scene_emissive_mat_index, eye=base.eye.copy(), frustum=base.frustum.copy(),
+                name=f"{base.name}-deformed", bvh_max_depth=base.bvh_max_depth)
+    out = refit_instances(mid, mid)
+    out.name = mid.name
+    return out
+
+
+def vertex_update_args(scene: Scene):
+    """(vertices (3 NT, 4), instance_boxes (NI, 6), normals (3 NT, 4), inv_transforms (NI, 16), emissives) of a scene: what
+    HipTracer.update_vertices takes to deform an uploaded scene into `scene` (polaris_hip_update_vertices)."""
+    inv, boxes, ems = instance_update_args(scene)
+    return scene.vertices.copy(), boxes, scene.normals.copy(), inv, ems
+
+
 def textured_materials_scene(aspect=1.0) -> Scene:
     """A small scene touching every material operator and texture format (mix, mixMap, bumpMap,
     normalMap, disperse; L8, L32F, RGBA8, RGBA32F) -- parity coverage, not a benchmark."""

@@ -324,6 +324,17 @@ class HipTracer:
         self._check(self._lib.polaris_hip_update_instances(self._h, C.byref(u)), self._h)
         del keep
 
+    def update_vertices(self, vertices, boxes, normals=None, inv=None, emissives=None) -> None:
+        """Deform the uploaded scene's meshes in place (polaris_hip_update_vertices): vertices (3 NT, 4) as the scene's,
+        boxes (NI, 6) world-space min.xyz, max.xyz of the deformed instances, normals (3 NT, 4) (None: unchanged), inv (NI, 16)
+        column-major inverse matrices (None: unchanged), emissives the scene's emissive array with new transform / area (None:
+        unchanged) -- scenes.vertex_update_args(scene) makes the tuple.  The scene must have been uploaded with the option
+        "vertex_update" on.  Queued state changes are committed first, as by Trace."""
+        self._commit()
+        u, keep = T.vertex_update(vertices, boxes, normals, inv, emissives)
+        self._check(self._lib.polaris_hip_update_vertices(self._h, C.byref(u)), self._h)
+        del keep
+
     def read_scene_records(self) -> tuple[np.ndarray, np.ndarray]:
         """(pair records, instance records) of the uploaded scene as the device holds them (polaris_hip_read_scene_records; test tap):
         arrays of ctypes_api.PAIR_RECORD and INST_RECORD."""
