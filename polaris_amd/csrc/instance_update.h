@@ -90,6 +90,20 @@ POL_HD inline void world_point(const double *fwd, const float *v, float *w) {
 	for (int r = 0; r < 3; r++) w[r] = (float)(fwd[4 * r] * p[0] + fwd[4 * r + 1] * p[1] + fwd[4 * r + 2] * p[2] + fwd[4 * r + 3]);
 }
 
+// An update's emissive list (null: unchanged) may differ from the uploaded one (ems) in transform and area only.  who: the entry, for msg.
+inline int check_update_emissives(const char *who, const PolarisEmissive *list, uint32_t n, const std::vector<PolarisEmissive> &ems, std::string &msg) {
+	if (list && n != ems.size()) {
+		msg = who + std::to_string(n) + " emissives, the uploaded scene has " + std::to_string(ems.size());
+		return POLARIS_E_BAD_ARGUMENT;
+	}
+	for (uint32_t e = 0; list && e < n; e++)
+		if (list[e].type != ems[e].type || list[e].tri_index != ems[e].tri_index || list[e].mat_node_index != ems[e].mat_node_index) {
+			msg = who + ("emissive " + std::to_string(e)) + " differs from the uploaded one in type, triangle or material node";
+			return POLARIS_E_BAD_ARGUMENT;
+		}
+	return 0;
+}
+
 // ---- host: the argument checks of polaris_hip_update_instances that need no device ----------------------------------------------------
 // have_plan: the scene was uploaded with the option instance_update on; NI, ems: the uploaded scene's instance count and emissive
 // list.  0 = accepted, else the POLARIS_E_* status the entry returns, with msg.
@@ -104,18 +118,7 @@ inline int check_instance_update(const PolarisInstanceUpdate *u, bool have_scene
 		return POLARIS_E_BAD_ARGUMENT;
 	}
 	if (!u->inv_transforms || !u->instance_boxes) { msg = "update_instances: matrix or box pointer is null"; return POLARIS_E_BAD_ARGUMENT; }
-	if (u->emissives) {
-		if (u->num_emissives != ems.size()) {
-			msg = "update_instances: " + std::to_string(u->num_emissives) + " emissives, the uploaded scene has " + std::to_string(ems.size());
-			return POLARIS_E_BAD_ARGUMENT;
-		}
-		for (uint32_t e = 0; e < u->num_emissives; e++)
-			if (u->emissives[e].type != ems[e].type || u->emissives[e].tri_index != ems[e].tri_index || u->emissives[e].mat_node_index != ems[e].mat_node_index) {
-				msg = "update_instances: emissive " + std::to_string(e) + " differs from the uploaded one in type, triangle or material node";
-				return POLARIS_E_BAD_ARGUMENT;
-			}
-	}
-	return 0;
+	return check_update_emissives("update_instances: ", u->emissives, u->num_emissives, ems, msg);
 }
 
 // ---- host: validation and the per-instance records ------------------------------------------------------------------------------

@@ -45,6 +45,48 @@ struct KernelTimer { double ms = 0.0; uint64_t launches = 0; };
 
 using DevPool = std::vector<DevArray<char>>; // buffers that live and die together (dev_alloc): the scene's, a pipeline's
 
+// moving instances in place (option "instance_update", polaris_hip_update_instances).  With the option on an upload
+// keeps the update plan (scene_layout.h UpdatePlan; its device copies and the kernels' scratch live in the scene's buffers and go with
+// the scene) and host copies of the emissive list and the packed light geometry.  Off, it stays empty and nothing is allocated.
+struct InstanceUpdateState {
+	bool on = false; // the uploaded scene has a plan
+	UpdatePlan plan;
+	std::vector<PolarisEmissive> emissives;
+	std::vector<float> light_geo;
+	PairNode *pairs = nullptr; InstRec *insts = nullptr; // the scene's records, writable (these four: set by every upload)
+	PolarisEmissive *d_emissives = nullptr; float *d_light_geo = nullptr;
+	UpdateNode *nodes = nullptr; uint32_t *level_first = nullptr, *tri_list = nullptr; uint2 *inst_range = nullptr;
+	PaddedBox *padded = nullptr; float *pads = nullptr;
+	UpdateBox *scratch = nullptr; InstUpdateRec *recs = nullptr; float *partial = nullptr;
+	uint32_t chunks = 1, chunk_tris = kExtentChunkTris; // k_instance_extent: chunks per instance, triangles per chunk
+};
+
+// deforming meshes in place (option "vertex_update", polaris_hip_update_vertices).  With the option on an upload keeps
+// everything the instance update keeps (whose plan carries the mesh plan: scene_layout.h MeshPlan) plus the device copies below, in
+// the scene's buffers like the rest, and a host copy of the current instance matrices.  Off, it stays empty.
+struct VertexUpdateState {
+	bool on = false; // the scene was uploaded with the option on (the mesh plan itself may still have been refused: upd.plan.mesh)
+	std::vector<float> inv; // [NI][16]: the current inverse matrices (upload, update_instances and update_vertices keep it current)
+	uint32_t num_triangles = 0, num_slots = 0;
+	float4 *vertices = nullptr, *normals = nullptr; TriRec *tris = nullptr; // the scene's arrays, writable (set by every upload)
+	uint32_t *slot_src = nullptr, *level_first = nullptr; MeshPlanNode *nodes = nullptr;
+	float4 *scratch = nullptr, *mesh_box = nullptr;
+};
+
+// The uploaded scene (buffers.go:180-201, re-laid out by scene_layout.h): everything that lives and dies with an upload.  Every device
+// pointer below points into `bufs`: assigning DeviceScene() forgets the scene, and a failed upload leaves no pointer behind.
+struct DeviceScene {
+	bool have_scene = false; // complete: set last by upload_scene; update_vertices clears it while it works
+	DevPool bufs;
+	BvhDev bvh{};
+	SceneDev scene{};
+	int max_stack = 0; uint32_t num_insts = 0; // (mesh instances: the length of bvh.insts)
+	int node_mode = kNodesGlobal; // where k_trace reads node records from (kernels.h NodeMode)
+	bool tiny_one = false;        // tiny-scene mode: the scene is one instance whose boxes all bound their subtrees (kernels.h k_trace, ONE); option tiny_one = 0 keeps the general variant
+	TraceLaunch trace[2];         // [any hit]: the scene's k_trace variant with its block size, dynamic LDS bytes and residency (select_trace)
+	InstanceUpdateState upd; VertexUpdateState vup; // kept with the options "instance_update" / "vertex_update" at upload
+};
+
 } // namespace
 
 // Every stream, event and device allocation of the handle is a member that owns it (device_mem.h), so `delete h` releases
@@ -94,17 +136,9 @@ struct polaris_hip_tracer {
 	std::mutex readers_mu;
 	std::vector<Reader> readers, reader_pool;
 
-	// scene (buffers.go:180-201), re-laid out by scene_layout.h
-	bool have_scene = false;
-	DevPool scene_bufs;
-	BvhDev bvh{};
-	SceneDev scene{};
-	int max_stack = 0;
-	int node_mode = kNodesGlobal; // where k_trace reads node records from (kernels.h NodeMode), resolved at upload
+	// the uploaded scene, and the options the next upload resolves into it
+	DeviceScene ds;
 	int opt_node_mode = -1;       // -1 = by scene size
-	uint32_t tex_bytes = 0; // size of the uploaded texture blob (without its padding)
-	TraceLaunch trace[2];   // [any hit]: the scene's k_trace variant with its block size, dynamic LDS bytes and residency, resolved at upload (select_trace)
-	bool tiny_one = false;        // tiny-scene mode: the scene is one instance whose boxes all bound their subtrees (kernels.h k_trace, ONE); option tiny_one = 0 keeps the general variant
 	int opt_tiny_one = 1;
 	int opt_lds_tris = -1;        // tiny-scene mode: triangle records kept in LDS; -1 = as many as fit, 0 = none (A/B aid)
 
@@ -149,42 +183,13 @@ struct polaris_hip_tracer {
 			return topology_known && o.topology_known && mesh_index == o.mesh_index && num_triangles == o.num_triangles;
 		}
 	};
-	uint32_t num_insts = 0; // mesh instances of the uploaded scene (the length of bvh.insts)
 	int opt_object_motion = 0;
 	InstTable mo_cur, mo_hist;           // the current scene's instance table, the history's
 	DevArray<uint32_t> gb_inst, tp_hinst; // INSTANCE plane, the history's
 	DevArray<float4> mo_table;           // motion table of the last PRIOR (temporal.h tp_motion_table), grow-only until free_temporal
 	std::vector<float> mo_table_host;
 
-	// moving instances in place (option "instance_update", polaris_hip_update_instances).  With the option on an upload
-	// keeps the update plan (scene_layout.h UpdatePlan; its device copies and the kernels' scratch live in scene_bufs and go with the
-	// scene) and host copies of the emissive list and the packed light geometry.  Off, `upd` stays empty and nothing is allocated.
-	int opt_instance_update = 0; // next upload
-	struct InstanceUpdateState {
-		bool on = false; // the uploaded scene has a plan
-		UpdatePlan plan;
-		std::vector<PolarisEmissive> emissives;
-		std::vector<float> light_geo;
-		PairNode *pairs = nullptr; InstRec *insts = nullptr; // the scene's records, writable
-		PolarisEmissive *d_emissives = nullptr; float *d_light_geo = nullptr;
-		UpdateNode *nodes = nullptr; uint32_t *level_first = nullptr, *tri_list = nullptr; uint2 *inst_range = nullptr;
-		PaddedBox *padded = nullptr; float *pads = nullptr;
-		UpdateBox *scratch = nullptr; InstUpdateRec *recs = nullptr; float *partial = nullptr;
-		uint32_t chunks = 1, chunk_tris = kExtentChunkTris; // k_instance_extent: chunks per instance, triangles per chunk
-	} upd;
-
-	// deforming meshes in place (option "vertex_update", polaris_hip_update_vertices).  With the option on an upload keeps
-	// everything the instance update keeps (`upd`, whose plan carries the mesh plan: scene_layout.h MeshPlan) plus the device copies
-	// below, in scene_bufs like the rest, and a host copy of the current instance matrices.  Off, `vup` stays empty.
-	int opt_vertex_update = 0; // next upload
-	struct VertexUpdateState {
-		bool on = false; // the scene was uploaded with the option on (the mesh plan itself may still have been refused: upd.plan.mesh)
-		std::vector<float> inv; // [NI][16]: the current inverse matrices (upload, update_instances and update_vertices keep it current)
-		uint32_t num_triangles = 0, num_slots = 0;
-		float4 *vertices = nullptr, *normals = nullptr; TriRec *tris = nullptr; // the scene's arrays, writable
-		uint32_t *slot_src = nullptr, *level_first = nullptr; MeshPlanNode *nodes = nullptr;
-		float4 *scratch = nullptr, *mesh_box = nullptr;
-	} vup;
+	int opt_instance_update = 0, opt_vertex_update = 0; // the in-place updates: the next upload keeps what they need in ds.upd / ds.vup
 
 	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
 	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
@@ -533,7 +538,7 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 		if (int rc = ensure_plane(h, h->gb_inst, F)) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
-	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->bvh, h->scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo,
+	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo,
 	             want_inst ? h->gb_inst.get() : nullptr);
 	HIP_TRY(h, hipGetLastError());
 	h->gb_valid = true;
@@ -541,7 +546,7 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 }
 
 // The last temporal sync's planes under the current camera (and, with object motion, the current scene's instance table) become
-// the history; no sync under them: the older history stays.  set_camera and, with object motion, upload_scene call it before they
+// the history; no sync under them: the older history stays.  set_camera and, with object motion, scene_changed call it before they
 // change what the planes were seen with (caller holds mu, temporal reuse on).
 void capture_history(polaris_hip_tracer *h) {
 	if (!h->tp_synced) return;
@@ -559,45 +564,52 @@ void capture_history(polaris_hip_tracer *h) {
 	h->va_have_hist = h->va_synced;
 }
 
-// The floats of an area light's packed record (shading.h, SceneT::light_geo) that depend on the emissive's transform and area; g[0..29]
-// hold the light's triangle.  upload_scene and update_instances share it.
-void derive_light_geo(const PolarisEmissive &em, float *g) {
-	// what areaLightGetPdf (emissive_sampler.cl:117-173) and areaLightGetSample (:96) derive from the light alone, with the
-	// kernels' own operations in the kernels' order (this file is compiled without FMA contraction; polaris_math.h is
-	// bit-identical on the host): v0, v1 - v0, v2 - v0 through mul4x1 (util/transform.cl:9-16), normalize(cross(e1, e2)), 1 / area
-	const float *m = em.transform;
-	auto xform = [&](const float p[3], float out[3]) {
-		out[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
-		out[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
-		out[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
-	};
-	const float v0[3] = {g[0], g[1], g[2]};
-	const float d1[3] = {g[4] - v0[0], g[5] - v0[1], g[6] - v0[2]}, d2[3] = {g[8] - v0[0], g[9] - v0[1], g[10] - v0[2]};
-	float tv0[3], te1[3], te2[3];
-	xform(v0, tv0); xform(d1, te1); xform(d2, te2);
-	const float cx = te1[1] * te2[2] - te1[2] * te2[1], cy = te1[2] * te2[0] - te1[0] * te2[2], cz = te1[0] * te2[1] - te1[1] * te2[0];
-	const float inv_len = 1.0f / pm_sqrt(cx * cx + cy * cy + cz * cz);
-	for (int k = 0; k < 3; k++) { g[32 + k] = tv0[k]; g[36 + k] = te1[k]; g[40 + k] = te2[k]; }
-	g[44] = cx * inv_len; g[45] = cy * inv_len; g[46] = cz * inv_len;
-	g[30] = 1.0f / em.area;
+// Nothing synced so far was seen under what holds from now on: the camera (set_camera) or the scene (scene_changed).
+void forget_syncs(polaris_hip_tracer *h) { h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false; }
+
+// What a change of the scene does to the G-buffer and the temporal history (upload_scene and the in-place updates, before they change
+// it; caller holds mu, every stream idle).  next: the instance table of the scene to come, which becomes mo_cur.  With object motion
+// the change is to the history what a camera move is: the planes synced under the old scene join it, and it survives if the scene to
+// come has the same instances of the same meshes (temporal.h: k_reproject carries a hit back through the two tables).  Otherwise,
+// and always with next = null (mo_cur stays), the history saw another scene and goes.
+void scene_changed(polaris_hip_tracer *h, const polaris_hip_tracer::InstTable *next) {
+	h->gb_valid = false;
+	bool keep = false;
+	if (next && motion_on(h)) {
+		capture_history(h);
+		keep = h->tp_have_hist && h->mo_hist.compatible(*next);
+	}
+	if (h->tp.max_history) {
+		if (!keep) h->tp_have_hist = h->va_have_hist = false;
+		forget_syncs(h);
+	}
+	if (next) h->mo_cur = *next;
+}
+
+// The record of the scene's one top-level instance travels in the kernel arguments: its matrix rows from the layout's or an update's record.
+template <class Rec>
+void set_root_inst(BvhDev &bvh, const Rec &I) {
+	bvh.root_inst.r0 = make_float4(I.r0[0], I.r0[1], I.r0[2], I.r0[3]);
+	bvh.root_inst.r1 = make_float4(I.r1[0], I.r1[1], I.r1[2], I.r1[3]);
+	bvh.root_inst.r2 = make_float4(I.r2[0], I.r2[1], I.r2[2], I.r2[3]);
 }
 
 // The scene's k_trace variants (closest hit, any hit) into the handle: STACK from the exact depth the scene needs, NODES from its
 // size (kernels.h, NodeMode), ONE in the tiny-scene mode; with the workgroup size.  plan_tiny_lds and trace_occupancy fill in the rest.
 void select_trace(polaris_hip_tracer *h) {
-	const bool tiny = h->node_mode == kNodesLdsAll;
+	const bool tiny = h->ds.node_mode == kNodesLdsAll;
 	for (int any = 0; any < 2; any++)
-		h->trace[any] = TraceLaunch{tiny ? &kTraceTiny[any][h->tiny_one] : &kTrace[any][h->max_stack <= 16 ? 0 : (h->max_stack <= 24 ? 1 : 2)][h->node_mode == kNodesLdsTop],
+		h->ds.trace[any] = TraceLaunch{tiny ? &kTraceTiny[any][h->ds.tiny_one] : &kTrace[any][h->ds.max_stack <= 16 ? 0 : (h->ds.max_stack <= 24 ? 1 : 2)][h->ds.node_mode == kNodesLdsTop],
 		                            tiny ? kTinyBlock : WG, 0, 6};
 }
 
 // The scene's k_trace variant over `chunks` chunks of st on stream q, under `timer` (null: a probe's launch, untimed).  camera: the closest-hit launch of a batch's
 // camera rays -- their common origin comes from the handle's one-record buffer (kernels.h k_trace, o_mask), the origin stream is neither written nor read for them.
 hipError_t launch_trace(polaris_hip_tracer *h, const char *timer, bool any_hit, hipStream_t q, Streams st, uint32_t grid, uint32_t chunks, float4 *acc, bool camera = false) {
-	const TraceLaunch &T = h->trace[any_hit];
+	const TraceLaunch &T = h->ds.trace[any_hit];
 	uint32_t o_mask = ~0u;
 	if (camera && !any_hit) { st.ray_o = h->d_cam_o; o_mask = 0u; }
-	return launch(h, timer, q, *T.v, grid, (uint32_t)T.block, T.lds_bytes, st, h->bvh, chunks, acc, h->d_stats, o_mask);
+	return launch(h, timer, q, *T.v, grid, (uint32_t)T.block, T.lds_bytes, st, h->ds.bvh, chunks, acc, h->d_stats, o_mask);
 }
 
 // Tiny-scene mode: lay out the dynamic LDS block of a k_trace workgroup for the uploaded scene (kernels.h, k_trace) -- the stack
@@ -606,9 +618,9 @@ hipError_t launch_trace(polaris_hip_tracer *h, const char *timer, bool any_hit, 
 int plan_tiny_lds(polaris_hip_tracer *h, size_t n_slots) {
 	// (no dummy row: the bytes in front of the stack serve; a scene that IS one instance is entered at ray set-up without an exit
 	// marker, which the layout's stack need counts)
-	const uint32_t rows = (uint32_t)std::max(1, h->max_stack - (h->bvh.root_is_instance ? 1 : 0));
+	const uint32_t rows = (uint32_t)std::max(1, h->ds.max_stack - (h->ds.bvh.root_is_instance ? 1 : 0));
 	constexpr uint32_t kRowBytes = kTinyBlock * (uint32_t)sizeof(int16_t), kTriBytes = 9 * sizeof(float) + sizeof(uint32_t);
-	const uint32_t nodes = h->bvh.num_pairs * (uint32_t)sizeof(PairNode);
+	const uint32_t nodes = h->ds.bvh.num_pairs * (uint32_t)sizeof(PairNode);
 	hipDeviceProp_t prop;
 	size_t lds_per_cu = 160 * 1024;
 	if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.maxSharedMemoryPerMultiProcessor > 0) lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
@@ -622,11 +634,11 @@ int plan_tiny_lds(polaris_hip_tracer *h, size_t n_slots) {
 	if (tris < n_slots / 2) tris = 0;
 	if (h->opt_lds_tris >= 0) tris = std::min<uint32_t>(tris, (uint32_t)h->opt_lds_tris);
 	for (;;) {
-		h->bvh.tiny_stack_off = stack_off(tris);
-		h->bvh.lds_tris = tris;
-		h->trace[0].lds_bytes = h->trace[1].lds_bytes = h->bvh.tiny_stack_off + rows * kRowBytes;
+		h->ds.bvh.tiny_stack_off = stack_off(tris);
+		h->ds.bvh.lds_tris = tris;
+		h->ds.trace[0].lds_bytes = h->ds.trace[1].lds_bytes = h->ds.bvh.tiny_stack_off + rows * kRowBytes;
 		int worst = 8;
-		for (const TraceLaunch &T : h->trace) {
+		for (const TraceLaunch &T : h->ds.trace) {
 			// (the attribute belongs to the kernel, not to this handle: always the most any scene may ask for, so that handles
 			// with different scenes in one process do not lower it under each other)
 			HIP_TRY(h, hipFuncSetAttribute(T.v->address(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(half - slack)));
@@ -637,16 +649,16 @@ int plan_tiny_lds(polaris_hip_tracer *h, size_t n_slots) {
 		if (worst >= 2 || tris == 0) break;
 		tris = tris > 32 ? tris - 32 : 0; // the allocation granularity was coarser than assumed: give some back
 	}
-	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] tiny mode: %u stack rows at %u, %u pair records, %u of %zu triangle records in LDS (%u bytes per workgroup)\n", rows, h->bvh.tiny_stack_off, h->bvh.num_pairs, h->bvh.lds_tris, n_slots, h->trace[0].lds_bytes);
+	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] tiny mode: %u stack rows at %u, %u pair records, %u of %zu triangle records in LDS (%u bytes per workgroup)\n", rows, h->ds.bvh.tiny_stack_off, h->ds.bvh.num_pairs, h->ds.bvh.lds_tris, n_slots, h->ds.trace[0].lds_bytes);
 	return POLARIS_OK;
 }
 
 // Resident workgroups per CU of the scene's k_trace variant.
 int trace_occupancy(polaris_hip_tracer *h, bool any_hit) {
-	const TraceLaunch &T = h->trace[any_hit];
+	const TraceLaunch &T = h->ds.trace[any_hit];
 	int n = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, T.v->address(), T.block, T.lds_bytes) != hipSuccess || n < 1) n = h->node_mode == kNodesLdsAll ? 1 : (h->max_stack <= 24 ? 6 : 5);
-	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] k_trace<%d> node mode %d: %d resident workgroups of %d threads per CU\n", (int)any_hit, h->node_mode, n, T.block);
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, T.v->address(), T.block, T.lds_bytes) != hipSuccess || n < 1) n = h->ds.node_mode == kNodesLdsAll ? 1 : (h->ds.max_stack <= 24 ? 6 : 5);
+	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] k_trace<%d> node mode %d: %d resident workgroups of %d threads per CU\n", (int)any_hit, h->ds.node_mode, n, T.block);
 	return std::min(n, 8);
 }
 
@@ -669,8 +681,8 @@ const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", 
 // `batch_chunks`: the chunks of one full batch of the Trace (the size of its shade launches).
 void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, uint32_t batch_chunks, BouncePlan *plan) {
 	// LDS-table variant of the shade kernels: only when all three tables fit (kernels.h, stage_scene)
-	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
-	                    h->scene.num_textures <= kLdsTextures;
+	const bool staged = h->opt_stage_lds && h->ds.scene.num_nodes <= kLdsMatNodes && h->ds.scene.num_emissives <= kLdsLights &&
+	                    h->ds.scene.num_textures <= kLdsTextures;
 	// First bounce of k_shade_wave.  The bounce where Russian roulette starts still finds the chunks as the previous bounce left them;
 	// only with the prefilter (shade_fate retires the rays roulette rejects, where some shading class cannot emit: otherwise nothing is
 	// retired) does a chunk of that bounce hold a sixth of its rays, and k_shade still pays a workgroup's latency chain per chunk.
@@ -680,7 +692,7 @@ void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, uin
 	if (wave_from < 0) {
 		wave_from = (int)r->min_bounces_for_rr + 1;
 		const uint64_t groups = ((uint64_t)batch_chunks + kSparseGroup - 1) / kSparseGroup;
-		if (h->opt_shade_prefilter && (h->scene.emit_classes & 0xFFFFu) != 0xFFFFu && groups >= (uint64_t)kWaveRouletteGroupsPerCu * (uint64_t)h->num_cus)
+		if (h->opt_shade_prefilter && (h->ds.scene.emit_classes & 0xFFFFu) != 0xFFFFu && groups >= (uint64_t)kWaveRouletteGroupsPerCu * (uint64_t)h->num_cus)
 			wave_from = (int)r->min_bounces_for_rr;
 	}
 	for (uint32_t b = 0; b < r->num_bounces; b++) {
@@ -690,7 +702,7 @@ void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, uin
 		const bool wave = h->opt_shade_wave && b > 0 && (int)b >= wave_from; // (never the first bounce: k_shade_wave reads the previous step's emit masks)
 		// bounce rays are shaded in the order of their material's shading class (kernels.h, k_shade SORT); camera rays are
 		// coherent as they come (64 neighbouring pixels per wave)
-		const bool sorted = b > 0 && h->scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
+		const bool sorted = b > 0 && h->ds.scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
 		pl.shade_timer = wave ? 3 : (b == 0 ? 0 : (sorted ? 1 : 2));
 		if (wave) pl.shade_wave = &kShadeWave[staged];
 		else pl.shade = &kShade[staged][pl.shade_timer];
@@ -732,22 +744,22 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 		// batches in flight a launch gets half the GPU at best, and at fewer than 4 chunks per resident wave a full-size grid
 		// leaves every wave a single chunk, i.e. nothing but its ramp-down.  One workgroup per CU then: a 64-row block of the
 		// headline frame 2.10 -> 1.83 ms, a 128-row block 3.30 -> 3.13 ms (256 rows +-0, the full frame +1 %: not applied there)
-		if (h->node_mode == kNodesLdsAll && std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes) > 1 && !exact && per_cu == 2 &&
+		if (h->ds.node_mode == kNodesLdsAll && std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes) > 1 && !exact && per_cu == 2 &&
 		    (uint64_t)wgs < 4ull * (uint64_t)h->num_cus * per_cu * (kTinyBlock / 64))
 			per_cu = 1;
 		if (h->opt_trace_wgs_per_cu > 0) per_cu = (uint32_t)h->opt_trace_wgs_per_cu;
 		if (h->opt_trace_grid > 0) return std::min<uint32_t>(wgs, (uint32_t)h->opt_trace_grid); // (A/B aid: an absolute persistent grid)
 		return std::min<uint32_t>(wgs, (uint32_t)h->num_cus * per_cu);
 	};
-	const uint32_t persistent = grid_of(h->trace[0].resident_per_cu), persistent_occl = grid_of(h->trace[1].resident_per_cu);
+	const uint32_t persistent = grid_of(h->ds.trace[0].resident_per_cu), persistent_occl = grid_of(h->ds.trace[1].resident_per_cu);
 	for (uint32_t b = 0; b < B; b++) {
 		const BouncePlan &pl = plan[b];
 		Streams S = P.st; // (in place: k_shade / k_shade_wave read a chunk's rays before they write into it)
 		if (!exact) { S.occ_e = P.nee[b]; S.vis = P.vis[b]; S.cnt_occ = P.cnt_occ_b[b]; } // this bounce's NEE records, visibility bytes and shadow-ray counts stay until k_fold_nee
 		float4 *const occl_acc = exact ? A.acc : nullptr;                // batched: unoccluded rays only mark their record (deferred)
-		if (pl.isect_packet) note(launch(h, "intersect_packet", q, *pl.isect_packet, wgs, WG, 0, S, h->bvh, nullptr, h->d_stats, h->cam.eye));
+		if (pl.isect_packet) note(launch(h, "intersect_packet", q, *pl.isect_packet, wgs, WG, 0, S, h->ds.bvh, nullptr, h->d_stats, h->cam.eye));
 		else if (h->opt_traversal) note(launch_trace(h, "intersect", false, q, S, persistent, wgs, nullptr, b == 0));
-		else note(launch(h, "intersect", q, kIntersect, wgs, WG, 0, S, h->bvh));
+		else note(launch(h, "intersect", q, kIntersect, wgs, WG, 0, S, h->ds.bvh));
 		A.bounce = b;
 		A.last_bounce = (b + 1 == B) ? 1 : 0;
 		A.emask_in = b == 0 ? nullptr : P.st.emask[(b + 1) & 1]; // the masks the previous step wrote
@@ -757,12 +769,12 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 			// the kernel's register count) nor than there are groups for their 4 waves
 			const uint32_t groups = (wgs + kSparseGroup - 1) / kSparseGroup;
 			const uint32_t grid = std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->opt_shade_wgs_per_cu)));
-			note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade_wave, grid, WG, 0, S, h->scene, A, wgs));
-		} else note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade, wgs, WG, 0, S, h->scene, A));
+			note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade_wave, grid, WG, 0, S, h->ds.scene, A, wgs));
+		} else note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade, wgs, WG, 0, S, h->ds.scene, A));
 		note(launch(h, "scan", q, kScan, K, 1024, 0, S, wgs_per_sample, b, A.last_bounce ? 0 : 1, h->d_stats));
-		if (pl.occl_packet) note(launch(h, "occlusion", q, *pl.occl_packet, wgs, WG, 0, S, h->bvh, occl_acc, h->d_stats, h->cam.eye));
+		if (pl.occl_packet) note(launch(h, "occlusion", q, *pl.occl_packet, wgs, WG, 0, S, h->ds.bvh, occl_acc, h->d_stats, h->cam.eye));
 		else if (h->opt_traversal) note(launch_trace(h, "occlusion", true, q, S, persistent_occl, wgs, occl_acc));
-		else note(launch(h, "occlusion", q, kOcclusion, wgs, WG, 0, S, h->bvh, occl_acc, h->d_stats));
+		else note(launch(h, "occlusion", q, kOcclusion, wgs, WG, 0, S, h->ds.bvh, occl_acc, h->d_stats));
 	}
 	if (!exact && B > 0) { // accumulateEmissiveSamples of the whole batch: the marked NEE records of every bounce into the per-path radiance
 		FoldArgs F{};
@@ -778,6 +790,219 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	note(hipEventRecord(P.done, q));
 	note(hipGetLastError()); // (whatever a launch left)
 	return first_err;
+}
+
+// ---- the scene: upload_scene's steps and what the in-place updates share (caller holds mu).  First: nothing of the handle may still run
+int make_idle(polaris_hip_tracer *h) {
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, sync_all(h));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return POLARIS_OK;
+}
+
+// Upload, step 1: the scene re-laid out for the kernels, with the plans the update options ask for.
+int layout_scene(polaris_hip_tracer *h, const PolarisSceneView &sc, SceneLayout &L) {
+	// Defaults by scene size (measured, DESIGN.md 3.1): small scenes live in L2/LDS and are bound by
+	// instruction issue -> small leaves and packet traversal of camera rays pay; scenes far larger than
+	// the caches are bound by node fetches -> fewer, fuller leaves and one ray per lane.
+	const int max_leaf = h->opt_max_leaf_tris >= 0 ? h->opt_max_leaf_tris : (sc.num_triangles <= 32768u ? 2 : 4);
+	std::string err;
+	for (int leaf_tris : {max_leaf, 0}) { // (0: without subdivision, where the deeper tree would not fit the traversal stack)
+		L = SceneLayout();
+		L.want_update_plan = h->opt_instance_update != 0;
+		L.want_mesh_plan = h->opt_vertex_update != 0;
+		err = build_layout(sc, L, leaf_tris);
+		if (err != "@retry-without-subdivision") break;
+	}
+	return err.empty() ? POLARIS_OK : fail(h, POLARIS_E_BAD_SCENE, "%s", err.c_str());
+}
+
+// Upload, step 3: the layout's records and the scene's arrays into h->ds.  geo: the packed light records.  The copies are only queued.
+int upload_arrays(polaris_hip_tracer *h, const PolarisSceneView &sc, const SceneLayout &L, const std::vector<float> &geo) {
+	DeviceScene &S = h->ds;
+	int rc = 0;
+	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
+	rc |= dev_upload(h, S.bufs, &pairs, L.pairs.data(), L.pairs.size());
+	rc |= dev_upload(h, S.bufs, &leaves, L.leaves.data(), L.leaves.size());
+	rc |= dev_upload(h, S.bufs, &tris, L.tris.data(), L.tris.size());
+	rc |= dev_upload(h, S.bufs, &insts, L.insts.data(), L.insts.size());
+	float4 *vertices, *normals; float2 *uvs; uint32_t *mat_index;
+	PolarisMaterialNode *nodes; PolarisEmissive *emissives; PolarisTextureMetadata *tex_meta; uint8_t *tex_data; float *light_geo;
+	const size_t nv = (size_t)sc.num_triangles * 3;
+	rc |= dev_upload(h, S.bufs, &vertices, sc.vertices, nv);
+	rc |= dev_upload(h, S.bufs, &normals, sc.normals, nv);
+	rc |= dev_upload(h, S.bufs, &uvs, sc.uvs, nv);
+	rc |= dev_upload(h, S.bufs, &mat_index, sc.material_index, sc.num_triangles);
+	rc |= dev_upload(h, S.bufs, &nodes, sc.material_nodes, sc.num_material_nodes);
+	rc |= dev_upload(h, S.bufs, &emissives, sc.emissives, sc.num_emissives);
+	rc |= dev_upload(h, S.bufs, &tex_meta, sc.texture_meta, sc.num_textures);
+	rc |= dev_upload(h, S.bufs, &light_geo, geo.data(), geo.size());
+	// the texture blob, padded: texels are fetched as the three dwords at their address whatever the format (shading.h, tex_fetch)
+	rc |= dev_alloc(h, S.bufs, &tex_data, (size_t)sc.texture_data_bytes + 16);
+	if (rc) return rc;
+	if (sc.texture_data_bytes) HIP_TRY(h, hipMemcpyAsync(tex_data, sc.texture_data, sc.texture_data_bytes, hipMemcpyHostToDevice, h->stream));
+	S.bvh = BvhDev{pairs, (uint32_t)L.pairs.size(), leaves, tris, insts, L.root_ref, 0, InstRec{}, 0, 0};
+	if (L.root_ref < 0 && (((uint32_t)~L.root_ref) & 15u) == 0u && !(((uint32_t)~L.root_ref) & kBigLeafFlag)) { // the top-level tree is a single leaf ...
+		const size_t root_inst = ((uint32_t)~L.root_ref) >> 4; // (... which, in the top-level tree, is an instance: its id is in the reference)
+		if (root_inst < L.insts.size()) { // its record goes with the kernel arguments
+			const InstH &I = L.insts[root_inst];
+			S.bvh.root_is_instance = 1;
+			set_root_inst(S.bvh, I);
+			S.bvh.root_inst.meta = make_int4(I.root_ref, (int)I.rank, (int)I.pad[0], 0);
+		}
+	}
+	S.scene = SceneDev{vertices, normals, uvs, mat_index, nodes, emissives, tex_meta, tex_data, sc.num_emissives,
+	                   sc.scene_diffuse_mat_index, sc.num_material_nodes, sc.num_textures, light_geo, sc.num_emissives ? pm_rcp((float)(int)sc.num_emissives) : 0.0f, L.tri_bits, L.emit_classes};
+	S.max_stack = L.max_stack; S.num_insts = (uint32_t)L.insts.size();
+	S.upd.pairs = pairs; S.upd.insts = insts; S.upd.d_emissives = emissives; S.upd.d_light_geo = light_geo; // what the in-place updates write
+	S.vup.vertices = vertices; S.vup.normals = normals; S.vup.tris = tris;
+	return POLARIS_OK;
+}
+
+// Upload, step 4: what the in-place updates keep (options instance_update / vertex_update, else nothing) -- the plans' device copies and
+// their kernels' scratch in the scene's buffers, the host copies (out of L and geo) in h->ds.upd / vup.  Waits for every copy of the upload.
+int keep_update_plans(polaris_hip_tracer *h, const PolarisSceneView &sc, SceneLayout &L, std::vector<float> &geo) {
+	DeviceScene &S = h->ds;
+	InstanceUpdateState &U = S.upd; VertexUpdateState &V = S.vup;
+	const uint32_t NI = sc.num_mesh_instances;
+	int rc = 0;
+	std::vector<uint2> inst_range;
+	if (L.want_update_plan) {
+		const UpdatePlan &P = L.plan;
+		uint32_t longest = 1;
+		inst_range.resize(NI);
+		for (uint32_t i = 0; i < NI; i++) {
+			const uint32_t m = P.mesh_of_inst[i];
+			inst_range[i] = make_uint2(P.tri_first[m], P.tri_first[m + 1] - P.tri_first[m]);
+			longest = std::max(longest, inst_range[i].y);
+		}
+		U.chunks = std::max(1u, std::min(std::min((longest + kExtentChunkTris - 1) / kExtentChunkTris, kExtentMaxChunks), (1u << 22) / NI));
+		U.chunk_tris = (longest + U.chunks - 1) / U.chunks;
+		rc |= dev_upload(h, S.bufs, &U.nodes, P.nodes.data(), P.nodes.size());
+		rc |= dev_upload(h, S.bufs, &U.level_first, P.level_first.data(), P.level_first.size());
+		rc |= dev_upload(h, S.bufs, &U.tri_list, P.tri_list.data(), P.tri_list.size());
+		rc |= dev_upload(h, S.bufs, &U.inst_range, inst_range.data(), inst_range.size());
+		rc |= dev_upload(h, S.bufs, &U.padded, P.padded.data(), P.padded.size());
+		rc |= dev_alloc(h, S.bufs, &U.pads, P.mesh_box.size());
+		rc |= dev_alloc(h, S.bufs, &U.scratch, P.nodes.size());
+		rc |= dev_alloc(h, S.bufs, &U.recs, (size_t)NI);
+		rc |= dev_alloc(h, S.bufs, &U.partial, (size_t)NI * U.chunks * 6);
+	}
+	if (L.want_mesh_plan && L.plan.mesh.on) {
+		const MeshPlan &M = L.plan.mesh;
+		rc |= dev_upload(h, S.bufs, &V.slot_src, M.slot_src.data(), M.slot_src.size());
+		rc |= dev_upload(h, S.bufs, &V.nodes, M.nodes.data(), M.nodes.size());
+		rc |= dev_upload(h, S.bufs, &V.level_first, M.level_first.data(), M.level_first.size());
+		rc |= dev_alloc(h, S.bufs, &V.scratch, 2 * M.nodes.size());
+		rc |= dev_alloc(h, S.bufs, &V.mesh_box, 2 * M.root.size());
+	}
+	if (rc) return rc;
+	HIP_TRY(h, hipStreamSynchronize(h->stream)); // (inst_range dies at return, the plan's vectors move, L and geo go with the caller)
+	if (L.want_mesh_plan) {
+		V.on = true;
+		V.num_triangles = sc.num_triangles;
+		V.num_slots = (uint32_t)L.tris.size();
+		V.inv.resize((size_t)NI * 16);
+		for (uint32_t i = 0; i < NI; i++) memcpy(V.inv.data() + 16 * (size_t)i, sc.mesh_instances[i].inv_transform, 16 * sizeof(float));
+	}
+	if (L.want_update_plan) {
+		U.on = true;
+		U.plan = std::move(L.plan);
+		U.emissives.assign(sc.emissives, sc.emissives + sc.num_emissives);
+		U.light_geo = std::move(geo);
+	}
+	return POLARIS_OK;
+}
+
+// Upload, step 5: how this scene is traversed -- node mode, tiny-scene mode, the k_trace variants with LDS block and residency, packet use.
+int choose_traversal(polaris_hip_tracer *h, const PolarisSceneView &sc, const SceneLayout &L) {
+	DeviceScene &S = h->ds;
+	// camera rays: the wave-packet kernel where a packet stays together AND the tree is small -- one instance, up to 32 K
+	// triangles.  Since the per-ray kernel's instruction diet (DESIGN.md 3.1) the two are level on the tiny scenes (headline 11.37 /
+	// 11.31 / 11.39 ms with packets against 11.42 / 11.32 / 11.38 without, round 4: the packet kernel stays there, it keeps the
+	// origin stream unwritten); on the 58 K-triangle ball the packet's dependent scalar node fetches cost more than the per-ray
+	// kernel's gathers (camera rays 5.5 vs 4.1 ms per 32 spp, frame -1.8 %); in a scene of many instances the packet's lanes part
+	// ways inside the instances (-5 % frame time per-ray on the 1 024-instance scene, -26 % on the 1 M-triangle terrain)
+	// (round 4, later: with the triangle records in LDS the per-ray kernel of the tiny-scene mode is ahead -- camera rays 0.93 vs
+	// 1.20 ms isolated, frame 10.96 vs 11.03 ms, three alternating runs: see below, after the node mode is known)
+	if (h->opt_packet_primary < 0) h->packet_primary = sc.num_triangles <= 32768u && sc.num_mesh_instances == 1;
+	// node records: whole tree in LDS for tiny scenes, its top for small ones, global memory otherwise (kernels.h NodeMode)
+	// (16-bit stack entries: triangle slots and instance ids must fit 11 bits, and no leaf reference may carry kBigLeafFlag)
+	// (... and the packed word of a slot holds the scene triangle in 11 bits too: scene_layout.h tiny_meta_word)
+	const bool tiny_ok = L.pairs.size() <= (size_t)kTinyPairs && L.tris.size() <= kTinyMaxIndex && sc.num_triangles <= kTinyMaxIndex && L.insts.size() <= kTinyMaxIndex &&
+	                     L.big_leaves == 0 && L.max_stack <= 16;
+	S.node_mode = tiny_ok ? kNodesLdsAll : (L.pairs.size() <= (size_t)(POLARIS_LDS_TOP_MAX_PAIRS) ? kNodesLdsTop : kNodesGlobal);
+	if (h->opt_node_mode >= 0 && (h->opt_node_mode != kNodesLdsAll || tiny_ok)) S.node_mode = h->opt_node_mode;
+	S.tiny_one = S.node_mode == kNodesLdsAll && h->opt_tiny_one && S.bvh.root_is_instance && L.unbounded_boxes == 0;
+	select_trace(h);
+	if (S.node_mode == kNodesLdsAll) {
+		if (int rc = plan_tiny_lds(h, L.tris.size())) return rc;
+		if (h->opt_packet_primary < 0 && S.bvh.lds_tris > 0) h->packet_primary = false;
+	}
+	for (int any = 0; any < 2; any++) S.trace[any].resident_per_cu = trace_occupancy(h, any != 0);
+	return POLARIS_OK;
+}
+
+// A refit kernel over the levels of its plan (level_first: the host copy): ONE workgroup looping over them, or a launch per level.
+template <class Kernel, class Args>
+void launch_levels(polaris_hip_tracer *h, const char *timer, hipStream_t q, const Kernel &kernel, const Args &A, const std::vector<uint32_t> &level_first, bool one_group) {
+	const uint32_t levels = (uint32_t)level_first.size() - 1;
+	if (one_group) (void)launch(h, timer, q, kernel, 1, kRefitBlock, 0, A, 0u, levels);
+	else
+		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
+			(void)launch(h, timer, q, kernel, (level_first[l + 1] - level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
+}
+
+// The device part of a vertex update on the main stream: the new arrays, the triangle records and the mesh trees' boxes from them, and
+// the deformed meshes' root boxes back into the plan -- a term of the padding of the boxes leaf subdivision added (subdivision_pad).
+int refit_meshes(polaris_hip_tracer *h, const PolarisVertexUpdate *u) {
+	InstanceUpdateState &U = h->ds.upd; VertexUpdateState &V = h->ds.vup;
+	const MeshPlan &M = U.plan.mesh;
+	hipStream_t q = h->stream;
+	const size_t nv = (size_t)V.num_triangles * 3;
+	HIP_TRY(h, hipMemcpyAsync(V.vertices, u->vertices, nv * sizeof(float4), hipMemcpyHostToDevice, q));
+	if (u->normals) HIP_TRY(h, hipMemcpyAsync(V.normals, u->normals, nv * sizeof(float4), hipMemcpyHostToDevice, q));
+	(void)launch(h, "tri_records", q, kTriRecords, (V.num_slots + kTriRecordBlock - 1) / kTriRecordBlock, kTriRecordBlock, 0, V.vertices, V.slot_src, V.num_slots, V.tris);
+	const MeshRefitArgs A{V.nodes, V.level_first, V.slot_src, V.vertices, V.scratch, U.pairs, U.padded, V.mesh_box};
+	launch_levels(h, "refit_mesh", q, kRefitMesh, A, M.level_first, M.nodes.size() <= kMeshRefitOneGroupNodes);
+	HIP_TRY(h, hipGetLastError());
+	std::vector<float> boxes(8 * M.root.size());
+	HIP_TRY(h, hipMemcpyAsync(boxes.data(), V.mesh_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, q));
+	HIP_TRY(h, hipStreamSynchronize(q));
+	for (size_t m = 0; m < M.root.size(); m++) {
+		memcpy(U.plan.mesh_box[m].min, boxes.data() + 8 * m, 12);
+		memcpy(U.plan.mesh_box[m].max, boxes.data() + 8 * m + 4, 12);
+	}
+	return POLARIS_OK;
+}
+
+// The end the two in-place updates share, on the main stream: the per-instance records, the paddings and -- geo not empty -- the
+// emissives (ems; null: the kept ones) with their packed light records go to the device; then the instance refit; when it is done,
+// the one-instance scene's record in the kernel arguments and the host copies of emissives and light records follow.
+int finish_update(polaris_hip_tracer *h, const std::vector<InstUpdateRec> &recs, const std::vector<float> &pads, const PolarisEmissive *ems, std::vector<float> &geo) {
+	InstanceUpdateState &U = h->ds.upd;
+	hipStream_t q = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
+	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	if (!geo.empty()) {
+		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, ems ? ems : U.emissives.data(), U.emissives.size() * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
+		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
+	}
+	// the world extent of every instance's mesh, the padding of the boxes leaf subdivision added, the top-level refit
+	const UpdatePlan &P = U.plan;
+	const uint32_t NI = h->ds.num_insts;
+	(void)launch(h, "instance_extent", q, kInstanceExtent, dim3(U.chunks, std::min(NI, 65535u)), kExtentBlock, 0, h->ds.scene.vertices, U.tri_list, U.inst_range, U.recs, NI, U.chunk_tris, U.partial);
+	if (!P.padded.empty())
+		(void)launch(h, "repad", q, kRepad, ((uint32_t)P.padded.size() + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, U.padded, (uint32_t)P.padded.size(), U.pads, U.pairs);
+	const RefitArgs A{U.nodes, U.level_first, U.scratch, U.pairs, U.insts, U.recs, U.partial, U.chunks};
+	launch_levels(h, "refit_top", q, kRefitTop, A, P.level_first, P.nodes.size() <= kRefitOneGroupNodes);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(q)); // (the arguments may go at return)
+	collect_timers(h);
+	if (h->ds.bvh.root_is_instance) set_root_inst(h->ds.bvh, recs[((uint32_t)~h->ds.bvh.root_ref) >> 4]);
+	if (ems) U.emissives.assign(ems, ems + U.emissives.size());
+	if (!geo.empty()) U.light_geo = std::move(geo);
+	return POLARIS_OK;
 }
 
 } // namespace
@@ -942,363 +1167,101 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!sc) return fail(h, POLARIS_E_BAD_ARGUMENT, "scene view is null");
 	SceneLayout L;
-	L.want_update_plan = h->opt_instance_update != 0;
-	L.want_mesh_plan = h->opt_vertex_update != 0;
-	// Defaults by scene size (measured, DESIGN.md 3.1): small scenes live in L2/LDS and are bound by
-	// instruction issue -> small leaves and packet traversal of camera rays pay; scenes far larger than
-	// the caches are bound by node fetches -> fewer, fuller leaves and one ray per lane.
-	const int max_leaf = h->opt_max_leaf_tris >= 0 ? h->opt_max_leaf_tris : (sc->num_triangles <= 32768u ? 2 : 4);
-	std::string err = build_layout(*sc, L, max_leaf);
-	if (err == "@retry-without-subdivision") { // the deeper tree would not fit the traversal stack
-		L = SceneLayout();
-		L.want_update_plan = h->opt_instance_update != 0;
-		L.want_mesh_plan = h->opt_vertex_update != 0;
-		err = build_layout(*sc, L, 0);
+	if (int rc = layout_scene(h, *sc, L)) return rc; // 1. the layout: a refused scene changes nothing, the old one stays
+	if (int rc = make_idle(h)) return rc;
+	h->ds = DeviceScene(); // the old scene goes before the new one is allocated: a large one may not fit twice
+	// 2. the history, judged by the instance table of the scene to come (kept with object motion only)
+	polaris_hip_tracer::InstTable next;
+	if (h->opt_object_motion) {
+		next.num_triangles = sc->num_triangles;
+		next.topology_known = true;
+		next.mesh_index.resize(sc->num_mesh_instances);
+		next.inv.resize((size_t)sc->num_mesh_instances * 16);
+		for (uint32_t i = 0; i < sc->num_mesh_instances; i++) {
+			next.mesh_index[i] = sc->mesh_instances[i].mesh_index;
+			memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
+		}
 	}
-	if (!err.empty()) return fail(h, POLARIS_E_BAD_SCENE, "%s", err.c_str());
-	HIP_TRY(h, hipSetDevice(h->device));
-	HIP_TRY(h, sync_all(h));
-	h->scene_bufs.clear();
-	h->upd = polaris_hip_tracer::InstanceUpdateState();
-	h->vup = polaris_hip_tracer::VertexUpdateState();
-	h->have_scene = false;
-	h->gb_valid = false;
-	{
-		// With object motion the upload is to the history what a camera move is: the planes synced under the old scene join it, and it
-		// survives if the new scene has the same instances of the same meshes (temporal.h: k_reproject carries a hit back through the
-		// two tables).  Otherwise the history saw the old scene and goes.
-		bool keep = false;
-		polaris_hip_tracer::InstTable next;
-		if (h->opt_object_motion) {
-			next.num_triangles = sc->num_triangles;
-			next.topology_known = true;
-			next.mesh_index.resize(sc->num_mesh_instances);
-			next.inv.resize((size_t)sc->num_mesh_instances * 16);
-			for (uint32_t i = 0; i < sc->num_mesh_instances; i++) {
-				next.mesh_index[i] = sc->mesh_instances[i].mesh_index;
-				memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
-			}
-		}
-		if (motion_on(h)) {
-			capture_history(h);
-			keep = h->tp_have_hist && h->mo_hist.compatible(next);
-		}
-		if (h->tp.max_history) {
-			if (!keep) h->tp_have_hist = h->va_have_hist = false;
-			h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
-		}
-		h->mo_cur = std::move(next);
-	}
-	int rc = 0;
-	PairNode *pairs; int2 *leaves; TriRec *tris; InstRec *insts;
-	rc |= dev_upload(h, h->scene_bufs, &pairs, L.pairs.data(), L.pairs.size());
-	rc |= dev_upload(h, h->scene_bufs, &leaves, L.leaves.data(), L.leaves.size());
-	rc |= dev_upload(h, h->scene_bufs, &tris, L.tris.data(), L.tris.size());
-	rc |= dev_upload(h, h->scene_bufs, &insts, L.insts.data(), L.insts.size());
-	float4 *vertices, *normals; float2 *uvs; uint32_t *mat_index;
-	PolarisMaterialNode *nodes; PolarisEmissive *emissives; PolarisTextureMetadata *tex_meta; uint8_t *tex_data; float *light_geo;
-	// the triangle of every area light, packed (shading.h, SceneT::light_geo; indices were range-checked by build_layout)
+	scene_changed(h, &next);
+	// 3. the arrays, with the triangle of every area light packed (shading.h, SceneT::light_geo); 4. what the updates keep
 	std::vector<float> geo((size_t)sc->num_emissives * kLightGeoFloats, 0.0f);
-	for (uint32_t e = 0; e < sc->num_emissives; e++) {
-		if (sc->emissives[e].type != POLARIS_EMISSIVE_AREA) continue;
-		const size_t off = (size_t)sc->emissives[e].tri_index * 3;
-		float *g = geo.data() + (size_t)e * kLightGeoFloats;
-		for (int v = 0; v < 3; v++) {
-			for (int k = 0; k < 3; k++) { g[4 * v + k] = sc->vertices[4 * (off + v) + k]; g[12 + 4 * v + k] = sc->normals[4 * (off + v) + k]; }
-			g[24 + 2 * v] = sc->uvs[2 * (off + v)]; g[25 + 2 * v] = sc->uvs[2 * (off + v) + 1];
-		}
-		derive_light_geo(sc->emissives[e], g);
-	}
-	const size_t nv = (size_t)sc->num_triangles * 3;
-	rc |= dev_upload(h, h->scene_bufs, &vertices, sc->vertices, nv);
-	rc |= dev_upload(h, h->scene_bufs, &normals, sc->normals, nv);
-	rc |= dev_upload(h, h->scene_bufs, &uvs, sc->uvs, nv);
-	rc |= dev_upload(h, h->scene_bufs, &mat_index, sc->material_index, sc->num_triangles);
-	rc |= dev_upload(h, h->scene_bufs, &nodes, sc->material_nodes, sc->num_material_nodes);
-	rc |= dev_upload(h, h->scene_bufs, &emissives, sc->emissives, sc->num_emissives);
-	rc |= dev_upload(h, h->scene_bufs, &tex_meta, sc->texture_meta, sc->num_textures);
-	rc |= dev_upload(h, h->scene_bufs, &light_geo, geo.data(), geo.size());
-	// the texture blob, padded: texels are fetched as the three dwords at their address whatever the format (shading.h, tex_fetch)
-	rc |= dev_alloc(h, h->scene_bufs, &tex_data, (size_t)sc->texture_data_bytes + 16);
-	polaris_hip_tracer::InstanceUpdateState U;
-	std::vector<uint2> inst_range;
-	if (L.want_update_plan) { // the update plan's device copies and the scratch of its kernels (instance_update.h)
-		const UpdatePlan &P = L.plan;
-		const uint32_t NI = sc->num_mesh_instances;
-		uint32_t longest = 1;
-		inst_range.resize(NI);
-		for (uint32_t i = 0; i < NI; i++) {
-			const uint32_t m = P.mesh_of_inst[i];
-			inst_range[i] = make_uint2(P.tri_first[m], P.tri_first[m + 1] - P.tri_first[m]);
-			longest = std::max(longest, inst_range[i].y);
-		}
-		U.chunks = std::max(1u, std::min(std::min((longest + kExtentChunkTris - 1) / kExtentChunkTris, kExtentMaxChunks), (1u << 22) / NI));
-		U.chunk_tris = (longest + U.chunks - 1) / U.chunks;
-		rc |= dev_upload(h, h->scene_bufs, &U.nodes, P.nodes.data(), P.nodes.size());
-		rc |= dev_upload(h, h->scene_bufs, &U.level_first, P.level_first.data(), P.level_first.size());
-		rc |= dev_upload(h, h->scene_bufs, &U.tri_list, P.tri_list.data(), P.tri_list.size());
-		rc |= dev_upload(h, h->scene_bufs, &U.inst_range, inst_range.data(), inst_range.size());
-		rc |= dev_upload(h, h->scene_bufs, &U.padded, P.padded.data(), P.padded.size());
-		rc |= dev_alloc(h, h->scene_bufs, &U.pads, P.mesh_box.size());
-		rc |= dev_alloc(h, h->scene_bufs, &U.scratch, P.nodes.size());
-		rc |= dev_alloc(h, h->scene_bufs, &U.recs, (size_t)NI);
-		rc |= dev_alloc(h, h->scene_bufs, &U.partial, (size_t)NI * U.chunks * 6);
-	}
-	polaris_hip_tracer::VertexUpdateState V;
-	if (L.want_mesh_plan && L.plan.mesh.on) { // the mesh plan's device copies and the scratch of its kernel (vertex_update.h)
-		const MeshPlan &M = L.plan.mesh;
-		rc |= dev_upload(h, h->scene_bufs, &V.slot_src, M.slot_src.data(), M.slot_src.size());
-		rc |= dev_upload(h, h->scene_bufs, &V.nodes, M.nodes.data(), M.nodes.size());
-		rc |= dev_upload(h, h->scene_bufs, &V.level_first, M.level_first.data(), M.level_first.size());
-		rc |= dev_alloc(h, h->scene_bufs, &V.scratch, 2 * M.nodes.size());
-		rc |= dev_alloc(h, h->scene_bufs, &V.mesh_box, 2 * M.root.size());
-	}
-	if (!rc && sc->texture_data_bytes) HIP_TRY(h, hipMemcpyAsync(tex_data, sc->texture_data, sc->texture_data_bytes, hipMemcpyHostToDevice, h->stream));
-	if (rc) { h->scene_bufs.clear(); return rc; }
-	HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors in L die at return
-	h->bvh = BvhDev{pairs, (uint32_t)L.pairs.size(), leaves, tris, insts, L.root_ref, 0, InstRec{}, 0, 0};
-	if (L.root_ref < 0 && (((uint32_t)~L.root_ref) & 15u) == 0u && !(((uint32_t)~L.root_ref) & kBigLeafFlag)) { // the top-level tree is a single leaf ...
-		const size_t root_inst = ((uint32_t)~L.root_ref) >> 4; // (... which, in the top-level tree, is an instance: its id is in the reference)
-		if (root_inst < L.insts.size()) { // its record goes with the kernel arguments
-			const InstH &I = L.insts[root_inst];
-			h->bvh.root_is_instance = 1;
-			h->bvh.root_inst.r0 = make_float4(I.r0[0], I.r0[1], I.r0[2], I.r0[3]);
-			h->bvh.root_inst.r1 = make_float4(I.r1[0], I.r1[1], I.r1[2], I.r1[3]);
-			h->bvh.root_inst.r2 = make_float4(I.r2[0], I.r2[1], I.r2[2], I.r2[3]);
-			h->bvh.root_inst.meta = make_int4(I.root_ref, (int)I.rank, (int)I.pad[0], 0);
-		}
-	}
-	h->scene = SceneDev{vertices, normals, uvs, mat_index, nodes, emissives, tex_meta, tex_data, sc->num_emissives,
-	                    sc->scene_diffuse_mat_index, sc->num_material_nodes, sc->num_textures, light_geo, sc->num_emissives ? pm_rcp((float)(int)sc->num_emissives) : 0.0f, L.tri_bits, L.emit_classes};
-	if (L.want_update_plan) {
-		U.on = true;
-		U.pairs = pairs; U.insts = insts; U.d_emissives = emissives; U.d_light_geo = light_geo;
-		U.plan = std::move(L.plan);
-		U.emissives.assign(sc->emissives, sc->emissives + sc->num_emissives);
-		U.light_geo = std::move(geo);
-		h->upd = std::move(U);
-	}
-	if (L.want_mesh_plan) {
-		V.on = true;
-		V.vertices = vertices; V.normals = normals; V.tris = tris;
-		V.num_triangles = sc->num_triangles;
-		V.num_slots = (uint32_t)L.tris.size();
-		V.inv.resize((size_t)sc->num_mesh_instances * 16);
-		for (uint32_t i = 0; i < sc->num_mesh_instances; i++) memcpy(V.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
-		h->vup = std::move(V);
-	}
-	h->max_stack = L.max_stack;
-	h->num_insts = (uint32_t)L.insts.size();
-	h->tex_bytes = sc->texture_data_bytes;
-	// camera rays: the wave-packet kernel where a packet stays together AND the tree is small -- one instance, up to 32 K
-	// triangles.  Since the per-ray kernel's instruction diet (DESIGN.md 3.1) the two are level on the tiny scenes (headline 11.37 /
-	// 11.31 / 11.39 ms with packets against 11.42 / 11.32 / 11.38 without, round 4: the packet kernel stays there, it keeps the
-	// origin stream unwritten); on the 58 K-triangle ball the packet's dependent scalar node fetches cost more than the per-ray
-	// kernel's gathers (camera rays 5.5 vs 4.1 ms per 32 spp, frame -1.8 %); in a scene of many instances the packet's lanes part
-	// ways inside the instances (-5 % frame time per-ray on the 1 024-instance scene, -26 % on the 1 M-triangle terrain)
-	// (round 4, later: with the triangle records in LDS the per-ray kernel of the tiny-scene mode is ahead -- camera rays 0.93 vs
-	// 1.20 ms isolated, frame 10.96 vs 11.03 ms, three alternating runs: see below, after the node mode is known)
-	if (h->opt_packet_primary < 0) h->packet_primary = sc->num_triangles <= 32768u && sc->num_mesh_instances == 1;
-	// node records: whole tree in LDS for tiny scenes, its top for small ones, global memory otherwise (kernels.h NodeMode)
-	// (16-bit stack entries: triangle slots and instance ids must fit 11 bits, and no leaf reference may carry kBigLeafFlag)
-	// (... and the packed word of a slot holds the scene triangle in 11 bits too: scene_layout.h tiny_meta_word)
-	const bool tiny_ok = L.pairs.size() <= (size_t)kTinyPairs && L.tris.size() <= kTinyMaxIndex && sc->num_triangles <= kTinyMaxIndex && L.insts.size() <= kTinyMaxIndex &&
-	                     L.big_leaves == 0 && L.max_stack <= 16;
-	h->node_mode = tiny_ok ? kNodesLdsAll : (L.pairs.size() <= (size_t)(POLARIS_LDS_TOP_MAX_PAIRS) ? kNodesLdsTop : kNodesGlobal);
-	if (h->opt_node_mode >= 0 && (h->opt_node_mode != kNodesLdsAll || tiny_ok)) h->node_mode = h->opt_node_mode;
-	h->tiny_one = h->node_mode == kNodesLdsAll && h->opt_tiny_one && h->bvh.root_is_instance && L.unbounded_boxes == 0;
-	select_trace(h);
-	if (h->node_mode == kNodesLdsAll) {
-		if (int prc = plan_tiny_lds(h, L.tris.size())) return prc;
-		if (h->opt_packet_primary < 0 && h->bvh.lds_tris > 0) h->packet_primary = false;
-	}
-	h->trace[0].resident_per_cu = trace_occupancy(h, false);
-	h->trace[1].resident_per_cu = trace_occupancy(h, true);
-	h->have_scene = true;
-	return POLARIS_OK;
-}
-
-// The three launches of an instance update on stream q: the world extent of every instance's mesh, the padding of the boxes leaf
-// subdivision added, the top-level refit.  The per-instance records and the paddings are on the device (U.recs, U.pads); errors are
-// left for hipGetLastError.  update_instances and update_vertices share it.
-void launch_instance_refit(polaris_hip_tracer *h, hipStream_t q) {
-	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
-	const UpdatePlan &P = U.plan;
-	const uint32_t NI = h->num_insts;
-	(void)launch(h, "instance_extent", q, kInstanceExtent, dim3(U.chunks, std::min(NI, 65535u)), kExtentBlock, 0, h->scene.vertices, U.tri_list, U.inst_range, U.recs, NI,
-	             U.chunk_tris, U.partial);
-	if (!P.padded.empty())
-		(void)launch(h, "repad", q, kRepad, ((uint32_t)P.padded.size() + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, U.padded, (uint32_t)P.padded.size(), U.pads, U.pairs);
-	const RefitArgs A{U.nodes, U.level_first, U.scratch, U.pairs, U.insts, U.recs, U.partial, U.chunks};
-	const uint32_t levels = (uint32_t)P.level_first.size() - 1;
-	if (P.nodes.size() <= kRefitOneGroupNodes) (void)launch(h, "refit_top", q, kRefitTop, 1, kRefitBlock, 0, A, 0u, levels);
-	else
-		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
-			(void)launch(h, "refit_top", q, kRefitTop, (P.level_first[l + 1] - P.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
+	pack_light_geo(sc->emissives, sc->num_emissives, sc->vertices, sc->normals, sc->uvs, geo.data());
+	int rc = upload_arrays(h, *sc, L, geo);
+	if (!rc) rc = keep_update_plans(h, *sc, L, geo);
+	if (!rc) rc = choose_traversal(h, *sc, L); // 5. how it is traversed
+	if (rc) h->ds = DeviceScene(); // a failed upload leaves no scene, and no pointer to one
+	else h->ds.have_scene = true;
+	return rc;
 }
 
 // Move the uploaded scene's mesh instances in place (include/polaris_hip.h; instance_update.h has the arithmetic).
 int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpdate *u) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
+	InstanceUpdateState &U = h->ds.upd;
 	std::string msg;
-	if (int st = check_instance_update(u, h->have_scene, U.on, h->num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
-	const uint32_t NI = h->num_insts;
-	std::vector<InstUpdateRec> recs;
-	std::vector<float> pads;
+	if (int st = check_instance_update(u, h->ds.have_scene, U.on, h->ds.num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
+	const uint32_t NI = h->ds.num_insts;
+	std::vector<InstUpdateRec> recs; std::vector<float> pads, geo;
 	if (int st = prepare_instance_update(U.plan, NI, u->inv_transforms, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str());
-	std::vector<float> geo;
 	if (u->emissives) { // the floats of the packed light records that depend on transform and area
 		geo = U.light_geo;
 		for (uint32_t e = 0; e < u->num_emissives; e++)
 			if (u->emissives[e].type == POLARIS_EMISSIVE_AREA) derive_light_geo(u->emissives[e], geo.data() + (size_t)e * kLightGeoFloats);
 	}
 	// ---- accepted: from here on the state changes ----
-	HIP_TRY(h, hipSetDevice(h->device));
-	HIP_TRY(h, sync_all(h));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->gb_valid = false;
-	{
-		// to the temporal history the update is what an upload_scene is (see there): with object motion the planes synced under the old
-		// matrices join the history, which stays -- instances and meshes are the same; without, the history saw the old scene and goes
-		bool keep = false;
-		polaris_hip_tracer::InstTable next = h->mo_cur;
-		if (h->opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
-		if (motion_on(h)) {
-			capture_history(h);
-			keep = h->tp_have_hist && h->mo_hist.compatible(next);
-		}
-		if (h->tp.max_history) {
-			if (!keep) h->tp_have_hist = h->va_have_hist = false;
-			h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
-		}
-		h->mo_cur = std::move(next);
-	}
-	if (h->vup.on) h->vup.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
-	hipStream_t q = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
-	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
-	if (u->emissives && u->num_emissives) {
-		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, u->emissives, (size_t)u->num_emissives * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
-		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
-	}
-	launch_instance_refit(h, q);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipStreamSynchronize(q)); // (recs, pads and geo die at return)
-	collect_timers(h);
-	if (h->bvh.root_is_instance) { // the one instance's record travels in the kernel arguments
-		const InstUpdateRec &R = recs[((uint32_t)~h->bvh.root_ref) >> 4];
-		h->bvh.root_inst.r0 = make_float4(R.r0[0], R.r0[1], R.r0[2], R.r0[3]);
-		h->bvh.root_inst.r1 = make_float4(R.r1[0], R.r1[1], R.r1[2], R.r1[3]);
-		h->bvh.root_inst.r2 = make_float4(R.r2[0], R.r2[1], R.r2[2], R.r2[3]);
-	}
-	if (u->emissives) {
-		U.emissives.assign(u->emissives, u->emissives + u->num_emissives);
-		U.light_geo = std::move(geo);
-	}
-	return POLARIS_OK;
+	if (int rc = make_idle(h)) return rc;
+	// to the temporal history the update is what an upload is: with object motion the planes synced under the old matrices join the
+	// history, which stays -- instances and meshes are the same; without, the history saw the old scene and goes
+	polaris_hip_tracer::InstTable next = h->mo_cur;
+	if (h->opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
+	scene_changed(h, &next);
+	if (h->ds.vup.on) h->ds.vup.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
+	return finish_update(h, recs, pads, u->emissives, geo);
 }
 
 // Deform the uploaded scene's meshes in place (include/polaris_hip.h; vertex_update.h has the arithmetic).
 int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate *u) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	polaris_hip_tracer::InstanceUpdateState &U = h->upd;
-	polaris_hip_tracer::VertexUpdateState &V = h->vup;
+	InstanceUpdateState &U = h->ds.upd; VertexUpdateState &V = h->ds.vup;
 	std::string msg;
-	if (int st = check_vertex_update(u, h->have_scene, V.on, U.plan.mesh, V.num_triangles, h->num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
-	const uint32_t NI = h->num_insts, NT = V.num_triangles;
-	if (int st = check_vertex_magnitudes(u->vertices, NT, msg)) return fail(h, st, "%s", msg.c_str());
+	if (int st = check_vertex_update(u, h->ds.have_scene, V.on, U.plan.mesh, V.num_triangles, h->ds.num_insts, U.emissives, msg)) return fail(h, st, "%s", msg.c_str());
+	const uint32_t NI = h->ds.num_insts;
+	if (int st = check_vertex_magnitudes(u->vertices, V.num_triangles, msg)) return fail(h, st, "%s", msg.c_str());
 	const float *inv = u->inv_transforms ? u->inv_transforms : V.inv.data();
-	std::vector<InstUpdateRec> recs;
-	std::vector<float> pads;
+	std::vector<InstUpdateRec> recs; std::vector<float> pads;
 	// (matrices and boxes are judged now; the records and paddings are made again below, once the deformed meshes' boxes are known)
 	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str());
-	// the packed light records: the triangle of every area light from the new arrays, then what derives from transform and area
-	const PolarisEmissive *ems = u->emissives ? u->emissives : U.emissives.data();
+	// the packed light records: the triangle of every area light from the new arrays (the uvs stay), then what derives from transform and area
 	std::vector<float> geo = U.light_geo;
-	for (size_t e = 0; e < U.emissives.size(); e++) {
-		if (ems[e].type != POLARIS_EMISSIVE_AREA) continue;
-		const size_t off = (size_t)ems[e].tri_index * 3;
-		float *g = geo.data() + e * kLightGeoFloats;
-		for (int v = 0; v < 3; v++)
-			for (int k = 0; k < 3; k++) {
-				g[4 * v + k] = u->vertices[4 * (off + v) + k];
-				if (u->normals) g[12 + 4 * v + k] = u->normals[4 * (off + v) + k];
-			}
-		derive_light_geo(ems[e], g);
-	}
+	pack_light_geo(u->emissives ? u->emissives : U.emissives.data(), U.emissives.size(), u->vertices, u->normals, nullptr, geo.data());
 	// ---- accepted: from here on the state changes ----
-	HIP_TRY(h, hipSetDevice(h->device));
-	HIP_TRY(h, sync_all(h));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->have_scene = false; // (a failing call below leaves the scene as a failed upload does)
-	h->gb_valid = false;
-	if (h->tp.max_history) { // the history never saw this scene
-		h->tp_have_hist = h->va_have_hist = false;
-		h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
-	}
+	if (int rc = make_idle(h)) return rc;
+	h->ds.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
+	scene_changed(h, nullptr); // the history never saw this scene
 	if (h->opt_object_motion && u->inv_transforms && h->mo_cur.inv.size() == (size_t)NI * 16) h->mo_cur.inv.assign(inv, inv + (size_t)NI * 16);
-	hipStream_t q = h->stream;
-	UpdatePlan &P = U.plan;
-	const MeshPlan &M = P.mesh;
-	const size_t nv = (size_t)NT * 3;
-	HIP_TRY(h, hipMemcpyAsync(V.vertices, u->vertices, nv * sizeof(float4), hipMemcpyHostToDevice, q));
-	if (u->normals) HIP_TRY(h, hipMemcpyAsync(V.normals, u->normals, nv * sizeof(float4), hipMemcpyHostToDevice, q));
-	(void)launch(h, "tri_records", q, kTriRecords, (V.num_slots + kTriRecordBlock - 1) / kTriRecordBlock, kTriRecordBlock, 0, V.vertices, V.slot_src, V.num_slots, V.tris);
-	const MeshRefitArgs A{V.nodes, V.level_first, V.slot_src, V.vertices, V.scratch, U.pairs, U.padded, V.mesh_box};
-	const uint32_t levels = (uint32_t)M.level_first.size() - 1;
-	if (M.nodes.size() <= kMeshRefitOneGroupNodes) (void)launch(h, "refit_mesh", q, kRefitMesh, 1, kRefitBlock, 0, A, 0u, levels);
-	else
-		for (uint32_t l = 0; l < levels; l++) // (at most kTraversalStack + 1 levels: build_layout refuses a deeper tree)
-			(void)launch(h, "refit_mesh", q, kRefitMesh, (M.level_first[l + 1] - M.level_first[l] + kRefitBlock - 1) / kRefitBlock, kRefitBlock, 0, A, l, 1u);
-	HIP_TRY(h, hipGetLastError());
-	// the deformed meshes' root boxes come back: a term of the padding of the boxes leaf subdivision added (subdivision_pad)
-	std::vector<float> boxes(8 * M.root.size());
-	HIP_TRY(h, hipMemcpyAsync(boxes.data(), V.mesh_box, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, q));
-	HIP_TRY(h, hipStreamSynchronize(q));
-	for (size_t m = 0; m < M.root.size(); m++) {
-		memcpy(P.mesh_box[m].min, boxes.data() + 8 * m, 12);
-		memcpy(P.mesh_box[m].max, boxes.data() + 8 * m + 4, 12);
-	}
-	if (int st = prepare_instance_update(P, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
-	HIP_TRY(h, hipMemcpyAsync(U.recs, recs.data(), recs.size() * sizeof(InstUpdateRec), hipMemcpyHostToDevice, q));
-	if (!pads.empty()) HIP_TRY(h, hipMemcpyAsync(U.pads, pads.data(), pads.size() * sizeof(float), hipMemcpyHostToDevice, q));
-	if (!U.emissives.empty()) {
-		HIP_TRY(h, hipMemcpyAsync(U.d_emissives, ems, U.emissives.size() * sizeof(PolarisEmissive), hipMemcpyHostToDevice, q));
-		HIP_TRY(h, hipMemcpyAsync(U.d_light_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, q));
-	}
-	launch_instance_refit(h, q);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipStreamSynchronize(q)); // (recs, pads and geo die at return)
-	collect_timers(h);
-	if (h->bvh.root_is_instance) { // the one instance's record travels in the kernel arguments
-		const InstUpdateRec &R = recs[((uint32_t)~h->bvh.root_ref) >> 4];
-		h->bvh.root_inst.r0 = make_float4(R.r0[0], R.r0[1], R.r0[2], R.r0[3]);
-		h->bvh.root_inst.r1 = make_float4(R.r1[0], R.r1[1], R.r1[2], R.r1[3]);
-		h->bvh.root_inst.r2 = make_float4(R.r2[0], R.r2[1], R.r2[2], R.r2[3]);
-	}
+	if (int rc = refit_meshes(h, u)) return rc;
+	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
+	if (int rc = finish_update(h, recs, pads, u->emissives, geo)) return rc;
 	if (u->inv_transforms) V.inv.assign(inv, inv + (size_t)NI * 16);
-	if (u->emissives) U.emissives.assign(u->emissives, u->emissives + u->num_emissives);
-	U.light_geo = std::move(geo);
-	h->have_scene = true;
+	h->ds.have_scene = true;
 	return POLARIS_OK;
 }
 
 int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, size_t n_bytes) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (which != POLARIS_REC_PAIRS && which != POLARIS_REC_INSTS && which != POLARIS_REC_COUNTS) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: unknown record kind %d", which);
-	uint64_t counts[4] = {h->bvh.num_pairs, h->num_insts, h->scene_bufs.size(), 0};
-	for (const DevArray<char> &b : h->scene_bufs) counts[3] += b.capacity();
+	uint64_t counts[4] = {h->ds.bvh.num_pairs, h->ds.num_insts, h->ds.bufs.size(), 0};
+	for (const DevArray<char> &b : h->ds.bufs) counts[3] += b.capacity();
 	const size_t need = which == POLARIS_REC_COUNTS ? sizeof counts : (size_t)counts[which] * 64;
 	if (!out || n_bytes < need) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: need %zu bytes", need);
 	if (which == POLARIS_REC_COUNTS) { memcpy(out, counts, sizeof counts); return POLARIS_OK; }
 	HIP_TRY(h, hipSetDevice(h->device));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	HIP_TRY(h, hipMemcpy(out, which == POLARIS_REC_PAIRS ? (const void *)h->bvh.pairs : (const void *)h->bvh.insts, need, hipMemcpyDeviceToHost));
+	HIP_TRY(h, hipMemcpy(out, which == POLARIS_REC_PAIRS ? (const void *)h->ds.bvh.pairs : (const void *)h->ds.bvh.insts, need, hipMemcpyDeviceToHost));
 	return POLARIS_OK;
 }
 
@@ -1308,7 +1271,7 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
 	if (h->tp.max_history) {
 		capture_history(h); // the last temporal sync's planes under the old camera become the history
-		h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false;
+		forget_syncs(h);
 	}
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
 	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
@@ -1365,16 +1328,16 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 			h->gb_valid = false;
 			h->mo_hist = polaris_hip_tracer::InstTable();
 			h->mo_cur = polaris_hip_tracer::InstTable(); // (kept with the option on only)
-			if (value && h->have_scene) {
+			if (value && h->ds.have_scene) {
 				// the scene was uploaded with the option off: its matrices come back from the device's instance records (rows 0-2 of
 				// inv_transform, all the traversal and the motion table use); the mesh indices do not (InstTable::topology_known)
-				std::vector<InstH> recs(h->num_insts);
+				std::vector<InstH> recs(h->ds.num_insts);
 				HIP_TRY(h, hipSetDevice(h->device));
 				HIP_TRY(h, hipStreamSynchronize(h->stream));
-				HIP_TRY(h, hipMemcpy(recs.data(), h->bvh.insts, recs.size() * sizeof(InstH), hipMemcpyDeviceToHost));
-				h->mo_cur.mesh_index.assign(h->num_insts, 0u);
-				h->mo_cur.inv.assign((size_t)h->num_insts * 16, 0.0f);
-				for (uint32_t i = 0; i < h->num_insts; i++) {
+				HIP_TRY(h, hipMemcpy(recs.data(), h->ds.bvh.insts, recs.size() * sizeof(InstH), hipMemcpyDeviceToHost));
+				h->mo_cur.mesh_index.assign(h->ds.num_insts, 0u);
+				h->mo_cur.inv.assign((size_t)h->ds.num_insts * 16, 0.0f);
+				for (uint32_t i = 0; i < h->ds.num_insts; i++) {
 					float *m = h->mo_cur.inv.data() + 16 * (size_t)i; // column major: m[4 * c + r]
 					for (int c = 0; c < 4; c++) { m[4 * c + 0] = recs[i].r0[c]; m[4 * c + 1] = recs[i].r1[c]; m[4 * c + 2] = recs[i].r2[c]; }
 					m[15] = 1.0f;
@@ -1413,7 +1376,7 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 		void now() { if (due && !done) { done = true; { std::lock_guard<std::mutex> lk(h->merge_mu); h->reset_epoch++; } h->reset_cv.notify_all(); } }
 		~ResetAnnounce() { now(); }
 	} announce{h, r && r->accumulated_samples == 0};
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // ErrNoSceneData, tracer.go:203-205
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // ErrNoSceneData, tracer.go:203-205
 	if (int rc = check_request(h, r)) return rc;
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set (UpdateState CameraData)");
 	const uint32_t B = r->num_bounces, spp = r->samples_per_pixel;
@@ -2168,7 +2131,7 @@ int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_
 		if (!h->va_valid || !h->tp.max_history || !h->tp_prior2) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no variance sync with temporal reuse under the current camera");
 		src = h->tp_prior2;
 	} else {
-		if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+		if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
 		if (int rc = ensure_gbuffer(h)) return rc;
 		src = which == POLARIS_AOV_GUIDE ? h->gb_guide : h->gb_albedo;
@@ -2182,7 +2145,7 @@ int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_
 int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // tracer.go:254-256
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // tracer.go:254-256
 	if (int rc = check_request(h, r)) return rc;
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
@@ -2226,7 +2189,7 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
                             float *wuvt, int32_t *tri) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (int rc = check_request(h, r)) return rc;
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set");
 	const uint32_t N = h->W * r->block_h, Npad = (N + WG - 1) / WG * WG;
@@ -2243,8 +2206,8 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
 	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
-	if (h->packet_primary) kPacket[kPacketClosest].enqueue(Npad / WG, WG, 0, q, st0, h->bvh, nullptr, h->d_stats, h->cam.eye);
-	else kIntersect.enqueue(Npad / WG, WG, 0, q, st0, h->bvh);
+	if (h->packet_primary) kPacket[kPacketClosest].enqueue(Npad / WG, WG, 0, q, st0, h->ds.bvh, nullptr, h->d_stats, h->cam.eye);
+	else kIntersect.enqueue(Npad / WG, WG, 0, q, st0, h->ds.bvh);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipMemcpyAsync(rd.data(), st0.ray_d, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2262,7 +2225,7 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 			o[4] = rd[i].x; o[5] = rd[i].y; o[6] = rd[i].z; o[7] = (float)(pw & 0xFFFFFF); // util/ray.cl:11
 		}
 		if (hit) hit[i] = t >= 0 ? 1 : 0;
-		if (t >= 0) t &= (int)((1u << h->scene.tri_bits) - 1u); // (the shading class rides above the triangle index)
+		if (t >= 0) t &= (int)((1u << h->ds.scene.tri_bits) - 1u); // (the shading class rides above the triangle index)
 		if (t >= 0) {
 			if (wuvt) {
 				float *o = wuvt + 4 * (size_t)i;
@@ -2277,9 +2240,9 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 int polaris_hip_probe(polaris_hip_tracer *h, int kind, uint32_t index, uint32_t n, const float *in, float *out) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (kind < 0 || kind > 3 || (n && (!in || !out))) return fail(h, POLARIS_E_BAD_ARGUMENT, "probe: bad kind or null buffers");
-	const uint32_t limit = (kind == kProbeBxdf || kind == kProbeMaterial) ? h->scene.num_nodes : (kind == kProbeTexture ? h->scene.num_textures : h->scene.num_emissives);
+	const uint32_t limit = (kind == kProbeBxdf || kind == kProbeMaterial) ? h->ds.scene.num_nodes : (kind == kProbeTexture ? h->ds.scene.num_textures : h->ds.scene.num_emissives);
 	if (index >= limit) return fail(h, POLARIS_E_BAD_ARGUMENT, "probe: index %u out of range (%u)", index, limit);
 	if (n == 0) return POLARIS_OK;
 	HIP_TRY(h, hipSetDevice(h->device));
@@ -2290,10 +2253,10 @@ int polaris_hip_probe(polaris_hip_tracer *h, int kind, uint32_t index, uint32_t 
 	HIP_TRY(h, d_in.alloc(nin));
 	HIP_TRY(h, d_out.alloc(nout));
 	HIP_TRY(h, hipMemcpyAsync(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice, q));
-	const bool staged = h->opt_stage_lds && h->scene.num_nodes <= kLdsMatNodes && h->scene.num_emissives <= kLdsLights &&
-	                    h->scene.num_textures <= kLdsTextures;
-	if (staged) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
-	else hipLaunchKernelGGL(k_probe<false>, dim3(grid_for(n)), dim3(WG), 0, q, h->scene, kind, index, n, d_in, d_out);
+	const bool staged = h->opt_stage_lds && h->ds.scene.num_nodes <= kLdsMatNodes && h->ds.scene.num_emissives <= kLdsLights &&
+	                    h->ds.scene.num_textures <= kLdsTextures;
+	if (staged) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->ds.scene, kind, index, n, d_in, d_out);
+	else hipLaunchKernelGGL(k_probe<false>, dim3(grid_for(n)), dim3(WG), 0, q, h->ds.scene, kind, index, n, d_in, d_out);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipStreamSynchronize(q));
@@ -2303,7 +2266,7 @@ int polaris_hip_probe(polaris_hip_tracer *h, int kind, uint32_t index, uint32_t 
 int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32_t n, int any_hit, int32_t *hit, float *wuvt, int32_t *tri) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (n && (!rays || !hit)) return fail(h, POLARIS_E_BAD_ARGUMENT, "probe_intersect: null buffers");
 	if (n > (1u << 24)) return fail(h, POLARIS_E_BAD_ARGUMENT, "probe_intersect: at most 2^24 rays per call");
 	if (n == 0) return POLARIS_OK;
@@ -2327,13 +2290,13 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 	// the traversal kernel the options select for bounce rays (any_hit: shadow rays); packet_primary=1 sends closest-hit
 	// probes through the wave-packet kernel instead
 	if (any_hit) {
-		if (h->opt_packet_shadow > 0) kPacket[kPacketAnyHit].enqueue(wgs, WG, 0, q, P.st, h->bvh, P.st.lsum, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace(h, nullptr, true, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace[1].resident_per_cu)), wgs, P.st.lsum);
-		else kOcclusion.enqueue(wgs, WG, 0, q, P.st, h->bvh, P.st.lsum, h->d_stats);
+		if (h->opt_packet_shadow > 0) kPacket[kPacketAnyHit].enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, P.st.lsum, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace(h, nullptr, true, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->ds.trace[1].resident_per_cu)), wgs, P.st.lsum);
+		else kOcclusion.enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, P.st.lsum, h->d_stats);
 	} else {
-		if (h->opt_packet_primary == 1) kPacket[kPacketClosest].enqueue(wgs, WG, 0, q, P.st, h->bvh, nullptr, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace(h, nullptr, false, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->trace[0].resident_per_cu)), wgs, nullptr);
-		else kIntersect.enqueue(wgs, WG, 0, q, P.st, h->bvh);
+		if (h->opt_packet_primary == 1) kPacket[kPacketClosest].enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, nullptr, h->d_stats, h->cam.eye);
+		else if (h->opt_traversal) (void)launch_trace(h, nullptr, false, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->ds.trace[0].resident_per_cu)), wgs, nullptr);
+		else kIntersect.enqueue(wgs, WG, 0, q, P.st, h->ds.bvh);
 	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(res.data(), any_hit ? P.st.lsum : P.st.hit, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2343,7 +2306,7 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 		int t;
 		memcpy(&t, &res[i].w, 4);
 		hit[i] = t >= 0 ? 1 : 0;
-		if (t >= 0) t &= (int)((1u << h->scene.tri_bits) - 1u);
+		if (t >= 0) t &= (int)((1u << h->ds.scene.tri_bits) - 1u);
 		if (t >= 0 && wuvt) { float *o = wuvt + 4 * (size_t)i; o[0] = 1.0f - (res[i].x + res[i].y); o[1] = res[i].x; o[2] = res[i].y; o[3] = res[i].z; } // intersect.cl:283-288
 		if (tri) tri[i] = t;
 	}
@@ -2540,7 +2503,7 @@ int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t
 	if (!out || n < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: need %zu words", need);
 	if (!h->opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
 	HIP_TRY(h, hipSetDevice(h->device));
-	if (!h->have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: camera not set");
 	if (!motion_on(h)) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
 	if (int rc = ensure_gbuffer(h)) return rc;

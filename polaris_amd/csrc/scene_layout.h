@@ -35,6 +35,7 @@
 #include <utility>
 #include <vector>
 
+#include "polaris_math.h"
 #include "polaris_types.h"
 
 namespace pol {
@@ -961,6 +962,48 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 		d.pad2 = (n_slots <= 2046u && NT <= 2046u) ? tiny_meta_word(d.rank, d.orig) : 0u; // (what the tiny-scene traversal mode keeps per slot)
 	}
 	return "";
+}
+
+// ---- the packed record of an area light (shading.h, SceneT::light_geo), made on the host ------------------------------------------
+constexpr uint32_t kLightGeoFloats = 48;
+// The floats of a record that depend on the emissive's transform and area; g[0..29] hold the light's triangle.
+inline void derive_light_geo(const PolarisEmissive &em, float *g) {
+	// what areaLightGetPdf (emissive_sampler.cl:117-173) and areaLightGetSample (:96) derive from the light alone, with the
+	// kernels' own operations in the kernels' order (compiled without FMA contraction; polaris_math.h is bit-identical on the
+	// host): v0, v1 - v0, v2 - v0 through mul4x1 (util/transform.cl:9-16), normalize(cross(e1, e2)), 1 / area
+	const float *m = em.transform;
+	auto xform = [&](const float p[3], float out[3]) {
+		out[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
+		out[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
+		out[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
+	};
+	const float v0[3] = {g[0], g[1], g[2]};
+	const float d1[3] = {g[4] - v0[0], g[5] - v0[1], g[6] - v0[2]}, d2[3] = {g[8] - v0[0], g[9] - v0[1], g[10] - v0[2]};
+	float tv0[3], te1[3], te2[3];
+	xform(v0, tv0); xform(d1, te1); xform(d2, te2);
+	const float cx = te1[1] * te2[2] - te1[2] * te2[1], cy = te1[2] * te2[0] - te1[0] * te2[2], cz = te1[0] * te2[1] - te1[1] * te2[0];
+	const float inv_len = 1.0f / pm_sqrt(cx * cx + cy * cy + cz * cz);
+	for (int k = 0; k < 3; k++) { g[32 + k] = tv0[k]; g[36 + k] = te1[k]; g[40 + k] = te2[k]; }
+	g[44] = cx * inv_len; g[45] = cy * inv_len; g[46] = cz * inv_len;
+	g[30] = 1.0f / em.area;
+}
+
+// The records of the emissives ems[0..n) in geo ([n][kLightGeoFloats]), for upload_scene and update_vertices: the triangle of every area light from the scene's
+// arrays (build_layout range-checked the indices), then derive_light_geo.  normals / uvs null: those floats stay what they are, as does the record of a light that is no area light.
+inline void pack_light_geo(const PolarisEmissive *ems, size_t n, const float *vertices, const float *normals, const float *uvs, float *geo) {
+	for (size_t e = 0; e < n; e++) {
+		if (ems[e].type != POLARIS_EMISSIVE_AREA) continue;
+		const size_t off = (size_t)ems[e].tri_index * 3;
+		float *g = geo + e * kLightGeoFloats;
+		for (int v = 0; v < 3; v++) {
+			for (int k = 0; k < 3; k++) {
+				g[4 * v + k] = vertices[4 * (off + v) + k];
+				if (normals) g[12 + 4 * v + k] = normals[4 * (off + v) + k];
+			}
+			if (uvs) { g[24 + 2 * v] = uvs[2 * (off + v)]; g[25 + 2 * v] = uvs[2 * (off + v) + 1]; }
+		}
+		derive_light_geo(ems[e], g);
+	}
 }
 
 } // namespace pol

@@ -14,6 +14,7 @@
 
 #include "polaris_math.h"
 #include "polaris_types.h"
+#include "scene_layout.h"
 
 namespace pol {
 
@@ -77,7 +78,7 @@ template <bool LDS> struct SceneT {
 	uint32_t num_emissives;
 	int32_t bg_node;                    // scene_diffuse_mat_index or -1
 	uint32_t num_nodes, num_textures;   // table sizes (LDS staging in k_shade)
-	// [num_emissives][kLightGeoFloats] the triangle of every area light, packed at upload (polaris_hip.hip, pack_light_geometry):
+	// [num_emissives][kLightGeoFloats] the triangle of every area light, packed on the host (scene_layout.h, pack_light_geo):
 	// v0 v1 v2 | n0 n1 n2 (xyz + pad each) | uv0 uv1 uv2, 1 / area | and what areaLightGetPdf derives from the light alone:
 	// transformed v0, transformed edges e1 e2, their unit normal (xyz + pad each).  light_sample / light_pdf read it instead
 	// of chasing emissive -> tri_index -> vertices / normals / uvs: with the table staged in LDS the light's geometry costs
@@ -91,7 +92,6 @@ template <bool LDS> struct SceneT {
 	// bit c: a hit of shading class c may end in an emissive leaf (scene_layout.h, emitting_classes); all ones without classes
 	uint32_t emit_classes;
 };
-constexpr uint32_t kLightGeoFloats = 48;
 typedef SceneT<false> SceneDev; // what the host fills in
 
 // ---- PRNG: samplers/random_sampler.cl:7-16 ---------------------------------------------

@@ -85,18 +85,7 @@ inline int check_vertex_update(const PolarisVertexUpdate *u, bool have_scene, bo
 		return POLARIS_E_BAD_ARGUMENT;
 	}
 	if (!u->vertices || !u->instance_boxes) { msg = "update_vertices: vertex or box pointer is null"; return POLARIS_E_BAD_ARGUMENT; }
-	if (u->emissives) {
-		if (u->num_emissives != ems.size()) {
-			msg = "update_vertices: " + std::to_string(u->num_emissives) + " emissives, the uploaded scene has " + std::to_string(ems.size());
-			return POLARIS_E_BAD_ARGUMENT;
-		}
-		for (uint32_t e = 0; e < u->num_emissives; e++)
-			if (u->emissives[e].type != ems[e].type || u->emissives[e].tri_index != ems[e].tri_index || u->emissives[e].mat_node_index != ems[e].mat_node_index) {
-				msg = "update_vertices: emissive " + std::to_string(e) + " differs from the uploaded one in type, triangle or material node";
-				return POLARIS_E_BAD_ARGUMENT;
-			}
-	}
-	return 0;
+	return check_update_emissives("update_vertices: ", u->emissives, u->num_emissives, ems, msg);
 }
 
 // build_layout's magnitude rule over the new vertices, with its text.

@@ -267,6 +267,55 @@ def test_option_off_changes_nothing_allocates_nothing_and_refuses(built):
         assert np.array_equal(bits(frames[how][0]), bits(frames["never heard"][0])) and frames[how][1] == frames["never heard"][1]
 
 
+def test_reupload_replaces_everything(built):
+    """Nothing of an uploaded scene outlives the next upload: tracer A uploads the cubes with instance_update, vertex_update and
+    object_motion on and syncs a frame under temporal reuse, turns the three options off and uploads the one-instance Cornell box; it
+    then owns, holds, traces, selects and refuses exactly what tracer B does, which only ever saw the Cornell box."""
+    from oracle import pybind as ob
+    from polaris_amd.tracer import ChangeType, HipTracer, TracerError, UpdateMode
+
+    first, second = scenes.SCENES["cubes"](), cases.case("one-instance")[0]
+    w = h = 32
+    on = ("instance_update", "vertex_update", "object_motion")
+    a, b = HipTracer("a", 0), make_hip_tracer(second, w, h)
+    try:
+        a.Init()
+        for k in on:
+            a.set_option(k, 1)
+        a.set_temporal(**T.TEMPORAL_DEFAULTS)
+        a.UpdateState(UpdateMode.Synchronous, ChangeType.FrameDimensions, (w, h))
+        upload(a, first)
+        a.UpdateState(UpdateMode.Synchronous, ChangeType.CameraData, first)
+        trace(a, w, h, 1, bounces=2)
+        sync(a, w, h, 1)
+        assert a.scene_counts()[2] > b.scene_counts()[2]      # (A held both plans)
+        for k in on:
+            a.set_option(k, 0)
+        upload(a, second)
+        a.UpdateState(UpdateMode.Synchronous, ChangeType.CameraData, second)
+        assert a.scene_counts() == b.scene_counts()            # pair records, instance records, allocations, bytes
+        ra, rb = a.read_scene_records(), b.read_scene_records()
+        assert ra[0].tobytes() == rb[0].tobytes() and ra[1].tobytes() == rb[1].tobytes()
+        frames = []
+        for tr in (a, b):
+            tr.set_option("time_kernels", 1)
+            tr.Trace(ob.make_request(w, h, spp=1, bounces=2), scenes.make_seeds(1, 2, base=21))
+            frames.append((tr.read_accumulator(0), tr.last_trace_stats))
+        assert np.array_equal(bits(frames[0][0]), bits(frames[1][0])) and np.abs(frames[0][0][..., :3]).sum() > 0
+        assert list(frames[0][1].rays_per_bounce[:2]) == list(frames[1][1].rays_per_bounce[:2])
+        assert a.kernel_symbol("intersect") == b.kernel_symbol("intersect") != ""
+        codes = {}
+        for name, tr in (("a", a), ("b", b)):
+            for call, args in ((tr.update_instances, scenes.instance_update_args(second)), (tr.update_vertices, scenes.vertex_update_args(second))):
+                with pytest.raises(TracerError) as e:
+                    call(*args)
+                codes.setdefault(name, []).append(e.value.code)
+        assert codes["a"] == codes["b"] == [E_UNSUPPORTED, E_UNSUPPORTED]
+    finally:
+        a.Close()
+        b.Close()
+
+
 # ---- 8. refusals ---------------------------------------------------------------------------------------------------------------
 def test_every_refusal_leaves_the_next_frame_as_the_one_before(built):
     from polaris_amd.tracer import ErrNoSceneData, HipTracer, TracerError
