@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 SPARSE = {"shade_sparse_from": 1}
 GROUP = 8                # kernels.h, kSparseShadeGroup
-MIN_GROUPS_PER_CU = 8    # polaris_hip.hip, kSparseMinGroupsPerCu: the automatic rule's launch size
+MIN_GROUPS_PER_CU = 8    # trace_plan.h, kSparseMinGroupsPerCu: the automatic rule's launch size
 
 
 def both_prefilters(ref, rr, opts, exact, what, **shape):

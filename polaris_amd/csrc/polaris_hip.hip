@@ -29,8 +29,11 @@
 #include "device_mem.h"
 #include "kernel_table.h"
 #include "polaris_hip.h"
+#include "trace_plan.h"
 
 using namespace pol;
+
+static_assert(kPlanChunk == WG && kPlanSparseGroup == kSparseGroup && kPlanTinyBlock == kTinyBlock, "trace_plan.h counts in the kernels' geometry (kernels.h)");
 
 #ifndef POLARIS_LDS_TOP_MAX_PAIRS
 #define POLARIS_LDS_TOP_MAX_PAIRS (8u * kLdsTopNodes)
@@ -229,9 +232,8 @@ struct polaris_hip_tracer {
 			for (auto &x : cnt_occ_b) x = nullptr;
 		}
 	};
-	static constexpr int kMaxPipes = 8;
+	static constexpr int kMaxPipes = pol::kMaxPipes;
 	Pipe pipe[kMaxPipes];
-	int opt_overlap = 4; // number of pipelines used (1 = no overlap)
 	DevArray<uint32_t> d_seeds; // grow-only
 	DevArray<unsigned long long> d_stats;
 	DevArray<float4> d_cam_o; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
@@ -239,27 +241,11 @@ struct polaris_hip_tracer {
 	DevArray<float4> staging; // peer-merge staging strip (grow-only)
 	int opt_ipc_staged = 0;  // testing aid: peers opened from now on are merged through the staging strip (the path of a GPU without peer access)
 
-	// options
-	int64_t opt_samples_per_batch = 0; // 0 = auto
-	int opt_exact = 0;
-	int opt_packet_shadow = 0;  // shadow rays of the first N bounces go through the packet kernel too
-	int opt_packet_primary = -1; // wave-packet traversal (k_trace_packet) for bounce 0: 1/0, -1 = by scene size (packet_primary below)
-	bool packet_primary = true;  // resolved at upload
+	// options: what a Trace plans from (trace_plan.h), and the rest
+	TraceOptions opt;
+	bool packet_primary = true;  // opt.packet_primary, resolved at upload where it is -1
 	int opt_time_kernels = 0;
-	int opt_trace_wgs_per_cu = 0; // 0 = auto (what the LDS stack admits)
-	int opt_trace_grid = 0;       // 0 = auto; > 0: the persistent traversal grid in workgroups (A/B aid)
 	int opt_max_leaf_tris = -1;   // subdivide bigger triangle leaves at upload (0 = keep the caller's leaves, -1 = by scene size)
-	int opt_stage_lds = 1;    // k_shade stages material nodes / lights / texture metadata in LDS when they fit
-	int opt_shade_wave = 1;   // 1 = persistent wave-per-chunk shading (k_shade_wave), 0 = one workgroup per chunk (k_shade)
-	int opt_shade_wgs_per_cu = 4;
-	int opt_shade_wave_from = -1; // first bounce shaded by k_shade_wave; -1 = automatic (plan_bounces): the bounce AFTER Russian roulette
-	                              // starts thinning the chunks (min_bounces_for_rr + 1), or the roulette bounce itself where the prefilter
-	                              // thins its chunks and the launch is large; earlier bounces use k_shade
-	int opt_shade_prefilter = 1; // the shade kernels retire rays that only count -- escaped, or rejected by Russian roulette off an emitter -- before shade_ray (kernels.h, shade_fate)
-	int opt_shade_sort = -1; // first bounce whose rays k_shade groups by shading class; -1 = default (1), POLARIS_MAX_BOUNCES = never
-	int opt_hit12 = 1;     // 12-byte hit records inside a Trace (A/B aid: 0 = 16)
-	int opt_o12 = 1;       // 12-byte origins of the closest-hit rays inside a Trace (A/B aid: 0 = 16)
-	int opt_traversal = 1; // 1 = persistent waves with lane refill (k_trace), 0 = one ray per lane (k_intersect/k_occlusion)
 
 	// per-kernel timing (option time_kernels)
 	struct Pending { const char *name; DevEvent a, b; };
@@ -662,119 +648,70 @@ int trace_occupancy(polaris_hip_tracer *h, bool any_hit) {
 	return std::min(n, 8);
 }
 
-// What one bounce of a Trace launches.  Every input is fixed per Trace (options, request) or per upload: planned once, before the batches.
-// isect_packet / occl_packet: the wave-packet kernel for the bounce's closest-hit / shadow rays; null: the scene's k_trace variant
-// (traversal = 1) or k_intersect / k_occlusion (traversal = 0).  Exactly one of shade / shade_wave is set.
-struct BouncePlan {
-	const PacketVariant *isect_packet = nullptr, *occl_packet = nullptr;
-	const ShadeVariant *shade = nullptr;
-	const ShadeWaveVariant *shade_wave = nullptr;
-	int shade_timer = 0; // index into kShadeTimer
-};
-// Automatic shade_wave_from: a full batch must hold this many groups of kSparseGroup chunks per CU for k_shade_wave to take the roulette
-// bounce itself (profiles/shade_sparse_ab.txt).
-constexpr uint32_t kWaveRouletteGroupsPerCu = 8;
-// one timer per kernel symbol: shade_first = k_shade<.., FIRST> (camera rays), shade_sort = k_shade<.., SORT, ..> (bounce rays in
-// class order), shade_plain = k_shade<.., false, false>, shade_wave = k_shade_wave
-const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"};
-
-// `batch_chunks`: the chunks of one full batch of the Trace (the size of its shade launches).
-void plan_bounces(const polaris_hip_tracer *h, const PolarisBlockRequest *r, uint32_t batch_chunks, BouncePlan *plan) {
-	// LDS-table variant of the shade kernels: only when all three tables fit (kernels.h, stage_scene)
-	const bool staged = h->opt_stage_lds && h->ds.scene.num_nodes <= kLdsMatNodes && h->ds.scene.num_emissives <= kLdsLights &&
-	                    h->ds.scene.num_textures <= kLdsTextures;
-	// First bounce of k_shade_wave.  The bounce where Russian roulette starts still finds the chunks as the previous bounce left them;
-	// only with the prefilter (shade_fate retires the rays roulette rejects, where some shading class cannot emit: otherwise nothing is
-	// retired) does a chunk of that bounce hold a sixth of its rays, and k_shade still pays a workgroup's latency chain per chunk.
-	// k_shade_wave screens and shades them a group at a time -- on launches large enough to keep its persistent grid busy: smaller
-	// ones (a row block of a multi-GPU frame, the frames of the tests) keep the plan they had.
-	int wave_from = h->opt_shade_wave_from;
-	if (wave_from < 0) {
-		wave_from = (int)r->min_bounces_for_rr + 1;
-		const uint64_t groups = ((uint64_t)batch_chunks + kSparseGroup - 1) / kSparseGroup;
-		if (h->opt_shade_prefilter && (h->ds.scene.emit_classes & 0xFFFFu) != 0xFFFFu && groups >= (uint64_t)kWaveRouletteGroupsPerCu * (uint64_t)h->num_cus)
-			wave_from = (int)r->min_bounces_for_rr;
-	}
-	for (uint32_t b = 0; b < r->num_bounces; b++) {
-		BouncePlan &pl = plan[b] = BouncePlan{};
-		if (b == 0 && h->packet_primary) pl.isect_packet = &kPacket[kPacketCamera];
-		if ((int)b < h->opt_packet_shadow) pl.occl_packet = &kPacket[kPacketAnyHit];
-		const bool wave = h->opt_shade_wave && b > 0 && (int)b >= wave_from; // (never the first bounce: k_shade_wave reads the previous step's emit masks)
-		// bounce rays are shaded in the order of their material's shading class (kernels.h, k_shade SORT); camera rays are
-		// coherent as they come (64 neighbouring pixels per wave)
-		const bool sorted = b > 0 && h->ds.scene.tri_bits < 31 && (int)b >= (h->opt_shade_sort >= 0 ? h->opt_shade_sort : 1);
-		pl.shade_timer = wave ? 3 : (b == 0 ? 0 : (sorted ? 1 : 2));
-		if (wave) pl.shade_wave = &kShadeWave[staged];
-		else pl.shade = &kShade[staged][pl.shade_timer];
-	}
+// What a Trace's plan needs to know of the uploaded scene and of the device (trace_plan.h, which holds every rule): filled here only.
+TraceScene plan_scene(const polaris_hip_tracer *h) {
+	TraceScene s;
+	s.tiny = h->ds.node_mode == kNodesLdsAll;
+	for (int any = 0; any < 2; any++) s.resident_per_cu[any] = h->ds.trace[any].resident_per_cu;
+	s.tables_fit_lds = h->ds.scene.num_nodes <= kLdsMatNodes && h->ds.scene.num_emissives <= kLdsLights && h->ds.scene.num_textures <= kLdsTextures;
+	s.emit_classes = h->ds.scene.emit_classes;
+	s.tri_bits = h->ds.scene.tri_bits;
+	s.packet_primary = h->packet_primary;
+	s.num_cus = h->num_cus;
+	return s;
 }
+
+// THE launch of a traversal over `chunks` chunks of st, by the kernel the plan chose for the ray set (trace_plan.h: batch_traversal,
+// probe_traversal, tap_traversal), under `timer` (null: a probe's or the tap's launch, untimed).  persistent_grid: k_trace's grid.
+hipError_t launch_traversal(polaris_hip_tracer *h, const char *timer, Traversal how, RayKind kind, hipStream_t q, const Streams &st, uint32_t persistent_grid, uint32_t chunks, float4 *acc) {
+	const bool any_hit = kind == RayKind::AnyHit;
+	if (how == Traversal::Packet)
+		return launch(h, timer, q, kPacket[any_hit ? kPacketAnyHit : (kind == RayKind::Camera ? kPacketCamera : kPacketClosest)], chunks, WG, 0, st, h->ds.bvh, acc, h->d_stats, h->cam.eye);
+	if (how == Traversal::Persistent) return launch_trace(h, timer, any_hit, q, st, persistent_grid, chunks, acc, kind == RayKind::Camera);
+	if (any_hit) return launch(h, timer, q, kOcclusion, chunks, WG, 0, st, h->ds.bvh, acc, h->d_stats);
+	return launch(h, timer, q, kIntersect, chunks, WG, 0, st, h->ds.bvh);
+}
+
+const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"}; // by ShadeKernel (trace_plan.h): one timer per kernel symbol
 
 // One wavefront batch: K samples starting at sample s0, on pipeline p, by the Trace's plan.
 // Returns the first launch error of the batch (checked after every batch by the caller: a failed launch in batch 1 is reported
 // before batch 2 is queued behind it).
-hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest *r, const BouncePlan *plan, uint32_t s0, uint32_t K, uint32_t N, uint32_t Npad,
-                        bool exact, hipEvent_t resolve_after) {
+hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest *r, const TracePlan &plan, uint32_t s0, uint32_t K, uint32_t N, hipEvent_t resolve_after) {
 	hipError_t first_err = hipSuccess;
 	auto note = [&](hipError_t e) { if (first_err == hipSuccess && e != hipSuccess) first_err = e; };
 	polaris_hip_tracer::Pipe &P = h->pipe[p];
-	const uint32_t B = r->num_bounces, stride = 1 + B;
+	const bool exact = plan.exact;
+	const uint32_t B = plan.bounces, stride = 1 + B, Npad = plan.Npad;
 	const uint32_t wgs_per_sample = Npad / WG, wgs = K * wgs_per_sample;
 	hipStream_t q = P.q;
-	P.st.hit12 = h->opt_hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
-	P.st.o12 = h->opt_o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
+	P.st.hit12 = plan.hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
+	P.st.o12 = plan.o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
 	note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->W, r->block_y,
-	            exact ? 0 : 1, (B > 0 && (h->packet_primary || h->opt_traversal)) ? 0 : 1)); // (neither the wave-packet kernel nor k_trace's camera launch reads the origin stream)
+	            exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
 	ShadeArgs A{};
 	A.seeds = h->d_seeds; A.seed_stride = stride; A.first_sample = s0;
 	A.N = N; A.Npad = Npad; A.W = h->W; A.blockY = r->block_y;
 	A.min_rr = r->min_bounces_for_rr;
 	A.exact = exact ? 1 : 0;
-	A.prefilter = h->opt_shade_prefilter ? 1 : 0;
+	A.prefilter = plan.prefilter ? 1 : 0;
 	A.acc = exact ? h->trace_acc : P.st.lsum;
-	// persistent grid: chunks are dealt to workgroups statically, so a workgroup that is not resident
-	// from the start begins with its whole share still to do -- the grid must not exceed what the GPU
-	// holds at once (measured: 8 workgroups per CU where 6 fit cost the closest-hit kernel 12 %).  One
-	// batch at a time: exactly the resident capacity.  Several batches in flight: two thirds of it per
-	// launch (the launches share the CUs; measured flat to +5 % across the bench scenes).
-	// (LDS: 16-entry stack: 16 KB per workgroup -> 8 by LDS, VGPRs allow 7-8 waves/SIMD; 32-entry: 5)
-	auto grid_of = [&](int resident) {
-		uint32_t per_cu = (uint32_t)std::max(1, resident);
-		if (std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes) > 1 && !exact && per_cu > 2) per_cu = std::max(2u, per_cu * 2u / 3u);
-		// tiny-scene mode (two 1 024-thread workgroups fill a CU), small launches -- a row block of a multi-GPU frame: with two
-		// batches in flight a launch gets half the GPU at best, and at fewer than 4 chunks per resident wave a full-size grid
-		// leaves every wave a single chunk, i.e. nothing but its ramp-down.  One workgroup per CU then: a 64-row block of the
-		// headline frame 2.10 -> 1.83 ms, a 128-row block 3.30 -> 3.13 ms (256 rows +-0, the full frame +1 %: not applied there)
-		if (h->ds.node_mode == kNodesLdsAll && std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes) > 1 && !exact && per_cu == 2 &&
-		    (uint64_t)wgs < 4ull * (uint64_t)h->num_cus * per_cu * (kTinyBlock / 64))
-			per_cu = 1;
-		if (h->opt_trace_wgs_per_cu > 0) per_cu = (uint32_t)h->opt_trace_wgs_per_cu;
-		if (h->opt_trace_grid > 0) return std::min<uint32_t>(wgs, (uint32_t)h->opt_trace_grid); // (A/B aid: an absolute persistent grid)
-		return std::min<uint32_t>(wgs, (uint32_t)h->num_cus * per_cu);
-	};
-	const uint32_t persistent = grid_of(h->ds.trace[0].resident_per_cu), persistent_occl = grid_of(h->ds.trace[1].resident_per_cu);
+	const uint32_t persistent = plan.trace_grid(false, wgs), persistent_occl = plan.trace_grid(true, wgs);
 	for (uint32_t b = 0; b < B; b++) {
-		const BouncePlan &pl = plan[b];
+		const BouncePlan &pl = plan.bounce[b];
 		Streams S = P.st; // (in place: k_shade / k_shade_wave read a chunk's rays before they write into it)
 		if (!exact) { S.occ_e = P.nee[b]; S.vis = P.vis[b]; S.cnt_occ = P.cnt_occ_b[b]; } // this bounce's NEE records, visibility bytes and shadow-ray counts stay until k_fold_nee
 		float4 *const occl_acc = exact ? A.acc : nullptr;                // batched: unoccluded rays only mark their record (deferred)
-		if (pl.isect_packet) note(launch(h, "intersect_packet", q, *pl.isect_packet, wgs, WG, 0, S, h->ds.bvh, nullptr, h->d_stats, h->cam.eye));
-		else if (h->opt_traversal) note(launch_trace(h, "intersect", false, q, S, persistent, wgs, nullptr, b == 0));
-		else note(launch(h, "intersect", q, kIntersect, wgs, WG, 0, S, h->ds.bvh));
+		const RayKind closest = b == 0 ? RayKind::Camera : RayKind::Closest;
+		note(launch_traversal(h, traversal_timer(pl.isect, closest), pl.isect, closest, q, S, persistent, wgs, nullptr));
 		A.bounce = b;
 		A.last_bounce = (b + 1 == B) ? 1 : 0;
 		A.emask_in = b == 0 ? nullptr : P.st.emask[(b + 1) & 1]; // the masks the previous step wrote
 		A.emask_out = P.st.emask[b & 1];
-		if (pl.shade_wave) {
-			// persistent waves pull groups of kSparseGroup chunks: no more workgroups than the GPU holds at once (4 per CU at
-			// the kernel's register count) nor than there are groups for their 4 waves
-			const uint32_t groups = (wgs + kSparseGroup - 1) / kSparseGroup;
-			const uint32_t grid = std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->opt_shade_wgs_per_cu)));
-			note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade_wave, grid, WG, 0, S, h->ds.scene, A, wgs));
-		} else note(launch(h, kShadeTimer[pl.shade_timer], q, *pl.shade, wgs, WG, 0, S, h->ds.scene, A));
+		if (pl.shade == kShadeByWave) note(launch(h, kShadeTimer[pl.shade], q, kShadeWave[plan.staged], plan.shade_wave_grid(wgs), WG, 0, S, h->ds.scene, A, wgs));
+		else note(launch(h, kShadeTimer[pl.shade], q, kShade[plan.staged][pl.shade], wgs, WG, 0, S, h->ds.scene, A));
 		note(launch(h, "scan", q, kScan, K, 1024, 0, S, wgs_per_sample, b, A.last_bounce ? 0 : 1, h->d_stats));
-		if (pl.occl_packet) note(launch(h, "occlusion", q, *pl.occl_packet, wgs, WG, 0, S, h->ds.bvh, occl_acc, h->d_stats, h->cam.eye));
-		else if (h->opt_traversal) note(launch_trace(h, "occlusion", true, q, S, persistent_occl, wgs, occl_acc));
-		else note(launch(h, "occlusion", q, kOcclusion, wgs, WG, 0, S, h->ds.bvh, occl_acc, h->d_stats));
+		note(launch_traversal(h, traversal_timer(pl.occl, RayKind::AnyHit), pl.occl, RayKind::AnyHit, q, S, persistent_occl, wgs, occl_acc));
 	}
 	if (!exact && B > 0) { // accumulateEmissiveSamples of the whole batch: the marked NEE records of every bounce into the per-path radiance
 		FoldArgs F{};
@@ -785,7 +722,7 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	if (!exact) {
 		// batches resolve into the trace accumulator in sample order: wait for the previous batch's resolve
 		if (resolve_after) note(hipStreamWaitEvent(q, resolve_after, 0));
-		note(launch(h, "resolve", q, kResolve[h->opt_moments], grid_for(N), WG, 0, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W));
+		note(launch(h, "resolve", q, kResolve[plan.moments], grid_for(N), WG, 0, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W));
 	}
 	note(hipEventRecord(P.done, q));
 	note(hipGetLastError()); // (whatever a launch left)
@@ -925,7 +862,7 @@ int choose_traversal(polaris_hip_tracer *h, const PolarisSceneView &sc, const Sc
 	// ways inside the instances (-5 % frame time per-ray on the 1 024-instance scene, -26 % on the 1 M-triangle terrain)
 	// (round 4, later: with the triangle records in LDS the per-ray kernel of the tiny-scene mode is ahead -- camera rays 0.93 vs
 	// 1.20 ms isolated, frame 10.96 vs 11.03 ms, three alternating runs: see below, after the node mode is known)
-	if (h->opt_packet_primary < 0) h->packet_primary = sc.num_triangles <= 32768u && sc.num_mesh_instances == 1;
+	if (h->opt.packet_primary < 0) h->packet_primary = sc.num_triangles <= 32768u && sc.num_mesh_instances == 1;
 	// node records: whole tree in LDS for tiny scenes, its top for small ones, global memory otherwise (kernels.h NodeMode)
 	// (16-bit stack entries: triangle slots and instance ids must fit 11 bits, and no leaf reference may carry kBigLeafFlag)
 	// (... and the packed word of a slot holds the scene triangle in 11 bits too: scene_layout.h tiny_meta_word)
@@ -937,7 +874,7 @@ int choose_traversal(polaris_hip_tracer *h, const PolarisSceneView &sc, const Sc
 	select_trace(h);
 	if (S.node_mode == kNodesLdsAll) {
 		if (int rc = plan_tiny_lds(h, L.tris.size())) return rc;
-		if (h->opt_packet_primary < 0 && S.bvh.lds_tris > 0) h->packet_primary = false;
+		if (h->opt.packet_primary < 0 && S.bvh.lds_tris > 0) h->packet_primary = false;
 	}
 	for (int any = 0; any < 2; any++) S.trace[any].resident_per_cu = trace_occupancy(h, any != 0);
 	return POLARIS_OK;
@@ -1292,33 +1229,33 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!key) return fail(h, POLARIS_E_BAD_ARGUMENT, "option key is null");
 	const std::string k(key);
-	if (k == "samples_per_batch") h->opt_samples_per_batch = value < 0 ? 0 : value;
+	if (k == "samples_per_batch") h->opt.samples_per_batch = value < 0 ? 0 : value;
 	else if (k == "exact_accumulate") {
 		if (value != 0 && h->opt_moments) return fail(h, POLARIS_E_UNSUPPORTED, "exact_accumulate has no per-sample radiance: it cannot be combined with moments");
-		h->opt_exact = value != 0;
+		h->opt.exact = value != 0;
 	} else if (k == "moments") {
-		if (value != 0 && h->opt_exact) return fail(h, POLARIS_E_UNSUPPORTED, "moments need per-sample radiance: exact_accumulate cannot keep them");
+		if (value != 0 && h->opt.exact) return fail(h, POLARIS_E_UNSUPPORTED, "moments need per-sample radiance: exact_accumulate cannot keep them");
 		if (value == 0 && h->va.sigma_variance != 0.0f) return fail(h, POLARIS_E_BAD_ARGUMENT, "moments cannot be turned off while variance guidance is on");
 		h->opt_moments = value != 0;
 	}
-	else if (k == "packet_primary") { h->opt_packet_primary = value < 0 ? -1 : (value != 0); if (value >= 0) h->packet_primary = value != 0; }
-	else if (k == "packet_shadow") h->opt_packet_shadow = (int)std::max<int64_t>(0, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
+	else if (k == "packet_primary") { h->opt.packet_primary = value < 0 ? -1 : (value != 0); if (value >= 0) h->packet_primary = value != 0; }
+	else if (k == "packet_shadow") h->opt.packet_shadow = (int)std::max<int64_t>(0, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
 	else if (k == "time_kernels") h->opt_time_kernels = value != 0;
 	else if (k == "node_mode") h->opt_node_mode = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 2)); // next upload; 2 only where the scene is tiny enough
-	else if (k == "traversal") h->opt_traversal = value != 0; // 0 = one ray per lane (k_intersect / k_occlusion), 1 = persistent waves with lane refill (k_trace)
-	else if (k == "shade_wave") h->opt_shade_wave = value != 0;
-	else if (k == "shade_wave_from") h->opt_shade_wave_from = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
-	else if (k == "shade_wgs_per_cu") h->opt_shade_wgs_per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(value, 64));
-	else if (k == "stage_lds") h->opt_stage_lds = value != 0;
-	else if (k == "shade_prefilter") h->opt_shade_prefilter = value != 0;
-	else if (k == "shade_sort") h->opt_shade_sort = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
+	else if (k == "traversal") h->opt.traversal = value != 0; // 0 = one ray per lane (k_intersect / k_occlusion), 1 = persistent waves with lane refill (k_trace)
+	else if (k == "shade_wave") h->opt.shade_wave = value != 0;
+	else if (k == "shade_wave_from") h->opt.shade_wave_from = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
+	else if (k == "shade_wgs_per_cu") h->opt.shade_wgs_per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(value, 64));
+	else if (k == "stage_lds") h->opt.stage_lds = value != 0;
+	else if (k == "shade_prefilter") h->opt.shade_prefilter = value != 0;
+	else if (k == "shade_sort") h->opt.shade_sort = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
 	else if (k == "ipc_staged") h->opt_ipc_staged = value != 0;
-	else if (k == "overlap") h->opt_overlap = (int)std::max<int64_t>(1, std::min<int64_t>(value, polaris_hip_tracer::kMaxPipes));
-	else if (k == "trace_grid") h->opt_trace_grid = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-	else if (k == "trace_wgs_per_cu") h->opt_trace_wgs_per_cu = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
+	else if (k == "overlap") h->opt.overlap = (int)std::max<int64_t>(1, std::min<int64_t>(value, polaris_hip_tracer::kMaxPipes));
+	else if (k == "trace_grid") h->opt.trace_grid = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+	else if (k == "trace_wgs_per_cu") h->opt.trace_wgs_per_cu = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
 	else if (k == "tiny_one") h->opt_tiny_one = value != 0; // next upload
-	else if (k == "hit12") h->opt_hit12 = value != 0;
-	else if (k == "o12") h->opt_o12 = value != 0;
+	else if (k == "hit12") h->opt.hit12 = value != 0;
+	else if (k == "o12") h->opt.o12 = value != 0;
 	else if (k == "lds_tris") h->opt_lds_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
 	else if (k == "object_motion") {
 		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "object_motion is 0 or 1");
@@ -1390,49 +1327,26 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	const uint32_t N = (uint32_t)N64, Npad = (N + WG - 1) / WG * WG;
 
 	HIP_TRY(h, hipSetDevice(h->device));
-	const bool exact = h->opt_exact != 0;
-	uint32_t K = 1;
-	if (!exact) {
-		// Up to ~32 M paths per batch, but at least two batches so that one's sparse late bounces run beside the other's
-		// dense early ones.  Bigger batches amortise the tail of every persistent launch (a workgroup finishes the longest
-		// of its last rays alone) over more chunks -- measured on the round-2 kernels: headline frame 2 x 16.8 M paths
-		// 17.5 ms, 4 x 8.4 M 18.3 ms, 8 x 4.2 M 19.8 ms, 1 x 33.5 M 18.8 ms; 1024^2 x 256 spp: 33.5 M per batch 130.7 ms,
-		// 16.8 M 134.9 ms, 8.4 M 142.4 ms.  (128 B of stream buffers per path: 4.3 GB per batch in flight, of 288 GB.)
-		if (h->opt_samples_per_batch > 0) K = (uint32_t)std::min<int64_t>(h->opt_samples_per_batch, 4096);
-		else K = std::min<uint32_t>(std::max<uint32_t>(1u, (uint32_t)((32u << 20) / Npad)), std::max(1u, (spp + 1) / 2));
-		K = std::max<uint32_t>(1u, std::min(K, std::max(spp, 1u)));
+	// plan (trace_plan.h): the batch size, clamped by the free device memory where the plan chose it itself
+	TracePlan plan = plan_trace(h->opt, plan_scene(h), h->opt_moments, spp, B, r->min_bounces_for_rr, Npad);
+	size_t free_b = 0, total_b = 0;
+	if (plan.wants_memory_clamp() && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		size_t have = 0; // what the pipelines already hold counts as available
+		for (auto &P : h->pipe) have += P.slots * slot_bytes(P.nee_bounces);
+		plan.clamp_to_memory(free_b + have);
 	}
-	// The batch buffers are 128 bytes per path slot + 16 per bounce (the NEE records are kept per bounce until the batch folds them) and up to `overlap`
-	// batches are in flight: 4.3 GB per pipeline at 33.5 M slots, nothing on a 288 GB MI355X but not on a smaller or shared device.  K chosen automatically is first clamped by the
-	// free device memory and, if an allocation still fails, halved and retried (a caller-chosen samples_per_batch is kept as it
-	// is: its failure is reported).
-	if (!exact && h->opt_samples_per_batch <= 0 && K > 1) {
-		size_t free_b = 0, total_b = 0;
-		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-			size_t have = 0; // what the pipelines already hold counts as available
-			const size_t slot_bytes = 144 + 17 * (size_t)std::max(1u, B); // stream buffers per path slot: 128 B + one NEE record array per bounce (+ the per-chunk words)
-			for (auto &P : h->pipe) have += P.slots * (144 + 17 * (size_t)std::max(1u, P.nee_bounces));
-			const size_t pipes = (size_t)std::max(1, std::min(h->opt_overlap, (int)polaris_hip_tracer::kMaxPipes));
-			const size_t budget = (free_b + have) / 10 * 9;
-			// (batches in flight = min(overlap, #batches): it grows towards `overlap` as K shrinks, so it is recomputed per step)
-			auto need = [&](uint32_t k) { return (size_t)k * Npad * slot_bytes * std::min<size_t>(pipes, (spp + k - 1) / k); };
-			while (K > 1 && need(K) > budget) K = (K + 1) / 2;
-		}
-	}
-	uint32_t n_batches = 0;
-	int n_pipes = 1;
+	// allocate: an allocation that fails for want of memory releases every pipeline's buffers and asks the plan for the next smaller batch
 	for (;;) {
-		n_batches = spp ? (spp + K - 1) / K : 0;
-		n_pipes = exact ? 1 : (int)std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)h->opt_overlap, n_batches));
 		int rc = POLARIS_OK;
-		for (int p = 0; p < n_pipes && rc == POLARIS_OK; p++) rc = ensure_streams(h, p, (size_t)K * Npad, false, exact ? 1u : B);
+		for (int p = 0; p < plan.n_pipes && rc == POLARIS_OK; p++) rc = ensure_streams(h, p, (size_t)plan.K * Npad, false, plan.exact ? 1u : B);
 		if (rc == POLARIS_OK) break;
-		if (exact || h->opt_samples_per_batch > 0 || K == 1) return rc;
-		(void)hipGetLastError(); // out of memory: release every pipeline's buffers, halve the batch, try again
+		if (!plan.shrink()) return rc;
+		(void)hipGetLastError();
 		for (auto &P : h->pipe)
 			if (P.q && P.slots) { (void)hipStreamSynchronize(P.q); P.release(); }
-		K = (K + 1) / 2;
 	}
+	const uint32_t K = plan.K;
+	const int n_pipes = plan.n_pipes;
 	HIP_TRY(h, h->d_seeds.reserve(need_seeds));
 	h->cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H); // resources.go:130-133
 	const size_t F = (size_t)h->W * h->H;
@@ -1471,13 +1385,11 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 		polaris_hip_tracer *h; int n; bool armed = true;
 		~DrainOnError() { if (armed) for (int p = 0; p < n; p++) (void)hipStreamSynchronize(h->pipe[p].q); }
 	} drain{h, n_pipes};
-	BouncePlan plan[POLARIS_MAX_BOUNCES];
-	plan_bounces(h, r, K * (Npad / WG), plan);
-	for (uint32_t b = 0; b < B && spp; b++) h->last_shade_timer[b] = plan[b].shade_timer;
+	for (uint32_t b = 0; b < B && spp; b++) h->last_shade_timer[b] = plan.bounce[b].shade;
 	uint32_t bi = 0;
 	for (uint32_t s0 = 0; s0 < spp; s0 += K, bi++) {
 		const int p = (int)(bi % (uint32_t)n_pipes), prev = (int)((bi + (uint32_t)n_pipes - 1) % (uint32_t)n_pipes);
-		HIP_TRY(h, launch_batch(h, p, r, plan, s0, std::min(K, spp - s0), N, Npad, exact, (n_pipes > 1 && bi > 0) ? h->pipe[prev].done : nullptr));
+		HIP_TRY(h, launch_batch(h, p, r, plan, s0, std::min(K, spp - s0), N, (n_pipes > 1 && bi > 0) ? h->pipe[prev].done : nullptr));
 	}
 	for (int p = 1; p < n_pipes; p++) HIP_TRY(h, hipStreamWaitEvent(q, h->pipe[p].done, 0)); // join
 	HIP_TRY(h, hipGetLastError());
@@ -2206,8 +2118,7 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
 	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
-	if (h->packet_primary) kPacket[kPacketClosest].enqueue(Npad / WG, WG, 0, q, st0, h->ds.bvh, nullptr, h->d_stats, h->cam.eye);
-	else kIntersect.enqueue(Npad / WG, WG, 0, q, st0, h->ds.bvh);
+	(void)launch_traversal(h, nullptr, tap_traversal(plan_scene(h)), RayKind::Closest, q, st0, 0, Npad / WG, nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipMemcpyAsync(rd.data(), st0.ray_d, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2253,9 +2164,7 @@ int polaris_hip_probe(polaris_hip_tracer *h, int kind, uint32_t index, uint32_t 
 	HIP_TRY(h, d_in.alloc(nin));
 	HIP_TRY(h, d_out.alloc(nout));
 	HIP_TRY(h, hipMemcpyAsync(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice, q));
-	const bool staged = h->opt_stage_lds && h->ds.scene.num_nodes <= kLdsMatNodes && h->ds.scene.num_emissives <= kLdsLights &&
-	                    h->ds.scene.num_textures <= kLdsTextures;
-	if (staged) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->ds.scene, kind, index, n, d_in, d_out);
+	if (tables_staged(h->opt, plan_scene(h))) hipLaunchKernelGGL(k_probe<true>, dim3(grid_for(n)), dim3(WG), 0, q, h->ds.scene, kind, index, n, d_in, d_out);
 	else hipLaunchKernelGGL(k_probe<false>, dim3(grid_for(n)), dim3(WG), 0, q, h->ds.scene, kind, index, n, d_in, d_out);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost, q));
@@ -2287,17 +2196,9 @@ int polaris_hip_probe_intersect(polaris_hip_tracer *h, const float *rays, uint32
 	HIP_TRY(h, d_rays.alloc((size_t)n * 8));
 	HIP_TRY(h, hipMemcpyAsync(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, q));
 	hipLaunchKernelGGL(k_probe_rays, dim3(wgs), dim3(WG), 0, q, P.st, d_rays, n, any_hit ? 1 : 0);
-	// the traversal kernel the options select for bounce rays (any_hit: shadow rays); packet_primary=1 sends closest-hit
-	// probes through the wave-packet kernel instead
-	if (any_hit) {
-		if (h->opt_packet_shadow > 0) kPacket[kPacketAnyHit].enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, P.st.lsum, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace(h, nullptr, true, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->ds.trace[1].resident_per_cu)), wgs, P.st.lsum);
-		else kOcclusion.enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, P.st.lsum, h->d_stats);
-	} else {
-		if (h->opt_packet_primary == 1) kPacket[kPacketClosest].enqueue(wgs, WG, 0, q, P.st, h->ds.bvh, nullptr, h->d_stats, h->cam.eye);
-		else if (h->opt_traversal) (void)launch_trace(h, nullptr, false, q, P.st, std::min<uint32_t>(wgs, (uint32_t)h->num_cus * (uint32_t)std::max(1, h->ds.trace[0].resident_per_cu)), wgs, nullptr);
-		else kIntersect.enqueue(wgs, WG, 0, q, P.st, h->ds.bvh);
-	}
+	// the traversal kernel the options select for bounce rays (any_hit: shadow rays; trace_plan.h, probe_traversal)
+	const RayKind kind = any_hit ? RayKind::AnyHit : RayKind::Closest;
+	(void)launch_traversal(h, nullptr, probe_traversal(h->opt, kind), kind, q, P.st, probe_grid(plan_scene(h), any_hit != 0, wgs), wgs, any_hit ? P.st.lsum : nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(res.data(), any_hit ? P.st.lsum : P.st.hit, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, q));
 	HIP_TRY(h, hipStreamSynchronize(q));
