@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include "device_mem.h"
+#include "frame_sync.h"
 #include "kernel_table.h"
 #include "polaris_hip.h"
 #include "trace_plan.h"
@@ -90,6 +91,53 @@ struct DeviceScene {
 	InstanceUpdateState upd; VertexUpdateState vup; // kept with the options "instance_update" / "vertex_update" at upload
 };
 
+// Everything behind the features of polaris_hip_sync_framebuffer: the parameters of denoising (polaris_hip_set_denoise),
+// temporal reuse across camera moves (_set_temporal) and variance guidance (_set_variance), the option "object_motion", every plane
+// they use and what of the planes is valid.  frame_sync.h holds the rules: nothing is allocated while its feature is off, the history
+// is the TEMPORAL plane, G-buffer, camera and (object motion) INSTANCE plane and instance table of the last temporal sync before the
+// latest change, swapped in by capture().  Each member below pairs ONE transition of SyncState with the planes it frees or swaps, so
+// the two cannot drift apart; nothing else assigns a validity flag.  Callers hold mu; where planes may go every stream is idle.
+struct FrameSync {
+	PolarisDenoiseParams dn{sizeof(PolarisDenoiseParams), 0, 0, 0.0f, 0.0f};
+	PolarisTemporalParams tp{sizeof(PolarisTemporalParams), 0, 0.0f, 0.0f};
+	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
+	int opt_object_motion = 0;
+	SyncState v;
+	DevArray<float4> pl[kNumPlanes4];     // the float4 planes, by Plane
+	DevArray<uint32_t> gb_inst, tp_hinst; // kInst, kHInst
+	DevArray<float4> mo_table;            // kMoTable
+	std::vector<float> mo_table_host;
+	CameraArgs tp_hcam{};                 // the history's camera
+
+	SyncFeatures features() const { return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0}; }
+	void drop(uint32_t set) {
+		for (uint32_t p = 0; p < kNumPlanes4; p++)
+			if (set >> p & 1) pl[p].reset();
+		if (set & kMotionPlanes) { gb_inst.reset(); tp_hinst.reset(); mo_table.reset(); } // (they go together; ensure_gbuffer recomputes the G-buffer when gb_inst is wanted and missing)
+	}
+	void capture(uint32_t swaps, const CameraArgs &cam) { // cam: what the planes that join the history were seen under
+		constexpr Plane twin[][2] = {{kTpOut, kTpHist}, {kGuide, kTpHGuide}, {kAlbedo, kTpHAlbedo}, {kVaOut, kVaHist}};
+		for (auto &t : twin)
+			if (swaps >> t[0] & 1) std::swap(pl[t[0]], pl[t[1]]);
+		if (swaps >> kInst & 1) std::swap(gb_inst, tp_hinst);
+		if (swaps) tp_hcam = cam;
+	}
+	void resized() { drop(v.resized()); }
+	void camera_moved(const CameraArgs &old) { capture(v.camera_moved(features()), old); }
+	void scene_changed(const InstTable *next, const CameraArgs &cam) { capture(v.scene_changed(features(), next), cam); } // (upload_scene and the in-place updates, before they change the scene)
+	void set_temporal(const PolarisTemporalParams &p) {
+		if (p.max_history == 0) { if (tp.max_history) drop(v.temporal_off()); }
+		else if (p.max_history != tp.max_history || pm_f2u(p.normal_threshold) != pm_f2u(tp.normal_threshold) || pm_f2u(p.depth_threshold) != pm_f2u(tp.depth_threshold))
+			v.temporal_params_changed();
+		tp = p;
+	}
+	void set_variance(const PolarisVarianceParams &p) {
+		if ((p.sigma_variance != 0.0f) != (va.sigma_variance != 0.0f)) drop(v.variance_toggled(p.sigma_variance != 0.0f));
+		va = p;
+	}
+	void set_object_motion(int on) { opt_object_motion = on; drop(v.motion_toggled(on != 0)); } // (on differs from the option's value)
+};
+
 } // namespace
 
 // Every stream, event and device allocation of the handle is a member that owns it (device_mem.h), so `delete h` releases
@@ -149,63 +197,9 @@ struct polaris_hip_tracer {
 	bool have_camera = false;
 	CameraArgs cam{};
 
-	// denoising of the synced frame (polaris_hip_set_denoise; kernels.h k_gbuffer / k_denoise).  Nothing is allocated while it
-	// is off: the G-buffer planes on first use (denoised sync or read_aov), the filter's three planes at the first denoised sync.
-	// All five are frame-sized float4 (80 B per pixel) and go with the frame buffers on resize.
-	PolarisDenoiseParams dn{sizeof(PolarisDenoiseParams), 0, 0, 0.0f, 0.0f};
-	DevArray<float4> gb_guide, gb_albedo;             // GUIDE / ALBEDO planes
-	bool gb_valid = false;                            // computed for the current scene, camera and frame size
-	DevArray<float4> dn_out, dn_ping, dn_pong;        // DENOISED plane, iteration buffers
-	bool dn_valid = false;                            // a denoised sync has written dn_out since the last resize
-
-	// temporal reuse across camera moves (polaris_hip_set_temporal; kernels.h k_reproject / k_temporal).  Nothing is allocated
-	// while it is off.  The history is the TEMPORAL plane, G-buffer and camera of the last temporal sync before the latest
-	// set_camera, which swaps the pointers (tp_out <-> tp_hist, gb_guide <-> tp_hguide, gb_albedo <-> tp_halbedo).  All five
-	// planes are frame-sized float4; resize frees them, upload_scene and max_history = 0 drop the history.
-	PolarisTemporalParams tp{sizeof(PolarisTemporalParams), 0, 0.0f, 0.0f};
-	DevArray<float4> tp_out, tp_prior;               // TEMPORAL / PRIOR planes
-	DevArray<float4> tp_hist, tp_hguide, tp_halbedo; // the history
-	CameraArgs tp_hcam{};
-	bool tp_have_hist = false;
-	bool tp_synced = false;      // a temporal sync ran under the current camera (tp_out and the G-buffer are this camera's)
-	bool tp_prior_valid = false; // tp_prior is the current history reprojected into the current camera with the current params
-
-	// temporal reuse across moving instances (option "object_motion").  In effect (motion_on) only with temporal
-	// reuse on; no device memory below is allocated otherwise.  The INSTANCE plane (one word per pixel, k_gbuffer) is swapped into
-	// the history like the G-buffer planes, and the history carries the instance table it was seen with; upload_scene keeps a
-	// history whose table is compatible with the new scene's.  The current scene's table is a host copy made by an upload with the
-	// option on (68 bytes an instance).  When the option is turned on after the scene, the matrices are read back from the device's
-	// instance records; the mesh indices are not there, so such a table is compatible with nothing: camera moves reuse the history
-	// at once, the first upload after it drops the history as without the option, and from that upload on the table is complete.
-	struct InstTable {
-		std::vector<uint32_t> mesh_index;
-		std::vector<float> inv; // 16 floats of inv_transform per instance
-		uint32_t num_triangles = 0;
-		bool topology_known = false; // mesh_index and num_triangles are the scene's
-		bool compatible(const InstTable &o) const {
-			return topology_known && o.topology_known && mesh_index == o.mesh_index && num_triangles == o.num_triangles;
-		}
-	};
-	int opt_object_motion = 0;
-	InstTable mo_cur, mo_hist;           // the current scene's instance table, the history's
-	DevArray<uint32_t> gb_inst, tp_hinst; // INSTANCE plane, the history's
-	DevArray<float4> mo_table;           // motion table of the last PRIOR (temporal.h tp_motion_table), grow-only until free_temporal
-	std::vector<float> mo_table_host;
-
+	FrameSync fs; // the synced frame's features, planes and history
 	int opt_instance_update = 0, opt_vertex_update = 0; // the in-place updates: the next upload keeps what they need in ds.upd / ds.vup
-
-	// variance guidance (polaris_hip_set_variance; kernels.h k_variance / k_denoise_variance).  It needs the option "moments"
-	// (k_resolve<true> / k_aggregate<true> keep the sum of L^2 in the accumulators' .w), read by merges under merge_mu, hence atomic.
-	// Nothing is allocated while it is off: the VARIANCE plane at the first variance sync.  With temporal reuse on as well,
-	// set_camera swaps va_out <-> va_hist like the TEMPORAL plane, and k_reproject<true> gathers the history's M2 into tp_prior2
-	// (h2 | 0 | 0 | m); both go when either feature goes (free_moment_history).
-	std::atomic<bool> opt_moments{false};
-	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
-	DevArray<float4> va_out;                      // VARIANCE plane (M1 | M2 | n_eff | v)
-	bool va_valid = false;                        // a variance sync has written va_out (under the current camera with temporal reuse)
-	DevArray<float4> va_hist, tp_prior2;
-	bool va_synced = false;   // temporal: a variance sync ran under the current camera (va_out is this camera's, cleared at its first sync)
-	bool va_have_hist = false; // temporal: va_hist belongs to the history
+	std::atomic<bool> opt_moments{false}; // option "moments" (the accumulators' .w keeps the sum of L^2; variance guidance needs it): merges read it under merge_mu, hence atomic
 
 	// wavefront batch state: up to kMaxPipes pipelines (option "overlap", default 4; a Trace uses min(overlap, #batches) of
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
@@ -469,107 +463,51 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
 
-// The free_* below: caller holds mu, every stream idle.  Every lazily allocated plane (ensure_plane) is reset by exactly one of them.
-void free_moment_history(polaris_hip_tracer *h) { // what exists only with temporal reuse AND variance guidance on: goes when either goes
-	h->va_hist.reset();
-	h->tp_prior2.reset();
-	h->va_synced = h->va_have_hist = false;
-}
-
-void free_temporal(polaris_hip_tracer *h) {
-	for (auto *p : {&h->tp_out, &h->tp_prior, &h->tp_hist, &h->tp_hguide, &h->tp_halbedo}) p->reset();
-	h->tp_have_hist = h->tp_synced = h->tp_prior_valid = false;
-	h->gb_inst.reset(); // (written only with temporal reuse on: ensure_gbuffer recomputes the G-buffer when it is wanted and missing)
-	h->tp_hinst.reset();
-	h->mo_table.reset();
-	free_moment_history(h);
-}
-
-void free_variance(polaris_hip_tracer *h) {
-	h->va_out.reset();
-	h->va_valid = false;
-}
-
-void free_denoise(polaris_hip_tracer *h) {
-	for (auto *p : {&h->gb_guide, &h->gb_albedo, &h->dn_out, &h->dn_ping, &h->dn_pong}) p->reset();
-	h->gb_valid = h->dn_valid = false;
-}
-
-// A frame-sized plane (F pixels) that exists from its first use on (caller holds mu).
-template <class T>
-int ensure_plane(polaris_hip_tracer *h, DevArray<T> &plane, size_t F) {
-	if (!plane) HIP_TRY(h, plane.alloc(F));
-	return POLARIS_OK;
-}
-
-// The filter's DENOISED plane and its two iteration buffers.
-int ensure_filter_planes(polaris_hip_tracer *h, size_t F) {
-	for (auto *p : {&h->dn_out, &h->dn_ping, &h->dn_pong})
-		if (int rc = ensure_plane(h, *p, F)) return rc;
-	return POLARIS_OK;
-}
-
-// Object motion is in effect: the option is on and temporal reuse is on.
-bool motion_on(const polaris_hip_tracer *h) { return h->opt_object_motion && h->tp.max_history; }
-
-// The GUIDE / ALBEDO planes of the current scene, camera and frame size (with object motion the INSTANCE plane too), computed if
-// they are not (caller holds mu; checks done).
-int ensure_gbuffer(polaris_hip_tracer *h) {
-	const bool want_inst = motion_on(h);
-	if (h->gb_valid && (!want_inst || h->gb_inst)) return POLARIS_OK;
+// The planes of the set `need` exist from their first use on, each of the frame's size; those of `clear` are cleared on the main stream,
+// those of `clear_new` if they are allocated here (caller holds mu).
+int ensure_planes(polaris_hip_tracer *h, uint32_t need, uint32_t clear = 0, uint32_t clear_new = 0) {
+	FrameSync &S = h->fs;
 	const size_t F = (size_t)h->W * h->H;
-	if (int rc = ensure_plane(h, h->gb_guide, F)) return rc;
-	if (int rc = ensure_plane(h, h->gb_albedo, F)) return rc;
-	if (want_inst)
-		if (int rc = ensure_plane(h, h->gb_inst, F)) return rc;
+	for (uint32_t p = 0; p < kNumPlanes4; p++) {
+		if (!(need >> p & 1)) continue;
+		if (!S.pl[p]) { HIP_TRY(h, S.pl[p].alloc(F)); clear |= clear_new & 1u << p; }
+		if (clear >> p & 1) HIP_TRY(h, hipMemsetAsync(S.pl[p], 0, F * sizeof(float4), h->stream));
+	}
+	if ((need >> kInst & 1) && !S.gb_inst) HIP_TRY(h, S.gb_inst.alloc(F));
+	return POLARIS_OK;
+}
+
+// The GUIDE / ALBEDO planes of the current scene, camera and frame size (with object motion in effect the INSTANCE plane too), computed
+// if they are not (caller holds mu; checks done).
+int ensure_gbuffer(polaris_hip_tracer *h) {
+	FrameSync &S = h->fs;
+	const bool want_inst = S.features().motion_on();
+	if (S.v.gbuffer() && (!want_inst || S.gb_inst)) return POLARIS_OK;
+	const size_t F = (size_t)h->W * h->H;
+	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0))) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
-	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->W, (uint32_t)F, h->gb_guide, h->gb_albedo,
-	             want_inst ? h->gb_inst.get() : nullptr);
+	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
+	             want_inst ? S.gb_inst.get() : nullptr);
 	HIP_TRY(h, hipGetLastError());
-	h->gb_valid = true;
+	S.v.gbuffer_computed();
 	return POLARIS_OK;
 }
 
-// The last temporal sync's planes under the current camera (and, with object motion, the current scene's instance table) become
-// the history; no sync under them: the older history stays.  set_camera and, with object motion, scene_changed call it before they
-// change what the planes were seen with (caller holds mu, temporal reuse on).
-void capture_history(polaris_hip_tracer *h) {
-	if (!h->tp_synced) return;
-	std::swap(h->tp_out, h->tp_hist);
-	std::swap(h->gb_guide, h->tp_hguide);
-	std::swap(h->gb_albedo, h->tp_halbedo);
-	h->tp_hcam = h->cam;
-	h->tp_have_hist = true;
-	if (motion_on(h)) {
-		std::swap(h->gb_inst, h->tp_hinst);
-		h->mo_hist = h->mo_cur;
+// The option "object_motion" was turned on after the upload: the scene's matrices come back from the device's instance records (rows 0-2
+// of inv_transform, all the traversal and the motion table use); the mesh indices do not (InstTable::topology_known).  Main stream idle.
+int read_back_instances(polaris_hip_tracer *h) {
+	std::vector<InstH> recs(h->ds.num_insts);
+	HIP_TRY(h, hipMemcpy(recs.data(), h->ds.bvh.insts, recs.size() * sizeof(InstH), hipMemcpyDeviceToHost));
+	InstTable &cur = h->fs.v.cur;
+	cur.mesh_index.assign(h->ds.num_insts, 0u);
+	cur.inv.assign((size_t)h->ds.num_insts * 16, 0.0f);
+	for (uint32_t i = 0; i < h->ds.num_insts; i++) {
+		float *m = cur.inv.data() + 16 * (size_t)i; // column major: m[4 * c + r]
+		for (int c = 0; c < 4; c++) { m[4 * c + 0] = recs[i].r0[c]; m[4 * c + 1] = recs[i].r1[c]; m[4 * c + 2] = recs[i].r2[c]; }
+		m[15] = 1.0f;
 	}
-	// (the VARIANCE plane joins the history only if it was written under the same camera; else the history has no M2)
-	if (h->va_synced) std::swap(h->va_out, h->va_hist);
-	h->va_have_hist = h->va_synced;
-}
-
-// Nothing synced so far was seen under what holds from now on: the camera (set_camera) or the scene (scene_changed).
-void forget_syncs(polaris_hip_tracer *h) { h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_valid = false; }
-
-// What a change of the scene does to the G-buffer and the temporal history (upload_scene and the in-place updates, before they change
-// it; caller holds mu, every stream idle).  next: the instance table of the scene to come, which becomes mo_cur.  With object motion
-// the change is to the history what a camera move is: the planes synced under the old scene join it, and it survives if the scene to
-// come has the same instances of the same meshes (temporal.h: k_reproject carries a hit back through the two tables).  Otherwise,
-// and always with next = null (mo_cur stays), the history saw another scene and goes.
-void scene_changed(polaris_hip_tracer *h, const polaris_hip_tracer::InstTable *next) {
-	h->gb_valid = false;
-	bool keep = false;
-	if (next && motion_on(h)) {
-		capture_history(h);
-		keep = h->tp_have_hist && h->mo_hist.compatible(*next);
-	}
-	if (h->tp.max_history) {
-		if (!keep) h->tp_have_hist = h->va_have_hist = false;
-		forget_syncs(h);
-	}
-	if (next) h->mo_cur = *next;
+	return POLARIS_OK;
 }
 
 // The record of the scene's one top-level instance travels in the kernel arguments: its matrix rows from the layout's or an update's record.
@@ -1079,9 +1017,7 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	std::lock_guard<std::mutex> lk_merge(h->merge_mu); // (the frame accumulator is the merge stream's)
 	HIP_TRY(h, sync_all(h));
 	free_ring(h); // (an IPC export dies with the buffers: peers close, the tracer exports again)
-	free_denoise(h);
-	if (h->tp.max_history) free_temporal(h);
-	if (h->va.sigma_variance != 0.0f) free_variance(h);
+	h->fs.resized();
 	h->frame_acc.reset();
 	h->framebuffer.reset();
 	h->W = h->H = 0;
@@ -1108,8 +1044,8 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 	if (int rc = make_idle(h)) return rc;
 	h->ds = DeviceScene(); // the old scene goes before the new one is allocated: a large one may not fit twice
 	// 2. the history, judged by the instance table of the scene to come (kept with object motion only)
-	polaris_hip_tracer::InstTable next;
-	if (h->opt_object_motion) {
+	InstTable next;
+	if (h->fs.opt_object_motion) {
 		next.num_triangles = sc->num_triangles;
 		next.topology_known = true;
 		next.mesh_index.resize(sc->num_mesh_instances);
@@ -1119,7 +1055,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 			memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
 		}
 	}
-	scene_changed(h, &next);
+	h->fs.scene_changed(&next, h->cam);
 	// 3. the arrays, with the triangle of every area light packed (shading.h, SceneT::light_geo); 4. what the updates keep
 	std::vector<float> geo((size_t)sc->num_emissives * kLightGeoFloats, 0.0f);
 	pack_light_geo(sc->emissives, sc->num_emissives, sc->vertices, sc->normals, sc->uvs, geo.data());
@@ -1150,9 +1086,9 @@ int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpd
 	if (int rc = make_idle(h)) return rc;
 	// to the temporal history the update is what an upload is: with object motion the planes synced under the old matrices join the
 	// history, which stays -- instances and meshes are the same; without, the history saw the old scene and goes
-	polaris_hip_tracer::InstTable next = h->mo_cur;
-	if (h->opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
-	scene_changed(h, &next);
+	InstTable next = h->fs.v.cur;
+	if (h->fs.opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
+	h->fs.scene_changed(&next, h->cam);
 	if (h->ds.vup.on) h->ds.vup.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
 	return finish_update(h, recs, pads, u->emissives, geo);
 }
@@ -1176,8 +1112,8 @@ int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate
 	// ---- accepted: from here on the state changes ----
 	if (int rc = make_idle(h)) return rc;
 	h->ds.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
-	scene_changed(h, nullptr); // the history never saw this scene
-	if (h->opt_object_motion && u->inv_transforms && h->mo_cur.inv.size() == (size_t)NI * 16) h->mo_cur.inv.assign(inv, inv + (size_t)NI * 16);
+	h->fs.scene_changed(nullptr, h->cam); // the history never saw this scene
+	if (h->fs.opt_object_motion && u->inv_transforms && h->fs.v.cur.inv.size() == (size_t)NI * 16) h->fs.v.cur.inv.assign(inv, inv + (size_t)NI * 16);
 	if (int rc = refit_meshes(h, u)) return rc;
 	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
 	if (int rc = finish_update(h, recs, pads, u->emissives, geo)) return rc;
@@ -1206,10 +1142,7 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
-	if (h->tp.max_history) {
-		capture_history(h); // the last temporal sync's planes under the old camera become the history
-		forget_syncs(h);
-	}
+	h->fs.camera_moved(h->cam); // (with temporal reuse the last temporal sync's planes under the old camera become the history)
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
 	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
 	h->cam.bl = make_float4(fr[8], fr[9], fr[10], fr[11]);
@@ -1220,7 +1153,6 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
 	HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
 	h->have_camera = true;
-	h->gb_valid = false;
 	return POLARIS_OK;
 }
 
@@ -1235,7 +1167,7 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 		h->opt.exact = value != 0;
 	} else if (k == "moments") {
 		if (value != 0 && h->opt.exact) return fail(h, POLARIS_E_UNSUPPORTED, "moments need per-sample radiance: exact_accumulate cannot keep them");
-		if (value == 0 && h->va.sigma_variance != 0.0f) return fail(h, POLARIS_E_BAD_ARGUMENT, "moments cannot be turned off while variance guidance is on");
+		if (value == 0 && h->fs.va.sigma_variance != 0.0f) return fail(h, POLARIS_E_BAD_ARGUMENT, "moments cannot be turned off while variance guidance is on");
 		h->opt_moments = value != 0;
 	}
 	else if (k == "packet_primary") { h->opt.packet_primary = value < 0 ? -1 : (value != 0); if (value >= 0) h->packet_primary = value != 0; }
@@ -1259,34 +1191,12 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "lds_tris") h->opt_lds_tris = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); // next upload
 	else if (k == "object_motion") {
 		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "object_motion is 0 or 1");
-		if ((int)value != h->opt_object_motion) { // the history (with or without an INSTANCE plane) and the G-buffer go with the old setting
-			h->opt_object_motion = (int)value;
-			h->tp_have_hist = h->tp_synced = h->tp_prior_valid = h->va_synced = h->va_have_hist = h->va_valid = false;
-			h->gb_valid = false;
-			h->mo_hist = polaris_hip_tracer::InstTable();
-			h->mo_cur = polaris_hip_tracer::InstTable(); // (kept with the option on only)
-			if (value && h->ds.have_scene) {
-				// the scene was uploaded with the option off: its matrices come back from the device's instance records (rows 0-2 of
-				// inv_transform, all the traversal and the motion table use); the mesh indices do not (InstTable::topology_known)
-				std::vector<InstH> recs(h->ds.num_insts);
-				HIP_TRY(h, hipSetDevice(h->device));
-				HIP_TRY(h, hipStreamSynchronize(h->stream));
-				HIP_TRY(h, hipMemcpy(recs.data(), h->ds.bvh.insts, recs.size() * sizeof(InstH), hipMemcpyDeviceToHost));
-				h->mo_cur.mesh_index.assign(h->ds.num_insts, 0u);
-				h->mo_cur.inv.assign((size_t)h->ds.num_insts * 16, 0.0f);
-				for (uint32_t i = 0; i < h->ds.num_insts; i++) {
-					float *m = h->mo_cur.inv.data() + 16 * (size_t)i; // column major: m[4 * c + r]
-					for (int c = 0; c < 4; c++) { m[4 * c + 0] = recs[i].r0[c]; m[4 * c + 1] = recs[i].r1[c]; m[4 * c + 2] = recs[i].r2[c]; }
-					m[15] = 1.0f;
-				}
-			}
-			if (!value && (h->gb_inst || h->tp_hinst || h->mo_table)) { // what exists only with the option on goes with it
-				HIP_TRY(h, hipSetDevice(h->device));
-				HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every launch that uses them is on the main stream)
-				h->gb_inst.reset();
-				h->tp_hinst.reset();
-				h->mo_table.reset();
-			}
+		if ((int)value != h->fs.opt_object_motion) {
+			HIP_TRY(h, hipSetDevice(h->device));
+			HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every launch that uses the planes that go is on the main stream)
+			h->fs.set_object_motion((int)value);
+			if (value && h->ds.have_scene)
+				if (int rc = read_back_instances(h)) return rc;
 		}
 	}
 	else if (k == "instance_update") { // next upload
@@ -1783,44 +1693,6 @@ int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 } // extern "C"
 
 namespace {
-// The filter and its tone-map on stream q (caller holds mu): the p.iterations a-trous iterations over the rows [y0, y1) of acc * weight
-// guided by (guide, albedo), through ping / pong into the DENOISED plane out, then out's rows tone-mapped with weight 1 into fb.
-// polaris_hip_sync_framebuffer and the test entry polaris_hip_denoise_planes both launch the filter through here.
-void launch_denoise(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, float weight, const float4 *guide, const float4 *albedo,
-                    float4 *ping, float4 *pong, float4 *out, uchar4 *fb, uint32_t W, uint32_t y0, uint32_t y1, float exposure,
-                    const PolarisDenoiseParams &p) {
-	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
-	{
-		Timed t(h, "denoise", kDenoise.symbol, q); // (one bracket around the K iterations)
-		const uint32_t K = p.iterations;
-		const float4 *in = nullptr;
-		for (uint32_t k = 0; k < K; k++) {
-			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
-			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, p.sigma_luminance);
-			kDenoise.enqueue(grid_for(n), WG, 0, q, acc, weight, guide, albedo, in, dst, W, y0, y1, it, k + 1 == K ? 1 : 0);
-			in = dst;
-		}
-	}
-	(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
-}
-
-// polaris_hip_sync_framebuffer with denoising on (caller holds mu; request checked): G-buffer if stale, K filter iterations over
-// the request's rows into the DENOISED plane, then the same tone-map over that plane with weight 1.
-int sync_denoised(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "denoising needs the camera (UpdateState CameraData)");
-	const size_t F = (size_t)h->W * h->H;
-	if (int rc = ensure_gbuffer(h)) return rc;
-	if (int rc = ensure_filter_planes(h, F)) return rc;
-	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	launch_denoise(h, h->stream, h->frame_acc, weight, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W,
-	               r->block_y, r->block_y + r->block_h, r->exposure, h->dn);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->dn_valid = true;
-	collect_timers(h);
-	return POLARIS_OK;
-}
-
 TpCamera tp_camera(const CameraArgs &c) {
 	return TpCamera{{c.tl.x, c.tl.y, c.tl.z, c.tl.w}, {c.tr.x, c.tr.y, c.tr.z, c.tr.w}, {c.bl.x, c.bl.y, c.bl.z, c.bl.w},
 	                {c.br.x, c.br.y, c.br.z, c.br.w}, {c.eye.x, c.eye.y, c.eye.z}};
@@ -1853,115 +1725,100 @@ hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *
 	return hipGetLastError();
 }
 
-// The variance launches of a sync on stream q (caller holds mu): k_variance over the rows [y0, y1) into var (the frame accumulator acc
-// with sync's n and weight; with temporal reuse the TEMPORAL plane tp and PRIOR2 prior2, else both null), then, with p.iterations > 0,
-// the variance-guided filter through ping / pong into out and out's rows tone-mapped with weight 1; with p.iterations = 0 the tone-map
-// of the plain (or temporal) sync, unchanged.  polaris_hip_sync_framebuffer and polaris_hip_variance_planes both launch through here.
-void launch_variance(polaris_hip_tracer *h, hipStream_t q, const float4 *acc, float nf, float weight, const float4 *tp, const float4 *prior2,
-                     const float4 *guide, const float4 *albedo, float4 *var, float4 *ping, float4 *pong, float4 *out, uchar4 *fb, uint32_t W,
-                     uint32_t y0, uint32_t y1, float exposure, const PolarisDenoiseParams &p, const PolarisVarianceParams &v) {
-	const size_t off = (size_t)y0 * W, n = (size_t)(y1 - y0) * W;
-	(void)launch(h, "variance", q, kVariance, grid_for(n), WG, 0, acc, nf, weight, tp, prior2, guide, albedo, var, W, y0, y1, dn_iter(0, p.normal_power_log2, p.sigma_depth, 0.0f), v.min_samples);
-	const float4 *c = tp ? tp : acc; // (the filter's and the tone-map's input: TEMPORAL with weight 1, or the accumulator)
-	const float cw = tp ? 1.0f : weight;
-	if (p.iterations == 0) {
-		(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, c + off, fb + off, (uint32_t)n, cw, exposure);
-		return;
-	}
-	{
-		Timed t(h, "denoise_variance", kDenoiseVariance.symbol, q); // (one bracket around the K iterations)
-		const uint32_t K = p.iterations;
+struct SyncIo { // what the steps of a sync read and write: the rows [y0, y1) of planes W wide (tp, prior, prior2: TEMPORAL, PRIOR, PRIOR2 with temporal reuse)
+	const float4 *acc; float nf, weight;
+	float4 *tp; const float4 *prior, *prior2, *guide, *albedo;
+	float4 *var, *ping, *pong, *out; uchar4 *fb;
+	uint32_t W, y0, y1; float exposure;
+};
+
+// The timed steps of a sync on stream q, in the plan's order (frame_sync.h plan_sync; caller holds mu): k_temporal into TEMPORAL, k_variance
+// into VARIANCE, the filter (variance-guided or not) over the plan's colour -- TEMPORAL with weight 1, or the accumulator with the sync's
+// weight -- into DENOISED, and the tone-map of the plan's source.  polaris_hip_sync_framebuffer and the test entries
+// polaris_hip_denoise_planes / _variance_planes all launch through here.
+void launch_steps(polaris_hip_tracer *h, hipStream_t q, const SyncPlan &P, const SyncIo &io, const PolarisDenoiseParams &p, const PolarisVarianceParams &v) {
+	const size_t off = (size_t)io.y0 * io.W, n = (size_t)(io.y1 - io.y0) * io.W;
+	const uint32_t grid = grid_for(n), W = io.W, y0 = io.y0, y1 = io.y1;
+	const bool temporal = P.color == SyncSource::Temporal, filtered = P.tonemap == SyncSource::Denoised;
+	const float4 *c = temporal ? io.tp : io.acc, *tp = temporal ? io.tp : nullptr, *prior2 = temporal ? io.prior2 : nullptr;
+	const float cw = temporal ? 1.0f : io.weight;
+	// THE a-trous loop: the iterations of one filter variant under one timer bracket, through ping / pong into out.  enqueue(in, dst, it,
+	// last) launches iteration `it` from `in` (null: the filter's own input) into dst.
+	auto atrous = [&](const char *timer, const char *symbol, float sigma_luminance, auto enqueue) {
+		Timed t(h, timer, symbol, q);
 		const float4 *in = nullptr;
-		for (uint32_t k = 0; k < K; k++) {
-			float4 *dst = k + 1 == K ? out : (k % 2 == 0 ? ping : pong);
-			const DnIter it = dn_iter(k, p.normal_power_log2, p.sigma_depth, 0.0f);
-			kDenoiseVariance.enqueue(grid_for(n), WG, 0, q, c, cw, var, guide, albedo, in, dst, W, y0, y1, it, v.sigma_variance, k + 1 == K ? 1 : 0);
+		for (uint32_t k = 0; k < p.iterations; k++) {
+			float4 *dst = k + 1 == p.iterations ? io.out : (k % 2 == 0 ? io.ping : io.pong);
+			enqueue(in, dst, dn_iter(k, p.normal_power_log2, p.sigma_depth, sigma_luminance), k + 1 == p.iterations ? 1 : 0);
 			in = dst;
 		}
+	};
+	for (int s = 0; s < P.n_steps; s++) {
+		const SyncStep step = P.steps[s];
+		const char *timer = kSyncStepTimer[(int)step];
+		if (step == SyncStep::Temporal) (void)launch(h, timer, q, kTemporal, grid, WG, 0, io.acc, io.prior, io.tp, W, y0, y1, io.nf, io.weight);
+		else if (step == SyncStep::Variance)
+			(void)launch(h, timer, q, kVariance, grid, WG, 0, io.acc, io.nf, io.weight, tp, prior2, io.guide, io.albedo, io.var, W, y0, y1, dn_iter(0, p.normal_power_log2, p.sigma_depth, 0.0f), v.min_samples);
+		else if (step == SyncStep::Denoise)
+			atrous(timer, kDenoise.symbol, p.sigma_luminance, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoise.enqueue(grid, WG, 0, q, c, cw, io.guide, io.albedo, in, dst, W, y0, y1, it, last); });
+		else if (step == SyncStep::DenoiseVariance)
+			atrous(timer, kDenoiseVariance.symbol, 0.0f, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoiseVariance.enqueue(grid, WG, 0, q, c, cw, io.var, io.guide, io.albedo, in, dst, W, y0, y1, it, v.sigma_variance, last); });
+		else (void)launch(h, timer, q, kTonemap, grid, WG, 0, (filtered ? io.out : c) + off, io.fb + off, (uint32_t)n, filtered ? 1.0f : cw, io.exposure);
 	}
-	(void)launch(h, "tonemap", q, kTonemap, grid_for(n), WG, 0, out + off, fb + off, (uint32_t)n, 1.0f, exposure);
 }
 
-// polaris_hip_sync_framebuffer with variance guidance on and temporal reuse off (caller holds mu; request checked): G-buffer if
-// stale, then launch_variance over the request's rows.
-int sync_variance(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "variance guidance needs the camera (UpdateState CameraData)");
-	const size_t F = (size_t)h->W * h->H;
+// What polaris_hip_sync_framebuffer queues with denoising, temporal reuse or variance guidance on (caller holds mu; request checked), by
+// the plan of frame_sync.h: G-buffer if stale, the planes the features need, TEMPORAL / VARIANCE cleared at their first sync under this
+// camera, PRIOR if stale, the merges queued so far, then the timed steps over the request's rows.
+int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight, const SyncFeatures &f) {
+	FrameSync &S = h->fs;
+	if (!h->have_camera)
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "%s needs the camera (UpdateState CameraData)", f.temporal ? "temporal reuse" : (f.variance ? "variance guidance" : "denoising"));
+	const SyncPlan P = plan_sync(f, S.v);
 	if (int rc = ensure_gbuffer(h)) return rc;
-	if (!h->va_out) {
-		if (int rc = ensure_plane(h, h->va_out, F)) return rc;
-		HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream));
-	}
-	if (h->dn.iterations)
-		if (int rc = ensure_filter_planes(h, F)) return rc;
-	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
-	launch_variance(h, h->stream, h->frame_acc, nf, weight, nullptr, nullptr, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong, h->dn_out,
-	                h->framebuffer, h->W, r->block_y, r->block_y + r->block_h, r->exposure, h->dn, h->va);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->va_valid = true;
-	if (h->dn.iterations) h->dn_valid = true;
-	collect_timers(h);
-	return POLARIS_OK;
-}
-
-// polaris_hip_sync_framebuffer with temporal reuse on (caller holds mu; request checked): G-buffer if stale, TEMPORAL cleared at
-// the first temporal sync under this camera, PRIOR if stale, the TEMPORAL rows of the request, then the filter (if on) or the
-// tone-map over them with weight 1.
-int sync_temporal(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight) {
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "temporal reuse needs the camera (UpdateState CameraData)");
-	const size_t F = (size_t)h->W * h->H, off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
-	const uint32_t y0 = r->block_y, y1 = r->block_y + r->block_h;
-	if (int rc = ensure_gbuffer(h)) return rc;
-	if (int rc = ensure_plane(h, h->tp_out, F)) return rc;
-	if (int rc = ensure_plane(h, h->tp_prior, F)) return rc;
-	if (h->dn.iterations)
-		if (int rc = ensure_filter_planes(h, F)) return rc;
-	const bool var = h->va.sigma_variance != 0.0f;
-	if (var) {
-		if (int rc = ensure_plane(h, h->va_out, F)) return rc;
-		if (int rc = ensure_plane(h, h->tp_prior2, F)) return rc;
-		if (!h->va_synced) HIP_TRY(h, hipMemsetAsync(h->va_out, 0, F * sizeof(float4), h->stream)); // (as TEMPORAL: rows no sync reaches)
-		h->va_synced = true;
-	}
-	if (!h->tp_synced) HIP_TRY(h, hipMemsetAsync(h->tp_out, 0, F * sizeof(float4), h->stream)); // (rows no sync reaches: no history)
-	h->tp_synced = true;
-	if (!h->tp_prior_valid) {
+	if (int rc = ensure_planes(h, P.need, P.clear, P.clear_new)) return rc;
+	if (P.prior) {
 		MotionArgs mo{};
-		const bool motion = motion_on(h) && h->tp_have_hist; // (a history kept with object motion on has an INSTANCE plane and a table of the scene's size)
-		if (motion && (h->mo_hist.inv.size() != h->mo_cur.inv.size() || h->mo_cur.mesh_index.empty() || !h->tp_hinst || !h->gb_inst))
+		if (P.motion && (S.v.hist.inv.size() != S.v.cur.inv.size() || S.v.cur.mesh_index.empty() || !S.tp_hinst || !S.gb_inst))
 			return fail(h, POLARIS_E_DEVICE, "temporal sync: the history's instance table does not fit the scene's"); // (cannot happen: upload_scene drops such a history)
-		if (motion) {
-			const uint32_t n_inst = (uint32_t)h->mo_cur.mesh_index.size();
-			h->mo_table_host.resize((size_t)n_inst * 16);
-			tp_motion_table(n_inst, h->mo_hist.inv.data(), h->mo_cur.inv.data(), h->mo_table_host.data());
-			HIP_TRY(h, h->mo_table.reserve((size_t)n_inst * 4)); // (the main stream is idle: every temporal sync ends with its synchronisation)
-			HIP_TRY(h, hipMemcpyAsync(h->mo_table, h->mo_table_host.data(), h->mo_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-			mo = MotionArgs{h->gb_inst, h->tp_hinst, h->mo_table, n_inst};
+		if (P.motion) {
+			const uint32_t n_inst = (uint32_t)S.v.cur.mesh_index.size();
+			S.mo_table_host.resize((size_t)n_inst * 16);
+			tp_motion_table(n_inst, S.v.hist.inv.data(), S.v.cur.inv.data(), S.mo_table_host.data());
+			HIP_TRY(h, S.mo_table.reserve((size_t)n_inst * 4)); // (the main stream is idle: every sync ends with its synchronisation)
+			HIP_TRY(h, hipMemcpyAsync(S.mo_table, S.mo_table_host.data(), S.mo_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+			mo = MotionArgs{S.gb_inst, S.tp_hinst, S.mo_table, n_inst};
 		}
-		HIP_TRY(h, launch_reproject(h, h->stream, h->tp_have_hist ? h->tp_hist : nullptr, h->tp_hguide, h->tp_halbedo, tp_camera(h->tp_hcam),
-		                            h->gb_guide, h->gb_albedo, tp_camera(h->cam), h->W, h->H, h->tp, h->tp_prior,
-		                            var && h->va_have_hist ? h->va_hist : nullptr, var ? h->tp_prior2 : nullptr, motion ? &mo : nullptr));
-		h->tp_prior_valid = true;
+		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam),
+		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->cam), h->W, h->H, S.tp, S.pl[kTpPrior],
+		                            P.m2 ? S.pl[kVaHist].get() : nullptr, f.variance ? S.pl[kTpPrior2].get() : nullptr, P.motion ? &mo : nullptr));
+		S.v.prior_computed();
 	}
 	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	const float nf = (float)(r->accumulated_samples + r->samples_per_pixel);
-	(void)launch(h, "temporal", h->stream, kTemporal, grid_for(n), WG, 0, h->frame_acc, h->tp_prior, h->tp_out, h->W, y0, y1, nf, weight);
-	if (var) {
-		launch_variance(h, h->stream, h->frame_acc, nf, weight, h->tp_out, h->tp_prior2, h->gb_guide, h->gb_albedo, h->va_out, h->dn_ping, h->dn_pong,
-		                h->dn_out, h->framebuffer, h->W, y0, y1, r->exposure, h->dn, h->va);
-	} else if (h->dn.iterations) {
-		launch_denoise(h, h->stream, h->tp_out, 1.0f, h->gb_guide, h->gb_albedo, h->dn_ping, h->dn_pong, h->dn_out, h->framebuffer, h->W, y0, y1,
-		               r->exposure, h->dn);
-	} else (void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->tp_out + off, h->framebuffer + off, (uint32_t)n, 1.0f, r->exposure);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	if (h->dn.iterations) h->dn_valid = true;
-	if (var) h->va_valid = true;
-	collect_timers(h);
+	launch_steps(h, h->stream, P, SyncIo{h->frame_acc, (float)(r->accumulated_samples + r->samples_per_pixel), weight, S.pl[kTpOut], S.pl[kTpPrior], S.pl[kTpPrior2],
+	                                     S.pl[kGuide], S.pl[kAlbedo], S.pl[kVaOut], S.pl[kDnPing], S.pl[kDnPong], S.pl[kDnOut], h->framebuffer, h->W, r->block_y,
+	                                     r->block_y + r->block_h, r->exposure}, S.dn, S.va);
 	return POLARIS_OK;
 }
+
+// The scratch of a *_planes test entry, which reads and writes no tracer state: one allocation carved into n4 float4 planes of F pixels
+// followed by n1 planes of F words (an INSTANCE plane, or RGBA8 pixels), and lists of copies on the main stream, which is drained
+// before the memory goes on every way out.
+struct PlaneScratch {
+	struct Copy { void *dst; const void *src; size_t bytes; }; // (either null: skipped)
+	hipStream_t q; size_t F, n4 = 0;
+	DevArray<char> mem;
+	StreamDrain drain{q}; // (declared after the memory)
+	hipError_t alloc(size_t n4_, size_t n1) { n4 = n4_; return mem.alloc((n4 * sizeof(float4) + n1 * sizeof(uint32_t)) * F); }
+	float4 *f4(size_t i) const { return (float4 *)mem.get() + i * F; }
+	uint32_t *word(size_t i) const { return (uint32_t *)f4(n4) + i * F; }
+	hipError_t copy(hipMemcpyKind kind, std::initializer_list<Copy> list) const {
+		for (const Copy &c : list)
+			if (c.dst && c.src)
+				if (hipError_t e = hipMemcpyAsync(c.dst, c.src, c.bytes, kind, q)) return e;
+		return hipSuccess;
+	}
+};
 } // namespace
 
 extern "C" {
@@ -1975,7 +1832,7 @@ int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_denoise: iterations %u (0..%u), normal_power_log2 %u (0..%u), sigmas %g / %g (0 or [%g, %g])",
 		            p->iterations, kDnMaxIterations, p->normal_power_log2, kDnMaxNormalPowerLog2, (double)p->sigma_depth,
 		            (double)p->sigma_luminance, (double)kDnSigmaMin, (double)kDnSigmaMax);
-	h->dn = *p;
+	h->fs.dn = *p;
 	return POLARIS_OK;
 }
 
@@ -1987,17 +1844,11 @@ int polaris_hip_set_temporal(polaris_hip_tracer *h, const PolarisTemporalParams 
 	if (tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_temporal: max_history %u (0..%u), normal_threshold %g ([-1, 1]), depth_threshold %g ([0, %g])",
 		            p->max_history, kTpMaxHistory, (double)p->normal_threshold, (double)p->depth_threshold, (double)kTpMaxDepthThreshold);
-	if (p->max_history == 0) {
-		if (h->tp.max_history) {
-			HIP_TRY(h, hipSetDevice(h->device));
-			HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every temporal launch is on the main stream)
-			free_temporal(h);
-		}
-	} else if (p->max_history != h->tp.max_history || pm_f2u(p->normal_threshold) != pm_f2u(h->tp.normal_threshold) ||
-	           pm_f2u(p->depth_threshold) != pm_f2u(h->tp.depth_threshold)) {
-		h->tp_prior_valid = false; // (recomputed at the next temporal sync)
+	if (p->max_history == 0 && h->fs.tp.max_history) { // its planes go
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every temporal launch is on the main stream)
 	}
-	h->tp = *p;
+	h->fs.set_temporal(*p);
 	return POLARIS_OK;
 }
 
@@ -2009,16 +1860,13 @@ int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams 
 	if (va_check(p->sigma_variance, p->min_samples))
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_variance: sigma_variance %g (0 or [%g, %g]), min_samples %u (1..%u)", (double)p->sigma_variance,
 		            (double)kDnSigmaMin, (double)kDnSigmaMax, p->min_samples, kVaMaxMinSamples);
-	const bool on = p->sigma_variance != 0.0f, was = h->va.sigma_variance != 0.0f;
+	const bool on = p->sigma_variance != 0.0f, was = h->fs.va.sigma_variance != 0.0f;
 	if (on && !h->opt_moments) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_variance: variance guidance needs the option moments = 1 first");
-	if (!on && was) {
+	if (!on && was) { // its planes go
 		HIP_TRY(h, hipSetDevice(h->device));
 		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every variance launch is on the main stream)
-		free_variance(h);
-		free_moment_history(h);
 	}
-	if (on != was) h->tp_prior_valid = false; // (PRIOR2 is written, or no longer, by the next temporal sync's reprojection)
-	h->va = *p;
+	h->fs.set_variance(*p);
 	return POLARIS_OK;
 }
 
@@ -2029,26 +1877,13 @@ int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_
 	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_PRIOR2)
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2,3,4,5,6}", need);
 	HIP_TRY(h, hipSetDevice(h->device));
-	const float4 *src;
-	if (which == POLARIS_AOV_DENOISED) {
-		if (!h->dn_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no denoised sync since the last resize");
-		src = h->dn_out;
-	} else if (which == POLARIS_AOV_TEMPORAL || which == POLARIS_AOV_PRIOR) {
-		if (!h->tp_synced || !h->tp_prior_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no temporal sync under the current camera");
-		src = which == POLARIS_AOV_TEMPORAL ? h->tp_out : h->tp_prior;
-	} else if (which == POLARIS_AOV_VARIANCE) {
-		if (!h->va_valid) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no variance sync%s", h->tp.max_history ? " under the current camera" : " since the last resize");
-		src = h->va_out;
-	} else if (which == POLARIS_AOV_PRIOR2) {
-		if (!h->va_valid || !h->tp.max_history || !h->tp_prior2) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: no variance sync with temporal reuse under the current camera");
-		src = h->tp_prior2;
-	} else {
+	if (const char *why = h->fs.v.aov_refusal(which, h->fs.tp.max_history != 0, h->fs.pl[kTpPrior2] != nullptr)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s", why);
+	if (which == POLARIS_AOV_GUIDE || which == POLARIS_AOV_ALBEDO) { // computed on demand
 		if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
 		if (int rc = ensure_gbuffer(h)) return rc;
-		src = which == POLARIS_AOV_GUIDE ? h->gb_guide : h->gb_albedo;
 	}
-	HIP_TRY(h, hipMemcpyAsync(out, src, need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(out, h->fs.pl[which], need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
@@ -2062,13 +1897,16 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
-	if (h->tp.max_history) return sync_temporal(h, r, weight);
-	if (h->va.sigma_variance != 0.0f) return sync_variance(h, r, weight);
-	if (h->dn.iterations) return sync_denoised(h, r, weight);
-	HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
-	(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->frame_acc + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
+	const SyncFeatures f = h->fs.features();
+	if (f.any()) {
+		if (int rc = enqueue_features(h, r, weight, f)) return rc;
+	} else {
+		HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
+		(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->frame_acc + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
+	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	if (f.any()) h->fs.v.synced(f);
 	collect_timers(h);
 	return POLARIS_OK;
 }
@@ -2271,19 +2109,16 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "denoise_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), or params "
 		            "(iterations 1..%u)", W, H, block_y, block_h, kDnMaxIterations);
 	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	DevArray<char> d;
-	StreamDrain drain{h->stream};
-	HIP_TRY(h, d.alloc(6 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
-	float4 *d_acc = (float4 *)d.get(), *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_ping = d_albedo + F, *d_pong = d_ping + F, *d_out = d_pong + F;
-	uchar4 *d_fb = (uchar4 *)(d_out + F);
-	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_out, denoised}};
-	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream));
-	launch_denoise(h, h->stream, d_acc, weight, d_guide, d_albedo, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure, *p);
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4), pixels = F * sizeof(uchar4);
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(6, 1));
+	float4 *d_acc = d.f4(0), *d_guide = d.f4(1), *d_albedo = d.f4(2), *d_ping = d.f4(3), *d_pong = d.f4(4), *d_out = d.f4(5);
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_acc, acc, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}, {d_out, denoised, plane}, {d_fb, rgba, pixels}}));
+	launch_steps(h, h->stream, plan_sync(SyncFeatures{true, false, false, false}, SyncState()),
+	             SyncIo{d_acc, 0.0f, weight, nullptr, nullptr, nullptr, d_guide, d_albedo, nullptr, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure}, *p, PolarisVarianceParams{});
 	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{denoised, d_out, plane}, {rgba, d_fb, pixels}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
@@ -2302,23 +2137,18 @@ int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const f
 		            "params (sigma_variance [%g, %g], min_samples 1..%u)", W, H, block_y, block_h, samples, (double)kDnSigmaMin, (double)kDnSigmaMax,
 		            kVaMaxMinSamples);
 	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	DevArray<char> d;
-	StreamDrain drain{h->stream};
-	HIP_TRY(h, d.alloc(7 * plane + F * sizeof(uchar4)));   // its own planes: no tracer state is read or written
-	float4 *d_acc = (float4 *)d.get(), *d_guide = d_acc + F, *d_albedo = d_guide + F, *d_var = d_albedo + F, *d_ping = d_var + F, *d_pong = d_ping + F,
-	       *d_out = d_pong + F;
-	uchar4 *d_fb = (uchar4 *)(d_out + F);
-	const std::pair<float4 *, const void *> in[] = {{d_acc, acc}, {d_guide, guide}, {d_albedo, albedo}, {d_var, variance}, {d_out, denoised}};
-	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(d_fb, rgba, F * sizeof(uchar4), hipMemcpyHostToDevice, h->stream));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4), pixels = F * sizeof(uchar4);
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(7, 1));
+	float4 *d_acc = d.f4(0), *d_guide = d.f4(1), *d_albedo = d.f4(2), *d_var = d.f4(3), *d_ping = d.f4(4), *d_pong = d.f4(5), *d_out = d.f4(6);
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_acc, acc, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}, {d_var, variance, plane}, {d_out, denoised, plane},
+	                                          {d_fb, rgba, pixels}}));
 	const float weight = (float)(1.0 / (float)samples); // (polaris_hip_sync_framebuffer's)
-	launch_variance(h, h->stream, d_acc, (float)samples, weight, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y,
-	                block_y + block_h, exposure, *p, *v);
+	launch_steps(h, h->stream, plan_sync(SyncFeatures{p->iterations != 0, false, true, false}, SyncState()),
+	             SyncIo{d_acc, (float)samples, weight, nullptr, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure}, *p, *v);
 	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, hipMemcpyAsync(variance, d_var, plane, hipMemcpyDeviceToHost, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(denoised, d_out, plane, hipMemcpyDeviceToHost, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(rgba, d_fb, F * sizeof(uchar4), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{variance, d_var, plane}, {denoised, d_out, plane}, {rgba, d_fb, pixels}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
@@ -2337,17 +2167,13 @@ int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, co
 		            "normal_threshold [-1, 1], depth_threshold [0, %g])", W, H, kTpMaxHistory, (double)kTpMaxDepthThreshold);
 	HIP_TRY(h, hipSetDevice(h->device));
 	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	DevArray<float4> d;
-	StreamDrain drain{h->stream};
-	HIP_TRY(h, d.alloc(6 * F));   // its own planes: no tracer state is read or written
-	float4 *d_hist = d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
-	       *d_prior = d_albedo + F;
-	const std::pair<float4 *, const void *> in[] = {{d_hist, history}, {d_hguide, prev_guide}, {d_halbedo, prev_albedo}, {d_guide, guide},
-	                                                {d_albedo, albedo}};
-	for (const auto &c : in) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(6, 0));
+	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}}));
 	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
 	                            W, H, *p, d_prior));
-	HIP_TRY(h, hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
@@ -2371,27 +2197,19 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
 	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
 	std::vector<float> table((size_t)n_instances * 16);
 	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
-	DevArray<float4> d, d_table;
-	DevArray<uint32_t> d_words;
-	StreamDrain drain{h->stream};
-	HIP_TRY(h, d.alloc(8 * F));   // its own planes: no tracer state is read or written
-	HIP_TRY(h, d_words.alloc(2 * F));
+	DevArray<float4> d_table;
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(8, 2));
 	HIP_TRY(h, d_table.alloc((size_t)n_instances * 4));
-	float4 *d_hist = d, *d_hguide = d_hist + F, *d_halbedo = d_hguide + F, *d_guide = d_halbedo + F, *d_albedo = d_guide + F,
-	       *d_prior = d_albedo + F, *d_hvar = d_prior + F, *d_prior2 = d_hvar + F;
-	uint32_t *d_hinst = d_words, *d_inst = d_hinst + F;
-	const std::pair<float4 *, const void *> in[] = {{d_hist, history}, {d_hguide, prev_guide}, {d_halbedo, prev_albedo}, {d_guide, guide},
-	                                                {d_albedo, albedo}, {d_hvar, history_variance}};
-	for (const auto &c : in)
-		if (c.second) HIP_TRY(h, hipMemcpyAsync(c.first, c.second, plane, hipMemcpyHostToDevice, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(d_hinst, prev_instance, F * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(d_inst, instance, F * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5), *d_hvar = d.f4(6), *d_prior2 = d.f4(7);
+	uint32_t *d_hinst = d.word(0), *d_inst = d.word(1);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane},
+	                                          {d_hvar, history_variance, plane}, {d_hinst, prev_instance, F * sizeof(uint32_t)}, {d_inst, instance, F * sizeof(uint32_t)},
+	                                          {d_table.get(), table.data(), table.size() * sizeof(float)}}));
 	const MotionArgs mo{d_inst, d_hinst, d_table, n_instances};
 	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
 	                            W, H, *p, d_prior, history_variance ? d_hvar : nullptr, prior2 ? d_prior2 : nullptr, &mo));
-	HIP_TRY(h, hipMemcpyAsync(prior, d_prior, plane, hipMemcpyDeviceToHost, h->stream));
-	if (prior2) HIP_TRY(h, hipMemcpyAsync(prior2, d_prior2, plane, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}, {prior2, d_prior2, plane}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;
@@ -2402,13 +2220,13 @@ int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t
 	std::lock_guard<std::mutex> lk(h->mu);
 	const size_t need = (size_t)h->W * h->H;
 	if (!out || n < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: need %zu words", need);
-	if (!h->opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
+	if (!h->fs.opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
 	HIP_TRY(h, hipSetDevice(h->device));
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: camera not set");
-	if (!motion_on(h)) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
+	if (!h->fs.features().motion_on()) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
 	if (int rc = ensure_gbuffer(h)) return rc;
-	HIP_TRY(h, hipMemcpyAsync(out, h->gb_inst, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(out, h->fs.gb_inst, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;

@@ -1,5 +1,5 @@
 """The denoiser's filter on the MI355X over the CPU suite's matrix and its edges, through polaris_hip_denoise_planes: the launches
-of a denoised sync (polaris_hip.hip launch_denoise) on caller planes, so shapes, parameters and planes no scene produces are
+of a denoised sync (polaris_hip.hip launch_steps) on caller planes, so shapes, parameters and planes no scene produces are
 reached.
 
 Bars, per (shape, parameters, planes): the DENOISED rows equal the CPU restatement (polaris_host_denoise) bit for bit (NaN equal

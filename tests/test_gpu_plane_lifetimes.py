@@ -3,7 +3,8 @@
 One tracer is taken through feature toggles and resizes that allocate, free, swap and re-allocate every filter plane; after every
 sync its RGBA8 frame buffer, every AOV that can be read and the refusal of every AOV that cannot must equal, byte for byte, those
 of a second tracer that was configured directly for that state and saw none of the earlier toggles and resizes.  A plane that
-outlives its feature or frame size, is freed while in use, or is missed by a free_* shows as a difference (or a fault) here.
+outlives its feature or frame size, is freed while in use, or is missing from
+the set its feature frees (frame_sync.h) shows as a difference (or a fault) here.
 
 Frames 24 x 16 and 40 x 12: 384 and 480 pixels, neither a multiple of the 256-thread workgroup.
 
@@ -80,8 +81,8 @@ def check(step, got, want, readable, frame):
     assert len(got["framebuffer"]) == frame[0] * frame[1] * 4 and any(got["framebuffer"]), step
 
 
-def fresh(sc, frame, *, variance=False, temporal=False):
-    tr = make_hip_tracer(sc, *frame)
+def fresh(sc, frame, *, variance=False, temporal=False, **options):
+    tr = make_hip_tracer(sc, *frame, **options)
     tr.set_denoise(**T.DENOISE_DEFAULTS)
     if variance:
         tr.set_variance(**T.VARIANCE_DEFAULTS)
@@ -161,6 +162,59 @@ def test_destroy_with_every_plane_allocated(built):
             tr.Close()
     check("cycle", snaps[1], snaps[0], set(AOVS), FRAME_A)
     check("cycle", snaps[2], snaps[0], set(AOVS), FRAME_A)
+
+
+def snapshot_with_instances(tr):
+    """snapshot() plus the INSTANCE plane's bytes or its refusal (allowed with object motion in effect only)."""
+    from polaris_amd.tracer import TracerError
+
+    snap = snapshot(tr)
+    try:
+        snap["instance"] = tr.read_instance_plane().tobytes()
+    except TracerError as e:
+        snap["instance"] = ("refused", e.code, str(e))
+    return snap
+
+
+def test_object_motion_toggles_drop_history_and_instance_planes(built):
+    """Denoise, variance guidance and temporal reuse on; the option object_motion goes 1 -> 0 -> 1 between syncs.  A toggle drops the
+    history and the G-buffer and, turned off, the INSTANCE planes and the motion table; turned on after the upload it reads the
+    instance matrices back from the device.  After every sync the tracer equals one configured directly for that state: the two syncs
+    around the camera move with the option on from the start, then a new tracer under the moved camera with the option off, then on."""
+    sc0, sc1 = scenes_pair()
+    both = dict(variance=True, temporal=True)
+    tr = fresh(sc0, FRAME_A, object_motion=1, **both)
+    ref = fresh(sc0, FRAME_A, object_motion=1, **both)
+    try:
+        for step, (sc, base) in enumerate(((sc0, 3), (sc1, 4)), 1):                  # 1. sync; 2. move the camera, sync
+            for t in (tr, ref):
+                if sc is sc1:
+                    set_camera(t, sc)
+                trace_sync(t, FRAME_A, base)
+            got = snapshot_with_instances(tr)
+            check(step, got, snapshot_with_instances(ref), set(AOVS), FRAME_A)
+            assert isinstance(got["instance"], bytes) and len(got["instance"]) == FRAME_A[0] * FRAME_A[1] * 4
+        prior = np.frombuffer(got["prior"], np.float32).reshape(FRAME_A[1], FRAME_A[0], 4)
+        assert (prior[..., 3] > 0).mean() > 0.5                                     # (the history is in play: m > 0 on most pixels)
+        for step, (on, base) in enumerate(((0, 5), (1, 6)), 3):                      # 3. option off, sync; 4. option on, sync
+            tr.set_option("object_motion", on)
+            trace_sync(tr, FRAME_A, base)
+            got = snapshot_with_instances(tr)
+            new = fresh(sc1, FRAME_A, object_motion=on, **both)
+            try:
+                trace_sync(new, FRAME_A, base)
+                check(step, got, snapshot_with_instances(new), set(AOVS), FRAME_A)
+            finally:
+                new.Close()
+            if on:
+                assert isinstance(got["instance"], bytes) and len(got["instance"]) == FRAME_A[0] * FRAME_A[1] * 4
+            else:
+                assert got["instance"][:2] == ("refused", 2) and "object_motion is off" in got["instance"][2]
+            prior = np.frombuffer(got["prior"], np.float32)
+            assert not prior.any()                                                  # (the toggle dropped the history: m = 0, PRIOR = 0)
+    finally:
+        tr.Close()
+        ref.Close()
 
 
 # ---- streams and events: every kind live, then released ---------------------------------------------------------------------
