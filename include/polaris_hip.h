@@ -46,7 +46,8 @@ extern "C" {
  * peer_info / merge_counts (which GPU a tracer really runs on, and which branch every merge took: what a multi-GPU bench line needs to prove
  * itself); PolarisIpcExport carries the exporting GPU's PCI bus id (544 -> 576 bytes); PolarisBvhBuildInput LEADS with `struct_size`
  * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end.  Still 5: + update_instances,
- * + update_vertices / PolarisVertexUpdate (additions only: older callers keep working). */
+ * + update_vertices / PolarisVertexUpdate, + update_materials / PolarisMaterialUpdate / update_texture and the record kinds
+ * POLARIS_REC_TRIS / POLARIS_REC_SHADING (additions only: older callers keep working). */
 #define POLARIS_HIP_ABI_VERSION 5
 
 /* status codes (0 = ok).  The first three mirror tracer/opencl/errors.go sentinels. */
@@ -587,13 +588,54 @@ typedef struct PolarisVertexUpdate {
 } PolarisVertexUpdate;
 int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate *u);
 
+/* Edit the uploaded scene's materials in place (no reference counterpart).  No upload option: every upload holds what
+ * the call needs.  Synchronous, under the handle's mutex, behind every stream, like an upload.  Afterwards the tracer behaves --
+ * accumulators, counters, probes, taps, G-buffer planes, the triangle records and the mask of emitting shading classes themselves --
+ * bit for bit as a fresh tracer does after polaris_hip_upload_scene of the uploaded scene's arrays with these substitutions:
+ *   - material_nodes = the new table (the same number of nodes: callers who want headroom upload spare, unreferenced leaves);
+ *   - material_index = the new roots (NULL: unchanged);
+ *   - scene_diffuse_mat_index = the given one (always taken: pass the uploaded value to keep it; -1 = no background);
+ *   - emissives[e].mat_node_index = emissive_mat_nodes[e] (NULL: unchanged).  The emissive list keeps its count, triangles, types,
+ *     transforms and areas: turning triangles into lights or removing lights needs an upload (a radiance of zero covers "off").
+ * The library recomputes what a full upload derives from these: the shading class of every material node, the class in the two words
+ * of every triangle record that carry it (kernel k_retag, timer "retag") and the mask of classes that can end in an emitter.
+ * Geometry, trees, slot order, node mode and the kernel selection do not depend on materials and stay.  No semantic check is made
+ * beyond the upload's own: an emissive entry whose triangle no longer has an emissive material behaves as after an upload of such arrays.
+ * polaris_hip_update_texture replaces the texels of ONE texture, same format and size as uploaded: n_bytes must equal
+ * bytes per texel * width * height of texture `index`.
+ * To the temporal history both calls are a scene it never saw: the history is dropped, with "object_motion" on or off, and the
+ * G-buffer is invalidated (the ALBEDO plane changes).
+ * A failing HIP call (POLARIS_E_DEVICE) after the arguments were accepted leaves the scene as a failed upload_scene does: upload again.
+ * Refusals are decided on the host before anything is touched and leave the tracer's state unchanged: POLARIS_E_NO_SCENE_DATA before
+ * an upload; POLARIS_E_BAD_ARGUMENT for a wrong struct_size, null material_nodes, a node, triangle or emissive count that differs
+ * from the uploaded one, a texture index out of range or an n_bytes that is not the texture's size; POLARIS_E_BAD_SCENE for every
+ * material rule of the upload, with the upload's text (unknown operator, child / texture / transmittance texture out of range,
+ * triangle material root, emissive material node or background index out of range).
+ */
+typedef struct PolarisMaterialUpdate {
+	uint32_t struct_size;                       /* = sizeof(PolarisMaterialUpdate) */
+	uint32_t num_material_nodes;                /* must equal the uploaded scene's */
+	const PolarisMaterialNode *material_nodes;  /* [num_material_nodes]: the whole new table */
+	uint32_t num_triangles;                     /* must equal the uploaded scene's when material_index is given */
+	const uint32_t *material_index;             /* NULL = unchanged; else [num_triangles] root node per triangle */
+	int32_t scene_diffuse_mat_index;            /* always taken: pass the uploaded value to keep it; -1 = no background */
+	const uint32_t *emissive_mat_nodes;         /* NULL = unchanged; else [num_emissives]: new PolarisEmissive.mat_node_index per entry */
+	uint32_t num_emissives;                     /* must equal the uploaded scene's when emissive_mat_nodes is given */
+} PolarisMaterialUpdate;
+int polaris_hip_update_materials(polaris_hip_tracer *h, const PolarisMaterialUpdate *u);
+int polaris_hip_update_texture(polaris_hip_tracer *h, uint32_t index, const void *texels, size_t n_bytes);
+
 /* Test tap (no reference counterpart): the device's pair records (POLARIS_REC_PAIRS: 64 bytes each, scene_layout.h PairNodeH) or
  * instance records (POLARIS_REC_INSTS: 64 bytes each, InstH) of the uploaded scene, copied back; POLARIS_REC_COUNTS: four uint64_t,
  * the number of pair records, of instance records, of device allocations the scene owns and the bytes in them (what the option
- * "instance_update" adds shows here, exactly; free device memory is everybody's).  n_bytes must be at least the size of what is asked for. */
+ * "instance_update" adds shows here, exactly; free device memory is everybody's); POLARIS_REC_TRIS: the triangle records (48 bytes
+ * each, TriH), one per triangle slot; POLARIS_REC_SHADING: four uint32_t, tri_bits, emit_classes, the background node as bits and the
+ * number of triangle slots.  n_bytes must be at least the size of what is asked for. */
 #define POLARIS_REC_PAIRS 0
 #define POLARIS_REC_INSTS 1
 #define POLARIS_REC_COUNTS 2
+#define POLARIS_REC_TRIS 3
+#define POLARIS_REC_SHADING 4
 int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, size_t n_bytes);
 
 /*
@@ -645,7 +687,7 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
  * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance), "instance_extent",
  * "repad" and "refit_top" (polaris_hip_update_instances), "tri_records" and "refit_mesh" (polaris_hip_update_vertices, which runs the
- * former three as well). */
+ * former three as well), "retag" (polaris_hip_update_materials). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

@@ -404,6 +404,49 @@ func (tr *Tracer) UpdateVertices(vertices []float32, boxes []float32, normals []
 	return tr.check(C.polaris_hip_update_vertices(tr.handle, &c))
 }
 
+// UpdateMaterials edits the uploaded scene's materials in place (polaris_hip_update_materials; DESIGN.md section 10g): nodes is the
+// whole new material node list (as many nodes as uploaded); materialIndex the root node of every triangle, or nil to keep the
+// uploaded ones; sceneDiffuse the background node, always taken (-1: none); emissiveMatNodes the new MaterialNodeIndex of every
+// emissive, or nil to keep the current ones.  Afterwards the tracer behaves as if the scene had been uploaded with these.  No upload
+// option is needed; a refusal leaves the tracer as it was.  The slices are only read during the call.
+func (tr *Tracer) UpdateMaterials(nodes []scene.MaterialNode, materialIndex []uint32, sceneDiffuse int32, emissiveMatNodes []uint32) error {
+	tr.Lock()
+	defer tr.Unlock()
+	if len(nodes) == 0 {
+		return fmt.Errorf("hip tracer (%s): UpdateMaterials wants the whole material node list", tr.dev.Name)
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	var c C.PolarisMaterialUpdate
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.num_material_nodes = C.uint32_t(len(nodes))
+	pin.Pin(&nodes[0])
+	c.material_nodes = (*C.PolarisMaterialNode)(unsafe.Pointer(&nodes[0]))
+	if n := len(materialIndex); n > 0 {
+		pin.Pin(&materialIndex[0])
+		c.material_index, c.num_triangles = (*C.uint32_t)(unsafe.Pointer(&materialIndex[0])), C.uint32_t(n)
+	}
+	c.scene_diffuse_mat_index = C.int32_t(sceneDiffuse)
+	if n := len(emissiveMatNodes); n > 0 {
+		pin.Pin(&emissiveMatNodes[0])
+		c.emissive_mat_nodes, c.num_emissives = (*C.uint32_t)(unsafe.Pointer(&emissiveMatNodes[0])), C.uint32_t(n)
+	}
+	return tr.check(C.polaris_hip_update_materials(tr.handle, &c))
+}
+
+// UpdateTexture replaces the texels of texture index in place (polaris_hip_update_texture): same format and size as uploaded.
+func (tr *Tracer) UpdateTexture(index uint32, texels []byte) error {
+	tr.Lock()
+	defer tr.Unlock()
+	if len(texels) == 0 {
+		return fmt.Errorf("hip tracer (%s): UpdateTexture wants the texture's texels", tr.dev.Name)
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&texels[0])
+	return tr.check(C.polaris_hip_update_texture(tr.handle, C.uint32_t(index), unsafe.Pointer(&texels[0]), C.size_t(len(texels))))
+}
+
 // VarianceParams configures variance-guided denoising (PolarisVarianceParams, include/polaris_hip.h; DESIGN.md section 10c).
 // SigmaVariance = 0 turns it off (the default); DefaultVariance holds the settings chosen on the CPU restatement.
 type VarianceParams struct {

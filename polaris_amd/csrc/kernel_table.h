@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "instance_update.h"
 #include "vertex_update.h"
+#include "material_update.h"
 
 namespace pol {
 
@@ -88,5 +89,8 @@ const auto kRefitTop = POLARIS_VARIANT(k_refit_top);
 // polaris_hip_update_vertices (vertex_update.h)
 const auto kTriRecords = POLARIS_VARIANT(k_tri_records);
 const auto kRefitMesh = POLARIS_VARIANT(k_refit_mesh);
+// polaris_hip_update_materials (material_update.h)
+const auto kRetag = POLARIS_VARIANT(k_retag);
+const auto kEmissiveNodes = POLARIS_VARIANT(k_emissive_nodes);
 
 } // namespace pol

@@ -77,10 +77,19 @@ struct VertexUpdateState {
 	float4 *scratch = nullptr, *mesh_box = nullptr;
 };
 
+// editing materials in place (polaris_hip_update_materials / polaris_hip_update_texture; no option): the few host-side
+// numbers the calls' checks need and the scene's tables, writable.  Set by every upload; nothing is allocated for it.
+struct MaterialUpdateState {
+	uint32_t num_triangles = 0, num_slots = 0;
+	bool meta_word = false; // the slots carry the tiny meta word (scene_layout.h: at most 2 046 slots and triangles)
+	std::vector<PolarisTextureMetadata> tex_meta; // 16 B per texture
+	TriRec *tris = nullptr; uint32_t *mat_index = nullptr; PolarisMaterialNode *nodes = nullptr; PolarisEmissive *emissives = nullptr; uint8_t *tex_data = nullptr;
+};
+
 // The uploaded scene (buffers.go:180-201, re-laid out by scene_layout.h): everything that lives and dies with an upload.  Every device
 // pointer below points into `bufs`: assigning DeviceScene() forgets the scene, and a failed upload leaves no pointer behind.
 struct DeviceScene {
-	bool have_scene = false; // complete: set last by upload_scene; update_vertices clears it while it works
+	bool have_scene = false; // complete: set last by upload_scene; update_vertices and the material edits clear it while they work
 	DevPool bufs;
 	BvhDev bvh{};
 	SceneDev scene{};
@@ -89,6 +98,7 @@ struct DeviceScene {
 	bool tiny_one = false;        // tiny-scene mode: the scene is one instance whose boxes all bound their subtrees (kernels.h k_trace, ONE); option tiny_one = 0 keeps the general variant
 	TraceLaunch trace[2];         // [any hit]: the scene's k_trace variant with its block size, dynamic LDS bytes and residency (select_trace)
 	InstanceUpdateState upd; VertexUpdateState vup; // kept with the options "instance_update" / "vertex_update" at upload
+	MaterialUpdateState mup;
 };
 
 // Everything behind the features of polaris_hip_sync_framebuffer: the parameters of denoising (polaris_hip_set_denoise),
@@ -233,6 +243,7 @@ struct polaris_hip_tracer {
 	DevArray<float4> d_cam_o; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
 	int num_cus = 256;
 	DevArray<float4> staging; // peer-merge staging strip (grow-only)
+	DevArray<uint32_t> d_retag; // polaris_hip_update_materials: the class of every material node (a byte each), then the emissives' new nodes (grow-only)
 	int opt_ipc_staged = 0;  // testing aid: peers opened from now on are merged through the staging strip (the path of a GPU without peer access)
 
 	// options: what a Trace plans from (trace_plan.h), and the rest
@@ -731,6 +742,10 @@ int upload_arrays(polaris_hip_tracer *h, const PolarisSceneView &sc, const Scene
 	S.max_stack = L.max_stack; S.num_insts = (uint32_t)L.insts.size();
 	S.upd.pairs = pairs; S.upd.insts = insts; S.upd.d_emissives = emissives; S.upd.d_light_geo = light_geo; // what the in-place updates write
 	S.vup.vertices = vertices; S.vup.normals = normals; S.vup.tris = tris;
+	S.mup.num_triangles = sc.num_triangles; S.mup.num_slots = (uint32_t)L.tris.size();
+	S.mup.meta_word = L.tris.size() <= 2046u && sc.num_triangles <= 2046u; // (build_layout's condition for TriH::pad2)
+	S.mup.tex_meta.assign(sc.texture_meta, sc.texture_meta + sc.num_textures);
+	S.mup.tris = tris; S.mup.mat_index = mat_index; S.mup.nodes = nodes; S.mup.emissives = emissives; S.mup.tex_data = tex_data;
 	return POLARIS_OK;
 }
 
@@ -1122,19 +1137,79 @@ int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate
 	return POLARIS_OK;
 }
 
+// Edit the uploaded scene's materials in place (include/polaris_hip.h; material_update.h has the arithmetic).
+int polaris_hip_update_materials(polaris_hip_tracer *h, const PolarisMaterialUpdate *u) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	DeviceScene &S = h->ds;
+	MaterialUpdateState &M = S.mup;
+	std::string msg;
+	if (int st = check_material_update(u, S.have_scene, S.scene.num_nodes, M.num_triangles, S.scene.num_emissives, S.scene.num_textures, msg)) return fail(h, st, "%s", msg.c_str());
+	// what an upload derives from the node table: the class of every node, the classes that can end in an emitter
+	std::vector<uint8_t> cls;
+	const uint32_t emit_classes = classify_materials(u->material_nodes, u->num_material_nodes, S.scene.tri_bits, cls);
+	// ---- accepted: from here on the state changes ----
+	if (int rc = make_idle(h)) return rc;
+	S.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
+	h->fs.scene_changed(nullptr, h->cam); // the history never saw this scene
+	hipStream_t q = h->stream;
+	const uint32_t NE = u->emissive_mat_nodes ? S.scene.num_emissives : 0, cls_words = (uint32_t)(cls.size() / 4);
+	HIP_TRY(h, h->d_retag.reserve((size_t)cls_words + NE + 4));
+	HIP_TRY(h, hipMemcpyAsync(M.nodes, u->material_nodes, (size_t)u->num_material_nodes * sizeof(PolarisMaterialNode), hipMemcpyHostToDevice, q));
+	HIP_TRY(h, hipMemcpyAsync(h->d_retag, cls.data(), cls.size(), hipMemcpyHostToDevice, q));
+	if (u->material_index) HIP_TRY(h, hipMemcpyAsync(M.mat_index, u->material_index, (size_t)M.num_triangles * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+	if (NE) {
+		HIP_TRY(h, hipMemcpyAsync(h->d_retag + cls_words, u->emissive_mat_nodes, (size_t)NE * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+		(void)launch(h, nullptr, q, kEmissiveNodes, (NE + kRetagBlock - 1) / kRetagBlock, kRetagBlock, 0, M.emissives, h->d_retag + cls_words, NE);
+	}
+	if (S.scene.tri_bits < 31) { // (else hits carry no class: nothing to retag, emit_classes stays all ones)
+		const uint32_t per_group = kRetagBlock * kRetagSlotsPerThread;
+		(void)launch(h, "retag", q, kRetag, (M.num_slots + per_group - 1) / per_group, kRetagBlock, 0, M.tris, M.num_slots, M.mat_index,
+		             reinterpret_cast<const uint8_t *>(h->d_retag.get()), u->num_material_nodes, S.scene.tri_bits, M.meta_word ? 1u : 0u);
+	}
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(q)); // (the caller's arrays and cls may go at return)
+	collect_timers(h);
+	S.scene.bg_node = u->scene_diffuse_mat_index;
+	S.scene.emit_classes = emit_classes; // (every Trace plans from it anew: plan_scene)
+	// the host copy of the emissive list the other two updates judge and re-send follows, or they would refuse the new list or revert the field
+	for (uint32_t e = 0; e < NE && e < S.upd.emissives.size(); e++) S.upd.emissives[e].mat_node_index = u->emissive_mat_nodes[e];
+	S.have_scene = true;
+	return POLARIS_OK;
+}
+
+int polaris_hip_update_texture(polaris_hip_tracer *h, uint32_t index, const void *texels, size_t n_bytes) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	DeviceScene &S = h->ds;
+	std::string msg;
+	if (int st = check_texture_update(index, texels, n_bytes, S.have_scene, S.mup.tex_meta, msg)) return fail(h, st, "%s", msg.c_str());
+	if (int rc = make_idle(h)) return rc;
+	S.have_scene = false;
+	h->fs.scene_changed(nullptr, h->cam);
+	if (n_bytes) HIP_TRY(h, hipMemcpyAsync(S.mup.tex_data + S.mup.tex_meta[index].data_offset, texels, n_bytes, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	S.have_scene = true;
+	return POLARIS_OK;
+}
+
 int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, size_t n_bytes) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
-	if (which != POLARIS_REC_PAIRS && which != POLARIS_REC_INSTS && which != POLARIS_REC_COUNTS) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: unknown record kind %d", which);
+	if (which < POLARIS_REC_PAIRS || which > POLARIS_REC_SHADING) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: unknown record kind %d", which);
 	uint64_t counts[4] = {h->ds.bvh.num_pairs, h->ds.num_insts, h->ds.bufs.size(), 0};
 	for (const DevArray<char> &b : h->ds.bufs) counts[3] += b.capacity();
-	const size_t need = which == POLARIS_REC_COUNTS ? sizeof counts : (size_t)counts[which] * 64;
+	const uint32_t shading[4] = {h->ds.scene.tri_bits, h->ds.scene.emit_classes, (uint32_t)h->ds.scene.bg_node, h->ds.mup.num_slots};
+	const size_t need = which == POLARIS_REC_COUNTS ? sizeof counts : which == POLARIS_REC_SHADING ? sizeof shading :
+	                    which == POLARIS_REC_TRIS ? (size_t)h->ds.mup.num_slots * sizeof(TriRec) : (size_t)counts[which] * 64;
 	if (!out || n_bytes < need) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_scene_records: need %zu bytes", need);
 	if (which == POLARIS_REC_COUNTS) { memcpy(out, counts, sizeof counts); return POLARIS_OK; }
+	if (which == POLARIS_REC_SHADING) { memcpy(out, shading, sizeof shading); return POLARIS_OK; }
 	HIP_TRY(h, hipSetDevice(h->device));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	HIP_TRY(h, hipMemcpy(out, which == POLARIS_REC_PAIRS ? (const void *)h->ds.bvh.pairs : (const void *)h->ds.bvh.insts, need, hipMemcpyDeviceToHost));
+	const void *src = which == POLARIS_REC_PAIRS ? (const void *)h->ds.bvh.pairs : which == POLARIS_REC_INSTS ? (const void *)h->ds.bvh.insts : (const void *)h->ds.bvh.tris;
+	HIP_TRY(h, hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
 	return POLARIS_OK;
 }
 

@@ -40,13 +40,20 @@
 
 namespace pol {
 
+// (functions the update kernels share with their host restatements: tiny_meta_word below, instance_update.h, vertex_update.h, material_update.h)
+#if defined(__HIPCC__)
+#define POL_HD __host__ __device__
+#else
+#define POL_HD
+#endif
+
 struct PairNodeH { float lo0[3]; int32_t ref0; float hi0[3]; int32_t pad0; float lo1[3]; int32_t ref1; float hi1[3]; int32_t pad1; };
 struct LeafInfoH { int32_t ldata, rdata; };
 struct TriH { float v0[3]; uint32_t rank; float e1[3]; uint32_t orig; float e2[3]; uint32_t pad2; };
 struct InstH { float r0[4], r1[4], r2[4]; int32_t root_ref; uint32_t rank; uint32_t pad[2]; };
 static_assert(sizeof(PairNodeH) == 64 && sizeof(TriH) == 48 && sizeof(InstH) == 64, "layout");
 // rank << 19 | shading class << 11 | scene triangle: one word per triangle slot for scenes of < 2 047 triangles (kernels.h tiny_meta_tri)
-inline uint32_t tiny_meta_word(uint32_t rank, uint32_t orig) { return rank << 19 | (orig >> 24 & 0xFFu) << 11 | (orig & 0x7FFu); }
+POL_HD inline uint32_t tiny_meta_word(uint32_t rank, uint32_t orig) { return rank << 19 | (orig >> 24 & 0xFFu) << 11 | (orig & 0x7FFu); }
 
 constexpr float kCullMargin = 1.001f; // a subtree is skipped when its box starts beyond kCullMargin x the best hit distance
 constexpr float kSplitCost = 1.0f;  // cost of one added pair-of-boxes step, in triangle tests (leaf subdivision)
@@ -55,12 +62,6 @@ constexpr float kMaxMatrixEntry = 1073741824.0f;   // 2^30: largest entry of an 
 constexpr int kTraversalStack = 32; // entries per ray, == BVH_MAX_STACK_SIZE (intersect.cl:4)
 
 constexpr uint32_t kBigLeafFlag = 1u << 30; // leaf code: count nibble 0 and this bit = "look the triangle range up in LeafInfo[node]"
-
-#if defined(__HIPCC__)
-#define POL_HD __host__ __device__
-#else
-#define POL_HD
-#endif
 
 // What polaris_hip_update_instances needs beside the uploaded records: the top-level tree as a refit schedule, the
 // triangles of every mesh, and the terms of the leaf-subdivision padding.  Filled by build_layout when want_update_plan is set.
@@ -260,6 +261,45 @@ inline uint32_t emitting_classes(const PolarisSceneView &sc, const std::vector<u
 }
 
 
+// The material rules of an upload: every index a material node, a triangle, an emissive or the background holds is in range.  ""
+// or the first broken rule.  build_layout and polaris_hip_update_materials (material_update.h) both call it, so one rule has one
+// text.  The update passes a view of the NEW tables: material_index null = unchanged (the uploaded roots are in range, the node
+// count is the same); emissives null with emissive_nodes given = only the new mat_node_index of every entry is judged (type and
+// triangle stay the uploaded ones); emissive_nodes null = the entries' own.
+inline std::string check_materials(const PolarisSceneView &sc, const uint32_t *emissive_nodes) {
+	const uint32_t NT = sc.num_triangles;
+	auto tex_ok = [&](int32_t t) { return t == -1 || (t >= 0 && (uint32_t)t < sc.num_textures); };
+	for (uint32_t i = 0; i < sc.num_material_nodes; i++) {
+		const PolarisMaterialNode &m = sc.material_nodes[i];
+		const std::string who = "material node " + std::to_string(i);
+		if (m.type >= POLARIS_MAT_OP_MIX) {
+			if (m.type > POLARIS_MAT_OP_DISPERSE) return who + ": unknown operator";
+			if (m.left_child >= sc.num_material_nodes) return who + ": left child out of range";
+			if ((m.type == POLARIS_MAT_OP_MIX || m.type == POLARIS_MAT_OP_MIX_MAP) &&
+			    (m.right_child < 0 || (uint32_t)m.right_child >= sc.num_material_nodes))
+				return who + ": right child out of range";
+			if (m.type == POLARIS_MAT_OP_MIX_MAP || m.type == POLARIS_MAT_OP_BUMP_MAP || m.type == POLARIS_MAT_OP_NORMAL_MAP) {
+				if (m.tex < 0 || (uint32_t)m.tex >= sc.num_textures) return who + ": operator texture out of range";
+			} else if (!tex_ok(m.tex)) // mix / disperse: unused by the operator, but a background or light reference may land on any node
+				return who + ": texture out of range";
+		} else {
+			if (!tex_ok(m.tex) || !tex_ok(m.roughness_tex)) return who + ": texture out of range";
+			if ((m.type == POLARIS_BXDF_DIELECTRIC || m.type == POLARIS_BXDF_ROUGH_DIELECTRIC) && !tex_ok(m.right_child))
+				return who + ": transmittance texture out of range";
+		}
+	}
+	for (uint32_t t = 0; sc.material_index && t < NT; t++)
+		if (sc.material_index[t] >= sc.num_material_nodes) return "triangle " + std::to_string(t) + ": material root out of range";
+	for (uint32_t e = 0; e < sc.num_emissives && (sc.emissives || emissive_nodes); e++) {
+		if (sc.emissives && sc.emissives[e].type > POLARIS_EMISSIVE_ENVIRONMENT) return "emissive " + std::to_string(e) + ": unknown type";
+		if ((emissive_nodes ? emissive_nodes[e] : sc.emissives[e].mat_node_index) >= sc.num_material_nodes) return "emissive " + std::to_string(e) + ": material node out of range";
+		if (sc.emissives && sc.emissives[e].type == POLARIS_EMISSIVE_AREA && sc.emissives[e].tri_index >= NT) return "emissive " + std::to_string(e) + ": triangle out of range";
+	}
+	if (sc.scene_diffuse_mat_index != -1 && (sc.scene_diffuse_mat_index < 0 || (uint32_t)sc.scene_diffuse_mat_index >= sc.num_material_nodes))
+		return "scene diffuse material index out of range";
+	return "";
+}
+
 inline bool is_leaf(const PolarisBvhNode &n) { return n.ldata <= 0; }
 
 // Returns "" on success, otherwise a description of the first inconsistency.
@@ -313,36 +353,10 @@ inline std::string build_layout(const PolarisSceneView &sc, SceneLayout &out, in
 		if (m.format != POLARIS_TEX_L8 && (m.data_offset & 3u))
 			return "texture " + std::to_string(t) + ": texel data not dword aligned";
 	}
-	auto tex_ok = [&](int32_t t) { return t == -1 || (t >= 0 && (uint32_t)t < sc.num_textures); };
-	for (uint32_t i = 0; i < sc.num_material_nodes; i++) {
-		const PolarisMaterialNode &m = sc.material_nodes[i];
-		const std::string who = "material node " + std::to_string(i);
-		if (m.type >= POLARIS_MAT_OP_MIX) {
-			if (m.type > POLARIS_MAT_OP_DISPERSE) return who + ": unknown operator";
-			if (m.left_child >= sc.num_material_nodes) return who + ": left child out of range";
-			if ((m.type == POLARIS_MAT_OP_MIX || m.type == POLARIS_MAT_OP_MIX_MAP) &&
-			    (m.right_child < 0 || (uint32_t)m.right_child >= sc.num_material_nodes))
-				return who + ": right child out of range";
-			if (m.type == POLARIS_MAT_OP_MIX_MAP || m.type == POLARIS_MAT_OP_BUMP_MAP || m.type == POLARIS_MAT_OP_NORMAL_MAP) {
-				if (m.tex < 0 || (uint32_t)m.tex >= sc.num_textures) return who + ": operator texture out of range";
-			} else if (!tex_ok(m.tex)) // mix / disperse: unused by the operator, but a background or light reference may land on any node
-				return who + ": texture out of range";
-		} else {
-			if (!tex_ok(m.tex) || !tex_ok(m.roughness_tex)) return who + ": texture out of range";
-			if ((m.type == POLARIS_BXDF_DIELECTRIC || m.type == POLARIS_BXDF_ROUGH_DIELECTRIC) && !tex_ok(m.right_child))
-				return who + ": transmittance texture out of range";
-		}
+	{
+		const std::string e = check_materials(sc, nullptr);
+		if (!e.empty()) return e;
 	}
-	for (uint32_t t = 0; t < NT; t++)
-		if (sc.material_index[t] >= sc.num_material_nodes) return "triangle " + std::to_string(t) + ": material root out of range";
-	for (uint32_t e = 0; e < sc.num_emissives; e++) {
-		const PolarisEmissive &em = sc.emissives[e];
-		if (em.type > POLARIS_EMISSIVE_ENVIRONMENT) return "emissive " + std::to_string(e) + ": unknown type";
-		if (em.mat_node_index >= sc.num_material_nodes) return "emissive " + std::to_string(e) + ": material node out of range";
-		if (em.type == POLARIS_EMISSIVE_AREA && em.tri_index >= NT) return "emissive " + std::to_string(e) + ": triangle out of range";
-	}
-	if (sc.scene_diffuse_mat_index != -1 && (sc.scene_diffuse_mat_index < 0 || (uint32_t)sc.scene_diffuse_mat_index >= sc.num_material_nodes))
-		return "scene diffuse material index out of range";
 
 	// ---- BVH: structure, ranks, stack depth ----------------------------------------------
 	// Pass 1 walks the caller's tree: validation, DFS ranks, which leaves are reachable.

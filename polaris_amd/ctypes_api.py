@@ -339,6 +339,43 @@ def vertex_update(vertices, boxes, normals=None, inv=None, emissives=None):
     return u, keep
 
 
+class MaterialUpdate(C.Structure):
+    """PolarisMaterialUpdate (include/polaris_hip.h): the materials polaris_hip_update_materials gives the uploaded scene."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("num_material_nodes", C.c_uint32), ("material_nodes", C.c_void_p),
+        ("num_triangles", C.c_uint32), ("material_index", C.c_void_p),
+        ("scene_diffuse_mat_index", C.c_int32), ("emissive_mat_nodes", C.c_void_p), ("num_emissives", C.c_uint32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(MaterialUpdate) == 56
+REC_TRIS, REC_SHADING = 3, 4   # polaris_hip_read_scene_records
+TRI_RECORD = np.dtype([("v0", "<f4", 3), ("rank", "<u4"), ("e1", "<f4", 3), ("orig", "<u4"), ("e2", "<f4", 3), ("word", "<u4")])
+assert TRI_RECORD.itemsize == 48
+
+
+def material_update(nodes, material_index=None, scene_diffuse=-1, emissive_mat_nodes=None):
+    """A MaterialUpdate over the given arrays, and the arrays it borrows (keep them alive while it is used)."""
+    nodes = np.ascontiguousarray(nodes, dtype=MATERIAL_NODE)
+    u = MaterialUpdate()
+    u.num_material_nodes, u.material_nodes = len(nodes), (nodes.ctypes.data if nodes.size else None)
+    u.scene_diffuse_mat_index = int(scene_diffuse)
+    keep = [nodes]
+    if material_index is not None:
+        mi = np.ascontiguousarray(material_index, dtype=np.uint32).reshape(-1)
+        u.num_triangles, u.material_index = len(mi), mi.ctypes.data
+        keep.append(mi)
+    if emissive_mat_nodes is not None:
+        em = np.ascontiguousarray(emissive_mat_nodes, dtype=np.uint32).reshape(-1)
+        u.num_emissives, u.emissive_mat_nodes = len(em), em.ctypes.data   # (an empty list is still a list: numpy's pointer is not null)
+        keep.append(em)
+    return u, keep
+
+
 def _ptr(a):
     return None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
 
@@ -376,6 +413,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
+    "polaris_hip_update_materials", "polaris_hip_update_texture",
 ]
 
 _lib = None
@@ -486,6 +524,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_update_instances.argtypes = [vp, C.POINTER(InstanceUpdate)]
     lib.polaris_hip_read_scene_records.argtypes = [vp, i32, vp, C.c_size_t]
     lib.polaris_hip_update_vertices.argtypes = [vp, C.POINTER(VertexUpdate)]
+    lib.polaris_hip_update_materials.argtypes = [vp, C.POINTER(MaterialUpdate)]
+    lib.polaris_hip_update_texture.argtypes = [vp, u32, vp, C.c_size_t]
     for name in C_ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("polaris_hip_device_count", "polaris_hip_abi_version"):

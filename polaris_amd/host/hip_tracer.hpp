@@ -69,6 +69,22 @@ public:
 		const char *m = polaris_hip_last_error(h_);
 		return Error{rc, std::string("hip tracer: ") + (m ? m : "update_vertices failed")};
 	}
+	// Edit the uploaded scene's materials in place (polaris_hip_update_materials / polaris_hip_update_texture; no upload option).
+	// Synchronous; a refusal leaves the tracer as it was.
+	Error UpdateMaterials(const PolarisMaterialUpdate *u) {
+		if (!h_) return Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: UpdateMaterials on a closed tracer"};
+		const int rc = polaris_hip_update_materials(h_, u);
+		if (rc == POLARIS_OK) return Error::Nil();
+		const char *m = polaris_hip_last_error(h_);
+		return Error{rc, std::string("hip tracer: ") + (m ? m : "update_materials failed")};
+	}
+	Error UpdateTexture(uint32_t index, const void *texels, size_t n_bytes) {
+		if (!h_) return Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: UpdateTexture on a closed tracer"};
+		const int rc = polaris_hip_update_texture(h_, index, texels, n_bytes);
+		if (rc == POLARIS_OK) return Error::Nil();
+		const char *m = polaris_hip_last_error(h_);
+		return Error{rc, std::string("hip tracer: ") + (m ? m : "update_texture failed")};
+	}
 	void ResetFrame() { if (h_) (void)polaris_hip_reset_frame(h_); } // the Reset stage on its own (also advances the epoch)
 	const PolarisTraceStats &LastTraceStats() const { return last_; }
 	polaris_hip_tracer *Handle() const { return h_; }

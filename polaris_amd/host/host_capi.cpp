@@ -156,6 +156,20 @@ int polaris_host_renderer_update_vertices(void *h, const PolarisVertexUpdate *u)
 		if (Error e = t->UpdateVertices(u)) { box->error = e.msg; return e.code; }
 	return 0;
 }
+// Editing the scene's materials in place (polaris_hip_update_materials / polaris_hip_update_texture) on every tracer,
+// as update_instances.  No upload option.
+int polaris_host_renderer_update_materials(void *h, const PolarisMaterialUpdate *u) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (Error e = t->UpdateMaterials(u)) { box->error = e.msg; return e.code; }
+	return 0;
+}
+int polaris_host_renderer_update_texture(void *h, uint32_t index, const void *texels, size_t n_bytes) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (Error e = t->UpdateTexture(index, texels, n_bytes)) { box->error = e.msg; return e.code; }
+	return 0;
+}
 // Denoising (polaris_hip_set_denoise) on every tracer, as set_option; only the primary's SyncFramebuffer runs, so only it filters.
 int polaris_host_renderer_set_denoise(void *h, const PolarisDenoiseParams *p) {
 	auto *box = static_cast<RendererBox *>(h);

@@ -36,6 +36,8 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_denoise.argtypes = [vp, C.POINTER(T.DenoiseParams)]
         lib.polaris_host_renderer_update_instances.argtypes = [vp, C.POINTER(T.InstanceUpdate)]
         lib.polaris_host_renderer_update_vertices.argtypes = [vp, C.POINTER(T.VertexUpdate)]
+        lib.polaris_host_renderer_update_materials.argtypes = [vp, C.POINTER(T.MaterialUpdate)]
+        lib.polaris_host_renderer_update_texture.argtypes = [vp, C.c_uint32, vp, C.c_size_t]
         lib.polaris_host_renderer_upload_scene.argtypes = [vp, C.POINTER(T.SceneView)]
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
@@ -186,6 +188,20 @@ class Renderer:
         if self._lib.polaris_host_renderer_update_vertices(self._h, C.byref(u)):
             raise RuntimeError(f"update_vertices failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
         del keep
+
+    def update_materials(self, nodes, material_index=None, scene_diffuse=-1, emissive_mat_nodes=None) -> None:
+        """polaris_hip_update_materials on every tracer: edit the scene's materials in place.  Arguments as
+        HipTracer.update_materials; no upload option."""
+        u, keep = T.material_update(nodes, material_index, scene_diffuse, emissive_mat_nodes)
+        if self._lib.polaris_host_renderer_update_materials(self._h, C.byref(u)):
+            raise RuntimeError(f"update_materials failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+        del keep
+
+    def update_texture(self, index: int, texels) -> None:
+        """polaris_hip_update_texture on every tracer: the texels of one texture, same format and size as uploaded."""
+        t = np.ascontiguousarray(texels)
+        if self._lib.polaris_host_renderer_update_texture(self._h, int(index), t.ctypes.data, t.nbytes):
+            raise RuntimeError(f"update_texture failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """polaris_hip_set_variance on every tracer, after the option "moments" on every tracer (polaris_host_renderer_set_variance)."""

@@ -18,7 +18,11 @@ the thresholds at their defaults).
 
 --variance SIGMA guides the filter by each pixel's variance (polaris_hip_set_variance with sigma_variance SIGMA, min_samples at its
 default, the option moments on every tracer; 0 = off); with --aov-dir the VARIANCE plane (M1 | M2 | n_eff | v) is also written as
-variance.npy."""
+variance.npy.
+
+--frames N --recolour NODE:r,g,b[:step] renders N frames with an edit of a material per frame instead of a camera move: frame k gives
+material node NODE the colour (r, g, b) + k * step * (1, 1, 1) through polaris_hip_update_materials -- the node
+table in place, no upload_scene -- then render(accumulated=0)."""
 import argparse
 import os
 import sys
@@ -76,6 +80,29 @@ def move_frames(r, sc, n: int, move: str, aspect: float):
         yield r.render(0)
 
 
+def parse_recolour(spec: str, num_nodes: int):
+    parts = spec.split(":")
+    try:
+        node, rgb = int(parts[0]), [float(x) for x in parts[1].split(",")]
+        step = float(parts[2]) if len(parts) > 2 else 0.0
+    except (ValueError, IndexError):
+        node, rgb, step = -1, [], 0.0
+    if len(parts) not in (2, 3) or len(rgb) != 3 or not 0 <= node < num_nodes:
+        raise ValueError(f"--recolour {spec!r}: NODE:r,g,b[:step] with NODE below {num_nodes}")
+    return node, np.array(rgb, np.float32), np.float32(step)
+
+
+def recolour_frames(r, sc, n: int, spec: str):
+    """Frame k: the scene's material nodes with node NODE's k[0..2] = (r, g, b) + k * step, given to every tracer in place
+    (Renderer.update_materials: the other arguments are the scene's own), then render(accumulated=0).  Yields (rows, ms)."""
+    node, rgb, step = parse_recolour(spec, len(sc.material_nodes))
+    nodes = np.ascontiguousarray(sc.material_nodes, dtype=T.MATERIAL_NODE).copy()
+    for k in range(n):
+        nodes["k"][node][:3] = rgb + np.float32(k) * step
+        r.update_materials(nodes, None, int(sc.scene_diffuse_mat_index), None)
+        yield r.render(0)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m polaris_amd.render", description=__doc__.split("\n")[0])
     ap.add_argument("scene", help="scene.obj")
@@ -94,6 +121,7 @@ def main(argv=None):
     ap.add_argument("--temporal", type=int, default=0, help="max_history of temporal reuse across camera moves (0 = off)")
     ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
     ap.add_argument("--move", default="right:0.05", help="DIR:OFFSET of every move with --frames (left, right, up, down, forward, backward)")
+    ap.add_argument("--recolour", default="", help="NODE:r,g,b[:step]: with --frames, edit material node NODE per frame in place instead of moving the camera")
     a = ap.parse_args(argv)
 
     rr = a.rr_bounces
@@ -115,7 +143,8 @@ def main(argv=None):
         if a.variance:
             r.set_variance(sigma_variance=a.variance, min_samples=T.VARIANCE_DEFAULTS["min_samples"])
         if a.frames:
-            for path, (rows, ms) in zip(frame_paths(a.out, a.frames), move_frames(r, sc, a.frames, a.move, a.width / a.height)):
+            frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height)
+            for path, (rows, ms) in zip(frame_paths(a.out, a.frames), frames):
                 r.save(path)
         else:
             rows, ms = r.render()

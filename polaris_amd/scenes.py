@@ -833,6 +833,42 @@ def vertex_update_args(scene: Scene):
     return scene.vertices.copy(), boxes, scene.normals.copy(), inv, ems
 
 
+def with_materials(base: Scene, nodes=None, material_index=None, scene_diffuse=None, emissive_mat_nodes=None, textures=None) -> Scene:
+    """`base` with other materials: the scene polaris_hip_update_materials / polaris_hip_update_texture make of an uploaded `base`
+    (DESIGN.md 10g).  nodes replace the material node table (as many as base's), material_index the triangles' roots, scene_diffuse
+    the background node (-1: none), emissive_mat_nodes every emissive's mat_node_index, textures {index: texels} the texels of
+    those textures (same format and size); None leaves base's.  Every geometry array is shared with base."""
+    nodes = base.material_nodes if nodes is None else np.ascontiguousarray(nodes, dtype=T.MATERIAL_NODE)
+    assert nodes.shape == base.material_nodes.shape
+    material_index = base.material_index if material_index is None else np.ascontiguousarray(material_index, dtype=np.uint32)
+    assert material_index.shape == base.material_index.shape
+    ems = base.emissives
+    if emissive_mat_nodes is not None:
+        ems = base.emissives.copy()
+        ems["mat_node_index"] = np.asarray(emissive_mat_nodes, dtype=np.uint32).reshape(len(ems))
+    blob = base.texture_data
+    if textures:
+        blob = base.texture_data.copy()
+        for index, texels in textures.items():
+            raw = np.frombuffer(np.ascontiguousarray(texels).tobytes(), dtype=np.uint8)
+            m = base.texture_meta[index]
+            bpp = {T.TEX_L8: 1, T.TEX_RGBA32F: 16}.get(int(m["format"]), 4)
+            assert len(raw) == bpp * int(m["width"]) * int(m["height"])
+            blob[int(m["data_offset"]):int(m["data_offset"]) + len(raw)] = raw
+    return Scene(bvh_nodes=base.bvh_nodes, mesh_instances=base.mesh_instances, material_nodes=nodes, emissives=ems, texture_data=blob,
+                 texture_meta=base.texture_meta, vertices=base.vertices, normals=base.normals, uvs=base.uvs, material_index=material_index,
+                 scene_diffuse_mat_index=base.scene_diffuse_mat_index if scene_diffuse is None else int(scene_diffuse),
+                 scene_emissive_mat_index=base.scene_emissive_mat_index, eye=base.eye.copy(), frustum=base.frustum.copy(),
+                 name=f"{base.name}-materials", bvh_max_depth=base.bvh_max_depth)
+
+
+def material_update_args(scene: Scene):
+    """(material nodes, material_index (NT,), scene_diffuse_mat_index, emissive mat_node_index (NE,)) of a scene: what
+    HipTracer.update_materials takes to give an uploaded scene `scene`'s materials (polaris_hip_update_materials)."""
+    return (scene.material_nodes.copy(), scene.material_index.copy(), int(scene.scene_diffuse_mat_index),
+            scene.emissives["mat_node_index"].astype(np.uint32))
+
+
 def textured_materials_scene(aspect=1.0) -> Scene:
     """A small scene touching every material operator and texture format (mix, mixMap, bumpMap,
     normalMap, disperse; L8, L32F, RGBA8, RGBA32F) -- parity coverage, not a benchmark."""

@@ -335,6 +335,37 @@ class HipTracer:
         self._check(self._lib.polaris_hip_update_vertices(self._h, C.byref(u)), self._h)
         del keep
 
+    def update_materials(self, nodes, material_index=None, scene_diffuse=-1, emissive_mat_nodes=None) -> None:
+        """Edit the uploaded scene's materials in place (polaris_hip_update_materials): nodes the whole new material
+        node table (as many as uploaded), material_index (NT,) the triangles' roots (None: unchanged), scene_diffuse the background
+        node (always taken: -1 = none), emissive_mat_nodes the new mat_node_index of every emissive (None: unchanged) --
+        scenes.material_update_args(scene) makes the tuple.  No upload option.  Queued state changes are committed first, as by Trace."""
+        self._commit()
+        u, keep = T.material_update(nodes, material_index, scene_diffuse, emissive_mat_nodes)
+        self._check(self._lib.polaris_hip_update_materials(self._h, C.byref(u)), self._h)
+        del keep
+
+    def update_texture(self, index: int, texels) -> None:
+        """Replace the texels of texture `index` in place (polaris_hip_update_texture): same format and size as uploaded."""
+        self._commit()
+        t = np.ascontiguousarray(texels)
+        self._check(self._lib.polaris_hip_update_texture(self._h, int(index), t.ctypes.data, t.nbytes), self._h)
+
+    def read_triangle_records(self) -> np.ndarray:
+        """The triangle records of the uploaded scene as the device holds them, one per slot (POLARIS_REC_TRIS; test tap): an array
+        of ctypes_api.TRI_RECORD."""
+        self._commit()
+        tris = np.zeros(int(self.read_shading_record()[3]), T.TRI_RECORD)
+        self._check(self._lib.polaris_hip_read_scene_records(self._h, T.REC_TRIS, tris.ctypes.data, max(tris.nbytes, 1)), self._h)
+        return tris
+
+    def read_shading_record(self) -> tuple[int, int, int, int]:
+        """(tri_bits, emit_classes, background node, triangle slots) of the uploaded scene: POLARIS_REC_SHADING."""
+        self._commit()
+        rec = np.zeros(4, np.uint32)
+        self._check(self._lib.polaris_hip_read_scene_records(self._h, T.REC_SHADING, rec.ctypes.data, rec.nbytes), self._h)
+        return int(rec[0]), int(rec[1]), int(rec[2].astype(np.int32)), int(rec[3])
+
     def read_scene_records(self) -> tuple[np.ndarray, np.ndarray]:
         """(pair records, instance records) of the uploaded scene as the device holds them (polaris_hip_read_scene_records; test tap):
         arrays of ctypes_api.PAIR_RECORD and INST_RECORD."""
