@@ -258,8 +258,9 @@ int polaris_hip_ipc_close(polaris_hip_tracer *dst, polaris_hip_peer *peer); /* w
  * device index of this process (-1: not visible here, e.g. under a per-rank visibility mask) and hipDeviceCanAccessPeer towards it
  * (-1: unknown).  ipc_open REFUSES (POLARIS_E_UNSUPPORTED) a ring on another GPU that this process cannot see at all -- there is no way to
  * tell whether the mapping would be reachable, and a kernel that reads an unreachable mapping faults the GPU; the caller falls back to
- * its strip transfers -- and marks a ring on a visible GPU without peer access for the staged path (POLARIS_MERGE_IPC_STAGED; option
- * "ipc_staged" = 1 forces that path for the peers opened afterwards: a testing aid).  The caller sets struct_size. */
+ * its strip transfers -- and marks every ring it does not KNOW to be reachable (a visible GPU without peer access, a failed query, no bus
+ * id on either side) for the staged path (POLARIS_MERGE_IPC_STAGED; option "ipc_staged" = 1 forces that path for the peers opened
+ * afterwards: a testing aid).  The caller sets struct_size. */
 typedef struct PolarisPeerInfo {
 	uint32_t struct_size;
 	uint32_t pid;             /* exporting process */
@@ -269,7 +270,7 @@ typedef struct PolarisPeerInfo {
 	int32_t can_access_peer;  /* hipDeviceCanAccessPeer(dst's device, local_device); -1 = unknown */
 	uint32_t depth, has_events;
 	char pci_bus_id[32];
-	int32_t staged;           /* 1: merges from this ring go through the staging strip (no peer access, or forced); 0: read where it lies */
+	int32_t staged;           /* 1: merges from this ring go through the staging strip (not known to be reachable, or forced); 0: read where it lies */
 	int32_t reserved;
 } PolarisPeerInfo;
 int polaris_hip_peer_info(polaris_hip_peer *peer, PolarisPeerInfo *out);
@@ -288,8 +289,10 @@ int polaris_hip_merge_slot(polaris_hip_tracer *dst, polaris_hip_tracer *src, uin
  *   PEER_ACCESS   ... source on another GPU of this process, read directly (hipDeviceEnablePeerAccess: xGMI peer read)
  *   STAGED        ... source on another GPU, no peer access: hipMemcpyPeerAsync into a staging strip, then added
  *   IPC_LOCAL     polaris_hip_merge_ipc, the peer's ring lives on dst's own GPU
- *   IPC_PEER      polaris_hip_merge_ipc, the peer's ring lives on another GPU and is read directly (IPC_UNKNOWN: the exporter gave no bus id)
- *   IPC_STAGED    polaris_hip_merge_ipc, the ring lives on a GPU this one has NO peer access to (hipDeviceCanAccessPeer = 0): the rows are
+ *   IPC_PEER      polaris_hip_merge_ipc, the peer's ring lives on another GPU and is read directly
+ *   IPC_UNKNOWN   no longer counted: a ring of unknown whereabouts (no bus id on either side) was read directly; it now goes through
+ *                 the staging strip and counts as IPC_STAGED (the constant stays: ABI)
+ *   IPC_STAGED    polaris_hip_merge_ipc, the ring is not KNOWN to be reachable (hipDeviceCanAccessPeer = 0 or failed, no bus id): the rows are
  *                 copied into a staging strip by the runtime (hipMemcpyAsync, which may go through the host) and added from there --
  *                 a kernel is never pointed at memory the device cannot reach
  *   DEVICE_STRIP  polaris_hip_merge_device (a strip some transport delivered: bench.py's fallback)

@@ -29,6 +29,7 @@
 #include "device_mem.h"
 #include "frame_sync.h"
 #include "kernel_table.h"
+#include "merge_plan.h"
 #include "polaris_hip.h"
 #include "trace_plan.h"
 
@@ -148,6 +149,154 @@ struct FrameSync {
 	void set_object_motion(int on) { opt_object_motion = on; drop(v.motion_toggled(on != 0)); } // (on differs from the option's value)
 };
 
+inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
+
+// The two accumulators (buffers.go:127-174) with everything MergeOutput needs around them; merge_plan.h holds the rules.  The TRACE
+// accumulator is a ring (polaris_hip_ipc_export): with depth > 1 every Trace writes the next slot, so a peer process may still read
+// frame f's rows while frame f + 1 is traced; depth 1 is the reference's single buffer.  It belongs to the handle's mu.  Each member
+// that moves the ring's index also does what the move means for the slots and their export events, so the three cannot drift apart.
+// The FRAME accumulator belongs to the MERGE stream: the Reset stage, MergeOutput and merge_device run there, under `mu` below
+// only -- never under the handle's mu, which a Trace holds from start to end -- so a secondary's MergeOutput onto the primary
+// overlaps the primary's own Trace (Exec1DNoWait, tracer/opencl/resources.go:119; renderer/default.go:188-191 calls it from the
+// secondaries' goroutines).  SyncFramebuffer makes the main stream wait for the merges queued so far.
+// Lock order: the handle's mu, then mu.  W / H / frame are written under both and may be read under either.
+struct FrameAccum {
+	uint32_t W = 0, H = 0;
+	DevArray<float4> frame;
+	DevArray<float4> ring[POLARIS_IPC_MAX_DEPTH];
+	RingIndex ix;
+	// One inter-process event PER RING SLOT, recorded at the end of the Trace that wrote the slot (once exported).  A slot's event
+	// is re-recorded only when a Trace comes round to the slot again -- which the caller's protocol forbids while a peer may still
+	// read it -- so a peer's wait on slot s's event names exactly the Trace whose rows it is about to read (round 4 had ONE event
+	// re-recorded by every Trace: a primary merging frame f while the peer was already in Trace f + 1 waited for whichever it got).
+	DevEvent ev_done[POLARIS_IPC_MAX_DEPTH];
+
+	DevStream q; // the merge stream
+	std::mutex mu;
+	DevEvent ev_merged;
+	DevArray<float4> staging;                    // peer-merge staging strip (grow-only; the merge stream's: merges are serialised on it)
+	uint64_t counts[POLARIS_MERGE_BRANCHES] = {}; // which branch every merge onto this tracer took (polaris_hip_merge_counts)
+	std::string error;                           // last error of a merge (the handle's `error` belongs to its mu)
+	uint64_t error_seq = 0;                      // (g_error_seq: which of the two is the newer one)
+	int ipc_staged = 0; // option, a testing aid: peers opened from now on are merged through the staging strip (the path of a GPU without peer access)
+	// Reset epoch: how many times a Trace with accumulated_samples == 0 (or reset_frame) has got as far as queueing the clear
+	// of the frame accumulator -- or has failed before it could.  A host that merges from other threads waits for the
+	// primary's epoch to advance before it queues this frame's merges (polaris_hip_wait_reset), instead of for the
+	// primary's whole Trace.
+	uint64_t reset_epoch = 0;
+	std::condition_variable reset_cv;
+	// Events recorded by OTHER handles' merge streams behind their reads of this handle's trace accumulator
+	// (polaris_hip_merge with dst != src): this handle's next Trace waits for them before it clears the rows.
+	struct Reader { DevEvent ev; int device; };
+	std::mutex readers_mu;
+	std::vector<Reader> readers, reader_pool;
+
+	// ---- the ring (caller holds the handle's mu; release, resize and redepth: mu too, every stream idle)
+	float4 *current() const { return ring[ix.pos]; }
+	float4 *slot(int s) const { const int i = ix.slot_of(s); return i < 0 ? nullptr : ring[i].get(); } // s < 0: the current one; null: out of range (or no frame yet)
+	void advance() { ix.advance(); }
+	void release() { // no frame: an IPC export dies with the buffers (peers close, the tracer exports again), and its events with it
+		for (auto &s : ring) s.reset();
+		for (auto &e : ev_done) e.reset();
+		ix.reset();
+		frame.reset();
+		W = H = 0;
+	}
+	static hipError_t alloc_cleared(DevArray<float4> &a, size_t F, hipStream_t main) {
+		const hipError_t e = a.alloc(F);
+		return e != hipSuccess ? e : hipMemsetAsync(a, 0, F * sizeof(float4), main);
+	}
+	hipError_t resize(uint32_t w, uint32_t h, hipStream_t main) { // a single cleared buffer each; the dimensions stand once all of it does
+		release();
+		hipError_t e = alloc_cleared(ring[0], (size_t)w * h, main);
+		if (e == hipSuccess) e = alloc_cleared(frame, (size_t)w * h, main);
+		if (e == hipSuccess) e = hipStreamSynchronize(main);
+		if (e == hipSuccess) { W = w; H = h; }
+		return e;
+	}
+	hipError_t redepth(uint32_t depth, hipStream_t main) { // grow or shrink the ring to `depth` slots (slot 0 always exists); new slots are cleared
+		for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) {
+			if (i >= depth) { ring[i].reset(); ev_done[i].reset(); }
+			else if (!ring[i])
+				if (const hipError_t e = alloc_cleared(ring[i], (size_t)W * H, main)) return e;
+		}
+		const hipError_t e = hipStreamSynchronize(main);
+		if (e == hipSuccess) ix.redepth(depth);
+		return e;
+	}
+
+	// ---- the frame accumulator and the merge stream
+	// Clear the frame accumulator and announce the reset (caller holds the handle's mu, not mu).  clear = false: a Trace that failed
+	// before it could queue the clear announces all the same, so that nobody waits for a reset that will not come.
+	hipError_t reset_frame(bool clear = true) {
+		hipError_t e = hipSuccess;
+		{
+			std::lock_guard<std::mutex> lk(mu);
+			if (clear) e = hipMemsetAsync(frame, 0, (size_t)W * H * sizeof(float4), q);
+			reset_epoch++;
+		}
+		reset_cv.notify_all();
+		return e;
+	}
+	// THE launch that adds n pixels of `rows` onto the frame accumulator from pixel `off` on, counted as `branch` (caller holds mu).
+	hipError_t add_rows(const float4 *rows, size_t off, size_t n, bool moments, int branch) {
+		kAggregate[moments].enqueue(grid_for(n), WG, 0, q, rows, frame + off, (uint32_t)n);
+		const hipError_t e = hipGetLastError();
+		if (e == hipSuccess) counts[branch]++;
+		return e;
+	}
+	bool need_staging(size_t n) { // the staging strip, big enough for n pixels (caller holds mu)
+		if (staging.capacity() >= n) return true;
+		(void)hipStreamSynchronize(q); // (an earlier merge may still read the strip that goes)
+		return staging.alloc(n) == hipSuccess;
+	}
+	int fail(int code, const char *msg) { // a merge's error (caller holds mu; the handle's `error` belongs to its mu, which a running Trace holds)
+		error = msg;
+		error_seq = ++g_error_seq;
+		g_thread_error = msg;
+		return code;
+	}
+	// Everything queued on the merge stream so far happens before whatever is queued on `main` next (caller holds the handle's mu).
+	hipError_t join_merges(hipStream_t main) {
+		std::lock_guard<std::mutex> lk(mu);
+		hipError_t e = hipEventRecord(ev_merged, q);
+		if (e == hipSuccess) e = hipStreamWaitEvent(main, ev_merged, 0);
+		return e;
+	}
+
+	// ---- other handles' reads of the trace accumulator
+	// Whatever other handles' merge streams still read of the trace accumulator happens before what is queued on `main` next (caller
+	// holds the handle's mu).  The events go back to the pool: a later record simply re-arms them.
+	hipError_t wait_readers(hipStream_t main) {
+		std::lock_guard<std::mutex> lk(readers_mu);
+		hipError_t first = hipSuccess;
+		for (auto &r : readers) {
+			const hipError_t e = hipStreamWaitEvent(main, r.ev, 0);
+			if (first == hipSuccess) first = e;
+			reader_pool.push_back(std::move(r));
+		}
+		readers.clear();
+		return first;
+	}
+	// An event on `device` (the current device) for a read of the trace accumulator; recorded by the reader, then handed back (add_reader).
+	DevEvent reader_event(int device) {
+		std::lock_guard<std::mutex> lk(readers_mu);
+		for (size_t i = 0; i < reader_pool.size(); i++)
+			if (reader_pool[i].device == device) {
+				DevEvent e = std::move(reader_pool[i].ev);
+				reader_pool.erase(reader_pool.begin() + (long)i);
+				return e;
+			}
+		DevEvent e;
+		if (e.create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError();
+		return e;
+	}
+	void add_reader(DevEvent e, int device) {
+		std::lock_guard<std::mutex> lk(readers_mu);
+		readers.push_back({std::move(e), device});
+	}
+};
+
 } // namespace
 
 // Every stream, event and device allocation of the handle is a member that owns it (device_mem.h), so `delete h` releases
@@ -156,46 +305,13 @@ struct FrameSync {
 struct polaris_hip_tracer {
 	int device = 0;
 	char pci_bus_id[32] = {}; // which GPU `device` is (device indices are per process); "" if the runtime does not say
-	uint64_t merge_counts[POLARIS_MERGE_BRANCHES] = {}; // which branch every merge onto this tracer took (under merge_mu; polaris_hip_merge_counts)
 	hipStream_t stream = nullptr; // the main stream: an alias of pipe[0].q, which owns it
 	std::mutex mu;
 	std::string error;
-	// The frame accumulator belongs to the MERGE stream: the Reset stage, MergeOutput and merge_device run there, under
-	// merge_mu only -- never under `mu`, which a Trace holds from start to end -- so a secondary's MergeOutput onto the
-	// primary overlaps the primary's own Trace (Exec1DNoWait, tracer/opencl/resources.go:119; renderer/default.go:188-191
-	// calls it from the secondaries' goroutines).  SyncFramebuffer makes the main stream wait for the merges queued so far.
-	// Lock order: mu, then merge_mu.  W / H / frame_acc are written under both and may be read under either.
-	DevStream merge_stream;
-	std::mutex merge_mu;
-	DevEvent ev_merged;
-	// Reset epoch: how many times a Trace with accumulated_samples == 0 (or reset_frame) has got as far as queueing the clear
-	// of the frame accumulator -- or has failed before it could.  A host that merges from other threads waits for the
-	// primary's epoch to advance before it queues this frame's merges (polaris_hip_wait_reset), instead of for the
-	// primary's whole Trace.
-	uint64_t reset_epoch = 0;
-	std::condition_variable reset_cv;
-	std::string merge_error;              // last error of a merge (under merge_mu); `error` belongs to mu
-	uint64_t error_seq = 0, merge_error_seq = 0; // which of the two is the newer one (g_error_seq)
+	uint64_t error_seq = 0; // (g_error_seq: whether `error` or fa.error is the newer one)
 
-	// frame-sized state (buffers.go:127-174)
-	uint32_t W = 0, H = 0;
-	float4 *trace_acc = nullptr; // == ring[ring_pos], which owns it
-	DevArray<float4> frame_acc;
+	FrameAccum fa; // the trace accumulator's ring, the frame accumulator and the merge stream (whose lock fa.mu is taken after mu)
 	DevArray<uchar4> framebuffer;
-	// The trace accumulator as a ring (polaris_hip_ipc_export): with depth > 1 every Trace writes the next slot, so a peer
-	// process may still read frame f's rows while frame f + 1 is traced.  Depth 1 = the reference's single buffer.
-	DevArray<float4> ring[POLARIS_IPC_MAX_DEPTH];
-	uint32_t ring_depth = 1, ring_pos = 0;
-	// One inter-process event PER RING SLOT, recorded at the end of the Trace that wrote the slot (once exported).  A slot's event
-	// is re-recorded only when a Trace comes round to the slot again -- which the caller's protocol forbids while a peer may still
-	// read it -- so a peer's wait on slot s's event names exactly the Trace whose rows it is about to read (round 4 had ONE event
-	// re-recorded by every Trace: a primary merging frame f while the peer was already in Trace f + 1 waited for whichever it got).
-	DevEvent ev_ipc_done[POLARIS_IPC_MAX_DEPTH];
-	// Events recorded by OTHER handles' merge streams behind their reads of this handle's trace accumulator
-	// (polaris_hip_merge with dst != src): this handle's next Trace waits for them before it clears the rows.
-	struct Reader { DevEvent ev; int device; };
-	std::mutex readers_mu;
-	std::vector<Reader> readers, reader_pool;
 
 	// the uploaded scene, and the options the next upload resolves into it
 	DeviceScene ds;
@@ -209,7 +325,7 @@ struct polaris_hip_tracer {
 
 	FrameSync fs; // the synced frame's features, planes and history
 	int opt_instance_update = 0, opt_vertex_update = 0; // the in-place updates: the next upload keeps what they need in ds.upd / ds.vup
-	std::atomic<bool> opt_moments{false}; // option "moments" (the accumulators' .w keeps the sum of L^2; variance guidance needs it): merges read it under merge_mu, hence atomic
+	std::atomic<bool> opt_moments{false}; // option "moments" (the accumulators' .w keeps the sum of L^2; variance guidance needs it): merges read it under fa.mu, hence atomic
 
 	// wavefront batch state: up to kMaxPipes pipelines (option "overlap", default 4; a Trace uses min(overlap, #batches) of
 	// them) so that consecutive batches overlap: the sparse late-bounce launches of batch i run beside the dense early
@@ -242,9 +358,7 @@ struct polaris_hip_tracer {
 	DevArray<unsigned long long> d_stats;
 	DevArray<float4> d_cam_o; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
 	int num_cus = 256;
-	DevArray<float4> staging; // peer-merge staging strip (grow-only)
 	DevArray<uint32_t> d_retag; // polaris_hip_update_materials: the class of every material node (a byte each), then the emissives' new nodes (grow-only)
-	int opt_ipc_staged = 0;  // testing aid: peers opened from now on are merged through the staging strip (the path of a GPU without peer access)
 
 	// options: what a Trace plans from (trace_plan.h), and the rest
 	TraceOptions opt;
@@ -255,7 +369,7 @@ struct polaris_hip_tracer {
 	// per-kernel timing (option time_kernels)
 	struct Pending { const char *name; DevEvent a, b; };
 	std::vector<Pending> pending;
-	std::vector<Pending> merge_pending; // launches on the merge stream (under merge_mu)
+	std::vector<Pending> merge_pending; // launches on the merge stream (under fa.mu)
 	std::vector<DevEvent> event_pool;
 	std::map<std::string, KernelTimer> timers;
 	std::map<std::string, const char *> timer_symbol; // timer name -> the kernel symbol it last bracketed (polaris_hip_kernel_symbol)
@@ -271,7 +385,7 @@ struct polaris_hip_peer {
 	IpcMapping mem[POLARIS_IPC_MAX_DEPTH];
 	DevEvent ev[POLARIS_IPC_MAX_DEPTH];        // per slot: the peer's "the Trace that wrote this slot is done" event (null: the exporter had none)
 	PolarisPeerInfo info{};                    // what the mapping is (polaris_hip_peer_info); info.same_device picks the merge branch counted
-	void drop_events() { for (auto &e : ev) e.reset(); } // under owner->merge_mu once the peer is published
+	void drop_events() { for (auto &e : ev) e.reset(); } // under owner->fa.mu once the peer is published
 };
 
 
@@ -316,7 +430,7 @@ struct Timed {
 	polaris_hip_tracer *h;
 	const char *name;
 	hipStream_t q;
-	bool on_merge; // a launch on the merge stream: the caller holds merge_mu (not mu), so the event pool is not touched
+	bool on_merge; // a launch on the merge stream: the caller holds fa.mu (not mu), so the event pool is not touched
 	DevEvent a, b;
 	Timed(polaris_hip_tracer *h_, const char *n, const char *symbol, hipStream_t q_, bool merge = false) : h(h_), name(n), q(q_), on_merge(merge) {
 		if (!h->opt_time_kernels || !name) return;
@@ -363,55 +477,12 @@ void collect_timers(polaris_hip_tracer *h) { // caller holds mu; the main stream
 		list.swap(keep);
 	};
 	take(h->pending, false);
-	std::lock_guard<std::mutex> lk(h->merge_mu); // (another thread may be queueing a merge right now: its events stay pending)
+	std::lock_guard<std::mutex> lk(h->fa.mu); // (another thread may be queueing a merge right now: its events stay pending)
 	take(h->merge_pending, true);
 }
 
-// Everything queued on the merge stream so far happens before whatever is queued on `q` next (caller holds mu).
-hipError_t join_merges(polaris_hip_tracer *h, hipStream_t q) {
-	std::lock_guard<std::mutex> lk(h->merge_mu);
-	hipError_t e = hipEventRecord(h->ev_merged, h->merge_stream);
-	if (e == hipSuccess) e = hipStreamWaitEvent(q, h->ev_merged, 0);
-	return e;
-}
-
-// Whatever other handles' merge streams still read of this handle's trace accumulator happens before what is queued on `q`
-// next (caller holds mu).  The events go back to the pool: a later record simply re-arms them.
-hipError_t wait_readers(polaris_hip_tracer *h, hipStream_t q) {
-	std::lock_guard<std::mutex> lk(h->readers_mu);
-	hipError_t first = hipSuccess;
-	for (auto &r : h->readers) {
-		const hipError_t e = hipStreamWaitEvent(q, r.ev, 0);
-		if (first == hipSuccess) first = e;
-		h->reader_pool.push_back(std::move(r));
-	}
-	h->readers.clear();
-	return first;
-}
-
-// An event on `device` (the current device) for a read of src's trace accumulator; recorded by the caller, then handed to src.
-DevEvent reader_event(polaris_hip_tracer *src, int device) {
-	std::lock_guard<std::mutex> lk(src->readers_mu);
-	for (size_t i = 0; i < src->reader_pool.size(); i++)
-		if (src->reader_pool[i].device == device) {
-			DevEvent e = std::move(src->reader_pool[i].ev);
-			src->reader_pool.erase(src->reader_pool.begin() + (long)i);
-			return e;
-		}
-	DevEvent e;
-	if (e.create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError();
-	return e;
-}
-
-void free_ring(polaris_hip_tracer *h) { // caller holds mu + merge_mu, every stream idle
-	for (auto &slot : h->ring) slot.reset();
-	h->trace_acc = nullptr;
-	h->ring_depth = 1;
-	h->ring_pos = 0;
-}
-
 hipError_t sync_all(polaris_hip_tracer *h) { // every pipeline of the handle idle (before anything the kernels use is freed)
-	hipError_t first = h->merge_stream ? hipStreamSynchronize(h->merge_stream) : hipSuccess;
+	hipError_t first = h->fa.q ? hipStreamSynchronize(h->fa.q) : hipSuccess;
 	for (int p = 0; p < polaris_hip_tracer::kMaxPipes; p++)
 		if (h->pipe[p].q) {
 			const hipError_t e = hipStreamSynchronize(h->pipe[p].q);
@@ -460,25 +531,24 @@ int ensure_streams(polaris_hip_tracer *h, int p, size_t slots, bool want_inst, u
 	return POLARIS_OK;
 }
 
-int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
-	if (!r) return fail(h, POLARIS_E_BAD_ARGUMENT, "block request is null");
-	if (h->W == 0 || h->H == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
-	if (r->frame_w != h->W || r->frame_h != h->H)
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "request frame %ux%u does not match the tracer's %ux%u", r->frame_w, r->frame_h, h->W, h->H);
-	if (r->block_h == 0 || (uint64_t)r->block_y + r->block_h > h->H)
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "block rows [%u,%u) outside the frame", r->block_y, r->block_y + r->block_h);
-	if (r->block_x != 0 || (r->block_w != 0 && r->block_w != h->W))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "only full-width row blocks are supported (BlockW = FrameW, renderer/default.go:110)");
-	return POLARIS_OK;
-}
+// A block refusal (merge_plan.h refuse_block) in words, by BlockRefusal; null: the caller's own (a call under mu names the numbers, a merge does not).
+const char *const kBlockRefusal[] = {nullptr, "block request is null", "frame dimensions not set (UpdateState FrameDimensions)", nullptr, nullptr,
+                                     "only full-width row blocks are supported (BlockW = FrameW, renderer/default.go:110)"};
 
-inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
+int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
+	switch (const BlockRefusal why = refuse_block(h->fa.W, h->fa.H, r)) {
+	case BlockRefusal::None: return POLARIS_OK;
+	case BlockRefusal::FrameMismatch: return fail(h, POLARIS_E_BAD_ARGUMENT, "request frame %ux%u does not match the tracer's %ux%u", r->frame_w, r->frame_h, h->fa.W, h->fa.H);
+	case BlockRefusal::RowsOutside: return fail(h, POLARIS_E_BAD_ARGUMENT, "block rows [%u,%u) outside the frame", r->block_y, r->block_y + r->block_h);
+	default: return fail(h, POLARIS_E_BAD_ARGUMENT, "%s", kBlockRefusal[(int)why]);
+	}
+}
 
 // The planes of the set `need` exist from their first use on, each of the frame's size; those of `clear` are cleared on the main stream,
 // those of `clear_new` if they are allocated here (caller holds mu).
 int ensure_planes(polaris_hip_tracer *h, uint32_t need, uint32_t clear = 0, uint32_t clear_new = 0) {
 	FrameSync &S = h->fs;
-	const size_t F = (size_t)h->W * h->H;
+	const size_t F = (size_t)h->fa.W * h->fa.H;
 	for (uint32_t p = 0; p < kNumPlanes4; p++) {
 		if (!(need >> p & 1)) continue;
 		if (!S.pl[p]) { HIP_TRY(h, S.pl[p].alloc(F)); clear |= clear_new & 1u << p; }
@@ -494,11 +564,11 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 	FrameSync &S = h->fs;
 	const bool want_inst = S.features().motion_on();
 	if (S.v.gbuffer() && (!want_inst || S.gb_inst)) return POLARIS_OK;
-	const size_t F = (size_t)h->W * h->H;
+	const size_t F = (size_t)h->fa.W * h->fa.H;
 	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0))) return rc;
 	CameraArgs cam = h->cam;
-	cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
-	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
+	cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
+	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
 	             want_inst ? S.gb_inst.get() : nullptr);
 	HIP_TRY(h, hipGetLastError());
 	S.v.gbuffer_computed();
@@ -636,15 +706,15 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	hipStream_t q = P.q;
 	P.st.hit12 = plan.hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
 	P.st.o12 = plan.o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
-	note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->W, r->block_y,
+	note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y,
 	            exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
 	ShadeArgs A{};
 	A.seeds = h->d_seeds; A.seed_stride = stride; A.first_sample = s0;
-	A.N = N; A.Npad = Npad; A.W = h->W; A.blockY = r->block_y;
+	A.N = N; A.Npad = Npad; A.W = h->fa.W; A.blockY = r->block_y;
 	A.min_rr = r->min_bounces_for_rr;
 	A.exact = exact ? 1 : 0;
 	A.prefilter = plan.prefilter ? 1 : 0;
-	A.acc = exact ? h->trace_acc : P.st.lsum;
+	A.acc = exact ? h->fa.current() : P.st.lsum;
 	const uint32_t persistent = plan.trace_grid(false, wgs), persistent_occl = plan.trace_grid(true, wgs);
 	for (uint32_t b = 0; b < B; b++) {
 		const BouncePlan &pl = plan.bounce[b];
@@ -671,7 +741,7 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	if (!exact) {
 		// batches resolve into the trace accumulator in sample order: wait for the previous batch's resolve
 		if (resolve_after) note(hipStreamWaitEvent(q, resolve_after, 0));
-		note(launch(h, "resolve", q, kResolve[plan.moments], grid_for(N), WG, 0, P.st.lsum, h->trace_acc, K, N, Npad, r->block_y * h->W));
+		note(launch(h, "resolve", q, kResolve[plan.moments], grid_for(N), WG, 0, P.st.lsum, h->fa.current(), K, N, Npad, r->block_y * h->fa.W));
 	}
 	note(hipEventRecord(P.done, q));
 	note(hipGetLastError()); // (whatever a launch left)
@@ -969,8 +1039,8 @@ int polaris_hip_create(int device_index, polaris_hip_tracer **out) {
 	h->stream = h->pipe[0].q;
 	for (int p = 0; p < polaris_hip_tracer::kMaxPipes && e == hipSuccess; p++) e = h->pipe[p].done.create(hipEventCreateWithFlags, hipEventDisableTiming);
 	if (e == hipSuccess) e = h->ev_fork.create(hipEventCreateWithFlags, hipEventDisableTiming);
-	if (e == hipSuccess) e = h->merge_stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking);
-	if (e == hipSuccess) e = h->ev_merged.create(hipEventCreateWithFlags, hipEventDisableTiming);
+	if (e == hipSuccess) e = h->fa.q.create(hipStreamCreateWithFlags, hipStreamNonBlocking);
+	if (e == hipSuccess) e = h->fa.ev_merged.create(hipEventCreateWithFlags, hipEventDisableTiming);
 	if (e == hipSuccess) e = h->d_stats.alloc(ST_COUNT);
 	if (e == hipSuccess) e = h->d_cam_o.alloc(1);
 	if (e == hipSuccess) {
@@ -996,9 +1066,9 @@ void polaris_hip_destroy(polaris_hip_tracer *h) {
 		if (h->stream) (void)hipStreamSynchronize(h->stream);
 		for (int p = 1; p < polaris_hip_tracer::kMaxPipes; p++)
 			if (h->pipe[p].q) (void)hipStreamSynchronize(h->pipe[p].q);
-		if (h->merge_stream) (void)hipStreamSynchronize(h->merge_stream);
+		if (h->fa.q) (void)hipStreamSynchronize(h->fa.q);
 		collect_timers(h);
-		std::lock_guard<std::mutex> lk_merge(h->merge_mu); // (a merge queued by another thread has left its critical section)
+		std::lock_guard<std::mutex> lk_merge(h->fa.mu); // (a merge queued by another thread has left its critical section)
 	}
 	// The members release themselves, outside the locks (they are members too) and in no particular order.  Releasing "under the
 	// locks and before the main stream goes", as this function once did by hand, was no constraint: a caller that destroys a handle
@@ -1017,8 +1087,8 @@ const char *polaris_hip_last_error(polaris_hip_tracer *h) {
 		seq = h->error_seq;
 	}
 	{
-		std::lock_guard<std::mutex> lk(h->merge_mu);
-		if (h->merge_error_seq > seq) copy = h->merge_error; // the newer of the two
+		std::lock_guard<std::mutex> lk(h->fa.mu);
+		if (h->fa.error_seq > seq) copy = h->fa.error; // the newer of the two
 	}
 	return copy.c_str();
 }
@@ -1029,24 +1099,15 @@ int polaris_hip_resize(polaris_hip_tracer *h, uint32_t frame_w, uint32_t frame_h
 	if (frame_w == 0 || frame_h == 0 || (uint64_t)frame_w * frame_h > (1ull << 28))
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "bad frame dimensions %ux%u", frame_w, frame_h);
 	HIP_TRY(h, hipSetDevice(h->device));
-	std::lock_guard<std::mutex> lk_merge(h->merge_mu); // (the frame accumulator is the merge stream's)
+	std::lock_guard<std::mutex> lk_merge(h->fa.mu); // (the frame accumulator is the merge stream's)
 	HIP_TRY(h, sync_all(h));
-	free_ring(h); // (an IPC export dies with the buffers: peers close, the tracer exports again)
+	h->fa.release(); // everything of the old size goes before anything of the new size is allocated; no frame until all of it stands
 	h->fs.resized();
-	h->frame_acc.reset();
 	h->framebuffer.reset();
-	h->W = h->H = 0;
 	const size_t F = (size_t)frame_w * frame_h;
-	HIP_TRY(h, h->ring[0].alloc(F));
-	h->trace_acc = h->ring[0];
-	HIP_TRY(h, h->frame_acc.alloc(F));
 	HIP_TRY(h, h->framebuffer.alloc(F));
-	HIP_TRY(h, hipMemsetAsync(h->trace_acc, 0, F * sizeof(float4), h->stream));
-	HIP_TRY(h, hipMemsetAsync(h->frame_acc, 0, F * sizeof(float4), h->stream));
 	HIP_TRY(h, hipMemsetAsync(h->framebuffer, 0, F * sizeof(uchar4), h->stream));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->W = frame_w;
-	h->H = frame_h;
+	HIP_TRY(h, h->fa.resize(frame_w, frame_h, h->stream)); // (waits for the main stream)
 	return POLARIS_OK;
 }
 
@@ -1256,7 +1317,7 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "stage_lds") h->opt.stage_lds = value != 0;
 	else if (k == "shade_prefilter") h->opt.shade_prefilter = value != 0;
 	else if (k == "shade_sort") h->opt.shade_sort = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
-	else if (k == "ipc_staged") h->opt_ipc_staged = value != 0;
+	else if (k == "ipc_staged") h->fa.ipc_staged = value != 0;
 	else if (k == "overlap") h->opt.overlap = (int)std::max<int64_t>(1, std::min<int64_t>(value, polaris_hip_tracer::kMaxPipes));
 	else if (k == "trace_grid") h->opt.trace_grid = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
 	else if (k == "trace_wgs_per_cu") h->opt.trace_wgs_per_cu = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
@@ -1294,10 +1355,9 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	// a Trace that resets the frame announces it (reset epoch) once the clear is queued -- or when it fails before that, so
 	// that nobody waits for a reset that will not come
 	struct ResetAnnounce {
-		polaris_hip_tracer *h; bool due, done = false;
-		void now() { if (due && !done) { done = true; { std::lock_guard<std::mutex> lk(h->merge_mu); h->reset_epoch++; } h->reset_cv.notify_all(); } }
-		~ResetAnnounce() { now(); }
-	} announce{h, r && r->accumulated_samples == 0};
+		FrameAccum &fa; bool due;
+		~ResetAnnounce() { if (due) (void)fa.reset_frame(false); }
+	} announce{h->fa, r && r->accumulated_samples == 0};
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // ErrNoSceneData, tracer.go:203-205
 	if (int rc = check_request(h, r)) return rc;
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set (UpdateState CameraData)");
@@ -1306,7 +1366,7 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	const size_t need_seeds = (size_t)spp * (1 + B);
 	if (need_seeds && (!seeds || n_seeds < need_seeds))
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "seed list has %zu entries, need samples*(1+bounces) = %zu", n_seeds, need_seeds);
-	const uint64_t N64 = (uint64_t)h->W * r->block_h;
+	const uint64_t N64 = (uint64_t)h->fa.W * r->block_h;
 	if (N64 > (1u << 24)) // the reference stores the path index as a float in ray.dir.w (util/ray.cl:9-12)
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "block has %llu pixels; the path index is exact only below 2^24", (unsigned long long)N64);
 	const uint32_t N = (uint32_t)N64, Npad = (N + WG - 1) / WG * WG;
@@ -1333,31 +1393,25 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	const uint32_t K = plan.K;
 	const int n_pipes = plan.n_pipes;
 	HIP_TRY(h, h->d_seeds.reserve(need_seeds));
-	h->cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H); // resources.go:130-133
-	const size_t F = (size_t)h->W * h->H;
+	h->cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H); // resources.go:130-133
+	const size_t F = (size_t)h->fa.W * h->fa.H;
 	hipStream_t q = h->stream;
 	// The next slot of the ring: a peer may still be reading the previous frame's rows (polaris_hip_ipc_export).  Advanced only
 	// HERE, behind the last step that can fail for want of memory (the batch buffers, the seed list): after a Trace that failed
 	// before it queued anything, trace_slot() / merge_slot / export_block still name the slot of the last frame that was traced.
-	if (h->ring_depth > 1) {
-		h->ring_pos = (h->ring_pos + 1) % h->ring_depth;
-		h->trace_acc = h->ring[h->ring_pos];
-	}
+	h->fa.advance();
 	HIP_TRY(h, hipEventRecord(h->ev_start, q));
-	if (r->accumulated_samples == 0) { // pipeline Reset stage (tracer.go:208-213): the frame accumulator lives on the merge stream
-		{
-			std::lock_guard<std::mutex> lk_merge(h->merge_mu);
-			HIP_TRY(h, hipMemsetAsync(h->frame_acc, 0, F * sizeof(float4), h->merge_stream));
-		}
-		announce.now(); // merges queued from here on land on the cleared accumulator
+	if (announce.due) { // pipeline Reset stage (tracer.go:208-213): the frame accumulator lives on the merge stream
+		announce.due = false;
+		HIP_TRY(h, h->fa.reset_frame()); // merges queued from here on land on the cleared accumulator
 	}
 	// A merge that still READS this tracer's trace accumulator (MergeOutput(self) runs on the merge stream; Trace -> MergeOutput(self)
 	// -> Trace without a SyncFramebuffer in between is the progressive loop) must be done before the rows are cleared and
 	// rewritten: a device-side wait, the host does not block.  (A merge queued by ANOTHER handle onto its own merge stream
 	// -- dst != src -- is ordered by the peer-read fence in polaris_hip_merge: src's `readers` event, below.)
-	HIP_TRY(h, join_merges(h, q));
-	HIP_TRY(h, wait_readers(h, q));
-	HIP_TRY(h, hipMemsetAsync(h->trace_acc, 0, F * sizeof(float4), q)); // ClearTraceAccumulator (tracer.go:215)
+	HIP_TRY(h, h->fa.join_merges(q));
+	HIP_TRY(h, h->fa.wait_readers(q));
+	HIP_TRY(h, hipMemsetAsync(h->fa.current(), 0, F * sizeof(float4), q)); // ClearTraceAccumulator (tracer.go:215)
 	HIP_TRY(h, hipMemsetAsync(h->d_stats, 0, ST_COUNT * sizeof(unsigned long long), q));
 	if (need_seeds) HIP_TRY(h, hipMemcpyAsync(h->d_seeds, seeds, need_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, q));
 	if (n_pipes > 1) { // fork: the other pipelines start after the clears and the seed upload
@@ -1380,7 +1434,7 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	HIP_TRY(h, hipGetLastError());
 	unsigned long long hs[ST_COUNT];
 	HIP_TRY(h, hipMemcpyAsync(hs, h->d_stats, sizeof hs, hipMemcpyDeviceToHost, q));
-	if (h->ev_ipc_done[h->ring_pos]) HIP_TRY(h, hipEventRecord(h->ev_ipc_done[h->ring_pos], q)); // what a peer process's merge of THIS slot waits for (polaris_hip_merge_ipc)
+	if (hipEvent_t done = h->fa.ev_done[h->fa.ix.pos]) HIP_TRY(h, hipEventRecord(done, q)); // what a peer process's merge of THIS slot waits for (polaris_hip_merge_ipc)
 	HIP_TRY(h, hipEventRecord(h->ev_stop, q));
 	HIP_TRY(h, hipStreamSynchronize(q));
 	drain.armed = false; // the join above made q wait for every pipeline
@@ -1415,130 +1469,131 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	return POLARIS_OK;
 }
 
-// MergeOutput, shared by polaris_hip_merge / _merge_slot (a tracer of this process) and polaris_hip_merge_ipc (another
-// process's ring, mapped here).  Everything on dst's merge stream, under dst->merge_mu only.
-static int merge_rows(polaris_hip_tracer *dst, polaris_hip_tracer *src, polaris_hip_peer *peer, int slot, const PolarisBlockRequest *r) {
-	// The source's trace accumulator is complete (its Trace is synchronous and has returned): snapshot what is needed of the
-	// source under ITS lock, briefly.  The destination is touched under merge_mu only -- never under dst->mu, which the
-	// destination's own Trace holds from start to end: a secondary's MergeOutput overlaps the primary's Trace
-	// (renderer/default.go:188-191 calls it from the secondaries' goroutines; Exec1DNoWait, resources.go:119).
-	int src_device = dst->device;
-	uint32_t src_w = 0, src_h = 0;
-	const float4 *src_acc = nullptr;
-	bool bad_slot = false;
-	if (src) {
-		std::lock_guard<std::mutex> lk_src(src->mu);
-		src_device = src->device; src_w = src->W; src_h = src->H;
-		if (slot < 0) src_acc = src->trace_acc;
-		else if ((uint32_t)slot < src->ring_depth) src_acc = src->ring[slot];
-		else bad_slot = true;
+// What a MergeOutput reads: one slot of a trace accumulator ring, resolved by the entry point that names it.
+struct MergeSource {
+	MergeKind kind = MergeKind::SameDevice;
+	const float4 *acc = nullptr; // the slot, from its first row on (null: the source has no frame)
+	uint32_t W = 0, H = 0;
+	int device = 0, slot = -1;         // the GPU it lies on (a peer's: dst's, where it is mapped) | a peer's slot
+	polaris_hip_tracer *src = nullptr; // a tracer of this process: fenced against its next Trace
+	polaris_hip_peer *peer = nullptr;  // another process's ring
+	const char *refusal = nullptr;     // why there is nothing to read
+};
+
+// A tracer of this process (polaris_hip_merge: slot < 0, its current slot; polaris_hip_merge_slot).  Its trace accumulator is complete
+// (its Trace is synchronous and has returned): snapshot what is needed of it under ITS lock, briefly, and before dst's merge lock.
+static MergeSource tracer_source(const polaris_hip_tracer *dst, polaris_hip_tracer *src, int slot) {
+	MergeSource S;
+	std::lock_guard<std::mutex> lk_src(src->mu);
+	S.src = src; S.device = src->device; S.W = src->fa.W; S.H = src->fa.H;
+	S.kind = S.device == dst->device ? MergeKind::SameDevice : MergeKind::OtherDevice;
+	S.acc = src->fa.slot(slot);
+	if (src->fa.ix.slot_of(slot) < 0) S.refusal = "merge: ring slot out of range";
+	return S;
+}
+
+// Another process's ring, mapped on dst's device (polaris_hip_merge_ipc; caller holds dst->fa.mu).
+static MergeSource peer_source(const polaris_hip_tracer *dst, polaris_hip_peer *peer, int slot) {
+	MergeSource S;
+	S.kind = MergeKind::PeerRing; S.peer = peer; S.slot = slot; S.device = dst->device; S.W = peer->W; S.H = peer->H;
+	if (peer->owner != dst) S.refusal = "merge_ipc: the peer was opened by another tracer";
+	else if ((uint32_t)slot >= peer->depth) S.refusal = "merge: ring slot out of range";
+	else S.acc = (const float4 *)peer->mem[slot].get();
+	return S;
+}
+
+// MergeOutput: the block's rows of S onto dst's frame accumulator.  Everything on dst's merge stream, under dst->fa.mu (which the
+// caller holds) only -- never under dst->mu, which the destination's own Trace holds from start to end.
+static int merge_rows(polaris_hip_tracer *dst, const MergeSource &S, const PolarisBlockRequest *r) {
+	FrameAccum &A = dst->fa;
+	if (S.refusal) return A.fail(POLARIS_E_BAD_ARGUMENT, S.refusal);
+	switch (const BlockRefusal why = refuse_block(A.W, A.H, r)) {
+	case BlockRefusal::None: break;
+	case BlockRefusal::FrameMismatch: return A.fail(POLARIS_E_BAD_ARGUMENT, "merge: request frame does not match the tracer's");
+	case BlockRefusal::RowsOutside: return A.fail(POLARIS_E_BAD_ARGUMENT, "merge: block rows outside the frame");
+	default: return A.fail(POLARIS_E_BAD_ARGUMENT, kBlockRefusal[(int)why]);
 	}
-	std::lock_guard<std::mutex> lk(dst->merge_mu);
-	auto fail_merge = [&](int code, const char *msg) { // (dst->error belongs to dst->mu, which a running Trace holds)
-		dst->merge_error = msg;
-		dst->merge_error_seq = ++g_error_seq;
-		g_thread_error = msg;
-		return code;
-	};
-	if (peer) {
-		if (peer->owner != dst) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge_ipc: the peer was opened by another tracer");
-		if (slot < 0 || (uint32_t)slot >= peer->depth) bad_slot = true;
-		else src_acc = (const float4 *)peer->mem[slot].get();
-		src_w = peer->W; src_h = peer->H;
-	}
-	if (bad_slot) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge: ring slot out of range");
-	if (!r) return fail_merge(POLARIS_E_BAD_ARGUMENT, "block request is null");
-	if (dst->W == 0 || dst->H == 0) return fail_merge(POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
-	if (r->frame_w != dst->W || r->frame_h != dst->H) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge: request frame does not match the tracer's");
-	if (r->block_h == 0 || (uint64_t)r->block_y + r->block_h > dst->H) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge: block rows outside the frame");
-	if (r->block_x != 0 || (r->block_w != 0 && r->block_w != dst->W)) return fail_merge(POLARIS_E_BAD_ARGUMENT, "only full-width row blocks are supported (BlockW = FrameW, renderer/default.go:110)");
-	if (src_w != dst->W || src_h != dst->H || !src_acc) return fail_merge(POLARIS_E_BAD_ARGUMENT, "merge: source tracer has different frame dimensions");
-	if (hipSetDevice(dst->device) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipSetDevice failed");
-	const size_t off = (size_t)r->block_y * dst->W, n = (size_t)r->block_h * dst->W;
-	const float4 *rows = src_acc + off;
-	hipStream_t q = dst->merge_stream;
-	if (peer && peer->ev[slot] && hipStreamWaitEvent(q, peer->ev[slot], 0) != hipSuccess) {
+	if (S.W != A.W || S.H != A.H || !S.acc) return A.fail(POLARIS_E_BAD_ARGUMENT, "merge: source tracer has different frame dimensions");
+	if (hipSetDevice(dst->device) != hipSuccess) return A.fail(POLARIS_E_DEVICE, "merge: hipSetDevice failed");
+	const size_t off = (size_t)r->block_y * A.W, n = (size_t)r->block_h * A.W;
+	const float4 *rows = S.acc + off;
+	if (S.peer && S.peer->ev[S.slot] && hipStreamWaitEvent(A.q, S.peer->ev[S.slot], 0) != hipSuccess) {
 		// The device-side wait is belt and braces: the slot was announced by a host message AFTER the peer's synchronous Trace returned, so
 		// its rows are complete.  A runtime that refuses to wait for another process's / another device's event must not cost the frame:
 		// drop the peer's events (the wait is not retried) and go on with the host-side ordering alone.
 		(void)hipGetLastError();
-		peer->drop_events();
+		S.peer->drop_events();
 		(void)hipGetLastError();
 		if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] merge_ipc: hipStreamWaitEvent on the peer's inter-process event failed; continuing with the host-side ordering\n");
 	}
-	int branch = peer ? (peer->info.same_device == 1 ? POLARIS_MERGE_IPC_LOCAL : (peer->info.same_device == 0 ? POLARIS_MERGE_IPC_PEER : POLARIS_MERGE_IPC_UNKNOWN)) : POLARIS_MERGE_LOCAL;
-	auto need_staging = [&]() -> bool { // the merge stream's staging strip, big enough for this block (merges are serialised on the stream)
-		if (dst->staging.capacity() >= n) return true;
-		(void)hipStreamSynchronize(q); // (an earlier merge may still read the strip that goes)
-		return dst->staging.alloc(n) == hipSuccess;
-	};
-	if (peer && peer->info.staged) { // no peer access to the ring's GPU (or forced): the RUNTIME moves the rows, the kernel adds a local strip
-		if (!need_staging()) return fail_merge(POLARIS_E_DEVICE, "merge: out of device memory for the staging strip");
-		if (hipMemcpyAsync(dst->staging, rows, n * sizeof(float4), hipMemcpyDefault, q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge_ipc: hipMemcpyAsync from the peer's ring failed");
-		rows = dst->staging;
-		branch = POLARIS_MERGE_IPC_STAGED;
-	}
-	if (!peer && src_device != dst->device) {
-		branch = POLARIS_MERGE_PEER_ACCESS;
-		int can = 0;
-		if (hipDeviceCanAccessPeer(&can, dst->device, src_device) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipDeviceCanAccessPeer failed");
-		bool direct = false;
-		if (can) {
-			hipError_t e = hipDeviceEnablePeerAccess(src_device, 0);
-			if (e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled) direct = true;
+	// the route (merge_plan.h): another GPU of this process is read in place only with peer access, asked for here
+	int can = -1;
+	bool enabled = false;
+	if (S.kind == MergeKind::OtherDevice) {
+		if (hipDeviceCanAccessPeer(&can, dst->device, S.device) != hipSuccess) can = -1;
+		else if (can) {
+			const hipError_t e = hipDeviceEnablePeerAccess(S.device, 0);
+			can = 1;
+			enabled = e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled;
 			(void)hipGetLastError();
 		}
-		if (!direct) { // staged copy over xGMI / PCIe, then add (the staging strip is the merge stream's: merges are serialised on it)
-			branch = POLARIS_MERGE_STAGED;
-			if (!need_staging()) return fail_merge(POLARIS_E_DEVICE, "merge: out of device memory for the staging strip");
-			if (hipMemcpyPeerAsync(dst->staging, dst->device, rows, src_device, n * sizeof(float4), q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipMemcpyPeerAsync failed");
-			rows = dst->staging;
-		}
 	}
+	const PolarisPeerInfo *I = S.peer ? &S.peer->info : nullptr;
+	const MergeRoute route = route_merge(S.kind, I ? I->same_device : -1, I && I->staged, can, enabled);
+	if (route.branch < 0) return A.fail(POLARIS_E_DEVICE, "merge: hipDeviceCanAccessPeer failed");
+	if (route.rows != RowsTravel::InPlace) { // the RUNTIME moves the rows into the staging strip, the kernel adds a local strip
+		if (!A.need_staging(n)) return A.fail(POLARIS_E_DEVICE, "merge: out of device memory for the staging strip");
+		if (route.rows == RowsTravel::DefaultCopy) {
+			if (hipMemcpyAsync(A.staging, rows, n * sizeof(float4), hipMemcpyDefault, A.q) != hipSuccess) return A.fail(POLARIS_E_DEVICE, "merge_ipc: hipMemcpyAsync from the peer's ring failed");
+		} else if (hipMemcpyPeerAsync(A.staging, dst->device, rows, S.device, n * sizeof(float4), A.q) != hipSuccess) return A.fail(POLARIS_E_DEVICE, "merge: hipMemcpyPeerAsync failed");
+		rows = A.staging;
+	}
+	hipError_t launched;
 	{
-		Timed t(dst, "aggregate", nullptr, q, true);
-		kAggregate[dst->opt_moments].enqueue(grid_for(n), WG, 0, q, rows, dst->frame_acc + off, (uint32_t)n);
+		Timed t(dst, "aggregate", nullptr, A.q, true);
+		launched = A.add_rows(rows, off, n, dst->opt_moments, route.branch);
 	}
-	if (hipGetLastError() != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: kernel launch failed");
-	dst->merge_counts[branch]++;
+	if (launched != hipSuccess) return A.fail(POLARIS_E_DEVICE, "merge: kernel launch failed");
 	// src's next Trace clears and rewrites the rows just queued for reading: it waits (on the device) for this event.  With
 	// src == dst the merge stream itself is joined by Trace (join_merges).  Recorded for a merge from a named ring slot too
 	// (merge_slot): with a ring of depth 1 that slot IS what the next Trace clears, and with a deeper ring the wait is for a
 	// kernel of microseconds.
-	if (src && src != dst) {
-		DevEvent e = reader_event(src, dst->device);
-		if (!e || hipEventRecord(e, q) != hipSuccess) { // cannot fence on the device: finish the read now
+	if (S.src && S.src != dst) {
+		DevEvent e = S.src->fa.reader_event(dst->device);
+		if (!e || hipEventRecord(e, A.q) != hipSuccess) { // cannot fence on the device: finish the read now
 			(void)hipGetLastError();
-			if (hipStreamSynchronize(q) != hipSuccess) return fail_merge(POLARIS_E_DEVICE, "merge: hipStreamSynchronize failed");
-		} else {
-			std::lock_guard<std::mutex> lk_r(src->readers_mu);
-			src->readers.push_back({std::move(e), dst->device});
-		}
+			if (hipStreamSynchronize(A.q) != hipSuccess) return A.fail(POLARIS_E_DEVICE, "merge: hipStreamSynchronize failed");
+		} else S.src->fa.add_reader(std::move(e), dst->device);
 	}
 	return POLARIS_OK; // asynchronous like Exec1DNoWait (resources.go:119); completed by sync_framebuffer
 }
 
 int polaris_hip_merge(polaris_hip_tracer *dst, polaris_hip_tracer *src, const PolarisBlockRequest *r) {
 	if (!dst || !src) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge: null tracer handle");
-	return merge_rows(dst, src, nullptr, -1, r);
+	const MergeSource S = tracer_source(dst, src, -1);
+	std::lock_guard<std::mutex> lk(dst->fa.mu);
+	return merge_rows(dst, S, r);
 }
 
 int polaris_hip_merge_slot(polaris_hip_tracer *dst, polaris_hip_tracer *src, uint32_t slot, const PolarisBlockRequest *r) {
 	if (!dst || !src) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_slot: null tracer handle");
 	if (slot >= POLARIS_IPC_MAX_DEPTH) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_slot: ring slot out of range");
-	return merge_rows(dst, src, nullptr, (int)slot, r);
+	const MergeSource S = tracer_source(dst, src, (int)slot);
+	std::lock_guard<std::mutex> lk(dst->fa.mu);
+	return merge_rows(dst, S, r);
 }
 
 int polaris_hip_merge_ipc(polaris_hip_tracer *dst, polaris_hip_peer *peer, uint32_t slot, const PolarisBlockRequest *r) {
 	if (!dst || !peer) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_ipc: null handle");
 	if (slot >= POLARIS_IPC_MAX_DEPTH) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_ipc: ring slot out of range");
-	return merge_rows(dst, nullptr, peer, (int)slot, r);
+	std::lock_guard<std::mutex> lk(dst->fa.mu);
+	return merge_rows(dst, peer_source(dst, peer, (int)slot), r);
 }
 
 int polaris_hip_trace_slot(polaris_hip_tracer *h, uint32_t *slot) {
 	if (!h || !slot) return fail(h, POLARIS_E_BAD_ARGUMENT, "trace_slot: null argument");
 	std::lock_guard<std::mutex> lk(h->mu);
-	*slot = h->ring_pos;
+	*slot = h->fa.ix.pos;
 	return POLARIS_OK;
 }
 
@@ -1548,52 +1603,37 @@ int polaris_hip_ipc_export(polaris_hip_tracer *h, uint32_t depth, PolarisIpcExpo
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!out) return fail(h, POLARIS_E_BAD_ARGUMENT, "ipc_export: out is null");
 	if (depth < 1 || depth > POLARIS_IPC_MAX_DEPTH) return fail(h, POLARIS_E_BAD_ARGUMENT, "ipc_export: depth must be 1..%d", POLARIS_IPC_MAX_DEPTH);
-	if (h->W == 0 || h->H == 0 || !h->ring[0]) return fail(h, POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
+	if (h->fa.W == 0 || h->fa.H == 0 || !h->fa.ring[0]) return fail(h, POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
 	static_assert(sizeof(hipIpcMemHandle_t) == 64 && sizeof(hipIpcEventHandle_t) == 64, "PolarisIpcExport holds 64-byte handles");
 	HIP_TRY(h, hipSetDevice(h->device));
-	std::lock_guard<std::mutex> lk_merge(h->merge_mu);
+	std::lock_guard<std::mutex> lk_merge(h->fa.mu);
 	HIP_TRY(h, sync_all(h));
-	const size_t F = (size_t)h->W * h->H;
-	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) { // grow or shrink the ring to `depth` slots (slot 0 always exists)
-		if (i < depth && !h->ring[i]) {
-			HIP_TRY(h, h->ring[i].alloc(F));
-			HIP_TRY(h, hipMemsetAsync(h->ring[i], 0, F * sizeof(float4), h->stream));
-		} else if (i >= depth) {
-			h->ring[i].reset();
-		}
-	}
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	h->ring_depth = depth;
-	h->ring_pos = h->ring_pos % depth;
-	h->trace_acc = h->ring[h->ring_pos];
+	HIP_TRY(h, h->fa.redepth(depth, h->stream));
 	memset(out, 0, sizeof *out);
-	out->abi_version = POLARIS_HIP_ABI_VERSION; out->depth = depth; out->frame_w = h->W; out->frame_h = h->H;
+	out->abi_version = POLARIS_HIP_ABI_VERSION; out->depth = depth; out->frame_w = h->fa.W; out->frame_h = h->fa.H;
 	out->device = h->device; out->pid = (uint32_t)getpid();
 	static_assert(sizeof out->pci_bus_id == sizeof h->pci_bus_id, "the export carries the tracer's bus id as it is");
 	memcpy(out->pci_bus_id, h->pci_bus_id, sizeof out->pci_bus_id);
 	for (uint32_t i = 0; i < depth; i++) {
 		hipIpcMemHandle_t mh;
-		HIP_TRY(h, hipIpcGetMemHandle(&mh, h->ring[i]));
+		HIP_TRY(h, hipIpcGetMemHandle(&mh, h->fa.ring[i]));
 		memcpy(out->mem[i], &mh, 64);
 	}
 	// the per-slot "Trace done" events: optional (a runtime that cannot export events still has the host-side ordering: Trace is
 	// synchronous, and a slot is only announced after the Trace that wrote it has returned).  All slots or none.
 	bool events = true;
-	for (uint32_t i = 0; i < POLARIS_IPC_MAX_DEPTH; i++) {
-		if (i >= depth) {
-			h->ev_ipc_done[i].reset();
-			continue;
-		}
-		if (!h->ev_ipc_done[i] && h->ev_ipc_done[i].create(hipEventCreateWithFlags, hipEventDisableTiming | hipEventInterprocess) != hipSuccess) {
+	for (uint32_t i = 0; i < depth; i++) { // (redepth dropped the events of the slots that went)
+		DevEvent &done = h->fa.ev_done[i];
+		if (!done && done.create(hipEventCreateWithFlags, hipEventDisableTiming | hipEventInterprocess) != hipSuccess) {
 			(void)hipGetLastError(); events = false; break;
 		}
 		hipIpcEventHandle_t eh;
-		if (hipEventRecord(h->ev_ipc_done[i], h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
-		    hipIpcGetEventHandle(&eh, h->ev_ipc_done[i]) == hipSuccess) memcpy(out->event[i], &eh, 64);
+		if (hipEventRecord(done, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
+		    hipIpcGetEventHandle(&eh, done) == hipSuccess) memcpy(out->event[i], &eh, 64);
 		else { (void)hipGetLastError(); events = false; break; }
 	}
 	if (!events) {
-		for (auto &e : h->ev_ipc_done) e.reset();
+		for (auto &e : h->fa.ev_done) e.reset();
 		memset(out->event, 0, sizeof out->event);
 	}
 	out->has_event = events ? 1 : 0;
@@ -1607,37 +1647,28 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 	*out = nullptr;
 	if (x->abi_version != POLARIS_HIP_ABI_VERSION) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_open: the export was made by ABI version %u, this library is %d", x->abi_version, POLARIS_HIP_ABI_VERSION);
 	if (x->depth < 1 || x->depth > POLARIS_IPC_MAX_DEPTH) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_open: bad ring depth %u", x->depth);
-	if (x->frame_w != dst->W || x->frame_h != dst->H || dst->W == 0) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_open: the peer's frame %ux%u does not match the tracer's %ux%u", x->frame_w, x->frame_h, dst->W, dst->H);
+	if (x->frame_w != dst->fa.W || x->frame_h != dst->fa.H || dst->fa.W == 0) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_open: the peer's frame %ux%u does not match the tracer's %ux%u", x->frame_w, x->frame_h, dst->fa.W, dst->fa.H);
 	if (x->pid == (uint32_t)getpid()) return fail(dst, POLARIS_E_UNSUPPORTED, "ipc_open: the export comes from this process (HIP cannot open its own IPC handle): use polaris_hip_merge / polaris_hip_merge_slot");
 	HIP_TRY(dst, hipSetDevice(dst->device));
 	std::unique_ptr<polaris_hip_peer> p(new polaris_hip_peer()); // (a failure below closes what was opened)
 	p->owner = dst; p->depth = x->depth; p->W = x->frame_w; p->H = x->frame_h;
 	{ // what the mapping is: the exporter's GPU by bus id, as this process sees it
 		PolarisPeerInfo &I = p->info;
-		I.struct_size = sizeof I; I.pid = x->pid; I.exporter_device = x->device; I.local_device = -1; I.same_device = -1; I.can_access_peer = -1;
+		I.struct_size = sizeof I; I.pid = x->pid; I.exporter_device = x->device;
 		I.depth = x->depth;
 		memcpy(I.pci_bus_id, x->pci_bus_id, sizeof I.pci_bus_id);
 		I.pci_bus_id[sizeof I.pci_bus_id - 1] = 0;
-		if (I.pci_bus_id[0] && dst->pci_bus_id[0]) {
-			I.same_device = strcmp(I.pci_bus_id, dst->pci_bus_id) == 0 ? 1 : 0;
-			int local = -1;
-			if (hipDeviceGetByPCIBusId(&local, I.pci_bus_id) == hipSuccess) I.local_device = local;
-			else (void)hipGetLastError();
-			if (I.same_device == 1) I.local_device = dst->device;
-			int can = 0;
-			if (I.local_device >= 0 && I.local_device != dst->device) {
-				if (hipDeviceCanAccessPeer(&can, dst->device, I.local_device) == hipSuccess) I.can_access_peer = can;
-				else (void)hipGetLastError();
-			}
-		}
-		// A kernel must never be pointed at memory its device cannot reach (a fault there can take the whole node down):
-		//   the ring is on another GPU this process cannot even SEE (a per-rank visibility mask): refuse, the caller has its strip fallback;
-		//   the ring is on a visible GPU without peer access: merges go through the staging strip (a runtime copy, then the add).
-		if (I.same_device == 0 && I.local_device < 0) {
+		// the runtime's answers; merge_plan.h classify_peer decides what they mean
+		const bool have_ids = I.pci_bus_id[0] && dst->pci_bus_id[0], same_id = have_ids && strcmp(I.pci_bus_id, dst->pci_bus_id) == 0;
+		int local = -1, can = -1;
+		if (have_ids && hipDeviceGetByPCIBusId(&local, I.pci_bus_id) != hipSuccess) { (void)hipGetLastError(); local = -1; }
+		if (have_ids && !same_id && local >= 0 && local != dst->device && hipDeviceCanAccessPeer(&can, dst->device, local) != hipSuccess) { (void)hipGetLastError(); can = -1; }
+		const PeerClass c = classify_peer(have_ids, same_id, dst->device, local, can, dst->fa.ipc_staged != 0);
+		I.same_device = c.same_device; I.local_device = c.local_device; I.can_access_peer = c.can_access_peer; I.staged = c.staged;
+		if (!c.visible) { // (a per-rank visibility mask: the caller has its strip fallback)
 			return fail(dst, POLARIS_E_UNSUPPORTED, "ipc_open: the peer's ring lives on GPU %s, which is not visible to this process (device visibility mask?): "
 			            "a peer mapping cannot be verified; use a transport that does not need one", I.pci_bus_id);
 		}
-		I.staged = (dst->opt_ipc_staged || (I.same_device == 0 && I.can_access_peer == 0)) ? 1 : 0;
 	}
 	for (uint32_t i = 0; i < x->depth; i++) {
 		hipIpcMemHandle_t mh;
@@ -1681,7 +1712,7 @@ int polaris_hip_ipc_open(polaris_hip_tracer *dst, const PolarisIpcExport *x, pol
 int polaris_hip_peer_info(polaris_hip_peer *p, PolarisPeerInfo *out) {
 	if (!p || !out) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "peer_info: null argument");
 	if (out->struct_size != sizeof(PolarisPeerInfo)) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "peer_info: struct_size %u, this library's PolarisPeerInfo has %zu bytes", out->struct_size, sizeof(PolarisPeerInfo));
-	std::lock_guard<std::mutex> lk(p->owner->merge_mu); // (a merge that finds the peer's events unusable drops them: has_events follows)
+	std::lock_guard<std::mutex> lk(p->owner->fa.mu); // (a merge that finds the peer's events unusable drops them: has_events follows)
 	*out = p->info;
 	out->has_events = p->ev[0] ? 1u : 0u;
 	return POLARIS_OK;
@@ -1689,17 +1720,17 @@ int polaris_hip_peer_info(polaris_hip_peer *p, PolarisPeerInfo *out) {
 
 int polaris_hip_merge_counts(polaris_hip_tracer *dst, uint64_t counts[POLARIS_MERGE_BRANCHES]) {
 	if (!dst || !counts) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_counts: null argument");
-	std::lock_guard<std::mutex> lk(dst->merge_mu);
-	for (int i = 0; i < POLARIS_MERGE_BRANCHES; i++) counts[i] = dst->merge_counts[i];
+	std::lock_guard<std::mutex> lk(dst->fa.mu);
+	for (int i = 0; i < POLARIS_MERGE_BRANCHES; i++) counts[i] = dst->fa.counts[i];
 	return POLARIS_OK;
 }
 
 int polaris_hip_ipc_close(polaris_hip_tracer *dst, polaris_hip_peer *p) {
 	if (!dst || !p) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_close: null argument");
 	if (p->owner != dst) return fail(dst, POLARIS_E_BAD_ARGUMENT, "ipc_close: the peer was opened by another tracer");
-	std::lock_guard<std::mutex> lk(dst->merge_mu);
+	std::lock_guard<std::mutex> lk(dst->fa.mu);
 	(void)hipSetDevice(dst->device);
-	(void)hipStreamSynchronize(dst->merge_stream); // a merge may still be reading the mapping
+	(void)hipStreamSynchronize(dst->fa.q); // a merge may still be reading the mapping
 	delete p;
 	(void)hipGetLastError();
 	return POLARIS_OK;
@@ -1711,8 +1742,8 @@ int polaris_hip_export_block(polaris_hip_tracer *h, const PolarisBlockRequest *r
 	if (int rc = check_request(h, r)) return rc;
 	if (!device_dst) return fail(h, POLARIS_E_BAD_ARGUMENT, "export: destination is null");
 	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
-	HIP_TRY(h, hipMemcpyAsync(device_dst, h->trace_acc + off, n * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+	const size_t off = (size_t)r->block_y * h->fa.W, n = (size_t)r->block_h * h->fa.W;
+	HIP_TRY(h, hipMemcpyAsync(device_dst, h->fa.current() + off, n * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	return POLARIS_OK;
 }
@@ -1723,44 +1754,35 @@ int polaris_hip_merge_device(polaris_hip_tracer *dst, const void *device_rows, c
 	if (int rc = check_request(dst, r)) return rc;
 	if (!device_rows) return fail(dst, POLARIS_E_BAD_ARGUMENT, "merge_device: source is null");
 	HIP_TRY(dst, hipSetDevice(dst->device));
-	const size_t off = (size_t)r->block_y * dst->W, n = (size_t)r->block_h * dst->W;
-	std::lock_guard<std::mutex> lk_merge(dst->merge_mu); // the frame accumulator is the merge stream's
-	kAggregate[dst->opt_moments].enqueue(grid_for(n), WG, 0, dst->merge_stream, (const float4 *)device_rows, dst->frame_acc + off, (uint32_t)n);
-	HIP_TRY(dst, hipGetLastError());
-	dst->merge_counts[POLARIS_MERGE_DEVICE_STRIP]++;
-	HIP_TRY(dst, hipStreamSynchronize(dst->merge_stream)); // the caller owns device_rows: do not outlive it
+	const size_t off = (size_t)r->block_y * dst->fa.W, n = (size_t)r->block_h * dst->fa.W;
+	std::lock_guard<std::mutex> lk_merge(dst->fa.mu); // the frame accumulator is the merge stream's
+	HIP_TRY(dst, dst->fa.add_rows((const float4 *)device_rows, off, n, dst->opt_moments, route_merge(MergeKind::DeviceStrip, -1, false, -1, false).branch));
+	HIP_TRY(dst, hipStreamSynchronize(dst->fa.q)); // the caller owns device_rows: do not outlive it
 	return POLARIS_OK;
 }
 
 int polaris_hip_reset_frame(polaris_hip_tracer *h) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (h->W == 0 || h->H == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
+	if (h->fa.W == 0 || h->fa.H == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "frame dimensions not set (UpdateState FrameDimensions)");
 	HIP_TRY(h, hipSetDevice(h->device));
-	{
-		std::lock_guard<std::mutex> lk_merge(h->merge_mu);
-		HIP_TRY(h, hipMemsetAsync(h->frame_acc, 0, (size_t)h->W * h->H * sizeof(float4), h->merge_stream));
-		h->reset_epoch++;
-	}
-	h->reset_cv.notify_all();
+	HIP_TRY(h, h->fa.reset_frame());
 	return POLARIS_OK;
 }
 
 int polaris_hip_reset_epoch(polaris_hip_tracer *h, uint64_t *epoch) {
 	if (!h || !epoch) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "reset_epoch: null argument");
-	std::lock_guard<std::mutex> lk(h->merge_mu);
-	*epoch = h->reset_epoch;
+	std::lock_guard<std::mutex> lk(h->fa.mu);
+	*epoch = h->fa.reset_epoch;
 	return POLARIS_OK;
 }
 
 int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::unique_lock<std::mutex> lk(h->merge_mu);
+	std::unique_lock<std::mutex> lk(h->fa.mu);
 	// (bounded: a caller that waits for a Trace nobody will issue gets an error instead of a hung thread)
-	if (!h->reset_cv.wait_for(lk, std::chrono::seconds(120), [&] { return h->reset_epoch > epoch; })) {
-		h->merge_error = "wait_reset: no Trace with accumulated_samples == 0 (or reset_frame) arrived within 120 s";
-		h->merge_error_seq = ++g_error_seq;
-		return POLARIS_E_TIMEOUT;
+	if (!h->fa.reset_cv.wait_for(lk, std::chrono::seconds(120), [&] { return h->fa.reset_epoch > epoch; })) {
+		return h->fa.fail(POLARIS_E_TIMEOUT, "wait_reset: no Trace with accumulated_samples == 0 (or reset_frame) arrived within 120 s");
 	}
 	return POLARIS_OK;
 }
@@ -1865,13 +1887,13 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 			mo = MotionArgs{S.gb_inst, S.tp_hinst, S.mo_table, n_inst};
 		}
 		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam),
-		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->cam), h->W, h->H, S.tp, S.pl[kTpPrior],
+		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->cam), h->fa.W, h->fa.H, S.tp, S.pl[kTpPrior],
 		                            P.m2 ? S.pl[kVaHist].get() : nullptr, f.variance ? S.pl[kTpPrior2].get() : nullptr, P.motion ? &mo : nullptr));
 		S.v.prior_computed();
 	}
-	HIP_TRY(h, join_merges(h, h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
-	launch_steps(h, h->stream, P, SyncIo{h->frame_acc, (float)(r->accumulated_samples + r->samples_per_pixel), weight, S.pl[kTpOut], S.pl[kTpPrior], S.pl[kTpPrior2],
-	                                     S.pl[kGuide], S.pl[kAlbedo], S.pl[kVaOut], S.pl[kDnPing], S.pl[kDnPong], S.pl[kDnOut], h->framebuffer, h->W, r->block_y,
+	HIP_TRY(h, h->fa.join_merges(h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
+	launch_steps(h, h->stream, P, SyncIo{h->fa.frame, (float)(r->accumulated_samples + r->samples_per_pixel), weight, S.pl[kTpOut], S.pl[kTpPrior], S.pl[kTpPrior2],
+	                                     S.pl[kGuide], S.pl[kAlbedo], S.pl[kVaOut], S.pl[kDnPing], S.pl[kDnPong], S.pl[kDnOut], h->framebuffer, h->fa.W, r->block_y,
 	                                     r->block_y + r->block_h, r->exposure}, S.dn, S.va);
 	return POLARIS_OK;
 }
@@ -1948,7 +1970,7 @@ int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams 
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	const size_t need = (size_t)h->W * h->H * 4;
+	const size_t need = (size_t)h->fa.W * h->fa.H * 4;
 	if (!out || n_floats < need || need == 0 || which < POLARIS_AOV_GUIDE || which > POLARIS_AOV_PRIOR2)
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: need %zu floats, which in {0,1,2,3,4,5,6}", need);
 	HIP_TRY(h, hipSetDevice(h->device));
@@ -1970,14 +1992,14 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // tracer.go:254-256
 	if (int rc = check_request(h, r)) return rc;
 	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t off = (size_t)r->block_y * h->W, n = (size_t)r->block_h * h->W;
+	const size_t off = (size_t)r->block_y * h->fa.W, n = (size_t)r->block_h * h->fa.W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
 	const SyncFeatures f = h->fs.features();
 	if (f.any()) {
 		if (int rc = enqueue_features(h, r, weight, f)) return rc;
 	} else {
-		HIP_TRY(h, join_merges(h, h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
-		(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->frame_acc + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
+		HIP_TRY(h, h->fa.join_merges(h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
+		(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->fa.frame + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
 	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1989,7 +2011,7 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	const size_t need = (size_t)h->W * h->H * 4;
+	const size_t need = (size_t)h->fa.W * h->fa.H * 4;
 	if (!rgba || n_bytes < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_framebuffer: need %zu bytes", need);
 	HIP_TRY(h, hipSetDevice(h->device));
 	HIP_TRY(h, hipMemcpyAsync(rgba, h->framebuffer, need, hipMemcpyDeviceToHost, h->stream));
@@ -2000,12 +2022,12 @@ int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_
 int polaris_hip_read_accumulator(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	const size_t need = (size_t)h->W * h->H * 4;
+	const size_t need = (size_t)h->fa.W * h->fa.H * 4;
 	if (!out || n_floats < need || need == 0 || which < 0 || which > 1)
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_accumulator: need %zu floats, which in {0,1}", need);
 	HIP_TRY(h, hipSetDevice(h->device));
-	if (which == 1) HIP_TRY(h, join_merges(h, h->stream));
-	HIP_TRY(h, hipMemcpyAsync(out, which == 0 ? h->trace_acc : h->frame_acc, need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+	if (which == 1) HIP_TRY(h, h->fa.join_merges(h->stream));
+	HIP_TRY(h, hipMemcpyAsync(out, which == 0 ? h->fa.current() : h->fa.frame, need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	return POLARIS_OK;
 }
@@ -2017,20 +2039,20 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (int rc = check_request(h, r)) return rc;
 	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set");
-	const uint32_t N = h->W * r->block_h, Npad = (N + WG - 1) / WG * WG;
+	const uint32_t N = h->fa.W * r->block_h, Npad = (N + WG - 1) / WG * WG;
 	HIP_TRY(h, hipSetDevice(h->device));
 	if (int rc = ensure_streams(h, 0, std::max<size_t>(h->pipe[0].slots, Npad), true)) return rc;
 	Streams &st0 = h->pipe[0].st;
 	st0.hit12 = 0; // (the tap returns the hit distance: 16-byte records)
 	st0.o12 = 0;
 	if (h->d_seeds.capacity() < 1) HIP_TRY(h, h->d_seeds.alloc(64));
-	h->cam.texel = make_float2(1.0f / (float)h->W, 1.0f / (float)h->H);
+	h->cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
 	hipStream_t q = h->stream;
 	std::vector<float4> ro(N), rd(N), ht(N);
 	std::vector<int> inst(N);
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
-	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->W, r->block_y, 1, 1);
+	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1, 1);
 	(void)launch_traversal(h, nullptr, tap_traversal(plan_scene(h)), RayKind::Closest, q, st0, 0, Npad / WG, nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2293,7 +2315,7 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
 int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	const size_t need = (size_t)h->W * h->H;
+	const size_t need = (size_t)h->fa.W * h->fa.H;
 	if (!out || n < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: need %zu words", need);
 	if (!h->fs.opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
 	HIP_TRY(h, hipSetDevice(h->device));

@@ -394,6 +394,43 @@ def test_trace_accumulator_ring_and_merge_from_a_slot(built, oracle):
         tr.Close()
 
 
+def test_resize_after_an_export_starts_a_new_ring(built):
+    """A resize drops the ring with its position: the tracer is back at the single buffer, slot 0, whatever slot the last Trace wrote;
+    the other slots are gone, slot 0 merges like the trace accumulator it is, and a new export starts its round from there."""
+    from oracle import pybind as ob
+    from polaris_amd import scenes
+    from polaris_amd.tracer import ChangeType, TracerError, UpdateMode
+
+    sc = scenes.SCENES["cubes"]()
+    W, H, B, spp = 33, 17, 1, 1
+    seeds = scenes.make_seeds(spp, B, base=77)
+    tr = make_hip_tracer(sc, W, H, exact_accumulate=1)
+    try:
+        tr.ipc_export(3)
+        for _ in range(2):
+            tr.Trace(ob.make_request(W, H, spp=spp, bounces=B), seeds)
+        assert tr.trace_slot() == 2
+        W, H = 20, 31
+        tr.UpdateState(UpdateMode.Synchronous, ChangeType.FrameDimensions, (W, H))
+        assert tr.trace_slot() == 0
+        with pytest.raises(TracerError, match="slot"):
+            tr.merge_slot(tr, 1, ob.make_request(W, H, spp=spp, bounces=B))
+        tr.Trace(ob.make_request(W, H, spp=spp, bounces=B), seeds)
+        assert tr.trace_slot() == 0
+        tr.merge_slot(tr, 0, ob.make_request(W, H, spp=spp, bounces=B, block_y=3, block_h=11))
+        frame, trace = tr.read_accumulator(1)[..., :3], tr.read_accumulator(0)[..., :3]
+        assert trace[3:14].any()
+        assert np.array_equal(bits(frame[3:14]), bits(trace[3:14])) and not frame[:3].any() and not frame[14:].any()
+        tr.ipc_export(2)
+        slots = []
+        for _ in range(2):
+            tr.Trace(ob.make_request(W, H, spp=spp, bounces=B), seeds)
+            slots.append(tr.trace_slot())
+        assert slots == [1, 0]
+    finally:
+        tr.Close()
+
+
 def test_progressive_accumulation(built, oracle):
     """accumulated_samples > 0 keeps the frame accumulator (tracer.go:208-213) and the tone-map
     weight is 1/(accumulated+spp) (resources.go:347)."""
