@@ -47,7 +47,7 @@ extern "C" {
  * itself); PolarisIpcExport carries the exporting GPU's PCI bus id (544 -> 576 bytes); PolarisBvhBuildInput LEADS with `struct_size`
  * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end.  Still 5: + update_instances,
  * + update_vertices / PolarisVertexUpdate, + update_materials / PolarisMaterialUpdate / update_texture and the record kinds
- * POLARIS_REC_TRIS / POLARIS_REC_SHADING (additions only: older callers keep working). */
+ * POLARIS_REC_TRIS / POLARIS_REC_SHADING, + set_lens / PolarisLensParams (additions only: older callers keep working). */
 #define POLARIS_HIP_ABI_VERSION 5
 
 /* status codes (0 = ok).  The first three mirror tracer/opencl/errors.go sentinels. */
@@ -113,6 +113,31 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *scen
 
 /* eye[3]; frustum[16] = corner rays TL, TR, BL, BR as float4 (scene.Camera.Frustrum). */
 int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const float frustum[16]);
+
+/* Thin-lens camera: depth of field (no reference counterpart; the reference's only PrimaryRayGenerator is the pinhole).  Off by
+ * default and while u = v = 0: every Trace, tap and sync then allocates and launches exactly what it did, under the same kernel
+ * symbols.  With it on, the camera rays of a Trace and of polaris_hip_tap_primary come from k_generate_lens: d is the pinhole's unit
+ * direction (same arithmetic, same first draw of the camera PRNG), the stream's SECOND draw is mapped to the unit disk (Shirley-Chiu
+ * concentric map) as (lx, ly), the ray starts at the lens point eye + lx u + ly v and passes through the pinhole ray's point on the
+ * plane of focus, eye + d focus_distance / (d . axis).  A direction with d . axis <= 0 keeps its pinhole ray.  DESIGN.md 10h has
+ * the exact float32 arithmetic.  The vectors are explicit, as set_camera's eye and frustum are: the library derives nothing.
+ * polaris_hip_set_camera does NOT touch them -- a caller that moves the camera sets the lens again (the layers above do it for
+ * their callers: polaris_amd/tracer.py set_lens, the host layer's CameraData.lens_radius).
+ * What stays pinhole: the G-buffer (GUIDE, ALBEDO, the INSTANCE plane) is still one ray from the eye through the pixel centre, and
+ * the temporal reprojection projects with the pinhole camera -- a strongly defocused region is filtered against sharp guide edges.
+ * A call that changes any byte of the parameters drops the temporal history (as max_history = 0 does; the G-buffer stays) and the
+ * caller restarts accumulation, as after a set_camera; a call with identical bytes does nothing.
+ * POLARIS_E_BAD_ARGUMENT, state unchanged: null params, another struct_size, a float that is not finite, an entry of u or v above
+ * 2^30 in magnitude, and with the lens on a focus_distance outside [1e-6, 1e30] or |axis|^2 outside [0.998, 1.002]. */
+typedef struct PolarisLensParams {
+	uint32_t struct_size;     /* = sizeof(PolarisLensParams) = 44 */
+	float    focus_distance;  /* distance of the plane of focus from the eye, measured along `axis` */
+	float    axis[3];         /* unit view axis (world space) */
+	float    u[3], v[3];      /* the two world-space vectors that span the aperture: a lens point is eye + lx u + ly v,
+	                             (lx, ly) uniform in the unit disk.  |u| = |v| = aperture radius for a round lens.
+	                             u = v = 0 (all six floats zero): the lens is OFF, nothing else is looked at */
+} PolarisLensParams;
+int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p);
 
 /* Tunables (not part of the reference interface).  Keys:
  *   "samples_per_batch"  samples traced concurrently as one wavefront batch (default: auto)
@@ -425,7 +450,8 @@ int polaris_hip_read_accumulator(polaris_hip_tracer *h, int which, float *out, s
 
 /* Test tap: generate + intersect the primary rays of one sample with camera seed `seed` and
  * return rays [N][8], hit flags [N], (w,u,v,t) [N][4] and (instance, triangle) [N][2];
- * N = frame_w*block_h.  Any output pointer may be NULL. */
+ * N = frame_w*block_h.  Any output pointer may be NULL.  With the lens on (polaris_hip_set_lens) the rays are k_generate_lens':
+ * rays[i][0..2] is ray i's own origin on the lens. */
 int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *req, uint32_t seed,
                             float *rays, int32_t *hit, float *wuvt, int32_t *tri);
 

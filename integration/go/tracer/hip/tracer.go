@@ -297,6 +297,30 @@ func (tr *Tracer) SetTemporal(p TemporalParams) error {
 	return tr.check(C.polaris_hip_set_temporal(tr.handle, &c))
 }
 
+// LensParams is the thin-lens camera (PolarisLensParams, include/polaris_hip.h; DESIGN.md section 10h): a lens point is
+// eye + lx U + ly V with (lx, ly) uniform in the unit disk, and every camera ray passes through its pinhole ray's point on the plane
+// FocusDistance along the unit vector Axis.  U = V = 0 turns the lens off (the default).
+type LensParams struct {
+	FocusDistance float32    // within [1e-6, 1e30] while the lens is on
+	Axis          [3]float32 // unit view axis, world space
+	U, V          [3]float32 // span the aperture; |U| = |V| = the radius of a round lens
+}
+
+// SetLens sets the thin lens.  UpdateState(CameraData) does not touch it: a caller that moves the camera derives Axis, U and V from
+// the new frustum (axis = normalize(TL + TR + BL + BR), u = r normalize(TR - TL), v = r normalize(TL - BL)) and calls SetLens again.
+// A changed lens drops the temporal history; the caller restarts accumulation as after a camera change.
+func (tr *Tracer) SetLens(p LensParams) error {
+	var c C.PolarisLensParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.focus_distance = C.float(p.FocusDistance)
+	for i := 0; i < 3; i++ {
+		c.axis[i] = C.float(p.Axis[i])
+		c.u[i] = C.float(p.U[i])
+		c.v[i] = C.float(p.V[i])
+	}
+	return tr.check(C.polaris_hip_set_lens(tr.handle, &c))
+}
+
 // SetObjectMotion turns the option "object_motion" on or off: with it on (and temporal reuse on) the history survives an
 // UpdateState(SceneData) that only moves mesh instances -- same instances, same meshes, same triangle count -- and is reprojected
 // through each instance's motion (DESIGN.md section 10d).  Changing it drops the history.

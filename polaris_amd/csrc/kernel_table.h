@@ -74,6 +74,7 @@ const decltype(POLARIS_VARIANT(k_reproject<false, false>)) kReproject[2][2] = {
 const auto kIntersect = POLARIS_VARIANT(k_intersect);
 const auto kOcclusion = POLARIS_VARIANT(k_occlusion);
 const auto kGenerate = POLARIS_VARIANT(k_generate);
+const auto kGenerateLens = POLARIS_VARIANT(k_generate_lens); // polaris_hip_set_lens: in k_generate's place while the lens is on
 const auto kScan = POLARIS_VARIANT(k_scan);
 const auto kFoldNee = POLARIS_VARIANT(k_fold_nee);
 const auto kTonemap = POLARIS_VARIANT(k_tonemap);

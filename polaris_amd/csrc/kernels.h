@@ -148,6 +148,23 @@ __device__ __forceinline__ float ibits(int i) { return __int_as_float(i); }
 // ------------------------------------------------------------------------------------------
 struct CameraArgs { float4 tl, tr, bl, br; float3 eye; float2 texel; };
 
+// The unit direction of the camera ray of pixel (gx, gy + blockY) under camera seed `seed`, camera.cl:38-56.  rng is left as the
+// camera stream after its first draw (the sub-pixel offset): the reference draws no more, k_generate_lens draws once more.
+__device__ __forceinline__ f3 camera_direction(const CameraArgs &cam, uint32_t seed, uint32_t gx, uint32_t gy, uint32_t blockY, Rng &rng) {
+	rng = {gx + seed, gy + seed}; // camera.cl:38
+	f2 s0 = rng_next(rng);
+	float ox = s0.x < 0.5f ? pm_sqrt(2.0f * s0.x) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.x);
+	float oy = s0.y < 0.5f ? pm_sqrt(2.0f * s0.y) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.y);
+	float tx = ((float)gx + ox) * cam.texel.x;
+	float ty = ((float)(gy + blockY) + oy) * cam.texel.y;
+	// mix(mix(TL, BL, ty), mix(TR, BR, ty), tx), then normalize over all four lanes (w = 0)
+	float lx = pm_mix(cam.tl.x, cam.bl.x, ty), ly = pm_mix(cam.tl.y, cam.bl.y, ty), lz = pm_mix(cam.tl.z, cam.bl.z, ty), lw = pm_mix(cam.tl.w, cam.bl.w, ty);
+	float rx = pm_mix(cam.tr.x, cam.br.x, ty), ry = pm_mix(cam.tr.y, cam.br.y, ty), rz = pm_mix(cam.tr.z, cam.br.z, ty), rw = pm_mix(cam.tr.w, cam.br.w, ty);
+	float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
+	float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
+	return mk3(dx * inv, dy * inv, dz * inv);
+}
+
 __global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, const uint32_t *seeds, uint32_t seed_stride,
                                                   uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
                                                   int zero_lsum, int write_origin) {
@@ -162,21 +179,56 @@ __global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, con
 	}
 	if (idx >= N) return;
 	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
-	const uint32_t gx = idx % W, gy = idx / W;
-	Rng rng = {gx + seed, gy + seed}; // camera.cl:38
-	f2 s0 = rng_next(rng);
-	float ox = s0.x < 0.5f ? pm_sqrt(2.0f * s0.x) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.x);
-	float oy = s0.y < 0.5f ? pm_sqrt(2.0f * s0.y) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.y);
-	float tx = ((float)gx + ox) * cam.texel.x;
-	float ty = ((float)(gy + blockY) + oy) * cam.texel.y;
-	// mix(mix(TL, BL, ty), mix(TR, BR, ty), tx), then normalize over all four lanes (w = 0)
-	float lx = pm_mix(cam.tl.x, cam.bl.x, ty), ly = pm_mix(cam.tl.y, cam.bl.y, ty), lz = pm_mix(cam.tl.z, cam.bl.z, ty), lw = pm_mix(cam.tl.w, cam.bl.w, ty);
-	float rx = pm_mix(cam.tr.x, cam.br.x, ty), ry = pm_mix(cam.tr.y, cam.br.y, ty), rz = pm_mix(cam.tr.z, cam.br.z, ty), rw = pm_mix(cam.tr.w, cam.br.w, ty);
-	float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
-	float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
+	Rng rng;
+	const f3 d = camera_direction(cam, seed, idx % W, idx / W, blockY, rng);
 	if (write_origin) store_ray_o(st, slot, make_float4(cam.eye.x, cam.eye.y, cam.eye.z, kFltMax)); // (the wave-packet kernel takes the eye from its arguments)
-	st.ray_d[slot] = make_float4(dx * inv, dy * inv, dz * inv, ibits((int)idx));
+	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
 	// (the throughput of a camera ray is 1: the first shade step does not read it, so it is not written)
+	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// The thin-lens generator (polaris_hip_set_lens; no reference counterpart): k_generate's ray moved onto a lens point.
+// The camera stream's SECOND draw goes through the concentric map (Shirley and Chiu 1997) to (lx, ly) in the unit disk; the ray
+// starts at eye + lx u + ly v and passes through the pinhole ray's point on the plane of focus, eye + d ft.  Every operation below
+// is rounded once, in the order written (tests/lens_oracle.py restates it).  Same launch shape and bookkeeping as k_generate; the
+// origins are always written: every kernel that traces these rays reads the origin stream.
+struct LensArgs { float focus_distance; float3 axis, u, v; };
+
+__global__ __launch_bounds__(WG) void k_generate_lens(Streams st, CameraArgs cam, LensArgs lens, const uint32_t *seeds, uint32_t seed_stride,
+                                                       uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
+                                                       int zero_lsum) {
+	const uint32_t wgs_per_sample = Npad / WG;
+	const uint32_t s = blockIdx.x / wgs_per_sample;
+	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
+	const uint32_t idx = idx0 + threadIdx.x;
+	const size_t slot = (size_t)blockIdx.x * WG + threadIdx.x;
+	if (threadIdx.x == 0) {
+		st.cnt_ray[blockIdx.x] = idx0 < N ? min((uint32_t)WG, N - idx0) : 0u;
+		st.pfx[blockIdx.x] = idx0;
+	}
+	if (idx >= N) return;
+	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
+	Rng rng;
+	f3 d = camera_direction(cam, seed, idx % W, idx / W, blockY, rng);
+	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z);
+	const f2 s1 = rng_next(rng);
+	const float a = 2.0f * s1.x - 1.0f, b = 2.0f * s1.y - 1.0f;
+	float r = 0.0f, phi = 0.0f;
+	if (a == 0.0f && b == 0.0f) {}
+	else if (__builtin_fabsf(a) > __builtin_fabsf(b)) { r = a; phi = 0.78539816339744830962f * (b / a); }
+	else { r = b; phi = 1.57079632679489661923f - 0.78539816339744830962f * (a / b); }
+	const float lx = r * pm_cos(phi), ly = r * pm_sin(phi);
+	const float c = d.x * lens.axis.x + d.y * lens.axis.y + d.z * lens.axis.z;
+	if (c > 0.0f) { // (else, NaN included: the pinhole ray)
+		const float ft = lens.focus_distance / c;
+		const float Lx = lx * lens.u.x + ly * lens.v.x, Ly = lx * lens.u.y + ly * lens.v.y, Lz = lx * lens.u.z + ly * lens.v.z;
+		const float qx = d.x * ft - Lx, qy = d.y * ft - Ly, qz = d.z * ft - Lz; // focus point minus lens point: the eye cancels
+		const float inv2 = 1.0f / pm_sqrt(qx * qx + qy * qy + qz * qz);
+		o = mk3(cam.eye.x + Lx, cam.eye.y + Ly, cam.eye.z + Lz);
+		d = mk3(qx * inv2, qy * inv2, qz * inv2);
+	}
+	store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
+	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
 	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 

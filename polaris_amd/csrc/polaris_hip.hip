@@ -142,6 +142,7 @@ struct FrameSync {
 			v.temporal_params_changed();
 		tp = p;
 	}
+	void lens_changed() { if (tp.max_history) drop(v.temporal_off()); } // the history saw another lens: it goes as with max_history = 0; the (pinhole) G-buffer stays
 	void set_variance(const PolarisVarianceParams &p) {
 		if ((p.sigma_variance != 0.0f) != (va.sigma_variance != 0.0f)) drop(v.variance_toggled(p.sigma_variance != 0.0f));
 		va = p;
@@ -322,6 +323,11 @@ struct polaris_hip_tracer {
 	// camera (tracer.go:175-179)
 	bool have_camera = false;
 	CameraArgs cam{};
+	PolarisLensParams lens{sizeof(PolarisLensParams), 0.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}}; // polaris_hip_set_lens; u = v = 0: off
+	bool lens_on() const { for (int i = 0; i < 3; i++) if (lens.u[i] != 0.0f || lens.v[i] != 0.0f) return true; return false; }
+	LensArgs lens_args() const {
+		return {lens.focus_distance, make_float3(lens.axis[0], lens.axis[1], lens.axis[2]), make_float3(lens.u[0], lens.u[1], lens.u[2]), make_float3(lens.v[0], lens.v[1], lens.v[2])};
+	}
 
 	FrameSync fs; // the synced frame's features, planes and history
 	int opt_instance_update = 0, opt_vertex_update = 0; // the in-place updates: the next upload keeps what they need in ds.upd / ds.vup
@@ -677,6 +683,7 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 	s.tri_bits = h->ds.scene.tri_bits;
 	s.packet_primary = h->packet_primary;
 	s.num_cus = h->num_cus;
+	s.lens = h->lens_on();
 	return s;
 }
 
@@ -706,8 +713,9 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	hipStream_t q = P.q;
 	P.st.hit12 = plan.hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
 	P.st.o12 = plan.o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
-	note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y,
-	            exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
+	if (plan.scene.lens) note(launch(h, "generate", q, kGenerateLens, wgs, WG, 0, P.st, h->cam, h->lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
+	else note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y,
+	                 exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
 	ShadeArgs A{};
 	A.seeds = h->d_seeds; A.seed_stride = stride; A.first_sample = s0;
 	A.N = N; A.Npad = Npad; A.W = h->fa.W; A.blockY = r->block_y;
@@ -721,7 +729,7 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 		Streams S = P.st; // (in place: k_shade / k_shade_wave read a chunk's rays before they write into it)
 		if (!exact) { S.occ_e = P.nee[b]; S.vis = P.vis[b]; S.cnt_occ = P.cnt_occ_b[b]; } // this bounce's NEE records, visibility bytes and shadow-ray counts stay until k_fold_nee
 		float4 *const occl_acc = exact ? A.acc : nullptr;                // batched: unoccluded rays only mark their record (deferred)
-		const RayKind closest = b == 0 ? RayKind::Camera : RayKind::Closest;
+		const RayKind closest = b == 0 ? plan.primary : RayKind::Closest;
 		note(launch_traversal(h, traversal_timer(pl.isect, closest), pl.isect, closest, q, S, persistent, wgs, nullptr));
 		A.bounce = b;
 		A.last_bounce = (b + 1 == B) ? 1 : 0;
@@ -1289,6 +1297,35 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
 	HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
 	h->have_camera = true;
+	return POLARIS_OK;
+}
+
+int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisLensParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: null params or struct_size != %zu", sizeof(PolarisLensParams));
+	const float *f = &p->focus_distance; // the ten floats after struct_size
+	static_assert(sizeof(PolarisLensParams) == 44 && offsetof(PolarisLensParams, focus_distance) == 4, "PolarisLensParams is struct_size and ten floats");
+	bool on = false;
+	for (int i = 0; i < 10; i++)
+		if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: float %d is not finite", i);
+	for (int i = 0; i < 3; i++) {
+		if (std::fabs(p->u[i]) > 0x1p30f || std::fabs(p->v[i]) > 0x1p30f) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: an entry of u or v is above 2^30");
+		on = on || p->u[i] != 0.0f || p->v[i] != 0.0f;
+	}
+	if (on) {
+		if (!(p->focus_distance >= 1e-6f && p->focus_distance <= 1e30f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: focus_distance %g outside [1e-6, 1e30]", (double)p->focus_distance);
+		const float a2 = p->axis[0] * p->axis[0] + p->axis[1] * p->axis[1] + p->axis[2] * p->axis[2];
+		if (!(a2 >= 0.998f && a2 <= 1.002f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: axis is not a unit vector (squared length %g)", (double)a2);
+	}
+	if (memcmp(p, &h->lens, sizeof h->lens) == 0) return POLARIS_OK; // identical bytes: nothing happens
+	if (h->fs.tp.max_history) { // the history's planes go
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every temporal launch is on the main stream)
+	}
+	h->fs.lens_changed();
+	h->lens = *p;
 	return POLARIS_OK;
 }
 
@@ -2052,7 +2089,8 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	std::vector<int> inst(N);
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
-	kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1, 1);
+	if (h->lens_on()) kGenerateLens.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
+	else kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1, 1);
 	(void)launch_traversal(h, nullptr, tap_traversal(plan_scene(h)), RayKind::Closest, q, st0, 0, Npad / WG, nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));

@@ -179,6 +179,36 @@ def temporal_params(max_history=32, normal_threshold=0.9, depth_threshold=0.1) -
     return p
 
 
+class LensParams(C.Structure):
+    """PolarisLensParams (include/polaris_hip.h): the thin-lens camera.  u = v = 0 is the lens OFF (the default)."""
+    _fields_ = [("struct_size", C.c_uint32), ("focus_distance", C.c_float), ("axis", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(LensParams) == 44
+
+
+def lens_params(focus_distance=0.0, axis=(0.0, 0.0, 0.0), u=(0.0, 0.0, 0.0), v=(0.0, 0.0, 0.0)) -> LensParams:
+    p = LensParams()
+    p.focus_distance = float(focus_distance)
+    for name, vec in (("axis", axis), ("u", u), ("v", v)):
+        setattr(p, name, (C.c_float * 3)(*[float(x) for x in vec]))
+    return p
+
+
+def lens_from_frustum(frustum, radius):
+    """(axis, u, v) of a round lens of this radius facing the way the frustum looks: axis = normalize(TL + TR + BL + BR),
+    u = radius * normalize(TR - TL), v = radius * normalize(TL - BL); computed in float64, rounded to float32 once."""
+    fr = np.asarray(frustum, np.float64).reshape(4, 4)[:, :3]
+    tl, tr, bl, br = fr
+    unit = lambda x: x / np.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])  # noqa: E731  (spelled out: the host layer's C++ derives the same bits)
+    return (unit(tl + tr + bl + br).astype(np.float32), (float(radius) * unit(tr - tl)).astype(np.float32),
+            (float(radius) * unit(tl - bl)).astype(np.float32))
+
+
 class VarianceParams(C.Structure):
     """PolarisVarianceParams (include/polaris_hip.h): variance-guided denoising from per-pixel luminance moments."""
     _fields_ = [("struct_size", C.c_uint32), ("sigma_variance", C.c_float), ("min_samples", C.c_uint32)]
@@ -413,7 +443,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
-    "polaris_hip_update_materials", "polaris_hip_update_texture",
+    "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens",
 ]
 
 _lib = None
@@ -513,6 +543,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_read_aov.argtypes = [vp, i32, vp, C.c_size_t]
     lib.polaris_hip_selftest_builtins.argtypes = [vp, u32, C.c_uint64, C.c_uint64, vp, vp]
     lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
+    lib.polaris_hip_set_lens.argtypes = [vp, C.POINTER(LensParams)]
     lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
     lib.polaris_hip_set_variance.argtypes = [vp, C.POINTER(VarianceParams)]
     lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),

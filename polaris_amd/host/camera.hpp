@@ -18,6 +18,7 @@ struct Camera {
 	types::Vec4 Frustrum[4]; // TL, TR, BL, BR (the reference's spelling)
 	float FOV = 45.0f;
 	bool InvertY = false;
+	float Aperture = 0, FocusDistance = 0; // thin lens: radius and distance of the plane of focus (no reference counterpart); Aperture 0 = pinhole
 
 	Camera(float fov = 45.0f) : FOV(fov) {}
 
@@ -57,6 +58,7 @@ struct Camera {
 		tracer::CameraData d;
 		d.eye[0] = Position.x; d.eye[1] = Position.y; d.eye[2] = Position.z;
 		for (int i = 0; i < 4; i++) { d.frustum[4 * i] = Frustrum[i].x; d.frustum[4 * i + 1] = Frustrum[i].y; d.frustum[4 * i + 2] = Frustrum[i].z; d.frustum[4 * i + 3] = Frustrum[i].w; }
+		d.lens_radius = Aperture; d.focus_distance = FocusDistance;
 		return d;
 	}
 

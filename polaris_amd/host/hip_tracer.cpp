@@ -1,6 +1,11 @@
 #include "hip_tracer.hpp"
 
+#include <cmath>
 #include <cstring>
+
+// The C ABI's polaris_hip_set_lens, referenced weakly: this file is also linked against stand-ins of the C ABI that know no lens
+// (tests/tools/mock_polaris_hip.cpp); there a CameraData with a lens is refused and one without asks nothing.
+extern "C" int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) __attribute__((weak));
 
 namespace polaris {
 namespace tracer {
@@ -32,6 +37,26 @@ Error HipTracer::check(int rc) {
 	if (rc == POLARIS_OK) return Error::Nil();
 	const char *m = polaris_hip_last_error(h_);
 	return Error{rc, std::string("hip tracer (") + dev_.Name + "): " + (m ? m : "")};
+}
+
+// The lens vectors of a CameraData (polaris_amd/ctypes_api.py lens_from_frustum, the same derivation): axis = normalize(TL + TR + BL +
+// BR), u = radius normalize(TR - TL), v = radius normalize(TL - BL), in double, rounded to float once.  lens_radius = 0: all zero (off).
+static PolarisLensParams lensFromFrustum(const CameraData &c) {
+	PolarisLensParams p{};
+	p.struct_size = sizeof p;
+	if (c.lens_radius == 0.0f) return p;
+	p.focus_distance = c.focus_distance;
+	const float *tl = c.frustum, *tr = c.frustum + 4, *bl = c.frustum + 8, *br = c.frustum + 12;
+	double a[3], u[3], v[3];
+	for (int k = 0; k < 3; k++) {
+		a[k] = (((double)tl[k] + (double)tr[k]) + (double)bl[k]) + (double)br[k];
+		u[k] = (double)tr[k] - (double)tl[k];
+		v[k] = (double)tl[k] - (double)bl[k];
+	}
+	auto unit = [](double x[3]) { const double n = std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]); for (int k = 0; k < 3; k++) x[k] = x[k] / n; };
+	unit(a); unit(u); unit(v);
+	for (int k = 0; k < 3; k++) { p.axis[k] = (float)a[k]; p.u[k] = (float)((double)c.lens_radius * u[k]); p.v[k] = (float)((double)c.lens_radius * v[k]); }
+	return p;
 }
 
 Error HipTracer::Init() {
@@ -66,7 +91,14 @@ Error HipTracer::commitChanges(Duration *took) { // tracer/opencl/tracer.go:161-
 	Error err;
 	if (has_dims_ && !err) { err = check(polaris_hip_resize(h_, dims_.w, dims_.h)); has_dims_ = false; }
 	if (has_scene_ && !err) { err = check(polaris_hip_upload_scene(h_, scene_)); has_scene_ = false; scene_ = nullptr; }
-	if (has_cam_ && !err) { err = check(polaris_hip_set_camera(h_, cam_.eye, cam_.frustum)); has_cam_ = false; }
+	if (has_cam_ && !err) {
+		err = check(polaris_hip_set_camera(h_, cam_.eye, cam_.frustum));
+		// set_camera leaves the lens vectors alone: they follow the new frustum here (identical bytes ask nothing of the library)
+		const PolarisLensParams lens = lensFromFrustum(cam_);
+		if (!err && polaris_hip_set_lens) err = check(polaris_hip_set_lens(h_, &lens));
+		else if (!err && cam_.lens_radius != 0.0f) err = Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: this C ABI has no polaris_hip_set_lens"};
+		has_cam_ = false;
+	}
 	stats_.UpdateTime = std::chrono::duration_cast<Duration>(clock_::now() - start);
 	if (took) *took = stats_.UpdateTime;
 	return err;

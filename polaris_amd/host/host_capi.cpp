@@ -44,6 +44,7 @@ struct RendererBox {
 	// injected seed lists (tests): tracer i draws from lists[i] while it has entries, then from the shared generator
 	std::vector<std::deque<uint32_t>> lists;
 	std::vector<tracer::hip::HipTracer *> hips; // owned by the renderer
+	tracer::CameraData cam; // the CameraData last given to every tracer (polaris_host_renderer_set_lens re-sends it with the lens)
 };
 } // namespace
 
@@ -114,6 +115,7 @@ void *polaris_host_renderer_new(const int *device_indices, uint32_t n_tracers, u
 	if (!e) e = box->r->UpdateAll(tracer::ChangeType::SceneData, scene);
 	if (!e) e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam);
 	if (e) { snprintf(err, 256, "%s", e.msg.c_str()); delete box; return nullptr; }
+	box->cam = cam;
 	return box;
 }
 // Test hooks: the host PRNG draws of tracer `tracer_index` (tracer.go:222, pipeline.go:146) come from this list until it is
@@ -202,7 +204,19 @@ int polaris_host_renderer_set_camera(void *h, const float eye[3], const float fr
 	tracer::CameraData cam;
 	memcpy(cam.eye, eye, sizeof cam.eye);
 	memcpy(cam.frustum, frustum, sizeof cam.frustum);
+	cam.lens_radius = box->cam.lens_radius; cam.focus_distance = box->cam.focus_distance; // (the lens stays on the camera as it moves)
 	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
+	box->cam = cam;
+	return 0;
+}
+// The thin lens (CameraData.lens_radius / focus_distance; polaris_hip_set_lens): the CameraData of every tracer again,
+// now with this lens, which every later polaris_host_renderer_set_camera keeps.  lens_radius = 0 turns it off.
+int polaris_host_renderer_set_lens(void *h, float lens_radius, float focus_distance) {
+	auto *box = static_cast<RendererBox *>(h);
+	tracer::CameraData cam = box->cam;
+	cam.lens_radius = lens_radius; cam.focus_distance = focus_distance;
+	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
+	box->cam = cam;
 	return 0;
 }
 // A plane of the primary's denoiser (polaris_hip_read_aov).

@@ -38,7 +38,9 @@ enum class UpdateMode : uint8_t { Synchronous = 0, Asynchronous = 1 };    // tra
 enum class ChangeType : uint8_t { FrameDimensions = 0, SceneData = 1, CameraData = 2 }; // tracer.go:71-78
 
 struct FrameDims { uint32_t w, h; };                 // payload of FrameDimensions ([2]uint32)
-struct CameraData { float eye[3]; float frustum[16]; }; // what tracer.go:177-179 uses of scene.Camera
+// What tracer.go:177-179 uses of scene.Camera, and the thin lens (no reference counterpart; both 0 = off, the pinhole): a round lens of
+// lens_radius focused at focus_distance along the view axis, which the tracer sets after the camera (hip_tracer.cpp, lensFromFrustum).
+struct CameraData { float eye[3]; float frustum[16]; float lens_radius = 0, focus_distance = 0; };
 
 class Tracer { // tracer/tracer.go:80-111
 public:

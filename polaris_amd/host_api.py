@@ -42,6 +42,7 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_read_aov.argtypes = [vp, C.c_int, vp, C.c_size_t]
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
         lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
+        lib.polaris_host_renderer_set_lens.argtypes = [vp, C.c_float, C.c_float]
         lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
         u32 = C.c_uint32
         lib.polaris_host_variance.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams), C.POINTER(T.VarianceParams), vp]
@@ -215,6 +216,12 @@ class Renderer:
         f = np.ascontiguousarray(frustum, dtype=np.float32).reshape(16)
         if self._lib.polaris_host_renderer_set_camera(self._h, e.ctypes.data, f.ctypes.data):
             raise RuntimeError(f"set_camera failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_lens(self, radius: float, focus_distance: float = 0.0) -> None:
+        """The thin lens on every tracer (CameraData.lens_radius / focus_distance: each tracer's UpdateState(CameraData) sets the lens
+        after the camera, from the frustum); later set_camera calls keep it.  radius = 0 turns it off."""
+        if self._lib.polaris_host_renderer_set_lens(self._h, float(radius), float(focus_distance)):
+            raise RuntimeError(f"set_lens failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
     def read_aov(self, which: int) -> np.ndarray:
         """The primary's (H, W, 4) denoiser plane (polaris_hip_read_aov)."""

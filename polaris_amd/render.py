@@ -22,7 +22,11 @@ variance.npy.
 
 --frames N --recolour NODE:r,g,b[:step] renders N frames with an edit of a material per frame instead of a camera move: frame k gives
 material node NODE the colour (r, g, b) + k * step * (1, 1, 1) through polaris_hip_update_materials -- the node
-table in place, no upload_scene -- then render(accumulated=0)."""
+table in place, no upload_scene -- then render(accumulated=0).
+
+--aperture R --focus D renders through a thin lens of radius R focused at distance D along the view axis (polaris_hip_set_lens,
+DESIGN.md 10h; it stays on the camera through --frames moves).  --focus-pixel x,y takes D from the GUIDE plane instead: the first hit
+under that pixel's centre, t * dot(centre direction, axis); a pixel that sees nothing is an error."""
 import argparse
 import os
 import sys
@@ -56,6 +60,24 @@ def aov_images(guide: np.ndarray, albedo: np.ndarray) -> dict:
     a[..., :3] = u8(albedo[..., :3] * f(255))
     out["normals"], out["depth"], out["albedo"] = n, d, a
     return out
+
+
+def focus_of_pixel(guide: np.ndarray, frustum, x: int, y: int) -> float:
+    """The focus distance that puts pixel (x, y)'s first hit in focus: its GUIDE distance t along the pinhole ray through the pixel
+    centre, projected onto the view axis.  ValueError outside the frame or where the pixel sees nothing."""
+    H, W = guide.shape[:2]
+    if not (0 <= x < W and 0 <= y < H):
+        raise ValueError(f"--focus-pixel {x},{y}: outside the {W}x{H} frame")
+    t = float(guide[y, x, 3])
+    if not t < 3.0e38:
+        raise ValueError(f"--focus-pixel {x},{y}: the pixel sees nothing to focus on")
+    fr = np.asarray(frustum, np.float64).reshape(4, 4)[:, :3]
+    tx, ty = (x + 0.5) / W, (y + 0.5) / H
+    left, right = fr[0] + (fr[2] - fr[0]) * ty, fr[1] + (fr[3] - fr[1]) * ty
+    d = left + (right - left) * tx
+    d /= np.sqrt(np.dot(d, d))
+    axis = T.lens_from_frustum(frustum, 1.0)[0].astype(np.float64)
+    return t * float(np.dot(d, axis))
 
 
 def parse_move(move: str):
@@ -122,7 +144,12 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
     ap.add_argument("--move", default="right:0.05", help="DIR:OFFSET of every move with --frames (left, right, up, down, forward, backward)")
     ap.add_argument("--recolour", default="", help="NODE:r,g,b[:step]: with --frames, edit material node NODE per frame in place instead of moving the camera")
+    ap.add_argument("--aperture", type=float, default=0.0, help="thin-lens radius in scene units (0 = pinhole)")
+    ap.add_argument("--focus", type=float, default=0.0, help="with --aperture: distance of the plane of focus along the view axis")
+    ap.add_argument("--focus-pixel", default="", help="with --aperture, x,y: focus on what this pixel's centre sees instead of --focus")
     a = ap.parse_args(argv)
+    if a.aperture < 0 or (a.aperture and not a.focus_pixel and not a.focus > 0):
+        ap.error("--aperture R needs --focus D > 0 or --focus-pixel x,y")
 
     rr = a.rr_bounces
     if rr == 0 or rr >= a.num_bounces:
@@ -142,6 +169,12 @@ def main(argv=None):
             r.set_temporal(max_history=a.temporal)
         if a.variance:
             r.set_variance(sigma_variance=a.variance, min_samples=T.VARIANCE_DEFAULTS["min_samples"])
+        if a.aperture:
+            focus = a.focus
+            if a.focus_pixel:
+                x, _, y = a.focus_pixel.partition(",")
+                focus = focus_of_pixel(r.read_aov(T.AOV_GUIDE), sc.frustum, int(x), int(y))
+            r.set_lens(a.aperture, focus)
         if a.frames:
             frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height)
             for path, (rows, ms) in zip(frame_paths(a.out, a.frames), frames):

@@ -69,6 +69,8 @@ class HipTracer:
         self._speed = 0
         self.last_trace_stats: T.TraceStats | None = None
         self._keepalive = None
+        self._camera = None   # the CameraData last committed (set_lens derives its vectors from it)
+        self._lens = None     # (radius, focus_distance) of set_lens: re-applied after every camera update
 
     # ---- tracer.Tracer ---------------------------------------------------------------------
     def Id(self) -> str:
@@ -157,6 +159,28 @@ class HipTracer:
         it off (the default) and drops the history."""
         p = T.temporal_params(max_history, normal_threshold, depth_threshold)
         self._check(self._lib.polaris_hip_set_temporal(self._h, C.byref(p)), self._h)
+
+    def set_lens(self, radius: float, focus_distance: float = 0.0) -> None:
+        """Thin-lens camera (polaris_hip_set_lens): a round lens of this radius focused at this distance along the view axis, with
+        the vectors of T.lens_from_frustum on the camera last given through UpdateState; re-applied after every later camera update.
+        radius = 0 turns the lens off (the default).  The caller restarts accumulation, as after a camera change."""
+        self._commit()
+        self._lens = (float(radius), float(focus_distance)) if radius != 0 else None
+        if self._lens is None:
+            self.set_lens_vectors(0.0, (0, 0, 0), (0, 0, 0), (0, 0, 0))
+        else:
+            self._apply_lens()
+
+    def set_lens_vectors(self, focus_distance: float, axis, u, v) -> None:
+        """The raw call: a lens point is eye + lx u + ly v, (lx, ly) uniform in the unit disk; u = v = 0 turns the lens off."""
+        p = T.lens_params(focus_distance, axis, u, v)
+        self._check(self._lib.polaris_hip_set_lens(self._h, C.byref(p)), self._h)
+
+    def _apply_lens(self) -> None:
+        if self._camera is None:
+            raise TracerError(2, "set_lens: no camera given through UpdateState yet")
+        axis, u, v = T.lens_from_frustum(self._camera.frustum, self._lens[0])
+        self.set_lens_vectors(self._lens[1], axis, u, v)
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """Variance-guided denoising at every SyncFramebuffer (polaris_hip_set_variance): turns the option "moments" on first, then
@@ -485,6 +509,9 @@ class HipTracer:
                 fr = np.ascontiguousarray(data.frustum, dtype=np.float32)
                 self._check(self._lib.polaris_hip_set_camera(self._h, eye.ctypes.data_as(C.POINTER(C.c_float)),
                                                              fr.ctypes.data_as(C.POINTER(C.c_float))), self._h)
+                self._camera = data
+                if self._lens is not None:   # (set_camera leaves the lens vectors alone: they follow the new frustum here)
+                    self._apply_lens()
             else:
                 raise TracerError(2, f"unsupported change type {change}")
         self._changes.clear()
