@@ -169,7 +169,19 @@ int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p);
  *                        after that still drops it (the old scene's mesh indices were not kept); set it before the scene.
  *                        Changing it drops the history and invalidates the G-buffer.  It never changes an accumulator or a
  *                        counter; off, no device memory is allocated and no kernel launched for it
- *   "instance_update"    0 (default) or 1, applies to the NEXT upload_scene: the upload keeps what polaris_hip_update_instances
+ *   "guide_specular"     0 (default) .. 8, anything else POLARIS_E_BAD_ARGUMENT: the number N of delta interactions the G-buffer's
+ *                        guide ray follows.  With N > 0 a pixel whose hit is a CONDUCTOR or DIELECTRIC leaf -- both
+ *                        delta BxDFs: a mirror, smooth glass -- continues in the mirror direction, or through the glass (refracted
+ *                        wherever refraction exists, reflected on total internal reflection), up to N times, and GUIDE / ALBEDO /
+ *                        INSTANCE describe the first surface it does not follow through (see the planes below): the filter and the
+ *                        reprojection then see what the pixel shows, not the smooth surface in front of it.  Every link is the first
+ *                        hit's own walk again (PRNG state (p, p), no path flags), the continuation ray is the shade kernels'.  A
+ *                        chain that is exhausted (N links followed, a delta leaf again) describes that delta surface with the
+ *                        accumulated distance and albedo; a delta direction that is not finite, all zero or beyond 2^10 in a
+ *                        component ends the chain at its surface.  0 is the first hit: k_gbuffer with its arguments, every plane
+ *                        bit for bit.  Changing the value invalidates the G-buffer and drops the temporal history, as changing
+ *                        "object_motion" does; setting the same value does nothing.  It never changes an accumulator or a counter
+ *   "instance_update"   0 (default) or 1, applies to the NEXT upload_scene: the upload keeps what polaris_hip_update_instances
  *                        needs (the top-level tree as a refit schedule, the triangle list of every mesh, host copies of the
  *                        emissive list and the packed light geometry).  Off, an upload keeps nothing extra: every
  *                        code path, allocation and launch is what it is without the option
@@ -380,8 +392,16 @@ int polaris_hip_set_denoise(polaris_hip_tracer *h, const PolarisDenoiseParams *p
  *   ALBEDO    first-hit albedo rgb (clamp(tint * k, 0, 1) for diffuse / conductor / rough conductor leaves, 1 otherwise) | the
  *             selected leaf's type as int bits; miss: 1, 1, 1 | -1
  *   DENOISED  the filtered running mean of the last denoised sync (rows outside its request: whatever an earlier sync left)
+ * With the option "guide_specular" = N > 0 "first hit" reads "the first surface the guide ray does not follow through" (at most N
+ * mirror / glass links):
+ *   GUIDE     that surface's shading normal | T, the float sum of the links' hit distances in order -- the unfolded path length:
+ *             eye + T d is the mirror image of the surface for a chain of planar mirrors, an approximation through curved
+ *             mirrors and refraction; a miss at any link is the miss above
+ *   ALBEDO    the product of the followed links' albedo (the rule above at each: tint * k for a mirror, 1 for glass) and that
+ *             surface's | that surface's leaf type.  An emitter seen in a mirror has type EMISSIVE: it passes through the filter
+ *             and is never a tap
  * The G-buffer is ONE ray per pixel through the pixel centre, computed on first use and kept until resize / upload_scene /
- * set_camera.  GUIDE / ALBEDO: POLARIS_E_NO_SCENE_DATA without a scene, POLARIS_E_BAD_ARGUMENT without a camera; DENOISED:
+ * set_camera / a change of "guide_specular".  GUIDE / ALBEDO: POLARIS_E_NO_SCENE_DATA without a scene, POLARIS_E_BAD_ARGUMENT without a camera; DENOISED:
  * POLARIS_E_BAD_ARGUMENT before any denoised sync. */
 #define POLARIS_AOV_GUIDE    0
 #define POLARIS_AOV_ALBEDO   1
@@ -535,7 +555,9 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
                                         const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2);
 
 /* The INSTANCE plane of the first-hit G-buffer (option "object_motion"): per pixel the mesh-instance index of the hit POLARIS_AOV_GUIDE
- * describes, 0xFFFFFFFF for a miss (where GUIDE's t is FLT_MAX); n >= frame_w * frame_h words.  Errors as polaris_hip_read_aov of
+ * describes, 0xFFFFFFFF for a miss (where GUIDE's t is FLT_MAX); n >= frame_w * frame_h words.  With the option "guide_specular" a
+ * pixel whose guide ray followed at least one link is 0xFFFFFFFF too: the reprojection gives a word >= n_instances no history, so with
+ * "object_motion" in effect what is seen through a mirror or glass takes none (with it off, camera moves reuse it).  Errors as polaris_hip_read_aov of
  * POLARIS_AOV_GUIDE; POLARIS_E_BAD_ARGUMENT with the option off, or without effect because temporal reuse is off. */
 int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n);
 

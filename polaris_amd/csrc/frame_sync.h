@@ -121,9 +121,12 @@ public:
 		return on ? 0 : kVariancePlanes | kMomentPlanes;
 	}
 	uint32_t motion_toggled(bool on) { // the history (with or without an INSTANCE plane) and the G-buffer go with the old setting
-		tp_have_hist = tp_synced = tp_prior_valid = va_synced = va_have_hist = va_valid = gb_valid = false;
+		guide_rule_changed();
 		cur = hist = InstTable();
 		return on ? 0 : kMotionPlanes;
+	}
+	void guide_rule_changed() { // (option "guide_specular") the G-buffer and a history seen with the other rule go; the planes and the instance table stay
+		tp_have_hist = tp_synced = tp_prior_valid = va_synced = va_have_hist = va_valid = gb_valid = false;
 	}
 	void gbuffer_computed() { gb_valid = true; }
 	void prior_computed() { tp_prior_valid = true; }

@@ -79,6 +79,7 @@ const auto kScan = POLARIS_VARIANT(k_scan);
 const auto kFoldNee = POLARIS_VARIANT(k_fold_nee);
 const auto kTonemap = POLARIS_VARIANT(k_tonemap);
 const auto kGbuffer = POLARIS_VARIANT(k_gbuffer);
+const auto kGbufferChain = POLARIS_VARIANT(k_gbuffer_chain); // option "guide_specular" > 0: in k_gbuffer's place
 const auto kDenoise = POLARIS_VARIANT(k_denoise);
 const auto kTemporal = POLARIS_VARIANT(k_temporal);
 const auto kVariance = POLARIS_VARIANT(k_variance);

@@ -1893,6 +1893,82 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 	albedo[idx] = make_float4(a.x, a.y, a.z, ibits((int)m.type));
 }
 
+// The G-buffer with the option "guide_specular" = max_links > 0, in k_gbuffer's place: the guide ray follows up to
+// max_links delta interactions (CONDUCTOR: the mirror direction; DIELECTRIC: bxdf_sample with the sample (1, 0), which refracts
+// wherever refraction exists and reflects on total internal reflection) and the planes describe the first surface it does not
+// follow through.  Every link is k_gbuffer's one hit again -- surfaceInit, PRNG state (p, p), no path flags: nothing is carried
+// from link to link but the ray, T and A -- and the continuation ray is shade_ray's (ind_origin, the direction not renormalised).
+// GUIDE = that surface's n | T, the float sum of the links' t in order; ALBEDO = the product of the links' albedo (k_gbuffer's
+// rule at each) | the last leaf's type; a miss at any link is k_gbuffer's miss.  INSTANCE = the hit's instance where no link was
+// followed, else 0xFFFFFFFF: a pixel seen through a chain takes no history across object motion.
+// A direction with a component that fails |c| <= 2^10 (NaN included), or all zero, ends the chain at its surface (the direction
+// rule of polaris_hip_probe_intersect): a degenerate IOR sends no such ray into the traversal.  max_links <= 8: every lane ends.
+__global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                      uint32_t *inst, int max_links) {
+	__shared__ int stk[kTraversalStack][WG];
+	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
+	if (idx >= n) return;
+	const uint32_t gx = idx % W, gy = idx / W;
+	const float tl[4] = {cam.tl.x, cam.tl.y, cam.tl.z, cam.tl.w}, tr[4] = {cam.tr.x, cam.tr.y, cam.tr.z, cam.tr.w};
+	const float bl[4] = {cam.bl.x, cam.bl.y, cam.bl.z, cam.bl.w}, br[4] = {cam.br.x, cam.br.y, cam.br.z, cam.br.w};
+	float dc[3];
+	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc);
+	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z), d = mk3(dc[0], dc[1], dc[2]);
+	f3 A = splat(1.0f);
+	float T = 0.0f;
+	for (int k = 0;; k++) {
+		HitRec h;
+		traverse<false>(B, o, d, kFltMax, stk, h);
+		if (h.tri < 0) {
+			guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
+			albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
+			if (inst) inst[idx] = kTpNoInstance;
+			return;
+		}
+		T = k == 0 ? h.t : T + h.t;
+		const int tri = h.tri & (int)((1u << S.tri_bits) - 1u);
+		// surfaceInit, as k_gbuffer
+		const float bu = h.u, bv = h.v, bw = 1.0f - (bu + bv);
+		const uint32_t off = (uint32_t)tri * 3;
+		Surf sf;
+		{
+			float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
+			sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
+			a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
+			sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
+			float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
+			sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
+		}
+		uint32_t flags = 0;
+		f3 tint = splat(1.0f);
+		Rng rng = {idx, idx};
+		MatT<false> m = select_material(S.mat_index[tri], sf, flags, tint, rng, S);
+		material_params(sf, m, S);
+		f3 a = splat(1.0f);
+		if (m.type == POLARIS_BXDF_DIFFUSE || m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_ROUGH_CONDUCTOR) {
+			const f3 c = tint * m.kcol;
+			a = mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
+		}
+		if ((m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_DIELECTRIC) && k < max_links) {
+			f3 out = splat(0.0f);
+			float pdf;
+			(void)bxdf_sample(sf, m, S, f2{1.0f, 0.0f}, -d, out, pdf);
+			const bool bounded = pm_fabs(out.x) <= 0x1p10f && pm_fabs(out.y) <= 0x1p10f && pm_fabs(out.z) <= 0x1p10f; // (false for a NaN)
+			if (bounded && (out.x != 0.0f || out.y != 0.0f || out.z != 0.0f)) {
+				A = A * a;
+				o = sf.p + (sf.n * pm_sign(dot(sf.n, out))) * kEps; // shade_ray's ind_origin
+				d = out;
+				continue;
+			}
+		}
+		const f3 Aa = A * a;
+		guide[idx] = make_float4(sf.n.x, sf.n.y, sf.n.z, T);
+		albedo[idx] = make_float4(Aa.x, Aa.y, Aa.z, ibits((int)m.type));
+		if (inst) inst[idx] = k == 0 ? (uint32_t)h.inst : kTpNoInstance;
+		return;
+	}
+}
+
 // One a-trous iteration over the rows [y0, y1) (n = (y1 - y0) * W pixels, rows in order from y0 * W).  r_in = null: iteration 0,
 // the taps demodulate the frame accumulator on the fly (c / max(albedo, 1e-3), c = acc * weight); otherwise r_in holds r^k.
 // last = 1: the result is remodulated (* max(albedo, 1e-3)) -- the DENOISED plane.  A pixel that is not filtered passes c through.

@@ -113,6 +113,7 @@ struct FrameSync {
 	PolarisTemporalParams tp{sizeof(PolarisTemporalParams), 0, 0.0f, 0.0f};
 	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
 	int opt_object_motion = 0;
+	int opt_guide_specular = 0; // delta links the guide ray follows (0: the first hit, k_gbuffer)
 	SyncState v;
 	DevArray<float4> pl[kNumPlanes4];     // the float4 planes, by Plane
 	DevArray<uint32_t> gb_inst, tp_hinst; // kInst, kHInst
@@ -148,6 +149,7 @@ struct FrameSync {
 		va = p;
 	}
 	void set_object_motion(int on) { opt_object_motion = on; drop(v.motion_toggled(on != 0)); } // (on differs from the option's value)
+	void set_guide_specular(int links) { opt_guide_specular = links; v.guide_rule_changed(); } // (links differs from the option's value)
 };
 
 inline uint32_t grid_for(size_t n) { return (uint32_t)((n + WG - 1) / WG); }
@@ -574,8 +576,12 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0))) return rc;
 	CameraArgs cam = h->cam;
 	cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
-	(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
-	             want_inst ? S.gb_inst.get() : nullptr);
+	if (S.opt_guide_specular == 0)
+		(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
+		             want_inst ? S.gb_inst.get() : nullptr);
+	else
+		(void)launch(h, "gbuffer", h->stream, kGbufferChain, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide],
+		             S.pl[kAlbedo], want_inst ? S.gb_inst.get() : nullptr, S.opt_guide_specular);
 	HIP_TRY(h, hipGetLastError());
 	S.v.gbuffer_computed();
 	return POLARIS_OK;
@@ -1371,6 +1377,10 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 			if (value && h->ds.have_scene)
 				if (int rc = read_back_instances(h)) return rc;
 		}
+	}
+	else if (k == "guide_specular") {
+		if (value < 0 || value > 8) return fail(h, POLARIS_E_BAD_ARGUMENT, "guide_specular is 0..8");
+		if ((int)value != h->fs.opt_guide_specular) h->fs.set_guide_specular((int)value); // (no plane is freed: nothing to wait for)
 	}
 	else if (k == "instance_update") { // next upload
 		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "instance_update is 0 or 1");

@@ -11,6 +11,9 @@ the reference does it (rr-bounces 0 or >= num-bounces -> num-bounces + 1).
 other settings at their defaults); --aov-dir DIR also writes the first-hit guide planes as normals.png / depth.png (the byte
 formulas of the reference's debug kernels, tracer/opencl/CL/kernels/debug.cl) and albedo.png.
 
+--guide-specular N lets the guide ray of that G-buffer follow up to N mirror and glass interactions (the tracer option "guide_specular",
+DESIGN.md 10i; 0..8, 0 = the first hit): what --denoise, --temporal and --aov-dir then see inside a mirror is the reflected surface.
+
 --frames N --move DIR:OFFSET renders N frames, each one render(accumulated=0) after a camera move (scene.Camera.Move, camera.go:76-97,
 DIR one of left, right, up, down, forward, backward), written as <out stem>_000.png, _001.png, ...: what the interactive renderer
 does while the user moves.  --temporal M reuses the last view's mean across the moves with max_history M (polaris_hip_set_temporal,
@@ -140,6 +143,7 @@ def main(argv=None):
     ap.add_argument("--denoise", type=int, default=0, help="a-trous filter iterations at the frame sync (0 = off)")
     ap.add_argument("--variance", type=float, default=0.0, help="sigma_variance of variance-guided denoising (0 = off)")
     ap.add_argument("--aov-dir", default=None, help="write normals.png, depth.png and albedo.png of the first-hit G-buffer here")
+    ap.add_argument("--guide-specular", type=int, default=0, help="delta (mirror / glass) links the G-buffer's guide ray follows, 0..8 (0 = first hit)")
     ap.add_argument("--temporal", type=int, default=0, help="max_history of temporal reuse across camera moves (0 = off)")
     ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
     ap.add_argument("--move", default="right:0.05", help="DIR:OFFSET of every move with --frames (left, right, up, down, forward, backward)")
@@ -163,6 +167,8 @@ def main(argv=None):
     r = host_api.Renderer(sc, devs, width=a.width, height=a.height, spp=a.spp, bounces=a.num_bounces, min_rr=rr,
                           exposure=a.exposure, seed=a.seed)
     try:
+        if a.guide_specular:
+            r.set_option("guide_specular", a.guide_specular)
         if a.denoise:
             r.set_denoise(iterations=a.denoise)
         if a.temporal:

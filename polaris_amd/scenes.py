@@ -991,6 +991,44 @@ def material_ball(aspect=1.0, detail=1.0) -> Scene:
     return sc
 
 
+MIRROR_ROOM_MIRROR = ((0.38, 0.2), (0.8, 0.82), 0.995)  # the planar mirror of mirror_room: (x, y) low corner, high corner, its plane z
+
+
+def mirror_room(aspect=1.0, eye=(0.5, 0.5, 0.06), fov=1.25) -> Scene:
+    """The denoiser's delta-chain scene (not in SCENES): a closed diffuse unit room seen from inside, the checker
+    floor of cornell_box, a ceiling light near the camera's wall, a planar conductor quad on the back wall (the floor, a diffuse
+    box and the light show in it), a conductor UV sphere and a thin dielectric slab (two interfaces, IOR 1.5) in front of the
+    x = 1 wall; the planar mirror shows neither of the last two.  One mesh, one instance, ~300 triangles, no bump maps.
+    eye, fov: the camera, which looks along +z (fov 0.6 from the default eye sees little but the mirror)."""
+    mt = MaterialTable()
+    white = mt.diffuse((0.725, 0.71, 0.68))
+    red = mt.diffuse((0.63, 0.065, 0.05))
+    green = mt.diffuse((0.14, 0.45, 0.091))
+    blue = mt.diffuse((0.2, 0.3, 0.7))
+    light = mt.emissive((17.0, 12.0, 4.0), 1.0)
+    floor_mat = mt.diffuse((0.725, 0.71, 0.68), tex=mt.texture(T.TEX_RGBA8, checker_rgba8()))
+    mirror = mt.conductor((0.9, 0.9, 0.95))
+    chrome = mt.conductor((0.95, 0.93, 0.88))
+    glass = mt.dielectric((1, 1, 1), (0.95, 0.98, 1.0), int_ior=1.5)
+    (mx0, my0), (mx1, my1), mz = MIRROR_ROOM_MIRROR
+    parts = [
+        quad((1, 0, 0), (0, 0, 0), (0, 0, 1), (1, 0, 1), floor_mat, uv=((0, 0), (4, 0), (4, 4), (0, 4))),  # floor
+        quad((1, 1, 0), (1, 1, 1), (0, 1, 1), (0, 1, 0), white),                                        # ceiling
+        quad((1, 0, 1), (0, 0, 1), (0, 1, 1), (1, 1, 1), white),                                        # back wall (z = 1)
+        quad((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), white),                                        # the wall behind the camera
+        quad((0, 0, 1), (0, 0, 0), (0, 1, 0), (0, 1, 1), green),                                        # x = 0
+        quad((1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0), red),                                          # x = 1
+        quad((0.65, 0.999, 0.12), (0.65, 0.999, 0.36), (0.35, 0.999, 0.36), (0.35, 0.999, 0.12), light),
+        quad((mx1, my0, mz), (mx0, my0, mz), (mx0, my1, mz), (mx1, my1, mz), mirror),                   # planar mirror, facing -z
+        box((0.56, 0.0, 0.26), (0.76, 0.3, 0.46), blue, rot_y=0.35),
+        uv_sphere((0.16, 0.14, 0.8), 0.14, chrome, n_lat=10, n_lon=14),                                  # (not seen in the planar mirror)
+        box((0.93, 0.0, 0.62), (0.96, 0.75, 0.95), glass),                                              # the slab (nor is it)
+    ]
+    sc = compile_scene([merge(parts)], [(0, np.eye(4))], mt, name="mirror-room")
+    sc.set_camera(eye=eye, look=(eye[0], eye[1], 1.0), fov=fov, aspect=aspect)
+    return sc
+
+
 def displaced_grid(n=64, size=10.0, amp=0.6, mat=0, seed=3):
     """(n x n) quads = 2 n^2 triangles of a smooth random height field (flat normals)."""
     rng = np.random.default_rng(seed)
