@@ -47,7 +47,8 @@ extern "C" {
  * itself); PolarisIpcExport carries the exporting GPU's PCI bus id (544 -> 576 bytes); PolarisBvhBuildInput LEADS with `struct_size`
  * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end.  Still 5: + update_instances,
  * + update_vertices / PolarisVertexUpdate, + update_materials / PolarisMaterialUpdate / update_texture and the record kinds
- * POLARIS_REC_TRIS / POLARIS_REC_SHADING, + set_lens / PolarisLensParams (additions only: older callers keep working). */
+ * POLARIS_REC_TRIS / POLARIS_REC_SHADING, + set_lens / PolarisLensParams, + set_shutter / PolarisShutterParams (additions only: older
+ * callers keep working). */
 #define POLARIS_HIP_ABI_VERSION 5
 
 /* status codes (0 = ok).  The first three mirror tracer/opencl/errors.go sentinels. */
@@ -138,6 +139,37 @@ typedef struct PolarisLensParams {
 	                             u = v = 0 (all six floats zero): the lens is OFF, nothing else is looked at */
 } PolarisLensParams;
 int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p);
+
+/* Camera shutter: motion blur of the camera and focus pulls inside one accumulation (no reference counterpart).  Off by default and
+ * while enabled = 0: every Trace, tap and sync then launches exactly what it did, under the same kernel symbols.  The state at
+ * shutter OPEN is what polaris_hip_set_camera and polaris_hip_set_lens hold; this struct is the state at shutter CLOSE.  With it on,
+ * the camera rays of a Trace and of polaris_hip_tap_primary come from k_generate_shutter<LENS>: after the sub-pixel draw (and, with the
+ * lens on, the lens draw) the camera PRNG's next draw gives the ray its time t in [0, 1), and the ray is generated by the camera
+ * whose eye, corner rays and (lens on) lens are a + (b - a) t per component between open a and close b -- uniform over the interval,
+ * corners and axis blended linearly (the axis is not renormalised; a caller who turns far inside one exposure subdivides it).  A close
+ * state equal to the open one gives the rays of the shutter-off generator bit for bit (a -0 entry becomes +0).  DESIGN.md 10j has the
+ * exact float32 arithmetic.
+ * The close state belongs to the open state it was set after: polaris_hip_set_camera switches the shutter off, and so does a
+ * polaris_hip_set_lens that changes a byte (one with identical bytes does nothing, as before).  The order of calls is therefore camera,
+ * lens, shutter; the layers above re-apply it for their callers.
+ * What stays at the open camera: the G-buffer (GUIDE, ALBEDO, the INSTANCE plane) and the temporal reprojection, which are pinhole at
+ * the open camera as they are under a lens.  Only the camera moves: instances and deforming meshes are not blurred.
+ * A call that changes the state drops the temporal history (as a changed lens does; the G-buffer stays) and the caller restarts
+ * accumulation; a call whose bytes equal the stored ones does nothing, and any two off states are equal.
+ * POLARIS_E_BAD_ARGUMENT, state unchanged: a null handle or params, another struct_size, enabled > 1, no camera set yet; with
+ * enabled = 1 an eye1 or frustum1 float that is not finite, and WHILE THE LENS IS ON the rules of polaris_hip_set_lens for the close
+ * lens: ten finite floats, entries of u1 / v1 at most 2^30 in magnitude, focus_distance1 within [1e-6, 1e30], |axis1|^2 within
+ * [0.998, 1.002] (u1 = v1 = 0 is allowed: the aperture closes over the interval).  With the lens off the ten lens floats are not
+ * looked at. */
+typedef struct PolarisShutterParams {
+	uint32_t struct_size;      /* = sizeof(PolarisShutterParams) = 124 */
+	uint32_t enabled;          /* 0 = off (default): nothing else is looked at.  1 = on.  Anything else: BAD_ARGUMENT */
+	float    eye1[3];          /* the eye at shutter close */
+	float    frustum1[16];     /* the corner rays TL, TR, BL, BR at shutter close, as set_camera's */
+	float    focus_distance1;  /* the lens at shutter close: looked at only while the lens is on */
+	float    axis1[3], u1[3], v1[3];
+} PolarisShutterParams;
+int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p);
 
 /* Tunables (not part of the reference interface).  Keys:
  *   "samples_per_batch"  samples traced concurrently as one wavefront batch (default: auto)
@@ -471,7 +503,7 @@ int polaris_hip_read_accumulator(polaris_hip_tracer *h, int which, float *out, s
 /* Test tap: generate + intersect the primary rays of one sample with camera seed `seed` and
  * return rays [N][8], hit flags [N], (w,u,v,t) [N][4] and (instance, triangle) [N][2];
  * N = frame_w*block_h.  Any output pointer may be NULL.  With the lens on (polaris_hip_set_lens) the rays are k_generate_lens':
- * rays[i][0..2] is ray i's own origin on the lens. */
+ * rays[i][0..2] is ray i's own origin on the lens; with the shutter on (polaris_hip_set_shutter) they are k_generate_shutter's. */
 int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *req, uint32_t seed,
                             float *rays, int32_t *hit, float *wuvt, int32_t *tri);
 

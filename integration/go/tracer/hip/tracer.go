@@ -321,6 +321,37 @@ func (tr *Tracer) SetLens(p LensParams) error {
 	return tr.check(C.polaris_hip_set_lens(tr.handle, &c))
 }
 
+// ShutterParams is the camera at shutter close (PolarisShutterParams, include/polaris_hip.h; DESIGN.md section 10j): every camera
+// ray gets its own time in [0, 1) and is generated by the camera blended between the state UpdateState(CameraData) and SetLens hold
+// (shutter open) and this one.  Lens is looked at only while the lens is on; its U = V = 0 closes the aperture over the interval.
+type ShutterParams struct {
+	Eye     [3]float32  // the eye at shutter close
+	Frustum [16]float32 // the corner rays TL, TR, BL, BR at shutter close
+	Lens    LensParams  // the lens at shutter close
+}
+
+// SetShutter turns the shutter on with this close state, or off with nil.  The close state belongs to the open one: UpdateState(CameraData)
+// and a SetLens that changes the lens switch the shutter off, so the order of calls is camera, lens, shutter.  A changed shutter drops the
+// temporal history; the caller restarts accumulation as after a camera change.
+func (tr *Tracer) SetShutter(p *ShutterParams) error {
+	var c C.PolarisShutterParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	if p != nil {
+		c.enabled = 1
+		for i := 0; i < 3; i++ {
+			c.eye1[i] = C.float(p.Eye[i])
+			c.axis1[i] = C.float(p.Lens.Axis[i])
+			c.u1[i] = C.float(p.Lens.U[i])
+			c.v1[i] = C.float(p.Lens.V[i])
+		}
+		for i := 0; i < 16; i++ {
+			c.frustum1[i] = C.float(p.Frustum[i])
+		}
+		c.focus_distance1 = C.float(p.Lens.FocusDistance)
+	}
+	return tr.check(C.polaris_hip_set_shutter(tr.handle, &c))
+}
+
 // SetObjectMotion turns the option "object_motion" on or off: with it on (and temporal reuse on) the history survives an
 // UpdateState(SceneData) that only moves mesh instances -- same instances, same meshes, same triangle count -- and is reprojected
 // through each instance's motion (DESIGN.md section 10d).  Changing it drops the history.

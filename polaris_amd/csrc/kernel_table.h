@@ -69,6 +69,8 @@ const decltype(POLARIS_VARIANT(k_aggregate<false>)) kAggregate[2] = {POLARIS_VAR
 const decltype(POLARIS_VARIANT(k_reproject<false, false>)) kReproject[2][2] = {
 	{POLARIS_VARIANT(k_reproject<false, false>), POLARIS_VARIANT(k_reproject<false, true>)},
 	{POLARIS_VARIANT(k_reproject<true, false>), POLARIS_VARIANT(k_reproject<true, true>)}};
+// k_generate_shutter<LENS>: [LENS].  polaris_hip_set_shutter: in k_generate's (k_generate_lens') place while the shutter is on
+const decltype(POLARIS_VARIANT(k_generate_shutter<false>)) kGenerateShutter[2] = {POLARIS_VARIANT(k_generate_shutter<false>), POLARIS_VARIANT(k_generate_shutter<true>)};
 
 // the kernels of one variant (k_intersect / k_occlusion: the plain traversal, option traversal = 0)
 const auto kIntersect = POLARIS_VARIANT(k_intersect);

@@ -148,11 +148,9 @@ __device__ __forceinline__ float ibits(int i) { return __int_as_float(i); }
 // ------------------------------------------------------------------------------------------
 struct CameraArgs { float4 tl, tr, bl, br; float3 eye; float2 texel; };
 
-// The unit direction of the camera ray of pixel (gx, gy + blockY) under camera seed `seed`, camera.cl:38-56.  rng is left as the
-// camera stream after its first draw (the sub-pixel offset): the reference draws no more, k_generate_lens draws once more.
-__device__ __forceinline__ f3 camera_direction(const CameraArgs &cam, uint32_t seed, uint32_t gx, uint32_t gy, uint32_t blockY, Rng &rng) {
-	rng = {gx + seed, gy + seed}; // camera.cl:38
-	f2 s0 = rng_next(rng);
+// camera_direction's arithmetic after the first draw of the camera stream, camera.cl:40-56: the unit direction of the camera ray of
+// pixel (gx, gy + blockY) whose sub-pixel draw is s0, under the corners of `cam` (k_generate_shutter passes the corners at the ray's time).
+__device__ __forceinline__ f3 camera_direction_from(const CameraArgs &cam, f2 s0, uint32_t gx, uint32_t gy, uint32_t blockY) {
 	float ox = s0.x < 0.5f ? pm_sqrt(2.0f * s0.x) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.x);
 	float oy = s0.y < 0.5f ? pm_sqrt(2.0f * s0.y) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.y);
 	float tx = ((float)gx + ox) * cam.texel.x;
@@ -163,6 +161,14 @@ __device__ __forceinline__ f3 camera_direction(const CameraArgs &cam, uint32_t s
 	float dx = pm_mix(lx, rx, tx), dy = pm_mix(ly, ry, tx), dz = pm_mix(lz, rz, tx), dw = pm_mix(lw, rw, tx);
 	float inv = 1.0f / pm_sqrt(dx * dx + dy * dy + dz * dz + dw * dw);
 	return mk3(dx * inv, dy * inv, dz * inv);
+}
+
+// The unit direction of the camera ray of pixel (gx, gy + blockY) under camera seed `seed`, camera.cl:38-56.  rng is left as the
+// camera stream after its first draw (the sub-pixel offset): the reference draws no more, k_generate_lens draws once more.
+__device__ __forceinline__ f3 camera_direction(const CameraArgs &cam, uint32_t seed, uint32_t gx, uint32_t gy, uint32_t blockY, Rng &rng) {
+	rng = {gx + seed, gy + seed}; // camera.cl:38
+	const f2 s0 = rng_next(rng);
+	return camera_direction_from(cam, s0, gx, gy, blockY);
 }
 
 __global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, const uint32_t *seeds, uint32_t seed_stride,
@@ -194,6 +200,26 @@ __global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, con
 // origins are always written: every kernel that traces these rays reads the origin stream.
 struct LensArgs { float focus_distance; float3 axis, u, v; };
 
+// k_generate_lens' lines after its two draws: the ray (o = the eye, d = the pinhole's unit direction) moved onto the lens point of the
+// draw s1.  A direction with d . axis <= 0 (NaN included) keeps its pinhole ray.
+__device__ __forceinline__ void lens_ray(const LensArgs &lens, f2 s1, f3 &o, f3 &d) {
+	const float a = 2.0f * s1.x - 1.0f, b = 2.0f * s1.y - 1.0f;
+	float r = 0.0f, phi = 0.0f;
+	if (a == 0.0f && b == 0.0f) {}
+	else if (__builtin_fabsf(a) > __builtin_fabsf(b)) { r = a; phi = 0.78539816339744830962f * (b / a); }
+	else { r = b; phi = 1.57079632679489661923f - 0.78539816339744830962f * (a / b); }
+	const float lx = r * pm_cos(phi), ly = r * pm_sin(phi);
+	const float c = d.x * lens.axis.x + d.y * lens.axis.y + d.z * lens.axis.z;
+	if (c > 0.0f) { // (else, NaN included: the pinhole ray)
+		const float ft = lens.focus_distance / c;
+		const float Lx = lx * lens.u.x + ly * lens.v.x, Ly = lx * lens.u.y + ly * lens.v.y, Lz = lx * lens.u.z + ly * lens.v.z;
+		const float qx = d.x * ft - Lx, qy = d.y * ft - Ly, qz = d.z * ft - Lz; // focus point minus lens point: the eye cancels
+		const float inv2 = 1.0f / pm_sqrt(qx * qx + qy * qy + qz * qz);
+		o = mk3(o.x + Lx, o.y + Ly, o.z + Lz);
+		d = mk3(qx * inv2, qy * inv2, qz * inv2);
+	}
+}
+
 __global__ __launch_bounds__(WG) void k_generate_lens(Streams st, CameraArgs cam, LensArgs lens, const uint32_t *seeds, uint32_t seed_stride,
                                                        uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
                                                        int zero_lsum) {
@@ -211,21 +237,51 @@ __global__ __launch_bounds__(WG) void k_generate_lens(Streams st, CameraArgs cam
 	Rng rng;
 	f3 d = camera_direction(cam, seed, idx % W, idx / W, blockY, rng);
 	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z);
-	const f2 s1 = rng_next(rng);
-	const float a = 2.0f * s1.x - 1.0f, b = 2.0f * s1.y - 1.0f;
-	float r = 0.0f, phi = 0.0f;
-	if (a == 0.0f && b == 0.0f) {}
-	else if (__builtin_fabsf(a) > __builtin_fabsf(b)) { r = a; phi = 0.78539816339744830962f * (b / a); }
-	else { r = b; phi = 1.57079632679489661923f - 0.78539816339744830962f * (a / b); }
-	const float lx = r * pm_cos(phi), ly = r * pm_sin(phi);
-	const float c = d.x * lens.axis.x + d.y * lens.axis.y + d.z * lens.axis.z;
-	if (c > 0.0f) { // (else, NaN included: the pinhole ray)
-		const float ft = lens.focus_distance / c;
-		const float Lx = lx * lens.u.x + ly * lens.v.x, Ly = lx * lens.u.y + ly * lens.v.y, Lz = lx * lens.u.z + ly * lens.v.z;
-		const float qx = d.x * ft - Lx, qy = d.y * ft - Ly, qz = d.z * ft - Lz; // focus point minus lens point: the eye cancels
-		const float inv2 = 1.0f / pm_sqrt(qx * qx + qy * qy + qz * qz);
-		o = mk3(cam.eye.x + Lx, cam.eye.y + Ly, cam.eye.z + Lz);
-		d = mk3(qx * inv2, qy * inv2, qz * inv2);
+	lens_ray(lens, rng_next(rng), o, d);
+	store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
+	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
+	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// The shutter generator (polaris_hip_set_shutter; no reference counterpart): every camera ray gets its own time t in
+// [0, 1) from the camera stream's NEXT draw (the second with the lens off, the third with it on; .y unused) and is generated by the
+// camera -- eye, corners, and with LENS the lens -- blended per component with pm_mix(open, close, t).  pm_mix(a, a, t) = a for a
+// finite a other than -0, so a close state equal to the open one gives k_generate's (LENS: k_generate_lens') rays bit for bit.
+// axis_t is not renormalised (it shortens to cos(theta / 2) between two axes theta apart: the plane of focus moves by at most
+// 1 / cos(theta / 2)).  tests/shutter_oracle.py restates it.  k_generate_lens' launch shape and bookkeeping; origins always written.
+__device__ __forceinline__ float3 mix3(float3 a, float3 b, float t) { return make_float3(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t)); }
+__device__ __forceinline__ float4 mix4(float4 a, float4 b, float t) { return make_float4(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t), pm_mix(a.w, b.w, t)); }
+
+template <bool LENS>
+__global__ __launch_bounds__(WG) void k_generate_shutter(Streams st, CameraArgs cam, CameraArgs cam1, LensArgs lens, LensArgs lens1, const uint32_t *seeds,
+                                                          uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
+                                                          int zero_lsum) {
+	const uint32_t wgs_per_sample = Npad / WG;
+	const uint32_t s = blockIdx.x / wgs_per_sample;
+	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
+	const uint32_t idx = idx0 + threadIdx.x;
+	const size_t slot = (size_t)blockIdx.x * WG + threadIdx.x;
+	if (threadIdx.x == 0) {
+		st.cnt_ray[blockIdx.x] = idx0 < N ? min((uint32_t)WG, N - idx0) : 0u;
+		st.pfx[blockIdx.x] = idx0;
+	}
+	if (idx >= N) return;
+	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
+	const uint32_t gx = idx % W, gy = idx / W;
+	Rng rng = {gx + seed, gy + seed}; // camera.cl:38
+	const f2 s0 = rng_next(rng);
+	f2 s1 = {0.0f, 0.0f};
+	if (LENS) s1 = rng_next(rng);
+	const float t = rng_next(rng).x;
+	CameraArgs ct;
+	ct.tl = mix4(cam.tl, cam1.tl, t); ct.tr = mix4(cam.tr, cam1.tr, t); ct.bl = mix4(cam.bl, cam1.bl, t); ct.br = mix4(cam.br, cam1.br, t);
+	ct.eye = mix3(cam.eye, cam1.eye, t);
+	ct.texel = cam.texel;
+	f3 d = camera_direction_from(ct, s0, gx, gy, blockY);
+	f3 o = mk3(ct.eye.x, ct.eye.y, ct.eye.z);
+	if (LENS) {
+		const LensArgs lt = {pm_mix(lens.focus_distance, lens1.focus_distance, t), mix3(lens.axis, lens1.axis, t), mix3(lens.u, lens1.u, t), mix3(lens.v, lens1.v, t)};
+		lens_ray(lt, s1, o, d);
 	}
 	store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
 	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));

@@ -144,6 +144,7 @@ struct FrameSync {
 		tp = p;
 	}
 	void lens_changed() { if (tp.max_history) drop(v.temporal_off()); } // the history saw another lens: it goes as with max_history = 0; the (pinhole) G-buffer stays
+	void shutter_changed() { lens_changed(); } // polaris_hip_set_shutter changed the state (or set_camera / set_lens switched it off): lens_changed's rule
 	void set_variance(const PolarisVarianceParams &p) {
 		if ((p.sigma_variance != 0.0f) != (va.sigma_variance != 0.0f)) drop(v.variance_toggled(p.sigma_variance != 0.0f));
 		va = p;
@@ -329,6 +330,17 @@ struct polaris_hip_tracer {
 	bool lens_on() const { for (int i = 0; i < 3; i++) if (lens.u[i] != 0.0f || lens.v[i] != 0.0f) return true; return false; }
 	LensArgs lens_args() const {
 		return {lens.focus_distance, make_float3(lens.axis[0], lens.axis[1], lens.axis[2]), make_float3(lens.u[0], lens.u[1], lens.u[2]), make_float3(lens.v[0], lens.v[1], lens.v[2])};
+	}
+	PolarisShutterParams shutter{sizeof(PolarisShutterParams), 0u, {}, {}, 0.0f, {}, {}, {}}; // polaris_hip_set_shutter: the camera and lens at shutter close; enabled = 0: off
+	bool shutter_on() const { return shutter.enabled != 0; }
+	CameraArgs shutter_cam() const { // (k_generate_shutter reads the texel of the open camera only)
+		const float *f = shutter.frustum1;
+		return {make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]), make_float4(f[8], f[9], f[10], f[11]), make_float4(f[12], f[13], f[14], f[15]),
+		        make_float3(shutter.eye1[0], shutter.eye1[1], shutter.eye1[2]), cam.texel};
+	}
+	LensArgs shutter_lens_args() const {
+		return {shutter.focus_distance1, make_float3(shutter.axis1[0], shutter.axis1[1], shutter.axis1[2]), make_float3(shutter.u1[0], shutter.u1[1], shutter.u1[2]),
+		        make_float3(shutter.v1[0], shutter.v1[1], shutter.v1[2])};
 	}
 
 	FrameSync fs; // the synced frame's features, planes and history
@@ -690,6 +702,7 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 	s.packet_primary = h->packet_primary;
 	s.num_cus = h->num_cus;
 	s.lens = h->lens_on();
+	s.shutter = h->shutter_on();
 	return s;
 }
 
@@ -719,7 +732,8 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	hipStream_t q = P.q;
 	P.st.hit12 = plan.hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
 	P.st.o12 = plan.o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
-	if (plan.scene.lens) note(launch(h, "generate", q, kGenerateLens, wgs, WG, 0, P.st, h->cam, h->lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
+	if (plan.scene.shutter) note(launch(h, "generate", q, kGenerateShutter[plan.scene.lens ? 1 : 0], wgs, WG, 0, P.st, h->cam, h->shutter_cam(), h->lens_args(), h->shutter_lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
+	else if (plan.scene.lens) note(launch(h, "generate", q, kGenerateLens, wgs, WG, 0, P.st, h->cam, h->lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
 	else note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y,
 	                 exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
 	ShadeArgs A{};
@@ -1288,10 +1302,30 @@ int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, 
 	return POLARIS_OK;
 }
 
+// The history goes where a lens or a shutter changes (FrameSync::lens_changed): its planes are freed, so the main stream, where every
+// temporal launch runs, is idle first.  The caller holds mu.
+static int idle_before_history_drop(polaris_hip_tracer *h) {
+	if (!h->fs.tp.max_history) return POLARIS_OK;
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return POLARIS_OK;
+}
+
+// polaris_hip_set_camera and a changed polaris_hip_set_lens switch the shutter off: its close state belonged to the open state they
+// replace.  Nothing happens for a caller that never set a shutter.  The caller holds mu.
+static int shutter_off(polaris_hip_tracer *h) {
+	if (!h->shutter_on()) return POLARIS_OK;
+	if (int rc = idle_before_history_drop(h)) return rc;
+	h->fs.shutter_changed();
+	h->shutter.enabled = 0;
+	return POLARIS_OK;
+}
+
 int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const float fr[16]) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
+	if (int rc = shutter_off(h)) return rc; // (the close state belonged to the camera that goes)
 	h->fs.camera_moved(h->cam); // (with temporal reuse the last temporal sync's planes under the old camera become the history)
 	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
 	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
@@ -1306,6 +1340,21 @@ int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const floa
 	return POLARIS_OK;
 }
 
+// The rules for the ten floats of a lens (focus distance, axis, u, v), for polaris_hip_set_lens and the close lens of
+// polaris_hip_set_shutter (`who`): all finite, entries of u and v at most 2^30, and for a lens that is `on` the ranges of the focus
+// distance and of the axis' length.  POLARIS_OK, or the refusal.
+static int check_lens_floats(polaris_hip_tracer *h, const char *who, const float *f, bool on) {
+	for (int i = 0; i < 10; i++)
+		if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: float %d is not finite", who, i);
+	for (int i = 4; i < 10; i++)
+		if (std::fabs(f[i]) > 0x1p30f) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: an entry of u or v is above 2^30", who);
+	if (!on) return POLARIS_OK;
+	if (!(f[0] >= 1e-6f && f[0] <= 1e30f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: focus_distance %g outside [1e-6, 1e30]", who, (double)f[0]);
+	const float a2 = f[1] * f[1] + f[2] * f[2] + f[3] * f[3];
+	if (!(a2 >= 0.998f && a2 <= 1.002f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: axis is not a unit vector (squared length %g)", who, (double)a2);
+	return POLARIS_OK;
+}
+
 int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
@@ -1313,25 +1362,38 @@ int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) {
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: null params or struct_size != %zu", sizeof(PolarisLensParams));
 	const float *f = &p->focus_distance; // the ten floats after struct_size
 	static_assert(sizeof(PolarisLensParams) == 44 && offsetof(PolarisLensParams, focus_distance) == 4, "PolarisLensParams is struct_size and ten floats");
-	bool on = false;
-	for (int i = 0; i < 10; i++)
-		if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: float %d is not finite", i);
-	for (int i = 0; i < 3; i++) {
-		if (std::fabs(p->u[i]) > 0x1p30f || std::fabs(p->v[i]) > 0x1p30f) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: an entry of u or v is above 2^30");
-		on = on || p->u[i] != 0.0f || p->v[i] != 0.0f;
-	}
-	if (on) {
-		if (!(p->focus_distance >= 1e-6f && p->focus_distance <= 1e30f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: focus_distance %g outside [1e-6, 1e30]", (double)p->focus_distance);
-		const float a2 = p->axis[0] * p->axis[0] + p->axis[1] * p->axis[1] + p->axis[2] * p->axis[2];
-		if (!(a2 >= 0.998f && a2 <= 1.002f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: axis is not a unit vector (squared length %g)", (double)a2);
-	}
+	bool on = false; // (a NaN in u or v counts as on here and is refused below)
+	for (int i = 4; i < 10; i++) on = on || f[i] != 0.0f;
+	if (int rc = check_lens_floats(h, "set_lens", f, on)) return rc;
 	if (memcmp(p, &h->lens, sizeof h->lens) == 0) return POLARIS_OK; // identical bytes: nothing happens
-	if (h->fs.tp.max_history) { // the history's planes go
-		HIP_TRY(h, hipSetDevice(h->device));
-		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every temporal launch is on the main stream)
-	}
+	if (int rc = idle_before_history_drop(h)) return rc;
 	h->fs.lens_changed();
 	h->lens = *p;
+	h->shutter.enabled = 0; // (the close lens belonged to the lens that went; the history is gone already)
+	return POLARIS_OK;
+}
+
+int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	static_assert(sizeof(PolarisShutterParams) == 124 && offsetof(PolarisShutterParams, eye1) == 8 && offsetof(PolarisShutterParams, focus_distance1) == 84,
+	              "PolarisShutterParams is struct_size, enabled, 19 camera floats and ten lens floats");
+	if (!p || p->struct_size != sizeof(PolarisShutterParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: null params or struct_size != %zu", sizeof(PolarisShutterParams));
+	if (p->enabled > 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: enabled is %u (0 or 1)", p->enabled);
+	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: camera not set (the close state belongs to an open one)");
+	if (p->enabled) {
+		const float *f = p->eye1; // the 19 camera floats: eye1, frustum1
+		for (int i = 0; i < 19; i++)
+			if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: camera float %d is not finite", i);
+		if (h->lens_on()) // the close lens is a lens that is on, whatever its u1 and v1
+			if (int rc = check_lens_floats(h, "set_shutter: close lens", &p->focus_distance1, true)) return rc;
+	}
+	if (p->enabled ? memcmp(p, &h->shutter, sizeof h->shutter) == 0 : !h->shutter_on()) return POLARIS_OK; // identical bytes, or off and off: nothing happens
+	if (int rc = idle_before_history_drop(h)) return rc;
+	h->fs.shutter_changed();
+	if (p->enabled) h->shutter = *p;
+	else h->shutter.enabled = 0;
 	return POLARIS_OK;
 }
 
@@ -2099,7 +2161,8 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	std::vector<int> inst(N);
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
-	if (h->lens_on()) kGenerateLens.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
+	if (h->shutter_on()) kGenerateShutter[h->lens_on() ? 1 : 0].enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->shutter_cam(), h->lens_args(), h->shutter_lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
+	else if (h->lens_on()) kGenerateLens.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
 	else kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1, 1);
 	(void)launch_traversal(h, nullptr, tap_traversal(plan_scene(h)), RayKind::Closest, q, st0, 0, Npad / WG, nullptr);
 	HIP_TRY(h, hipGetLastError());

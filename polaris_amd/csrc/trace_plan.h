@@ -53,10 +53,11 @@ struct TraceScene {
 	bool packet_primary = true;       // option packet_primary, resolved by the upload where it is -1
 	int num_cus = 256;
 	bool lens = false;                // polaris_hip_set_lens is on: the camera rays start on the lens, each at its own origin
+	bool shutter = false;             // polaris_hip_set_shutter is on: each camera ray starts at the eye of its own time; plans exactly as `lens`
 };
 
 // ---- which traversal kernel traces a set of rays
-enum class RayKind { Camera, Closest, AnyHit }; // Camera: closest hit of a batch's camera rays, which share their origin (pinhole only)
+enum class RayKind { Camera, Closest, AnyHit }; // Camera: closest hit of a batch's camera rays, which share their origin (pinhole only, shutter off)
 enum class Traversal { Packet, Persistent, Plain }; // k_trace_packet | the scene's k_trace variant | k_intersect / k_occlusion
 
 inline Traversal traversal_unless_packet(bool packet, const TraceOptions &o) { return packet ? Traversal::Packet : (o.traversal ? Traversal::Persistent : Traversal::Plain); }
@@ -123,7 +124,7 @@ struct TracePlan {
 	bool staged = false;     // the shade kernels' LDS-table variants
 	bool moments = false, prefilter = true, hit12 = true, o12 = true; // the options the launches pass on
 	bool generate_writes_origins = true; // (neither the wave-packet kernel nor k_trace's camera launch reads the origin stream)
-	RayKind primary = RayKind::Camera;   // bounce 0's closest-hit rays; Closest under a lens: the same kernel family, reading the origin stream
+	RayKind primary = RayKind::Camera;   // bounce 0's closest-hit rays; Closest under a lens or a shutter: the same kernel family, reading the origin stream
 	BouncePlan bounce[POLARIS_MAX_BOUNCES];
 
 	uint32_t pipes_wanted() const { return (uint32_t)std::max(1, std::min(opt.overlap, kMaxPipes)); }
@@ -219,8 +220,9 @@ inline TracePlan plan_trace(const TraceOptions &opt, const TraceScene &scene, bo
 	p.k_chosen = opt.samples_per_batch > 0;
 	p.staged = tables_staged(opt, scene);
 	p.moments = moments; p.prefilter = opt.shade_prefilter != 0; p.hit12 = opt.hit12 != 0; p.o12 = opt.o12 != 0;
-	p.generate_writes_origins = scene.lens || !(bounces > 0 && (scene.packet_primary || opt.traversal));
-	p.primary = scene.lens ? RayKind::Closest : RayKind::Camera;
+	const bool own_origins = scene.lens || scene.shutter; // a generator that gives every camera ray its own origin
+	p.generate_writes_origins = own_origins || !(bounces > 0 && (scene.packet_primary || opt.traversal));
+	p.primary = own_origins ? RayKind::Closest : RayKind::Camera;
 	for (uint32_t b = 0; b < bounces; b++) {
 		p.bounce[b].isect = batch_traversal(opt, scene, b == 0 ? p.primary : RayKind::Closest, b);
 		p.bounce[b].occl = batch_traversal(opt, scene, RayKind::AnyHit, b);

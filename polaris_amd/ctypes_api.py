@@ -209,6 +209,34 @@ def lens_from_frustum(frustum, radius):
             (float(radius) * unit(tl - bl)).astype(np.float32))
 
 
+class ShutterParams(C.Structure):
+    """PolarisShutterParams (include/polaris_hip.h): the camera (and, while the lens is on, the lens) at shutter close.  enabled = 0 is
+    the shutter OFF (the default)."""
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("eye1", C.c_float * 3), ("frustum1", C.c_float * 16),
+                ("focus_distance1", C.c_float), ("axis1", C.c_float * 3), ("u1", C.c_float * 3), ("v1", C.c_float * 3)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(ShutterParams) == 124
+
+
+def shutter_params(eye1=None, frustum1=None, focus_distance1=0.0, axis1=(0.0, 0.0, 0.0), u1=(0.0, 0.0, 0.0), v1=(0.0, 0.0, 0.0)) -> ShutterParams:
+    """eye1 = None: the shutter off (all else zero); else enabled = 1 with this close camera and close lens."""
+    p = ShutterParams()
+    if eye1 is None:
+        return p
+    p.enabled = 1
+    p.eye1 = (C.c_float * 3)(*[float(x) for x in np.asarray(eye1).reshape(3)])
+    p.frustum1 = (C.c_float * 16)(*[float(x) for x in np.asarray(frustum1).reshape(16)])
+    p.focus_distance1 = float(focus_distance1)
+    for name, vec in (("axis1", axis1), ("u1", u1), ("v1", v1)):
+        setattr(p, name, (C.c_float * 3)(*[float(x) for x in vec]))
+    return p
+
+
 class VarianceParams(C.Structure):
     """PolarisVarianceParams (include/polaris_hip.h): variance-guided denoising from per-pixel luminance moments."""
     _fields_ = [("struct_size", C.c_uint32), ("sigma_variance", C.c_float), ("min_samples", C.c_uint32)]
@@ -443,7 +471,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
-    "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens",
+    "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens", "polaris_hip_set_shutter",
 ]
 
 _lib = None
@@ -544,6 +572,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_selftest_builtins.argtypes = [vp, u32, C.c_uint64, C.c_uint64, vp, vp]
     lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
     lib.polaris_hip_set_lens.argtypes = [vp, C.POINTER(LensParams)]
+    lib.polaris_hip_set_shutter.argtypes = [vp, C.POINTER(ShutterParams)]
     lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
     lib.polaris_hip_set_variance.argtypes = [vp, C.POINTER(VarianceParams)]
     lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),

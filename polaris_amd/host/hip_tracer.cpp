@@ -6,6 +6,8 @@
 // The C ABI's polaris_hip_set_lens, referenced weakly: this file is also linked against stand-ins of the C ABI that know no lens
 // (tests/tools/mock_polaris_hip.cpp); there a CameraData with a lens is refused and one without asks nothing.
 extern "C" int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) __attribute__((weak));
+// polaris_hip_set_shutter likewise: without it only a CameraData that has a close state is refused.
+extern "C" int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p) __attribute__((weak));
 
 namespace polaris {
 namespace tracer {
@@ -41,12 +43,12 @@ Error HipTracer::check(int rc) {
 
 // The lens vectors of a CameraData (polaris_amd/ctypes_api.py lens_from_frustum, the same derivation): axis = normalize(TL + TR + BL +
 // BR), u = radius normalize(TR - TL), v = radius normalize(TL - BL), in double, rounded to float once.  lens_radius = 0: all zero (off).
-static PolarisLensParams lensFromFrustum(const CameraData &c) {
+static PolarisLensParams lensFromFrustum(const float *frustum, float lens_radius, float focus_distance) {
 	PolarisLensParams p{};
 	p.struct_size = sizeof p;
-	if (c.lens_radius == 0.0f) return p;
-	p.focus_distance = c.focus_distance;
-	const float *tl = c.frustum, *tr = c.frustum + 4, *bl = c.frustum + 8, *br = c.frustum + 12;
+	if (lens_radius == 0.0f) return p;
+	p.focus_distance = focus_distance;
+	const float *tl = frustum, *tr = frustum + 4, *bl = frustum + 8, *br = frustum + 12;
 	double a[3], u[3], v[3];
 	for (int k = 0; k < 3; k++) {
 		a[k] = (((double)tl[k] + (double)tr[k]) + (double)bl[k]) + (double)br[k];
@@ -55,7 +57,22 @@ static PolarisLensParams lensFromFrustum(const CameraData &c) {
 	}
 	auto unit = [](double x[3]) { const double n = std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]); for (int k = 0; k < 3; k++) x[k] = x[k] / n; };
 	unit(a); unit(u); unit(v);
-	for (int k = 0; k < 3; k++) { p.axis[k] = (float)a[k]; p.u[k] = (float)((double)c.lens_radius * u[k]); p.v[k] = (float)((double)c.lens_radius * v[k]); }
+	for (int k = 0; k < 3; k++) { p.axis[k] = (float)a[k]; p.u[k] = (float)((double)lens_radius * u[k]); p.v[k] = (float)((double)lens_radius * v[k]); }
+	return p;
+}
+
+// The shutter of a CameraData: off without a close state; else the close camera, and under a lens the close lens -- the vectors of
+// frustum1 with the same radius, focused at focus_distance1 (polaris_amd/tracer.py set_shutter, the same derivation).
+static PolarisShutterParams shutterOf(const CameraData &c) {
+	PolarisShutterParams p{};
+	p.struct_size = sizeof p;
+	if (!c.has_close) return p;
+	p.enabled = 1;
+	memcpy(p.eye1, c.eye1, sizeof p.eye1);
+	memcpy(p.frustum1, c.frustum1, sizeof p.frustum1);
+	const PolarisLensParams l = lensFromFrustum(c.frustum1, c.lens_radius, c.focus_distance1 > 0.0f ? c.focus_distance1 : c.focus_distance);
+	p.focus_distance1 = l.focus_distance;
+	memcpy(p.axis1, l.axis, sizeof p.axis1); memcpy(p.u1, l.u, sizeof p.u1); memcpy(p.v1, l.v, sizeof p.v1);
 	return p;
 }
 
@@ -94,9 +111,13 @@ Error HipTracer::commitChanges(Duration *took) { // tracer/opencl/tracer.go:161-
 	if (has_cam_ && !err) {
 		err = check(polaris_hip_set_camera(h_, cam_.eye, cam_.frustum));
 		// set_camera leaves the lens vectors alone: they follow the new frustum here (identical bytes ask nothing of the library)
-		const PolarisLensParams lens = lensFromFrustum(cam_);
+		const PolarisLensParams lens = lensFromFrustum(cam_.frustum, cam_.lens_radius, cam_.focus_distance);
 		if (!err && polaris_hip_set_lens) err = check(polaris_hip_set_lens(h_, &lens));
 		else if (!err && cam_.lens_radius != 0.0f) err = Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: this C ABI has no polaris_hip_set_lens"};
+		// camera, lens, then shutter: set_camera has switched it off, so a CameraData without a close state asks nothing more
+		const PolarisShutterParams shutter = shutterOf(cam_);
+		if (!err && polaris_hip_set_shutter) err = check(polaris_hip_set_shutter(h_, &shutter));
+		else if (!err && cam_.has_close) err = Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: this C ABI has no polaris_hip_set_shutter"};
 		has_cam_ = false;
 	}
 	stats_.UpdateTime = std::chrono::duration_cast<Duration>(clock_::now() - start);

@@ -204,7 +204,7 @@ int polaris_host_renderer_set_camera(void *h, const float eye[3], const float fr
 	tracer::CameraData cam;
 	memcpy(cam.eye, eye, sizeof cam.eye);
 	memcpy(cam.frustum, frustum, sizeof cam.frustum);
-	cam.lens_radius = box->cam.lens_radius; cam.focus_distance = box->cam.focus_distance; // (the lens stays on the camera as it moves)
+	cam.lens_radius = box->cam.lens_radius; cam.focus_distance = box->cam.focus_distance; // (the lens stays on the camera as it moves; the close state went with the old camera)
 	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
 	box->cam = cam;
 	return 0;
@@ -215,6 +215,22 @@ int polaris_host_renderer_set_lens(void *h, float lens_radius, float focus_dista
 	auto *box = static_cast<RendererBox *>(h);
 	tracer::CameraData cam = box->cam;
 	cam.lens_radius = lens_radius; cam.focus_distance = focus_distance;
+	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
+	box->cam = cam;
+	return 0;
+}
+// The camera shutter (CameraData.has_close / eye1 / frustum1 / focus_distance1; polaris_hip_set_shutter): the CameraData of
+// every tracer again, now with this close state, which belongs to the camera as it is: the next polaris_host_renderer_set_camera drops
+// it, polaris_host_renderer_set_lens keeps it.  eye1 = null turns it off.  focus_distance1 <= 0: the open lens' focus distance.
+int polaris_host_renderer_set_shutter(void *h, const float eye1[3], const float frustum1[16], float focus_distance1) {
+	auto *box = static_cast<RendererBox *>(h);
+	tracer::CameraData cam = box->cam;
+	cam.has_close = eye1 != nullptr && frustum1 != nullptr;
+	if (cam.has_close) {
+		memcpy(cam.eye1, eye1, sizeof cam.eye1);
+		memcpy(cam.frustum1, frustum1, sizeof cam.frustum1);
+		cam.focus_distance1 = focus_distance1 > 0.0f ? focus_distance1 : 0.0f;
+	}
 	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
 	box->cam = cam;
 	return 0;

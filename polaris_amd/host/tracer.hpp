@@ -40,7 +40,12 @@ enum class ChangeType : uint8_t { FrameDimensions = 0, SceneData = 1, CameraData
 struct FrameDims { uint32_t w, h; };                 // payload of FrameDimensions ([2]uint32)
 // What tracer.go:177-179 uses of scene.Camera, and the thin lens (no reference counterpart; both 0 = off, the pinhole): a round lens of
 // lens_radius focused at focus_distance along the view axis, which the tracer sets after the camera (hip_tracer.cpp, lensFromFrustum).
-struct CameraData { float eye[3]; float frustum[16]; float lens_radius = 0, focus_distance = 0; };
+// has_close: the camera at shutter close (polaris_hip_set_shutter, set after the lens): eye1, frustum1, and under a lens its focus distance
+// there (focus_distance1, 0: the open one; the close lens' vectors follow frustum1 with the same radius).  Without it the shutter is off.
+struct CameraData {
+	float eye[3]; float frustum[16]; float lens_radius = 0, focus_distance = 0;
+	bool has_close = false; float eye1[3] = {0, 0, 0}; float frustum1[16] = {}; float focus_distance1 = 0;
+};
 
 class Tracer { // tracer/tracer.go:80-111
 public:

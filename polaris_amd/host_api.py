@@ -43,6 +43,7 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_temporal.argtypes = [vp, C.POINTER(T.TemporalParams)]
         lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
         lib.polaris_host_renderer_set_lens.argtypes = [vp, C.c_float, C.c_float]
+        lib.polaris_host_renderer_set_shutter.argtypes = [vp, vp, vp, C.c_float]
         lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
         u32 = C.c_uint32
         lib.polaris_host_variance.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams), C.POINTER(T.VarianceParams), vp]
@@ -222,6 +223,20 @@ class Renderer:
         after the camera, from the frustum); later set_camera calls keep it.  radius = 0 turns it off."""
         if self._lib.polaris_host_renderer_set_lens(self._h, float(radius), float(focus_distance)):
             raise RuntimeError(f"set_lens failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_shutter(self, eye_close, frustum_close=None, focus_close: float | None = None) -> None:
+        """The camera shutter on every tracer (CameraData.has_close: each tracer's UpdateState(CameraData) sets camera, lens, then
+        shutter): camera rays spread in time between the camera as it is and this close eye and frustum; under set_lens the close lens
+        follows frustum_close and is focused at focus_close (default: the open focus).  The next set_camera drops it; set_lens keeps it.
+        set_shutter(None) turns it off."""
+        if eye_close is None:
+            rc = self._lib.polaris_host_renderer_set_shutter(self._h, None, None, 0.0)
+        else:
+            e = np.ascontiguousarray(eye_close, dtype=np.float32).reshape(3)
+            f = np.ascontiguousarray(frustum_close, dtype=np.float32).reshape(16)
+            rc = self._lib.polaris_host_renderer_set_shutter(self._h, e.ctypes.data, f.ctypes.data, 0.0 if focus_close is None else float(focus_close))
+        if rc:
+            raise RuntimeError(f"set_shutter failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
     def read_aov(self, which: int) -> np.ndarray:
         """The primary's (H, W, 4) denoiser plane (polaris_hip_read_aov)."""

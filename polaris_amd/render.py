@@ -29,7 +29,11 @@ table in place, no upload_scene -- then render(accumulated=0).
 
 --aperture R --focus D renders through a thin lens of radius R focused at distance D along the view axis (polaris_hip_set_lens,
 DESIGN.md 10h; it stays on the camera through --frames moves).  --focus-pixel x,y takes D from the GUIDE plane instead: the first hit
-under that pixel's centre, t * dot(centre direction, axis); a pixel that sees nothing is an error."""
+under that pixel's centre, t * dot(centre direction, axis); a pixel that sees nothing is an error.
+
+--frames N --shutter F (0 <= F <= 1, default 0 = an instantaneous exposure) leaves the shutter open for the fraction F of the way to
+the next frame (polaris_hip_set_shutter): frame k's camera rays spread in time between its camera and the camera one
+more move of F * OFFSET on -- camera motion blur.  A lens stays on both ends, with the same radius and focus distance."""
 import argparse
 import os
 import sys
@@ -95,13 +99,16 @@ def frame_paths(out: str, n: int) -> list:
     return [f"{stem}_{k:03d}{ext or '.png'}" for k in range(n)]
 
 
-def move_frames(r, sc, n: int, move: str, aspect: float):
+def move_frames(r, sc, n: int, move: str, aspect: float, shutter: float = 0.0):
     """Frame k: the scene's camera after k + 1 moves (one camera object, as the interactive renderer's), then render(accumulated=0).
+    shutter F > 0: the frame's shutter closes at the camera after one more move of F x the offset (set after the camera it belongs to).
     Yields (rows, ms) after each frame."""
     step = parse_move(move)
     for k in range(n):
         eye, fr = host_api.camera_move(sc.camera, [step] * (k + 1), aspect=aspect)
         r.set_camera(eye, fr)
+        if shutter:
+            r.set_shutter(*host_api.camera_move(sc.camera, [step] * (k + 1) + [(step[0], shutter * step[1])], aspect=aspect))
         yield r.render(0)
 
 
@@ -151,7 +158,10 @@ def main(argv=None):
     ap.add_argument("--aperture", type=float, default=0.0, help="thin-lens radius in scene units (0 = pinhole)")
     ap.add_argument("--focus", type=float, default=0.0, help="with --aperture: distance of the plane of focus along the view axis")
     ap.add_argument("--focus-pixel", default="", help="with --aperture, x,y: focus on what this pixel's centre sees instead of --focus")
+    ap.add_argument("--shutter", type=float, default=0.0, help="with --frames (camera moves): the shutter stays open this fraction 0..1 of the way to the next frame (0 = off)")
     a = ap.parse_args(argv)
+    if not 0.0 <= a.shutter <= 1.0 or (a.shutter and (not a.frames or a.recolour)):
+        ap.error("--shutter F needs 0 <= F <= 1, --frames and no --recolour")
     if a.aperture < 0 or (a.aperture and not a.focus_pixel and not a.focus > 0):
         ap.error("--aperture R needs --focus D > 0 or --focus-pixel x,y")
 
@@ -182,7 +192,7 @@ def main(argv=None):
                 focus = focus_of_pixel(r.read_aov(T.AOV_GUIDE), sc.frustum, int(x), int(y))
             r.set_lens(a.aperture, focus)
         if a.frames:
-            frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height)
+            frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height, a.shutter)
             for path, (rows, ms) in zip(frame_paths(a.out, a.frames), frames):
                 r.save(path)
         else:

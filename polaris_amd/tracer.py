@@ -71,6 +71,7 @@ class HipTracer:
         self._keepalive = None
         self._camera = None   # the CameraData last committed (set_lens derives its vectors from it)
         self._lens = None     # (radius, focus_distance) of set_lens: re-applied after every camera update
+        self._shutter = None  # (eye_close, frustum_close, focus_close) of set_shutter: forgotten at every camera update, re-sent after a set_lens
 
     # ---- tracer.Tracer ---------------------------------------------------------------------
     def Id(self) -> str:
@@ -170,6 +171,8 @@ class HipTracer:
             self.set_lens_vectors(0.0, (0, 0, 0), (0, 0, 0), (0, 0, 0))
         else:
             self._apply_lens()
+        if self._shutter is not None:   # (a changed lens switched the shutter off: it comes back with the close lens of the new one)
+            self._apply_shutter()
 
     def set_lens_vectors(self, focus_distance: float, axis, u, v) -> None:
         """The raw call: a lens point is eye + lx u + ly v, (lx, ly) uniform in the unit disk; u = v = 0 turns the lens off."""
@@ -181,6 +184,36 @@ class HipTracer:
             raise TracerError(2, "set_lens: no camera given through UpdateState yet")
         axis, u, v = T.lens_from_frustum(self._camera.frustum, self._lens[0])
         self.set_lens_vectors(self._lens[1], axis, u, v)
+
+    def set_shutter(self, eye_close, frustum_close=None, focus_close: float | None = None) -> None:
+        """Camera shutter (polaris_hip_set_shutter): every camera ray gets its own time in [0, 1) between the camera last given through
+        UpdateState (shutter open) and this eye and frustum (shutter close) -- camera motion blur.  With set_lens(radius, focus)
+        active the close lens has the vectors of T.lens_from_frustum(frustum_close, radius) and is focused at focus_close (default: the
+        open focus) -- a focus pull.  set_shutter(None) turns it off (the default).  The close camera belongs to the open one: a camera
+        update through UpdateState forgets the shutter; a set_lens re-sends it with the new close lens.  The caller restarts accumulation.
+        (A lens given through set_lens_vectors is not known here: its close lens goes through set_shutter_params.)"""
+        self._commit()
+        if eye_close is None:
+            self._shutter = None
+            self.set_shutter_params(T.shutter_params())
+            return
+        if frustum_close is None:
+            raise TracerError(2, "set_shutter: a close eye needs a close frustum")
+        self._shutter = (np.array(eye_close, np.float32).reshape(3), np.array(frustum_close, np.float32).reshape(16),
+                         None if focus_close is None else float(focus_close))
+        self._apply_shutter()
+
+    def set_shutter_params(self, p: T.ShutterParams) -> None:
+        """The raw call (T.shutter_params builds the struct)."""
+        self._check(self._lib.polaris_hip_set_shutter(self._h, C.byref(p)), self._h)
+
+    def _apply_shutter(self) -> None:
+        eye1, frustum1, focus1 = self._shutter
+        if self._lens is None:
+            self.set_shutter_params(T.shutter_params(eye1, frustum1))
+        else:
+            axis1, u1, v1 = T.lens_from_frustum(frustum1, self._lens[0])
+            self.set_shutter_params(T.shutter_params(eye1, frustum1, self._lens[1] if focus1 is None else focus1, axis1, u1, v1))
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """Variance-guided denoising at every SyncFramebuffer (polaris_hip_set_variance): turns the option "moments" on first, then
@@ -510,6 +543,7 @@ class HipTracer:
                 self._check(self._lib.polaris_hip_set_camera(self._h, eye.ctypes.data_as(C.POINTER(C.c_float)),
                                                              fr.ctypes.data_as(C.POINTER(C.c_float))), self._h)
                 self._camera = data
+                self._shutter = None         # (set_camera switched the shutter off: its close camera belonged to the camera that went)
                 if self._lens is not None:   # (set_camera leaves the lens vectors alone: they follow the new frustum here)
                     self._apply_lens()
             else:
