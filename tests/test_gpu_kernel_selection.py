@@ -7,12 +7,18 @@ traces the CPU oracle's frame (exact mode: bit for bit), so a variant that is se
 
 Frames of 64 x 48, 2 samples, 4 bounces, Russian roulette from bounce 2: the shade steps are first / sort / sort / wave by default.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from batched_oracle import per_sample_reference
 from conftest import bits, make_hip_tracer
-from test_gpu_parity import _nested_shells_scene, counters
+from test_gpu_parity import counters
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from stack_scenes import _nested_shells_scene  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

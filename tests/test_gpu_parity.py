@@ -8,11 +8,17 @@ Bars (stated per test):
   (tests/batched_oracle.py) -- wherever a second oracle pass is cheap; against the oracle's reference order it differs only by
   the association of the per-sample sums: per-pixel RMSE <= 1e-6 (north_star bar: 1e-4), the bar the full-size frames keep.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from batched_oracle import per_sample_reference
 from conftest import bits, golden_files, load_golden, make_hip_tracer
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from stack_scenes import _nested_shells_scene  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -732,48 +738,6 @@ def test_big_scene_kernel_variants_agree_with_the_oracle(built, oracle, name):
             tr.Close()
         assert counters(st, B) == counters(wst, B), opts
         assert np.array_equal(bits(got[..., :3]), bits(want[..., :3])), opts
-
-
-def _nested_shells_scene(n=22):
-    """A tree whose rays NEED a deep stack: n camera-facing triangles at z = -0.05 x 1.6^k, each 1.6^k big (every camera ray's line
-    crosses every one of their boxes), under a HAND-MADE BVH in the reference's encoding (optimized_scene.go:14-64): a chain that splits
-    the outermost triangle off per level -- node j = { leaf of triangle n-1-j, node j+1 }.  Both children of every node lie on a camera
-    ray; the traversal takes the nearer one (the rest of the chain) first and pushes the far leaf: one stack entry per level, n - 1 = 21
-    of them, well beyond the 16 the spill variant keeps in LDS.  (Any tree whose boxes bound their contents is a valid input.)  A light
-    behind the camera faces the shells: the innermost one is lit, its shadow rays walk the same chain."""
-    from polaris_amd import ctypes_api as T
-    from polaris_amd import scenes
-
-    tris = []
-    for k in range(n):
-        sz, z = 0.15 * 1.6 ** k, -0.05 * 1.6 ** k
-        tris.append([[-sz, -sz, z], [sz, -sz, z], [0.0, 1.5 * sz, z]])
-    tris.append([[-2.0, -2.0, 3.0], [0.0, 3.0, 3.0], [2.0, -2.0, 3.0]])      # the light: behind the camera, facing the shells (-z)
-    n += 1
-    verts = np.asarray(tris, np.float32)
-    mt = scenes.MaterialTable()
-    d, e = mt.diffuse((0.6, 0.7, 0.8)), mt.emissive((3, 3, 3))
-    mat = np.full(n, d, np.uint32)
-    mat[-1] = e
-    mesh = scenes.Mesh(verts, scenes._flat_normals(verts), np.zeros((n, 3, 2), np.float32), mat)
-    sc = scenes.compile_scene([mesh], [(0, np.eye(4))], mt, max_leaf=1, name="nested-shells")
-    sc.set_camera(eye=(0.0, 0.0, 1.0), look=(0.0, 0.0, -1.0), fov=0.4, aspect=4 / 3)
-    v = sc.vertices[:, :3].reshape(n, 3, 3)
-    order = np.argsort(-v[:, 0, 2], kind="stable")   # compiled triangle indices, nearest (largest z) first
-    nodes = np.zeros(2 * n, T.BVH_NODE)
-    lo, hi = v.min(axis=1), v.max(axis=1)
-    nodes[0] = (lo.min(axis=0), 0, hi.max(axis=0), 0)                         # the top-level tree: one leaf = instance 0
-    for k in range(n):                                                        # leaf of the k-th nearest triangle: node n + k
-        t = int(order[k])
-        nodes[n + k] = (lo[t], -t, hi[t], 1)
-    for j in range(n - 1):                                                    # inner node j: node 1 + j over the j-th .. nearest triangles
-        members = order[: n - j]
-        far_leaf = n + (n - 1 - j)
-        rest = 1 + j + 1 if j + 1 < n - 1 else n + 0                          # the last inner node holds the two nearest leaves
-        nodes[1 + j] = (lo[members].min(axis=0), far_leaf, hi[members].max(axis=0), rest)
-    sc.bvh_nodes = nodes
-    sc.mesh_instances["bvh_root"] = 1
-    return sc
 
 
 def test_rays_that_hold_twenty_stack_entries(built, oracle):

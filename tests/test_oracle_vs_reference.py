@@ -213,6 +213,37 @@ def test_tie_scenes_bit_exact(oracle, ref_pm, family):
     assert compared == len(TS.FAMILIES[family]) >= 3
 
 
+@pytest.mark.parametrize("family", ["single", "instanced"])
+def test_stack_scenes_bit_exact(oracle, ref_pm, family):
+    """Scenes whose layout needs exactly 15, 16, 17, 24, 25, 31 and 32 traversal-stack entries, plain and mirrored, and rays that hold
+    them all (tests/tools/stack_scenes.py; the reference's BVH_MAX_STACK_SIZE is the same 32, so the last is its limit too): closest
+    hits -- flags, (instance, triangle), bits of (w, u, v, t) -- and any-hit flags of the restatement equal the compiled reference's,
+    also with maxDist at, one ulp below and one ulp above each hit.  The same inputs run every HIP traversal kernel against the oracle
+    (tests/test_gpu_stack_depth.py)."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+    import stack_scenes as SS
+    import tie_scenes as TS
+
+    tags = [t for t in SS.TRACED if SS.CASES[t]["family"] == family]       # (`retry` is a single-instance scene)
+    for tag in tags:
+        sc, rays = SS.case(tag)
+        hit, wuvt, it = oracle.intersect(sc, rays, any_hit=False)
+        occ, _, _ = oracle.intersect(sc, rays, any_hit=True)
+        assert 0 < (hit != 0).sum() < len(rays) and 0 < (occ != 0).sum() < len(rays), tag
+        r_hit, r_wuvt, r_it = ref_pm.intersect(sc, rays, any_hit=False)
+        assert same_bits(r_hit, hit) and same_bits(r_it, it) and same_bits(r_wuvt, wuvt), tag
+        assert same_bits(ref_pm.intersect(sc, rays, any_hit=True)[0], occ), tag
+        for key, r in TS.shadow_variants(rays, hit, wuvt[:, 3]).items():
+            assert same_bits(ref_pm.intersect(sc, r, any_hit=True)[0], oracle.intersect(sc, r, any_hit=True)[0]), (tag, key)
+            s_hit, s_wuvt, s_it = oracle.intersect(sc, r, any_hit=False)
+            q_hit, q_wuvt, q_it = ref_pm.intersect(sc, r, any_hit=False)
+            assert same_bits(q_hit, s_hit) and same_bits(q_it, s_it) and same_bits(q_wuvt, s_wuvt), (tag, key)
+    assert len(tags) >= 14
+
+
 @pytest.mark.parametrize("name", SCENES)
 def test_libm_build_agrees_pixel_by_pixel(oracle, ref_libm, name):
     """The same reference kernels with glibc's libm behind sin / cos / atan / atan2 / acos / pow / sqrt instead of
