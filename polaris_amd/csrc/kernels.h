@@ -163,41 +163,10 @@ __device__ __forceinline__ f3 camera_direction_from(const CameraArgs &cam, f2 s0
 	return mk3(dx * inv, dy * inv, dz * inv);
 }
 
-// The unit direction of the camera ray of pixel (gx, gy + blockY) under camera seed `seed`, camera.cl:38-56.  rng is left as the
-// camera stream after its first draw (the sub-pixel offset): the reference draws no more, k_generate_lens draws once more.
-__device__ __forceinline__ f3 camera_direction(const CameraArgs &cam, uint32_t seed, uint32_t gx, uint32_t gy, uint32_t blockY, Rng &rng) {
-	rng = {gx + seed, gy + seed}; // camera.cl:38
-	const f2 s0 = rng_next(rng);
-	return camera_direction_from(cam, s0, gx, gy, blockY);
-}
-
-__global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, const uint32_t *seeds, uint32_t seed_stride,
-                                                  uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
-                                                  int zero_lsum, int write_origin) {
-	const uint32_t wgs_per_sample = Npad / WG;
-	const uint32_t s = blockIdx.x / wgs_per_sample;
-	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
-	const uint32_t idx = idx0 + threadIdx.x;
-	const size_t slot = (size_t)blockIdx.x * WG + threadIdx.x;
-	if (threadIdx.x == 0) {
-		st.cnt_ray[blockIdx.x] = idx0 < N ? min((uint32_t)WG, N - idx0) : 0u;
-		st.pfx[blockIdx.x] = idx0; // rays are dense at bounce 0: reference position == index
-	}
-	if (idx >= N) return;
-	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
-	Rng rng;
-	const f3 d = camera_direction(cam, seed, idx % W, idx / W, blockY, rng);
-	if (write_origin) store_ray_o(st, slot, make_float4(cam.eye.x, cam.eye.y, cam.eye.z, kFltMax)); // (the wave-packet kernel takes the eye from its arguments)
-	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
-	// (the throughput of a camera ray is 1: the first shade step does not read it, so it is not written)
-	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
 // The thin-lens generator (polaris_hip_set_lens; no reference counterpart): k_generate's ray moved onto a lens point.
 // The camera stream's SECOND draw goes through the concentric map (Shirley and Chiu 1997) to (lx, ly) in the unit disk; the ray
 // starts at eye + lx u + ly v and passes through the pinhole ray's point on the plane of focus, eye + d ft.  Every operation below
-// is rounded once, in the order written (tests/lens_oracle.py restates it).  Same launch shape and bookkeeping as k_generate; the
-// origins are always written: every kernel that traces these rays reads the origin stream.
+// is rounded once, in the order written (tests/lens_oracle.py restates it).
 struct LensArgs { float focus_distance; float3 axis, u, v; };
 
 // k_generate_lens' lines after its two draws: the ray (o = the eye, d = the pinhole's unit direction) moved onto the lens point of the
@@ -220,50 +189,32 @@ __device__ __forceinline__ void lens_ray(const LensArgs &lens, f2 s1, f3 &o, f3 
 	}
 }
 
-__global__ __launch_bounds__(WG) void k_generate_lens(Streams st, CameraArgs cam, LensArgs lens, const uint32_t *seeds, uint32_t seed_stride,
-                                                       uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
-                                                       int zero_lsum) {
-	const uint32_t wgs_per_sample = Npad / WG;
-	const uint32_t s = blockIdx.x / wgs_per_sample;
-	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
-	const uint32_t idx = idx0 + threadIdx.x;
-	const size_t slot = (size_t)blockIdx.x * WG + threadIdx.x;
-	if (threadIdx.x == 0) {
-		st.cnt_ray[blockIdx.x] = idx0 < N ? min((uint32_t)WG, N - idx0) : 0u;
-		st.pfx[blockIdx.x] = idx0;
-	}
-	if (idx >= N) return;
-	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
-	Rng rng;
-	f3 d = camera_direction(cam, seed, idx % W, idx / W, blockY, rng);
-	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z);
-	lens_ray(lens, rng_next(rng), o, d);
-	store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
-	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
-	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
 // The shutter generator (polaris_hip_set_shutter; no reference counterpart): every camera ray gets its own time t in
 // [0, 1) from the camera stream's NEXT draw (the second with the lens off, the third with it on; .y unused) and is generated by the
 // camera -- eye, corners, and with LENS the lens -- blended per component with pm_mix(open, close, t).  pm_mix(a, a, t) = a for a
 // finite a other than -0, so a close state equal to the open one gives k_generate's (LENS: k_generate_lens') rays bit for bit.
 // axis_t is not renormalised (it shortens to cos(theta / 2) between two axes theta apart: the plane of focus moves by at most
-// 1 / cos(theta / 2)).  tests/shutter_oracle.py restates it.  k_generate_lens' launch shape and bookkeeping; origins always written.
+// 1 / cos(theta / 2)).  tests/shutter_oracle.py restates it.
 __device__ __forceinline__ float3 mix3(float3 a, float3 b, float t) { return make_float3(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t)); }
 __device__ __forceinline__ float4 mix4(float4 a, float4 b, float t) { return make_float4(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t), pm_mix(a.w, b.w, t)); }
 
-template <bool LENS>
-__global__ __launch_bounds__(WG) void k_generate_shutter(Streams st, CameraArgs cam, CameraArgs cam1, LensArgs lens, LensArgs lens1, const uint32_t *seeds,
-                                                          uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
-                                                          int zero_lsum) {
+// THE body of the four generators: one lane = one camera ray of sample s = workgroup / (Npad / WG), pixel idx of the block.  The
+// camera stream Rng{gx + seed, gy + seed} (camera.cl:38) is drawn in this order: the sub-pixel offset (the reference draws no more),
+// with LENS the lens point, with SHUTTER the ray's time.  cam1 / lens1 (the close state) are read with SHUTTER only, lens / lens1
+// with LENS only.  A lens or a shutter always writes the origins -- every kernel that traces their rays reads the origin stream --;
+// write_origin is the pinhole's alone (the wave-packet kernel and k_trace's camera launch take the eye from elsewhere).
+template <bool LENS, bool SHUTTER>
+__device__ __forceinline__ void generate_rays(const Streams &st, const CameraArgs &cam, const CameraArgs &cam1, const LensArgs &lens, const LensArgs &lens1,
+                                              const uint32_t *seeds, uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W,
+                                              uint32_t blockY, int zero_lsum, int write_origin) {
 	const uint32_t wgs_per_sample = Npad / WG;
 	const uint32_t s = blockIdx.x / wgs_per_sample;
 	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
 	const uint32_t idx = idx0 + threadIdx.x;
 	const size_t slot = (size_t)blockIdx.x * WG + threadIdx.x;
-	if (threadIdx.x == 0) {
+	if (threadIdx.x == 0) { // the per-workgroup bookkeeping the shade kernels and k_scan continue
 		st.cnt_ray[blockIdx.x] = idx0 < N ? min((uint32_t)WG, N - idx0) : 0u;
-		st.pfx[blockIdx.x] = idx0;
+		st.pfx[blockIdx.x] = idx0; // rays are dense at bounce 0: reference position == index
 	}
 	if (idx >= N) return;
 	const uint32_t seed = seeds[(size_t)(first_sample + s) * seed_stride];
@@ -272,20 +223,38 @@ __global__ __launch_bounds__(WG) void k_generate_shutter(Streams st, CameraArgs 
 	const f2 s0 = rng_next(rng);
 	f2 s1 = {0.0f, 0.0f};
 	if (LENS) s1 = rng_next(rng);
-	const float t = rng_next(rng).x;
-	CameraArgs ct;
-	ct.tl = mix4(cam.tl, cam1.tl, t); ct.tr = mix4(cam.tr, cam1.tr, t); ct.bl = mix4(cam.bl, cam1.bl, t); ct.br = mix4(cam.br, cam1.br, t);
-	ct.eye = mix3(cam.eye, cam1.eye, t);
-	ct.texel = cam.texel;
+	CameraArgs ct = cam;
+	LensArgs lt = lens;
+	if (SHUTTER) {
+		const float t = rng_next(rng).x;
+		ct.tl = mix4(cam.tl, cam1.tl, t); ct.tr = mix4(cam.tr, cam1.tr, t); ct.bl = mix4(cam.bl, cam1.bl, t); ct.br = mix4(cam.br, cam1.br, t);
+		ct.eye = mix3(cam.eye, cam1.eye, t); // (the texel stays the open camera's)
+		if (LENS) lt = {pm_mix(lens.focus_distance, lens1.focus_distance, t), mix3(lens.axis, lens1.axis, t), mix3(lens.u, lens1.u, t), mix3(lens.v, lens1.v, t)};
+	}
 	f3 d = camera_direction_from(ct, s0, gx, gy, blockY);
 	f3 o = mk3(ct.eye.x, ct.eye.y, ct.eye.z);
-	if (LENS) {
-		const LensArgs lt = {pm_mix(lens.focus_distance, lens1.focus_distance, t), mix3(lens.axis, lens1.axis, t), mix3(lens.u, lens1.u, t), mix3(lens.v, lens1.v, t)};
-		lens_ray(lt, s1, o, d);
-	}
-	store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
+	if (LENS) lens_ray(lt, s1, o, d);
+	if (LENS || SHUTTER || write_origin) store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
 	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
+	// (the throughput of a camera ray is 1: the first shade step does not read it, so it is not written)
 	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(WG) void k_generate(Streams st, CameraArgs cam, const uint32_t *seeds, uint32_t seed_stride,
+                                                  uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
+                                                  int zero_lsum, int write_origin) {
+	generate_rays<false, false>(st, cam, cam, LensArgs{}, LensArgs{}, seeds, seed_stride, first_sample, N, Npad, W, blockY, zero_lsum, write_origin);
+}
+__global__ __launch_bounds__(WG) void k_generate_lens(Streams st, CameraArgs cam, LensArgs lens, const uint32_t *seeds, uint32_t seed_stride,
+                                                       uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
+                                                       int zero_lsum) {
+	generate_rays<true, false>(st, cam, cam, lens, lens, seeds, seed_stride, first_sample, N, Npad, W, blockY, zero_lsum, 1);
+}
+template <bool LENS>
+__global__ __launch_bounds__(WG) void k_generate_shutter(Streams st, CameraArgs cam, CameraArgs cam1, LensArgs lens, LensArgs lens1, const uint32_t *seeds,
+                                                          uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
+                                                          int zero_lsum) {
+	generate_rays<LENS, true>(st, cam, cam1, lens, lens1, seeds, seed_stride, first_sample, N, Npad, W, blockY, zero_lsum, 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1109,6 +1078,21 @@ __device__ __forceinline__ void terminal_add(const ShadeArgs &A, uint32_t cell, 
 	}
 }
 
+// surfaceInit, util/surface.cl:12-33: position, unit normal and uv of triangle `tri` at the hit's barycentrics (intersect.cl:283-286).
+template <class Scene>
+__device__ __forceinline__ Surf surface_at(const Scene &S, int tri, float bu, float bv) {
+	const float bw = 1.0f - (bu + bv);
+	const uint32_t off = (uint32_t)tri * 3;
+	Surf sf;
+	float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
+	sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
+	a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
+	sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
+	float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
+	sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
+	return sf;
+}
+
 // One ray through shadeHits / shade*RayMisses.  `gid_ref` is the ray's position in the reference's
 // compacted buffer (PRNG state, pt_integrator.cl:81), `sample` the sample the workgroup belongs to.
 // The shadow ray (origin|maxDist, dir|accumulator cell, NEE radiance) is handed to `occ_sink` the moment it exists -- the
@@ -1141,18 +1125,7 @@ __device__ __forceinline__ void shade_ray(const SceneT<LDS> &S, const ShadeArgs 
 	Rng rng = {seed, gid_ref}; // pt_integrator.cl:81-84
 	const f2 sample0 = rng_next(rng), sample1 = rng_next(rng), sample2 = rng_next(rng);
 	const f3 in_dir = -xyz(d4);
-	// surfaceInit, util/surface.cl:12-33
-	const float bu = h4.x, bv = h4.y, bw = 1.0f - (bu + bv); // intersect.cl:283-286
-	const uint32_t off = (uint32_t)tri * 3;
-	Surf sf;
-	{
-		float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
-		sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
-		a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
-		sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
-		float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
-		sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
-	}
+	Surf sf = surface_at(S, tri, h4.x, h4.y);
 	f3 tint = splat(1.0f);
 	MatT<LDS> m = select_material(S.mat_index[tri], sf, flags, tint, rng, S);
 	material_params(sf, m, S);
@@ -1902,50 +1875,44 @@ __global__ __launch_bounds__(WG) void k_builtin_sweep(uint32_t fn, uint64_t firs
 // (p, p), no path flags).  GUIDE = n after bump / normal maps | t (miss: 0, 0, 0, FLT_MAX); ALBEDO = clamp(tint * kcol, 0, 1)
 // for diffuse and (rough) conductor leaves, 1 for the other leaves | the leaf type's bits (miss: 1, 1, 1 | -1).
 // inst (option "object_motion"; null: not written): the INSTANCE plane, the first hit's mesh-instance index (miss: 0xFFFFFFFF).
+// What the two G-buffer kernels share beside surface_at: the guide ray of pixel (gx, gy) (temporal.h: k_reproject re-derives it), the
+// record of a miss and the albedo of a leaf.  (The walk itself is written out in both: shared, k_gbuffer_chain takes 3 more VGPRs.)
+__device__ __forceinline__ f3 gbuffer_centre_ray(const CameraArgs &cam, uint32_t gx, uint32_t gy) {
+	const float tl[4] = {cam.tl.x, cam.tl.y, cam.tl.z, cam.tl.w}, tr[4] = {cam.tr.x, cam.tr.y, cam.tr.z, cam.tr.w};
+	const float bl[4] = {cam.bl.x, cam.bl.y, cam.bl.z, cam.bl.w}, br[4] = {cam.br.x, cam.br.y, cam.br.z, cam.br.w};
+	float dc[3];
+	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc);
+	return mk3(dc[0], dc[1], dc[2]);
+}
+__device__ __forceinline__ void gbuffer_miss(uint32_t idx, float4 *guide, float4 *albedo, uint32_t *inst) {
+	guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
+	albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
+	if (inst) inst[idx] = kTpNoInstance;
+}
+__device__ __forceinline__ f3 gbuffer_albedo(const MatT<false> &m, f3 tint) {
+	if (m.type != POLARIS_BXDF_DIFFUSE && m.type != POLARIS_BXDF_CONDUCTOR && m.type != POLARIS_BXDF_ROUGH_CONDUCTOR) return splat(1.0f);
+	const f3 c = tint * m.kcol;
+	return mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
+}
+
 __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
                                                 uint32_t *inst) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
-	const uint32_t gx = idx % W, gy = idx / W;
-	const float tl[4] = {cam.tl.x, cam.tl.y, cam.tl.z, cam.tl.w}, tr[4] = {cam.tr.x, cam.tr.y, cam.tr.z, cam.tr.w};
-	const float bl[4] = {cam.bl.x, cam.bl.y, cam.bl.z, cam.bl.w}, br[4] = {cam.br.x, cam.br.y, cam.br.z, cam.br.w};
-	float dc[3];
-	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc); // (temporal.h: k_reproject re-derives this ray)
-	const f3 d = mk3(dc[0], dc[1], dc[2]);
 	HitRec h;
-	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), d, kFltMax, stk, h);
-	if (h.tri < 0) {
-		guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
-		albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
-		if (inst) inst[idx] = kTpNoInstance;
-		return;
-	}
+	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), gbuffer_centre_ray(cam, idx % W, idx / W), kFltMax, stk, h);
+	if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst);
 	if (inst) inst[idx] = (uint32_t)h.inst; // (traverse enters the one instance of a root_is_instance scene through its leaf reference too)
 	const int tri = h.tri & (int)((1u << S.tri_bits) - 1u); // (the shading class rides above the index)
-	// surfaceInit, util/surface.cl:12-33 (as shade_ray)
-	const float bu = h.u, bv = h.v, bw = 1.0f - (bu + bv);
-	const uint32_t off = (uint32_t)tri * 3;
-	Surf sf;
-	{
-		float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
-		sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
-		a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
-		sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
-		float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
-		sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
-	}
+	Surf sf = surface_at(S, tri, h.u, h.v);
 	uint32_t flags = 0;
 	f3 tint = splat(1.0f);
 	Rng rng = {idx, idx}; // debug.cl:89-91
 	MatT<false> m = select_material(S.mat_index[tri], sf, flags, tint, rng, S);
 	material_params(sf, m, S);
+	const f3 a = gbuffer_albedo(m, tint);
 	guide[idx] = make_float4(sf.n.x, sf.n.y, sf.n.z, h.t);
-	f3 a = splat(1.0f);
-	if (m.type == POLARIS_BXDF_DIFFUSE || m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_ROUGH_CONDUCTOR) {
-		const f3 c = tint * m.kcol;
-		a = mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
-	}
 	albedo[idx] = make_float4(a.x, a.y, a.z, ibits((int)m.type));
 }
 
@@ -1964,47 +1931,22 @@ __global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, Came
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
-	const uint32_t gx = idx % W, gy = idx / W;
-	const float tl[4] = {cam.tl.x, cam.tl.y, cam.tl.z, cam.tl.w}, tr[4] = {cam.tr.x, cam.tr.y, cam.tr.z, cam.tr.w};
-	const float bl[4] = {cam.bl.x, cam.bl.y, cam.bl.z, cam.bl.w}, br[4] = {cam.br.x, cam.br.y, cam.br.z, cam.br.w};
-	float dc[3];
-	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc);
-	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z), d = mk3(dc[0], dc[1], dc[2]);
+	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z), d = gbuffer_centre_ray(cam, idx % W, idx / W);
 	f3 A = splat(1.0f);
 	float T = 0.0f;
 	for (int k = 0;; k++) {
 		HitRec h;
 		traverse<false>(B, o, d, kFltMax, stk, h);
-		if (h.tri < 0) {
-			guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
-			albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
-			if (inst) inst[idx] = kTpNoInstance;
-			return;
-		}
+		if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst);
 		T = k == 0 ? h.t : T + h.t;
 		const int tri = h.tri & (int)((1u << S.tri_bits) - 1u);
-		// surfaceInit, as k_gbuffer
-		const float bu = h.u, bv = h.v, bw = 1.0f - (bu + bv);
-		const uint32_t off = (uint32_t)tri * 3;
-		Surf sf;
-		{
-			float4 a = S.vertices[off], b = S.vertices[off + 1], c = S.vertices[off + 2];
-			sf.p = mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z);
-			a = S.normals[off]; b = S.normals[off + 1]; c = S.normals[off + 2];
-			sf.n = normalize(mk3(bw * a.x + bu * b.x + bv * c.x, bw * a.y + bu * b.y + bv * c.y, bw * a.z + bu * b.z + bv * c.z));
-			float2 ua = S.uvs[off], ub = S.uvs[off + 1], uc = S.uvs[off + 2];
-			sf.uv = {bw * ua.x + bu * ub.x + bv * uc.x, bw * ua.y + bu * ub.y + bv * uc.y};
-		}
+		Surf sf = surface_at(S, tri, h.u, h.v);
 		uint32_t flags = 0;
 		f3 tint = splat(1.0f);
 		Rng rng = {idx, idx};
 		MatT<false> m = select_material(S.mat_index[tri], sf, flags, tint, rng, S);
 		material_params(sf, m, S);
-		f3 a = splat(1.0f);
-		if (m.type == POLARIS_BXDF_DIFFUSE || m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_ROUGH_CONDUCTOR) {
-			const f3 c = tint * m.kcol;
-			a = mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
-		}
+		const f3 a = gbuffer_albedo(m, tint);
 		if ((m.type == POLARIS_BXDF_CONDUCTOR || m.type == POLARIS_BXDF_DIELECTRIC) && k < max_links) {
 			f3 out = splat(0.0f);
 			float pdf;

@@ -26,6 +26,7 @@
 
 #include <unistd.h>
 
+#include "camera_state.h"
 #include "device_mem.h"
 #include "frame_sync.h"
 #include "kernel_table.h"
@@ -119,7 +120,7 @@ struct FrameSync {
 	DevArray<uint32_t> gb_inst, tp_hinst; // kInst, kHInst
 	DevArray<float4> mo_table;            // kMoTable
 	std::vector<float> mo_table_host;
-	CameraArgs tp_hcam{};                 // the history's camera
+	CameraFloats tp_hcam{};               // the history's camera
 
 	SyncFeatures features() const { return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0}; }
 	void drop(uint32_t set) {
@@ -127,7 +128,7 @@ struct FrameSync {
 			if (set >> p & 1) pl[p].reset();
 		if (set & kMotionPlanes) { gb_inst.reset(); tp_hinst.reset(); mo_table.reset(); } // (they go together; ensure_gbuffer recomputes the G-buffer when gb_inst is wanted and missing)
 	}
-	void capture(uint32_t swaps, const CameraArgs &cam) { // cam: what the planes that join the history were seen under
+	void capture(uint32_t swaps, const CameraFloats &cam) { // cam: what the planes that join the history were seen under
 		constexpr Plane twin[][2] = {{kTpOut, kTpHist}, {kGuide, kTpHGuide}, {kAlbedo, kTpHAlbedo}, {kVaOut, kVaHist}};
 		for (auto &t : twin)
 			if (swaps >> t[0] & 1) std::swap(pl[t[0]], pl[t[1]]);
@@ -135,16 +136,15 @@ struct FrameSync {
 		if (swaps) tp_hcam = cam;
 	}
 	void resized() { drop(v.resized()); }
-	void camera_moved(const CameraArgs &old) { capture(v.camera_moved(features()), old); }
-	void scene_changed(const InstTable *next, const CameraArgs &cam) { capture(v.scene_changed(features(), next), cam); } // (upload_scene and the in-place updates, before they change the scene)
+	void camera_moved(const CameraFloats &old) { capture(v.camera_moved(features()), old); }
+	void scene_changed(const InstTable *next, const CameraFloats &cam) { capture(v.scene_changed(features(), next), cam); } // (upload_scene and the in-place updates, before they change the scene)
 	void set_temporal(const PolarisTemporalParams &p) {
 		if (p.max_history == 0) { if (tp.max_history) drop(v.temporal_off()); }
 		else if (p.max_history != tp.max_history || pm_f2u(p.normal_threshold) != pm_f2u(tp.normal_threshold) || pm_f2u(p.depth_threshold) != pm_f2u(tp.depth_threshold))
 			v.temporal_params_changed();
 		tp = p;
 	}
-	void lens_changed() { if (tp.max_history) drop(v.temporal_off()); } // the history saw another lens: it goes as with max_history = 0; the (pinhole) G-buffer stays
-	void shutter_changed() { lens_changed(); } // polaris_hip_set_shutter changed the state (or set_camera / set_lens switched it off): lens_changed's rule
+	void lens_changed() { if (tp.max_history) drop(v.temporal_off()); } // the history saw another lens or shutter (camera_state.h, kCamDropHistory): it goes as with max_history = 0; the (pinhole) G-buffer stays
 	void set_variance(const PolarisVarianceParams &p) {
 		if ((p.sigma_variance != 0.0f) != (va.sigma_variance != 0.0f)) drop(v.variance_toggled(p.sigma_variance != 0.0f));
 		va = p;
@@ -323,25 +323,7 @@ struct polaris_hip_tracer {
 	int opt_tiny_one = 1;
 	int opt_lds_tris = -1;        // tiny-scene mode: triangle records kept in LDS; -1 = as many as fit, 0 = none (A/B aid)
 
-	// camera (tracer.go:175-179)
-	bool have_camera = false;
-	CameraArgs cam{};
-	PolarisLensParams lens{sizeof(PolarisLensParams), 0.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}}; // polaris_hip_set_lens; u = v = 0: off
-	bool lens_on() const { for (int i = 0; i < 3; i++) if (lens.u[i] != 0.0f || lens.v[i] != 0.0f) return true; return false; }
-	LensArgs lens_args() const {
-		return {lens.focus_distance, make_float3(lens.axis[0], lens.axis[1], lens.axis[2]), make_float3(lens.u[0], lens.u[1], lens.u[2]), make_float3(lens.v[0], lens.v[1], lens.v[2])};
-	}
-	PolarisShutterParams shutter{sizeof(PolarisShutterParams), 0u, {}, {}, 0.0f, {}, {}, {}}; // polaris_hip_set_shutter: the camera and lens at shutter close; enabled = 0: off
-	bool shutter_on() const { return shutter.enabled != 0; }
-	CameraArgs shutter_cam() const { // (k_generate_shutter reads the texel of the open camera only)
-		const float *f = shutter.frustum1;
-		return {make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]), make_float4(f[8], f[9], f[10], f[11]), make_float4(f[12], f[13], f[14], f[15]),
-		        make_float3(shutter.eye1[0], shutter.eye1[1], shutter.eye1[2]), cam.texel};
-	}
-	LensArgs shutter_lens_args() const {
-		return {shutter.focus_distance1, make_float3(shutter.axis1[0], shutter.axis1[1], shutter.axis1[2]), make_float3(shutter.u1[0], shutter.u1[1], shutter.u1[2]),
-		        make_float3(shutter.v1[0], shutter.v1[1], shutter.v1[2])};
-	}
+	CameraState camera; // camera, lens and shutter as the caller sent them (tracer.go:175-179; camera_state.h holds the setters' rules)
 
 	FrameSync fs; // the synced frame's features, planes and history
 	int opt_instance_update = 0, opt_vertex_update = 0; // the in-place updates: the next upload keeps what they need in ds.upd / ds.vup
@@ -564,6 +546,23 @@ int check_request(polaris_hip_tracer *h, const PolarisBlockRequest *r) {
 	}
 }
 
+// The kernels' arguments of the handle's camera for its W x H frame: the open camera and lens, and the shutter's close ones (what a
+// generator does not read is not looked at).  The only place the texel is computed (resources.go:130-133); the close camera
+// carries the open one's, which is all k_generate_shutter reads.
+struct CameraDev { CameraArgs cam, cam1; LensArgs lens, lens1; };
+CameraDev camera_args(const polaris_hip_tracer *h) {
+	const CameraState &c = h->camera;
+	const float2 texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
+	auto cam = [&](const float *eye, const float *f) {
+		return CameraArgs{make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]), make_float4(f[8], f[9], f[10], f[11]),
+		                  make_float4(f[12], f[13], f[14], f[15]), make_float3(eye[0], eye[1], eye[2]), texel};
+	};
+	auto lens = [](const float *f) { // the ten floats: focus distance, axis, u, v
+		return LensArgs{f[0], make_float3(f[1], f[2], f[3]), make_float3(f[4], f[5], f[6]), make_float3(f[7], f[8], f[9])};
+	};
+	return {cam(c.open.eye, c.open.frustum), cam(c.shutter.eye1, c.shutter.frustum1), lens(&c.lens.focus_distance), lens(&c.shutter.focus_distance1)};
+}
+
 // The planes of the set `need` exist from their first use on, each of the frame's size; those of `clear` are cleared on the main stream,
 // those of `clear_new` if they are allocated here (caller holds mu).
 int ensure_planes(polaris_hip_tracer *h, uint32_t need, uint32_t clear = 0, uint32_t clear_new = 0) {
@@ -586,8 +585,7 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 	if (S.v.gbuffer() && (!want_inst || S.gb_inst)) return POLARIS_OK;
 	const size_t F = (size_t)h->fa.W * h->fa.H;
 	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0))) return rc;
-	CameraArgs cam = h->cam;
-	cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
+	const CameraArgs cam = camera_args(h).cam;
 	if (S.opt_guide_specular == 0)
 		(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
 		             want_inst ? S.gb_inst.get() : nullptr);
@@ -701,8 +699,8 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 	s.tri_bits = h->ds.scene.tri_bits;
 	s.packet_primary = h->packet_primary;
 	s.num_cus = h->num_cus;
-	s.lens = h->lens_on();
-	s.shutter = h->shutter_on();
+	s.lens = h->camera.lens_on();
+	s.shutter = h->camera.shutter_on();
 	return s;
 }
 
@@ -711,13 +709,26 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 hipError_t launch_traversal(polaris_hip_tracer *h, const char *timer, Traversal how, RayKind kind, hipStream_t q, const Streams &st, uint32_t persistent_grid, uint32_t chunks, float4 *acc) {
 	const bool any_hit = kind == RayKind::AnyHit;
 	if (how == Traversal::Packet)
-		return launch(h, timer, q, kPacket[any_hit ? kPacketAnyHit : (kind == RayKind::Camera ? kPacketCamera : kPacketClosest)], chunks, WG, 0, st, h->ds.bvh, acc, h->d_stats, h->cam.eye);
+		return launch(h, timer, q, kPacket[any_hit ? kPacketAnyHit : (kind == RayKind::Camera ? kPacketCamera : kPacketClosest)], chunks, WG, 0, st, h->ds.bvh, acc, h->d_stats, make_float3(h->camera.open.eye[0], h->camera.open.eye[1], h->camera.open.eye[2]));
 	if (how == Traversal::Persistent) return launch_trace(h, timer, any_hit, q, st, persistent_grid, chunks, acc, kind == RayKind::Camera);
 	if (any_hit) return launch(h, timer, q, kOcclusion, chunks, WG, 0, st, h->ds.bvh, acc, h->d_stats);
 	return launch(h, timer, q, kIntersect, chunks, WG, 0, st, h->ds.bvh);
 }
 
-const char *const kShadeTimer[4] = {"shade_first", "shade_sort", "shade_plain", "shade_wave"}; // by ShadeKernel (trace_plan.h): one timer per kernel symbol
+// THE launch of the camera's generator (camera_state.h Generator) over `wgs` workgroups of st: the rays of samples first_sample.. of the
+// seed list with `stride` seeds per sample, rows from block_y, under `timer` (null: the tap's launch, untimed).  write_origin: the pinhole's alone.
+hipError_t launch_generate(polaris_hip_tracer *h, const char *timer, hipStream_t q, const Streams &st, uint32_t stride, uint32_t first_sample, uint32_t wgs, uint32_t N,
+                           uint32_t Npad, uint32_t block_y, int zero_lsum, int write_origin) {
+	const CameraDev c = camera_args(h);
+	const uint32_t *seeds = h->d_seeds;
+	switch (const Generator g = h->camera.generator()) {
+	case Generator::Pinhole: return launch(h, timer, q, kGenerate, wgs, WG, 0, st, c.cam, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum, write_origin);
+	case Generator::Lens: return launch(h, timer, q, kGenerateLens, wgs, WG, 0, st, c.cam, c.lens, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum);
+	default: return launch(h, timer, q, kGenerateShutter[g == Generator::ShutterLens], wgs, WG, 0, st, c.cam, c.cam1, c.lens, c.lens1, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum);
+	}
+}
+
+const char *const kShadeTimer[4] ={"shade_first", "shade_sort", "shade_plain", "shade_wave"}; // by ShadeKernel (trace_plan.h): one timer per kernel symbol
 
 // One wavefront batch: K samples starting at sample s0, on pipeline p, by the Trace's plan.
 // Returns the first launch error of the batch (checked after every batch by the caller: a failed launch in batch 1 is reported
@@ -732,10 +743,7 @@ hipError_t launch_batch(polaris_hip_tracer *h, int p, const PolarisBlockRequest 
 	hipStream_t q = P.q;
 	P.st.hit12 = plan.hit12 ? 1u : 0u; // (a Trace never reads a hit's distance: kernels.h Streams::hit12)
 	P.st.o12 = plan.o12 ? 1u : 0u;     // (... and its closest-hit rays all have the max distance FLT_MAX: Streams::o12)
-	if (plan.scene.shutter) note(launch(h, "generate", q, kGenerateShutter[plan.scene.lens ? 1 : 0], wgs, WG, 0, P.st, h->cam, h->shutter_cam(), h->lens_args(), h->shutter_lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
-	else if (plan.scene.lens) note(launch(h, "generate", q, kGenerateLens, wgs, WG, 0, P.st, h->cam, h->lens_args(), h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y, exact ? 0 : 1));
-	else note(launch(h, "generate", q, kGenerate, wgs, WG, 0, P.st, h->cam, h->d_seeds, stride, s0, N, Npad, h->fa.W, r->block_y,
-	                 exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
+	note(launch_generate(h, "generate", q, P.st, stride, s0, wgs, N, Npad, r->block_y, exact ? 0 : 1, plan.generate_writes_origins ? 1 : 0));
 	ShadeArgs A{};
 	A.seeds = h->d_seeds; A.seed_stride = stride; A.first_sample = s0;
 	A.N = N; A.Npad = Npad; A.W = h->fa.W; A.blockY = r->block_y;
@@ -1159,7 +1167,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 			memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
 		}
 	}
-	h->fs.scene_changed(&next, h->cam);
+	h->fs.scene_changed(&next, h->camera.open);
 	// 3. the arrays, with the triangle of every area light packed (shading.h, SceneT::light_geo); 4. what the updates keep
 	std::vector<float> geo((size_t)sc->num_emissives * kLightGeoFloats, 0.0f);
 	pack_light_geo(sc->emissives, sc->num_emissives, sc->vertices, sc->normals, sc->uvs, geo.data());
@@ -1192,7 +1200,7 @@ int polaris_hip_update_instances(polaris_hip_tracer *h, const PolarisInstanceUpd
 	// history, which stays -- instances and meshes are the same; without, the history saw the old scene and goes
 	InstTable next = h->fs.v.cur;
 	if (h->fs.opt_object_motion) next.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
-	h->fs.scene_changed(&next, h->cam);
+	h->fs.scene_changed(&next, h->camera.open);
 	if (h->ds.vup.on) h->ds.vup.inv.assign(u->inv_transforms, u->inv_transforms + (size_t)NI * 16);
 	return finish_update(h, recs, pads, u->emissives, geo);
 }
@@ -1216,7 +1224,7 @@ int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate
 	// ---- accepted: from here on the state changes ----
 	if (int rc = make_idle(h)) return rc;
 	h->ds.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
-	h->fs.scene_changed(nullptr, h->cam); // the history never saw this scene
+	h->fs.scene_changed(nullptr, h->camera.open); // the history never saw this scene
 	if (h->fs.opt_object_motion && u->inv_transforms && h->fs.v.cur.inv.size() == (size_t)NI * 16) h->fs.v.cur.inv.assign(inv, inv + (size_t)NI * 16);
 	if (int rc = refit_meshes(h, u)) return rc;
 	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
@@ -1240,7 +1248,7 @@ int polaris_hip_update_materials(polaris_hip_tracer *h, const PolarisMaterialUpd
 	// ---- accepted: from here on the state changes ----
 	if (int rc = make_idle(h)) return rc;
 	S.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
-	h->fs.scene_changed(nullptr, h->cam); // the history never saw this scene
+	h->fs.scene_changed(nullptr, h->camera.open); // the history never saw this scene
 	hipStream_t q = h->stream;
 	const uint32_t NE = u->emissive_mat_nodes ? S.scene.num_emissives : 0, cls_words = (uint32_t)(cls.size() / 4);
 	HIP_TRY(h, h->d_retag.reserve((size_t)cls_words + NE + 4));
@@ -1275,7 +1283,7 @@ int polaris_hip_update_texture(polaris_hip_tracer *h, uint32_t index, const void
 	if (int st = check_texture_update(index, texels, n_bytes, S.have_scene, S.mup.tex_meta, msg)) return fail(h, st, "%s", msg.c_str());
 	if (int rc = make_idle(h)) return rc;
 	S.have_scene = false;
-	h->fs.scene_changed(nullptr, h->cam);
+	h->fs.scene_changed(nullptr, h->camera.open);
 	if (n_bytes) HIP_TRY(h, hipMemcpyAsync(S.mup.tex_data + S.mup.tex_meta[index].data_offset, texels, n_bytes, hipMemcpyHostToDevice, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	S.have_scene = true;
@@ -1302,99 +1310,40 @@ int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, 
 	return POLARIS_OK;
 }
 
-// The history goes where a lens or a shutter changes (FrameSync::lens_changed): its planes are freed, so the main stream, where every
-// temporal launch runs, is idle first.  The caller holds mu.
-static int idle_before_history_drop(polaris_hip_tracer *h) {
-	if (!h->fs.tp.max_history) return POLARIS_OK;
-	HIP_TRY(h, hipSetDevice(h->device));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	return POLARIS_OK;
-}
-
-// polaris_hip_set_camera and a changed polaris_hip_set_lens switch the shutter off: its close state belonged to the open state they
-// replace.  Nothing happens for a caller that never set a shutter.  The caller holds mu.
-static int shutter_off(polaris_hip_tracer *h) {
-	if (!h->shutter_on()) return POLARIS_OK;
-	if (int rc = idle_before_history_drop(h)) return rc;
-	h->fs.shutter_changed();
-	h->shutter.enabled = 0;
+// What the three camera setters share: perform what the transition asks (camera_state.h CameraTodo) and commit its state, or
+// report its refusal; a step that fails here leaves the camera as it was.  The caller holds mu.  eye: polaris_hip_set_camera's.
+static int apply_camera_step(polaris_hip_tracer *h, const CameraStep &s, const float *eye = nullptr) {
+	if (!s.refusal.empty()) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s", s.refusal.c_str());
+	const bool drop = (s.todo & kCamDropHistory) && h->fs.tp.max_history;
+	if (drop || eye) HIP_TRY(h, hipSetDevice(h->device));
+	if (drop) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the history's planes are freed: the main stream, where every temporal launch runs, is idle first
+	if (eye) { // the one origin record of every camera ray: what k_generate would write per ray (kernels.h)
+		const float4 o4 = make_float4(eye[0], eye[1], eye[2], kFltMax);
+		// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
+		HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
+	}
+	if (drop) h->fs.lens_changed();
+	if (s.todo & kCamMoved) h->fs.camera_moved(h->camera.open); // (with temporal reuse the last temporal sync's planes under the old camera become the history)
+	h->camera = s.next;
 	return POLARIS_OK;
 }
 
 int polaris_hip_set_camera(polaris_hip_tracer *h, const float eye[3], const float fr[16]) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!eye || !fr) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera pointers are null");
-	if (int rc = shutter_off(h)) return rc; // (the close state belonged to the camera that goes)
-	h->fs.camera_moved(h->cam); // (with temporal reuse the last temporal sync's planes under the old camera become the history)
-	h->cam.tl = make_float4(fr[0], fr[1], fr[2], fr[3]);
-	h->cam.tr = make_float4(fr[4], fr[5], fr[6], fr[7]);
-	h->cam.bl = make_float4(fr[8], fr[9], fr[10], fr[11]);
-	h->cam.br = make_float4(fr[12], fr[13], fr[14], fr[15]);
-	h->cam.eye = make_float3(eye[0], eye[1], eye[2]);
-	const float4 o4 = make_float4(eye[0], eye[1], eye[2], kFltMax); // what k_generate would write per camera ray (kernels.h)
-	HIP_TRY(h, hipSetDevice(h->device));
-	// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
-	HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
-	h->have_camera = true;
-	return POLARIS_OK;
-}
-
-// The rules for the ten floats of a lens (focus distance, axis, u, v), for polaris_hip_set_lens and the close lens of
-// polaris_hip_set_shutter (`who`): all finite, entries of u and v at most 2^30, and for a lens that is `on` the ranges of the focus
-// distance and of the axis' length.  POLARIS_OK, or the refusal.
-static int check_lens_floats(polaris_hip_tracer *h, const char *who, const float *f, bool on) {
-	for (int i = 0; i < 10; i++)
-		if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: float %d is not finite", who, i);
-	for (int i = 4; i < 10; i++)
-		if (std::fabs(f[i]) > 0x1p30f) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: an entry of u or v is above 2^30", who);
-	if (!on) return POLARIS_OK;
-	if (!(f[0] >= 1e-6f && f[0] <= 1e30f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: focus_distance %g outside [1e-6, 1e30]", who, (double)f[0]);
-	const float a2 = f[1] * f[1] + f[2] * f[2] + f[3] * f[3];
-	if (!(a2 >= 0.998f && a2 <= 1.002f)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: axis is not a unit vector (squared length %g)", who, (double)a2);
-	return POLARIS_OK;
+	return apply_camera_step(h, h->camera.set_camera(eye, fr), eye);
 }
 
 int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!p || p->struct_size != sizeof(PolarisLensParams))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_lens: null params or struct_size != %zu", sizeof(PolarisLensParams));
-	const float *f = &p->focus_distance; // the ten floats after struct_size
-	static_assert(sizeof(PolarisLensParams) == 44 && offsetof(PolarisLensParams, focus_distance) == 4, "PolarisLensParams is struct_size and ten floats");
-	bool on = false; // (a NaN in u or v counts as on here and is refused below)
-	for (int i = 4; i < 10; i++) on = on || f[i] != 0.0f;
-	if (int rc = check_lens_floats(h, "set_lens", f, on)) return rc;
-	if (memcmp(p, &h->lens, sizeof h->lens) == 0) return POLARIS_OK; // identical bytes: nothing happens
-	if (int rc = idle_before_history_drop(h)) return rc;
-	h->fs.lens_changed();
-	h->lens = *p;
-	h->shutter.enabled = 0; // (the close lens belonged to the lens that went; the history is gone already)
-	return POLARIS_OK;
+	return apply_camera_step(h, h->camera.set_lens(p));
 }
 
 int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	static_assert(sizeof(PolarisShutterParams) == 124 && offsetof(PolarisShutterParams, eye1) == 8 && offsetof(PolarisShutterParams, focus_distance1) == 84,
-	              "PolarisShutterParams is struct_size, enabled, 19 camera floats and ten lens floats");
-	if (!p || p->struct_size != sizeof(PolarisShutterParams))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: null params or struct_size != %zu", sizeof(PolarisShutterParams));
-	if (p->enabled > 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: enabled is %u (0 or 1)", p->enabled);
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: camera not set (the close state belongs to an open one)");
-	if (p->enabled) {
-		const float *f = p->eye1; // the 19 camera floats: eye1, frustum1
-		for (int i = 0; i < 19; i++)
-			if (!std::isfinite(f[i])) return fail(h, POLARIS_E_BAD_ARGUMENT, "set_shutter: camera float %d is not finite", i);
-		if (h->lens_on()) // the close lens is a lens that is on, whatever its u1 and v1
-			if (int rc = check_lens_floats(h, "set_shutter: close lens", &p->focus_distance1, true)) return rc;
-	}
-	if (p->enabled ? memcmp(p, &h->shutter, sizeof h->shutter) == 0 : !h->shutter_on()) return POLARIS_OK; // identical bytes, or off and off: nothing happens
-	if (int rc = idle_before_history_drop(h)) return rc;
-	h->fs.shutter_changed();
-	if (p->enabled) h->shutter = *p;
-	else h->shutter.enabled = 0;
-	return POLARIS_OK;
+	return apply_camera_step(h, h->camera.set_shutter(p));
 }
 
 int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value) {
@@ -1469,7 +1418,7 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	} announce{h->fa, r && r->accumulated_samples == 0};
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded"); // ErrNoSceneData, tracer.go:203-205
 	if (int rc = check_request(h, r)) return rc;
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set (UpdateState CameraData)");
+	if (!h->camera.have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set (UpdateState CameraData)");
 	const uint32_t B = r->num_bounces, spp = r->samples_per_pixel;
 	if (B > POLARIS_MAX_BOUNCES) return fail(h, POLARIS_E_BAD_ARGUMENT, "num_bounces %u exceeds %d", B, POLARIS_MAX_BOUNCES);
 	const size_t need_seeds = (size_t)spp * (1 + B);
@@ -1502,7 +1451,6 @@ int polaris_hip_trace(polaris_hip_tracer *h, const PolarisBlockRequest *r, const
 	const uint32_t K = plan.K;
 	const int n_pipes = plan.n_pipes;
 	HIP_TRY(h, h->d_seeds.reserve(need_seeds));
-	h->cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H); // resources.go:130-133
 	const size_t F = (size_t)h->fa.W * h->fa.H;
 	hipStream_t q = h->stream;
 	// The next slot of the ring: a peer may still be reading the previous frame's rows (polaris_hip_ipc_export).  Advanced only
@@ -1899,10 +1847,6 @@ int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 } // extern "C"
 
 namespace {
-TpCamera tp_camera(const CameraArgs &c) {
-	return TpCamera{{c.tl.x, c.tl.y, c.tl.z, c.tl.w}, {c.tr.x, c.tr.y, c.tr.z, c.tr.w}, {c.bl.x, c.bl.y, c.bl.z, c.bl.w},
-	                {c.br.x, c.br.y, c.br.z, c.br.w}, {c.eye.x, c.eye.y, c.eye.z}};
-}
 TpCamera tp_camera(const float eye[3], const float fr[16]) {
 	return TpCamera{{fr[0], fr[1], fr[2], fr[3]}, {fr[4], fr[5], fr[6], fr[7]}, {fr[8], fr[9], fr[10], fr[11]}, {fr[12], fr[13], fr[14], fr[15]},
 	                {eye[0], eye[1], eye[2]}};
@@ -1978,7 +1922,7 @@ void launch_steps(polaris_hip_tracer *h, hipStream_t q, const SyncPlan &P, const
 // camera, PRIOR if stale, the merges queued so far, then the timed steps over the request's rows.
 int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float weight, const SyncFeatures &f) {
 	FrameSync &S = h->fs;
-	if (!h->have_camera)
+	if (!h->camera.have_camera)
 		return fail(h, POLARIS_E_BAD_ARGUMENT, "%s needs the camera (UpdateState CameraData)", f.temporal ? "temporal reuse" : (f.variance ? "variance guidance" : "denoising"));
 	const SyncPlan P = plan_sync(f, S.v);
 	if (int rc = ensure_gbuffer(h)) return rc;
@@ -1995,8 +1939,8 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 			HIP_TRY(h, hipMemcpyAsync(S.mo_table, S.mo_table_host.data(), S.mo_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
 			mo = MotionArgs{S.gb_inst, S.tp_hinst, S.mo_table, n_inst};
 		}
-		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam),
-		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->cam), h->fa.W, h->fa.H, S.tp, S.pl[kTpPrior],
+		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam.eye, S.tp_hcam.frustum),
+		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->camera.open.eye, h->camera.open.frustum), h->fa.W, h->fa.H, S.tp, S.pl[kTpPrior],
 		                            P.m2 ? S.pl[kVaHist].get() : nullptr, f.variance ? S.pl[kTpPrior2].get() : nullptr, P.motion ? &mo : nullptr));
 		S.v.prior_computed();
 	}
@@ -2086,7 +2030,7 @@ int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_
 	if (const char *why = h->fs.v.aov_refusal(which, h->fs.tp.max_history != 0, h->fs.pl[kTpPrior2] != nullptr)) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s", why);
 	if (which == POLARIS_AOV_GUIDE || which == POLARIS_AOV_ALBEDO) { // computed on demand
 		if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
-		if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
+		if (!h->camera.have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_aov: camera not set");
 		if (int rc = ensure_gbuffer(h)) return rc;
 	}
 	HIP_TRY(h, hipMemcpyAsync(out, h->fs.pl[which], need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2147,7 +2091,7 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	std::lock_guard<std::mutex> lk(h->mu);
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
 	if (int rc = check_request(h, r)) return rc;
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set");
+	if (!h->camera.have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "camera not set");
 	const uint32_t N = h->fa.W * r->block_h, Npad = (N + WG - 1) / WG * WG;
 	HIP_TRY(h, hipSetDevice(h->device));
 	if (int rc = ensure_streams(h, 0, std::max<size_t>(h->pipe[0].slots, Npad), true)) return rc;
@@ -2155,15 +2099,12 @@ int polaris_hip_tap_primary(polaris_hip_tracer *h, const PolarisBlockRequest *r,
 	st0.hit12 = 0; // (the tap returns the hit distance: 16-byte records)
 	st0.o12 = 0;
 	if (h->d_seeds.capacity() < 1) HIP_TRY(h, h->d_seeds.alloc(64));
-	h->cam.texel = make_float2(1.0f / (float)h->fa.W, 1.0f / (float)h->fa.H);
 	hipStream_t q = h->stream;
 	std::vector<float4> ro(N), rd(N), ht(N);
 	std::vector<int> inst(N);
 	StreamDrain drain{q}; // (`seed` and the vectors are read and written by asynchronous copies)
 	HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, sizeof seed, hipMemcpyHostToDevice, q));
-	if (h->shutter_on()) kGenerateShutter[h->lens_on() ? 1 : 0].enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->shutter_cam(), h->lens_args(), h->shutter_lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
-	else if (h->lens_on()) kGenerateLens.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->lens_args(), h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1);
-	else kGenerate.enqueue(Npad / WG, WG, 0, q, st0, h->cam, h->d_seeds, 1u, 0u, N, Npad, h->fa.W, r->block_y, 1, 1);
+	(void)launch_generate(h, nullptr, q, st0, 1u, 0u, Npad / WG, N, Npad, r->block_y, 1, 1);
 	(void)launch_traversal(h, nullptr, tap_traversal(plan_scene(h)), RayKind::Closest, q, st0, 0, Npad / WG, nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipMemcpyAsync(ro.data(), st0.ray_o, N * sizeof(float4), hipMemcpyDeviceToHost, q));
@@ -2431,7 +2372,7 @@ int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t
 	if (!h->fs.opt_object_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: the option object_motion is off");
 	HIP_TRY(h, hipSetDevice(h->device));
 	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
-	if (!h->have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: camera not set");
+	if (!h->camera.have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: camera not set");
 	if (!h->fs.features().motion_on()) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
 	if (int rc = ensure_gbuffer(h)) return rc;
 	HIP_TRY(h, hipMemcpyAsync(out, h->fs.gb_inst, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
