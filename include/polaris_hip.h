@@ -201,6 +201,19 @@ int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p
  *                        after that still drops it (the old scene's mesh indices were not kept); set it before the scene.
  *                        Changing it drops the history and invalidates the G-buffer.  It never changes an accumulator or a
  *                        counter; off, no device memory is allocated and no kernel launched for it
+ *   "vertex_motion"      0 (default) or 1, anything else POLARIS_E_BAD_ARGUMENT: temporal reuse survives polaris_hip_update_vertices
+ *                        (DESIGN.md 10k).  In effect only while "object_motion" is in effect, the option is 1 and the scene was uploaded
+ *                        with "vertex_update" on.  Then update_vertices is to the history what polaris_hip_update_instances is: the
+ *                        planes of a temporal sync under the old vertices join the history, which stays; the first-hit G-buffer gains
+ *                        a HIT plane (polaris_hip_read_hit_plane); just before the first update that would overwrite the vertices a
+ *                        history was seen with, they are copied on the device ([3 num_triangles] float4, scene order); and the
+ *                        reprojection takes a first hit whose triangle changed to the point of the old triangle at the same
+ *                        barycentrics, through inverse(inv_transform_history[k]), before it projects it into the history camera.  A
+ *                        triangle whose nine coordinates did not change takes "object_motion"'s path bit for bit.  update_materials,
+ *                        update_texture and an incompatible upload_scene drop the history as without it.  Changing the value drops
+ *                        the history and invalidates the G-buffer, as changing "object_motion" does; setting the same value does
+ *                        nothing.  It never changes an accumulator or a counter; off or without effect, every upload, update, sync
+ *                        and G-buffer allocates and launches exactly what it does without the option
  *   "guide_specular"     0 (default) .. 8, anything else POLARIS_E_BAD_ARGUMENT: the number N of delta interactions the G-buffer's
  *                        guide ray follows.  With N > 0 a pixel whose hit is a CONDUCTOR or DIELECTRIC leaf -- both
  *                        delta BxDFs: a mirror, smooth glass -- continues in the mirror direction, or through the glass (refracted
@@ -592,6 +605,27 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
  * "object_motion" in effect what is seen through a mirror or glass takes none (with it off, camera moves reuse it).  Errors as polaris_hip_read_aov of
  * POLARIS_AOV_GUIDE; POLARIS_E_BAD_ARGUMENT with the option off, or without effect because temporal reuse is off. */
 int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n);
+
+/* polaris_hip_reproject_motion_planes with vertex motion (option "vertex_motion"): also the current frame's HIT plane (W x H x 4
+ * words as polaris_hip_read_hit_plane returns them) and the vertices of the num_triangles (1..2^24) scene triangles as the scene holds
+ * them now and as the history saw them ([3 num_triangles][4] floats each, scene order, w ignored).  A pixel whose HIT triangle is
+ * >= num_triangles or whose INSTANCE word is >= n_instances has no history; one whose triangle has the same 36 bytes of xyz in both
+ * arrays is reprojected as by polaris_hip_reproject_motion_planes; any other from the point of the old triangle at the hit's
+ * barycentrics, taken to the world through inverse(prev_inv_transforms[k]) -- the launch of the first temporal sync after an
+ * update_vertices.  Uses buffers of its own; no state of the tracer is read or changed. */
+int polaris_hip_reproject_deform_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                        const uint32_t *prev_instance, const float prev_eye[3], const float prev_frustum[16], const float *guide,
+                                        const float *albedo, const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t W,
+                                        uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
+                                        const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2,
+                                        const uint32_t *hit, const float *vertices, const float *prev_vertices, uint32_t num_triangles);
+
+/* The HIT plane of the first-hit G-buffer (option "vertex_motion"): per pixel four words, the scene triangle of the hit
+ * POLARIS_AOV_GUIDE describes | the bits of its barycentric u | of v | 0 -- what the surface was interpolated from; 0xFFFFFFFF | 0 |
+ * 0 | 0 for a miss and, with the option "guide_specular", for a pixel whose guide ray followed at least one link (as the INSTANCE
+ * word).  n_words >= 4 * frame_w * frame_h.  Errors as polaris_hip_read_instance_plane; POLARIS_E_BAD_ARGUMENT with the option off or
+ * not in effect. */
+int polaris_hip_read_hit_plane(polaris_hip_tracer *h, uint32_t *out, size_t n_words);
 
 /*
  * Move mesh instances in place (no reference counterpart: the reference uploads the whole scene, tracer.go:166-173).

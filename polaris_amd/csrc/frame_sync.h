@@ -3,7 +3,7 @@
 // whether an AOV can be read (SyncState::aov_refusal).
 //
 // No HIP here and no device pointer: FrameSync in polaris_hip.hip owns the planes and pairs every transition with the frees and
-// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d describe the features.
+// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d and 10k describe the features.
 #pragma once
 
 #include <cstdint>
@@ -23,14 +23,17 @@ enum Plane : uint32_t {
 	kNumPlanes4,
 	kInst = kNumPlanes4, kHInst,             // INSTANCE (one word per pixel, with object motion in effect), the history's
 	kMoTable,                                // motion table of the last PRIOR (temporal.h tp_motion_table): not frame-sized, grow-only
+	kHit,                                    // HIT (one uint4 per pixel, with vertex motion in effect): no history twin.  With it go the vertices the
+	                                         // history was seen with and the deformation table, which are not frame-sized and grow only
 };
 static_assert(kGuide == POLARIS_AOV_GUIDE && kAlbedo == POLARIS_AOV_ALBEDO && kDnOut == POLARIS_AOV_DENOISED && kTpOut == POLARIS_AOV_TEMPORAL &&
               kTpPrior == POLARIS_AOV_PRIOR && kVaOut == POLARIS_AOV_VARIANCE && kTpPrior2 == POLARIS_AOV_PRIOR2, "read_aov reads plane `which`");
 template <class... P> constexpr uint32_t planes(P... p) { return (0u | ... | (1u << p)); }
 // Every plane is freed with exactly one of these sets.  kMomentPlanes exist only with temporal reuse AND variance guidance on and
-// go when either goes; kMotionPlanes only with object motion in effect.
+// go when either goes; kMotionPlanes only with object motion in effect -- and kHit's, which exist only with vertex motion in effect,
+// go with them or with kVertexMotionPlanes alone.
 constexpr uint32_t kDenoisePlanes = planes(kGuide, kAlbedo, kDnOut, kDnPing, kDnPong), kMomentPlanes = planes(kVaHist, kTpPrior2),
-                   kMotionPlanes = planes(kInst, kHInst, kMoTable), kVariancePlanes = planes(kVaOut),
+                   kMotionPlanes = planes(kInst, kHInst, kMoTable), kVertexMotionPlanes = planes(kHit), kVariancePlanes = planes(kVaOut),
                    kTemporalPlanes = planes(kTpOut, kTpPrior, kTpHist, kTpHGuide, kTpHAlbedo) | kMotionPlanes | kMomentPlanes;
 
 // The instance table a scene was seen with (option "object_motion"): a host copy made by an upload with the option on.  Turned on after
@@ -45,11 +48,13 @@ struct InstTable {
 	}
 };
 
-// The features in force at an event.  motion: the option "object_motion"; it is in effect only with temporal reuse on.
+// The features in force at an event.  motion: the option "object_motion"; it is in effect only with temporal reuse on.  deform: the
+// option "vertex_motion" on a scene uploaded with "vertex_update"; it is in effect only with object motion in effect.
 struct SyncFeatures {
-	bool denoise = false, temporal = false, variance = false, motion = false;
+	bool denoise = false, temporal = false, variance = false, motion = false, deform = false;
 	bool any() const { return denoise || temporal || variance; }
 	bool motion_on() const { return motion && temporal; }
+	bool deform_on() const { return deform && motion_on(); }
 };
 
 class SyncState {
@@ -61,6 +66,7 @@ class SyncState {
 	bool va_valid = false;       // a variance sync has written VARIANCE (under the current camera with temporal reuse)
 	bool va_synced = false;      // temporal: a variance sync ran under the current camera (VARIANCE is this camera's)
 	bool va_have_hist = false;   // temporal: the history has a VARIANCE plane (its M2)
+	bool hist_verts_current = true; // vertex motion: the history was seen with the vertices the device holds now (no snapshot is needed)
 
 	// Nothing synced so far was seen under what holds from now on: the camera or the scene.
 	void forget_syncs() { tp_synced = tp_prior_valid = va_synced = va_valid = false; }
@@ -72,6 +78,7 @@ class SyncState {
 		tp_have_hist = true;
 		va_have_hist = va_synced;
 		if (motion_on) hist = cur;
+		hist_verts_current = true; // (the sync that joins the history ran under the scene as it is)
 		return planes(kTpOut, kGuide, kAlbedo) | (motion_on ? planes(kInst) : 0) | (va_synced ? planes(kVaOut) : 0);
 	}
 
@@ -81,6 +88,7 @@ public:
 	bool gbuffer() const { return gb_valid; }
 	bool prior() const { return tp_prior_valid; }
 	bool have_history() const { return tp_have_hist; }       bool history_has_m2() const { return va_have_hist; }
+	bool history_has_snapshot() const { return tp_have_hist && !hist_verts_current; } // (a dropped history forgets its snapshot)
 	bool temporal_synced() const { return tp_synced; }       bool variance_synced() const { return va_synced; }
 
 	// ---- the transitions.  Those that return a set of planes: the owner frees them (or swaps them, where it says so).
@@ -113,6 +121,14 @@ public:
 		if (next) cur = *next;
 		return swaps;
 	}
+	// polaris_hip_update_vertices with vertex motion in effect, after its scene_changed(f, next) and just before it overwrites the vertex
+	// array: true -> the owner copies the array into the snapshot first (a history exists that was seen with it).  false: there is no
+	// history, or it was seen with older vertices, whose snapshot stays (two deformations without a temporal sync in between).
+	bool vertices_changing(const SyncFeatures &f) {
+		if (!f.deform_on() || !tp_have_hist || !hist_verts_current) return false;
+		hist_verts_current = false;
+		return true;
+	}
 	void temporal_params_changed() { tp_prior_valid = false; } // (PRIOR is recomputed at the next temporal sync)
 	uint32_t temporal_off() { tp_have_hist = tp_synced = tp_prior_valid = va_synced = va_have_hist = false; return kTemporalPlanes; }
 	uint32_t variance_toggled(bool on) { // (PRIOR2 is written, or no longer, by the next temporal sync's reprojection)
@@ -124,6 +140,10 @@ public:
 		guide_rule_changed();
 		cur = hist = InstTable();
 		return on ? 0 : kMotionPlanes;
+	}
+	uint32_t deform_toggled(bool on) { // (option "vertex_motion", or an upload that puts it in or out of effect) as motion_toggled; the instance table stays
+		guide_rule_changed();
+		return on ? 0 : kVertexMotionPlanes;
 	}
 	void guide_rule_changed() { // (option "guide_specular") the G-buffer and a history seen with the other rule go; the planes and the instance table stay
 		tp_have_hist = tp_synced = tp_prior_valid = va_synced = va_have_hist = va_valid = gb_valid = false;
@@ -158,13 +178,14 @@ struct SyncPlan {
 	uint32_t clear_new = 0; // of those, cleared when this sync allocates them
 	bool prior = false;     // PRIOR is stale: recomputed from the history (none: cleared) by kReproject[m2][motion]
 	bool history = false, m2 = false, motion = false;
+	bool deform = false;    // the history has a snapshot of the vertices: kReprojectDeform[m2] in kReproject's place
 	SyncStep steps[4] = {}; // the timed steps in launch order
 	int n_steps = 0;
 	SyncSource color = SyncSource::Accumulator, tonemap = SyncSource::Accumulator; // what the filter reads | what the tone-map reads (the filter's output, or its input where none runs)
 };
 inline SyncPlan plan_sync(const SyncFeatures &f, const SyncState &v) {
 	SyncPlan p;
-	p.need = planes(kGuide, kAlbedo) | (f.motion_on() ? planes(kInst) : 0) | (f.denoise ? planes(kDnOut, kDnPing, kDnPong) : 0) |
+	p.need = planes(kGuide, kAlbedo) | (f.motion_on() ? planes(kInst) : 0) | (f.deform_on() ? planes(kHit) : 0) | (f.denoise ? planes(kDnOut, kDnPing, kDnPong) : 0) |
 	         (f.temporal ? planes(kTpOut, kTpPrior) : 0) | (f.variance ? planes(kVaOut) : 0) | (f.temporal && f.variance ? planes(kTpPrior2) : 0);
 	if (f.temporal) {
 		p.clear = (v.temporal_synced() ? 0 : planes(kTpOut)) | (f.variance && !v.variance_synced() ? planes(kVaOut) : 0);
@@ -172,6 +193,7 @@ inline SyncPlan plan_sync(const SyncFeatures &f, const SyncState &v) {
 		p.history = p.prior && v.have_history();
 		p.m2 = p.history && f.variance && v.history_has_m2();
 		p.motion = p.history && f.motion; // (a history kept with object motion on has an INSTANCE plane and a table of the scene's size)
+		p.deform = p.motion && f.deform && v.history_has_snapshot();
 		p.steps[p.n_steps++] = SyncStep::Temporal;
 		p.color = SyncSource::Temporal;
 	} else if (f.variance) p.clear_new = planes(kVaOut);

@@ -69,6 +69,8 @@ const decltype(POLARIS_VARIANT(k_aggregate<false>)) kAggregate[2] = {POLARIS_VAR
 const decltype(POLARIS_VARIANT(k_reproject<false, false>)) kReproject[2][2] = {
 	{POLARIS_VARIANT(k_reproject<false, false>), POLARIS_VARIANT(k_reproject<false, true>)},
 	{POLARIS_VARIANT(k_reproject<true, false>), POLARIS_VARIANT(k_reproject<true, true>)}};
+// k_reproject_deform<M2>: [M2].  Option "vertex_motion": in k_reproject<M2, true>'s place while the history has a snapshot of the vertices
+const decltype(POLARIS_VARIANT(k_reproject_deform<false>)) kReprojectDeform[2] = {POLARIS_VARIANT(k_reproject_deform<false>), POLARIS_VARIANT(k_reproject_deform<true>)};
 // k_generate_shutter<LENS>: [LENS].  polaris_hip_set_shutter: in k_generate's (k_generate_lens') place while the shutter is on
 const decltype(POLARIS_VARIANT(k_generate_shutter<false>)) kGenerateShutter[2] = {POLARIS_VARIANT(k_generate_shutter<false>), POLARIS_VARIANT(k_generate_shutter<true>)};
 

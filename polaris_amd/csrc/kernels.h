@@ -1875,6 +1875,8 @@ __global__ __launch_bounds__(WG) void k_builtin_sweep(uint32_t fn, uint64_t firs
 // (p, p), no path flags).  GUIDE = n after bump / normal maps | t (miss: 0, 0, 0, FLT_MAX); ALBEDO = clamp(tint * kcol, 0, 1)
 // for diffuse and (rough) conductor leaves, 1 for the other leaves | the leaf type's bits (miss: 1, 1, 1 | -1).
 // inst (option "object_motion"; null: not written): the INSTANCE plane, the first hit's mesh-instance index (miss: 0xFFFFFFFF).
+// hit (option "vertex_motion"; null: not written): the HIT plane, the first hit's scene triangle | bits of u | bits of v | 0, what
+// surface_at took the surface from (miss: 0xFFFFFFFF | 0 | 0 | 0).
 // What the two G-buffer kernels share beside surface_at: the guide ray of pixel (gx, gy) (temporal.h: k_reproject re-derives it), the
 // record of a miss and the albedo of a leaf.  (The walk itself is written out in both: shared, k_gbuffer_chain takes 3 more VGPRs.)
 __device__ __forceinline__ f3 gbuffer_centre_ray(const CameraArgs &cam, uint32_t gx, uint32_t gy) {
@@ -1884,10 +1886,11 @@ __device__ __forceinline__ f3 gbuffer_centre_ray(const CameraArgs &cam, uint32_t
 	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc);
 	return mk3(dc[0], dc[1], dc[2]);
 }
-__device__ __forceinline__ void gbuffer_miss(uint32_t idx, float4 *guide, float4 *albedo, uint32_t *inst) {
+__device__ __forceinline__ void gbuffer_miss(uint32_t idx, float4 *guide, float4 *albedo, uint32_t *inst, uint4 *hit) {
 	guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
 	albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
 	if (inst) inst[idx] = kTpNoInstance;
+	if (hit) hit[idx] = make_uint4(kTpNoTriangle, 0u, 0u, 0u);
 }
 __device__ __forceinline__ f3 gbuffer_albedo(const MatT<false> &m, f3 tint) {
 	if (m.type != POLARIS_BXDF_DIFFUSE && m.type != POLARIS_BXDF_CONDUCTOR && m.type != POLARIS_BXDF_ROUGH_CONDUCTOR) return splat(1.0f);
@@ -1896,15 +1899,16 @@ __device__ __forceinline__ f3 gbuffer_albedo(const MatT<false> &m, f3 tint) {
 }
 
 __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
-                                                uint32_t *inst) {
+                                                uint32_t *inst, uint4 *hit) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
 	HitRec h;
 	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), gbuffer_centre_ray(cam, idx % W, idx / W), kFltMax, stk, h);
-	if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst);
+	if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst, hit);
 	if (inst) inst[idx] = (uint32_t)h.inst; // (traverse enters the one instance of a root_is_instance scene through its leaf reference too)
 	const int tri = h.tri & (int)((1u << S.tri_bits) - 1u); // (the shading class rides above the index)
+	if (hit) hit[idx] = make_uint4((uint32_t)tri, pm_f2u(h.u), pm_f2u(h.v), 0u);
 	Surf sf = surface_at(S, tri, h.u, h.v);
 	uint32_t flags = 0;
 	f3 tint = splat(1.0f);
@@ -1923,11 +1927,12 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 // from link to link but the ray, T and A -- and the continuation ray is shade_ray's (ind_origin, the direction not renormalised).
 // GUIDE = that surface's n | T, the float sum of the links' t in order; ALBEDO = the product of the links' albedo (k_gbuffer's
 // rule at each) | the last leaf's type; a miss at any link is k_gbuffer's miss.  INSTANCE = the hit's instance where no link was
-// followed, else 0xFFFFFFFF: a pixel seen through a chain takes no history across object motion.
+// followed, else 0xFFFFFFFF: a pixel seen through a chain takes no history across object motion.  HIT likewise: the first hit's
+// word where no link was followed, else the miss word.
 // A direction with a component that fails |c| <= 2^10 (NaN included), or all zero, ends the chain at its surface (the direction
 // rule of polaris_hip_probe_intersect): a degenerate IOR sends no such ray into the traversal.  max_links <= 8: every lane ends.
 __global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
-                                                      uint32_t *inst, int max_links) {
+                                                      uint32_t *inst, uint4 *hit, int max_links) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
@@ -1937,7 +1942,7 @@ __global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, Came
 	for (int k = 0;; k++) {
 		HitRec h;
 		traverse<false>(B, o, d, kFltMax, stk, h);
-		if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst);
+		if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst, hit);
 		T = k == 0 ? h.t : T + h.t;
 		const int tri = h.tri & (int)((1u << S.tri_bits) - 1u);
 		Surf sf = surface_at(S, tri, h.u, h.v);
@@ -1963,6 +1968,7 @@ __global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, Came
 		guide[idx] = make_float4(sf.n.x, sf.n.y, sf.n.z, T);
 		albedo[idx] = make_float4(Aa.x, Aa.y, Aa.z, ibits((int)m.type));
 		if (inst) inst[idx] = k == 0 ? (uint32_t)h.inst : kTpNoInstance;
+		if (hit) hit[idx] = k == 0 ? make_uint4((uint32_t)tri, pm_f2u(h.u), pm_f2u(h.v), 0u) : make_uint4(kTpNoTriangle, 0u, 0u, 0u);
 		return;
 	}
 }
@@ -2046,6 +2052,60 @@ __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const floa
 		tp_reproject<M2, true>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2, inst[i],
 		                       n_inst, entry);
 	} else tp_reproject<M2>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2);
+	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
+	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
+}
+
+// k_reproject<M2, true> with the option "vertex_motion" in effect and a history that has a snapshot of the vertices:
+// each pixel also loads its HIT word (one uint4); a filtered pixel with a triangle < n_tris gathers the triangle's three vertices as
+// the scene holds them (verts) and as the history saw them (hverts), six float4, and takes k_reproject's path when their xyz are
+// equal; a pixel whose triangle changed reads its instance's entry of the deformation table (deform: four float4 per instance,
+// temporal.h tp_deform_table) and not the motion table.  One thread per pixel, no LDS.
+template <bool M2>
+__global__ __launch_bounds__(WG) void k_reproject_deform(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
+                                                         const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
+                                                         uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                         const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                         const float4 *motion, uint32_t n_inst, const uint4 *hit, const float4 *verts,
+                                                         const float4 *hverts, const float4 *deform, uint32_t n_tris) {
+	const uint32_t i = blockIdx.x * WG + threadIdx.x;
+	if (i >= W * H) return;
+	const float4 g = guide[i];
+	const float gi[4] = {g.x, g.y, g.z, g.w};
+	const uint4 h4 = hit[i];
+	const uint32_t hi[3] = {h4.x, h4.y, h4.z};
+	auto load = [&](uint32_t j, TpTap &t) {
+		const float4 c = hist[j], n = hguide[j];
+		t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
+		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
+		t.leaf = halbedo[j].w;
+		if (M2) t.m2 = hvar[j].y;
+		t.inst = hinst[j];
+	};
+	auto table = [](const float4 *tab) {
+		return [tab](uint32_t k, float *D) -> uint32_t { // (k < n_inst: tp_reproject checks)
+			const float4 *e = tab + 4 * (size_t)k;
+			const uint32_t flag = pm_f2u(e[3].x);
+			if (flag == kTpMoved) {
+				const float4 r0 = e[0], r1 = e[1], r2 = e[2];
+				D[0] = r0.x; D[1] = r0.y; D[2] = r0.z; D[3] = r0.w;
+				D[4] = r1.x; D[5] = r1.y; D[6] = r1.z; D[7] = r1.w;
+				D[8] = r2.x; D[9] = r2.y; D[10] = r2.z; D[11] = r2.w;
+			}
+			return flag;
+		};
+	};
+	auto triangle = [&](uint32_t T, float *a, float *b) { // (T < n_tris: tp_reproject checks)
+		const size_t off = 3 * (size_t)T;
+		for (int k = 0; k < 3; k++) {
+			const float4 v = verts[off + k], w = hverts[off + k];
+			a[3 * k] = v.x; a[3 * k + 1] = v.y; a[3 * k + 2] = v.z;
+			b[3 * k] = w.x; b[3 * k + 1] = w.y; b[3 * k + 2] = w.z;
+		}
+	};
+	float o[4], o2[4];
+	tp_reproject<M2, true, true>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2, inst[i],
+	                             n_inst, table(motion), hi, n_tris, triangle, table(deform));
 	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
 	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
 }

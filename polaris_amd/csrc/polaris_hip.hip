@@ -103,7 +103,7 @@ struct DeviceScene {
 	MaterialUpdateState mup;
 };
 
-// Everything behind the features of polaris_hip_sync_framebuffer (DESIGN.md 10-10d): the parameters of denoising (polaris_hip_set_denoise),
+// Everything behind the features of polaris_hip_sync_framebuffer (DESIGN.md 10-10d, 10k): the parameters of denoising (polaris_hip_set_denoise),
 // temporal reuse across camera moves (_set_temporal) and variance guidance (_set_variance), the option "object_motion", every plane
 // they use and what of the planes is valid.  frame_sync.h holds the rules: nothing is allocated while its feature is off, the history
 // is the TEMPORAL plane, G-buffer, camera and (object motion) INSTANCE plane and instance table of the last temporal sync before the
@@ -115,18 +115,24 @@ struct FrameSync {
 	PolarisVarianceParams va{sizeof(PolarisVarianceParams), 0.0f, 0};
 	int opt_object_motion = 0;
 	int opt_guide_specular = 0; // delta links the guide ray follows (0: the first hit, k_gbuffer)
+	int opt_vertex_motion = 0;  // DESIGN.md 10k; it can be in effect only on a scene uploaded with "vertex_update":
+	bool scene_deformable = false;
 	SyncState v;
 	DevArray<float4> pl[kNumPlanes4];     // the float4 planes, by Plane
 	DevArray<uint32_t> gb_inst, tp_hinst; // kInst, kHInst
 	DevArray<float4> mo_table;            // kMoTable
 	std::vector<float> mo_table_host;
+	DevArray<uint4> gb_hit;               // kHit, and what goes with it: the vertices the history was seen with ([3 NT], scene order) and the
+	DevArray<float4> vert_snap, de_table; // deformation table (temporal.h tp_deform_table), both grow-only
+	std::vector<float> de_table_host;
 	CameraFloats tp_hcam{};               // the history's camera
 
-	SyncFeatures features() const { return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0}; }
+	SyncFeatures features() const { return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0, opt_vertex_motion != 0 && scene_deformable}; }
 	void drop(uint32_t set) {
 		for (uint32_t p = 0; p < kNumPlanes4; p++)
 			if (set >> p & 1) pl[p].reset();
 		if (set & kMotionPlanes) { gb_inst.reset(); tp_hinst.reset(); mo_table.reset(); } // (they go together; ensure_gbuffer recomputes the G-buffer when gb_inst is wanted and missing)
+		if (set & (kMotionPlanes | kVertexMotionPlanes)) { gb_hit.reset(); vert_snap.reset(); de_table.reset(); }
 	}
 	void capture(uint32_t swaps, const CameraFloats &cam) { // cam: what the planes that join the history were seen under
 		constexpr Plane twin[][2] = {{kTpOut, kTpHist}, {kGuide, kTpHGuide}, {kAlbedo, kTpHAlbedo}, {kVaOut, kVaHist}};
@@ -150,6 +156,12 @@ struct FrameSync {
 		va = p;
 	}
 	void set_object_motion(int on) { opt_object_motion = on; drop(v.motion_toggled(on != 0)); } // (on differs from the option's value)
+	void set_vertex_motion(int on) { opt_vertex_motion = on; drop(v.deform_toggled(features().deform)); } // (on differs from the option's value)
+	void set_scene_deformable(bool d) { // an upload, before its scene_changed: with the option on, a scene that puts it in or out of effect is a toggle
+		const bool toggled = opt_vertex_motion && d != scene_deformable;
+		scene_deformable = d;
+		if (toggled) drop(v.deform_toggled(d));
+	}
 	void set_guide_specular(int links) { opt_guide_specular = links; v.guide_rule_changed(); } // (links differs from the option's value)
 };
 
@@ -574,24 +586,26 @@ int ensure_planes(polaris_hip_tracer *h, uint32_t need, uint32_t clear = 0, uint
 		if (clear >> p & 1) HIP_TRY(h, hipMemsetAsync(S.pl[p], 0, F * sizeof(float4), h->stream));
 	}
 	if ((need >> kInst & 1) && !S.gb_inst) HIP_TRY(h, S.gb_inst.alloc(F));
+	if ((need >> kHit & 1) && !S.gb_hit) HIP_TRY(h, S.gb_hit.alloc(F));
 	return POLARIS_OK;
 }
 
-// The GUIDE / ALBEDO planes of the current scene, camera and frame size (with object motion in effect the INSTANCE plane too), computed
+// The GUIDE / ALBEDO planes of the current scene, camera and frame size (with object motion in effect the INSTANCE plane too, with vertex
+// motion in effect the HIT plane), computed
 // if they are not (caller holds mu; checks done).
 int ensure_gbuffer(polaris_hip_tracer *h) {
 	FrameSync &S = h->fs;
-	const bool want_inst = S.features().motion_on();
-	if (S.v.gbuffer() && (!want_inst || S.gb_inst)) return POLARIS_OK;
+	const bool want_inst = S.features().motion_on(), want_hit = S.features().deform_on();
+	if (S.v.gbuffer() && (!want_inst || S.gb_inst) && (!want_hit || S.gb_hit)) return POLARIS_OK;
 	const size_t F = (size_t)h->fa.W * h->fa.H;
-	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0))) return rc;
+	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0) | (want_hit ? planes(kHit) : 0))) return rc;
 	const CameraArgs cam = camera_args(h).cam;
 	if (S.opt_guide_specular == 0)
 		(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
-		             want_inst ? S.gb_inst.get() : nullptr);
+		             want_inst ? S.gb_inst.get() : nullptr, want_hit ? S.gb_hit.get() : nullptr);
 	else
 		(void)launch(h, "gbuffer", h->stream, kGbufferChain, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide],
-		             S.pl[kAlbedo], want_inst ? S.gb_inst.get() : nullptr, S.opt_guide_specular);
+		             S.pl[kAlbedo], want_inst ? S.gb_inst.get() : nullptr, want_hit ? S.gb_hit.get() : nullptr, S.opt_guide_specular);
 	HIP_TRY(h, hipGetLastError());
 	S.v.gbuffer_computed();
 	return POLARIS_OK;
@@ -1167,6 +1181,7 @@ int polaris_hip_upload_scene(polaris_hip_tracer *h, const PolarisSceneView *sc) 
 			memcpy(next.inv.data() + 16 * (size_t)i, sc->mesh_instances[i].inv_transform, 16 * sizeof(float));
 		}
 	}
+	h->fs.set_scene_deformable(h->opt_vertex_update != 0);
 	h->fs.scene_changed(&next, h->camera.open);
 	// 3. the arrays, with the triangle of every area light packed (shading.h, SceneT::light_geo); 4. what the updates keep
 	std::vector<float> geo((size_t)sc->num_emissives * kLightGeoFloats, 0.0f);
@@ -1224,8 +1239,21 @@ int polaris_hip_update_vertices(polaris_hip_tracer *h, const PolarisVertexUpdate
 	// ---- accepted: from here on the state changes ----
 	if (int rc = make_idle(h)) return rc;
 	h->ds.have_scene = false; // (a failing call below leaves no scene, as a failed upload does)
-	h->fs.scene_changed(nullptr, h->camera.open); // the history never saw this scene
-	if (h->fs.opt_object_motion && u->inv_transforms && h->fs.v.cur.inv.size() == (size_t)NI * 16) h->fs.v.cur.inv.assign(inv, inv + (size_t)NI * 16);
+	if (h->fs.features().deform_on()) {
+		// with vertex motion in effect the update is to the history what update_instances is: the planes synced under the old vertices join
+		// it and it stays -- topology, instances and meshes are the same -- and the vertices it was seen with are kept before they go
+		InstTable next = h->fs.v.cur;
+		if (u->inv_transforms) next.inv.assign(inv, inv + (size_t)NI * 16);
+		h->fs.scene_changed(&next, h->camera.open);
+		if (h->fs.v.vertices_changing(h->fs.features())) {
+			const size_t nv = (size_t)V.num_triangles * 3;
+			HIP_TRY(h, h->fs.vert_snap.reserve(nv)); // (the main stream is idle)
+			HIP_TRY(h, hipMemcpyAsync(h->fs.vert_snap, V.vertices, nv * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+		}
+	} else {
+		h->fs.scene_changed(nullptr, h->camera.open); // the history never saw this scene
+		if (h->fs.opt_object_motion && u->inv_transforms && h->fs.v.cur.inv.size() == (size_t)NI * 16) h->fs.v.cur.inv.assign(inv, inv + (size_t)NI * 16);
+	}
 	if (int rc = refit_meshes(h, u)) return rc;
 	if (int st = prepare_instance_update(U.plan, NI, inv, u->instance_boxes, recs, pads, msg)) return fail(h, st, "%s", msg.c_str()); // (judged above: cannot fail)
 	if (int rc = finish_update(h, recs, pads, u->emissives, geo)) return rc;
@@ -1387,6 +1415,14 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 			h->fs.set_object_motion((int)value);
 			if (value && h->ds.have_scene)
 				if (int rc = read_back_instances(h)) return rc;
+		}
+	}
+	else if (k == "vertex_motion") {
+		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "vertex_motion is 0 or 1");
+		if ((int)value != h->fs.opt_vertex_motion) {
+			HIP_TRY(h, hipSetDevice(h->device));
+			HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every launch that uses the planes that go is on the main stream)
+			h->fs.set_vertex_motion((int)value);
 		}
 	}
 	else if (k == "guide_specular") {
@@ -1857,19 +1893,28 @@ TpCamera tp_camera(const float eye[3], const float fr[16]) {
 // launch it through here.
 // prior2 != null (variance guidance on): PRIOR2 too, from the history's VARIANCE plane hvar (null: the history has no M2, PRIOR2 = 0).
 // mo != null (object motion): the two INSTANCE planes and the motion table of the instances between the history and now.
-struct MotionArgs { const uint32_t *inst, *hinst; const float4 *table; uint32_t n_inst; };
+// mo->hit != null (vertex motion, the history has a snapshot): the HIT plane, the scene's vertices, the history's and the deformation table.
+struct MotionArgs {
+	const uint32_t *inst, *hinst; const float4 *table; uint32_t n_inst;
+	const uint4 *hit = nullptr; const float4 *verts = nullptr, *hverts = nullptr, *deform = nullptr; uint32_t n_tris = 0;
+};
 hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *hist, const float4 *hguide, const float4 *halbedo, const TpCamera &hcam,
                       const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
                       float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr, const MotionArgs *mo = nullptr) {
 	const size_t F = (size_t)W * H;
 	const bool none = !hist || !tp_projectable(hcam) || p.max_history == 0; // no history anywhere: m = 0
 	const bool m2 = prior2 && hvar && !none;                                // (else the PRIOR as without variance guidance, PRIOR2 = 0)
+	const bool deform = mo && mo->hit;
 	const auto &variant = kReproject[m2][mo != nullptr];
-	Timed t(h, "reproject", none ? nullptr : variant.symbol, q);
+	Timed t(h, "reproject", none ? nullptr : (deform ? kReprojectDeform[m2].symbol : variant.symbol), q);
 	if (prior2 && !m2)
 		if (hipError_t e = hipMemsetAsync(prior2, 0, F * sizeof(float4), q)) return e;
 	if (none) return hipMemsetAsync(prior, 0, F * sizeof(float4), q);
-	variant.enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold, p.depth_threshold,
+	if (deform)
+		kReprojectDeform[m2].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold,
+		                             p.depth_threshold, prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo->inst, mo->hinst, mo->table, mo->n_inst,
+		                             mo->hit, mo->verts, mo->hverts, mo->deform, mo->n_tris);
+	else variant.enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold, p.depth_threshold,
 	                prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo ? mo->inst : nullptr, mo ? mo->hinst : nullptr, mo ? mo->table : nullptr,
 	                mo ? mo->n_inst : 0u);
 	return hipGetLastError();
@@ -1938,6 +1983,15 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 			HIP_TRY(h, S.mo_table.reserve((size_t)n_inst * 4)); // (the main stream is idle: every sync ends with its synchronisation)
 			HIP_TRY(h, hipMemcpyAsync(S.mo_table, S.mo_table_host.data(), S.mo_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
 			mo = MotionArgs{S.gb_inst, S.tp_hinst, S.mo_table, n_inst};
+			if (P.deform) { // the history has a snapshot of the vertices: its instances' mesh -> world beside the motion table
+				if (!S.gb_hit || !S.vert_snap || !h->ds.vup.on || S.vert_snap.capacity() < (size_t)h->ds.vup.num_triangles * 3)
+					return fail(h, POLARIS_E_DEVICE, "temporal sync: the history's vertices do not fit the scene's"); // (cannot happen: the topology is the history's)
+				S.de_table_host.resize((size_t)n_inst * 16);
+				tp_deform_table(n_inst, S.v.hist.inv.data(), S.de_table_host.data());
+				HIP_TRY(h, S.de_table.reserve((size_t)n_inst * 4));
+				HIP_TRY(h, hipMemcpyAsync(S.de_table, S.de_table_host.data(), S.de_table_host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+				mo.hit = S.gb_hit; mo.verts = h->ds.vup.vertices; mo.hverts = S.vert_snap; mo.deform = S.de_table; mo.n_tris = h->ds.vup.num_triangles;
+			}
 		}
 		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam.eye, S.tp_hcam.frustum),
 		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->camera.open.eye, h->camera.open.frustum), h->fa.W, h->fa.H, S.tp, S.pl[kTpPrior],
@@ -2376,6 +2430,66 @@ int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t
 	if (!h->fs.features().motion_on()) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_instance_plane: object_motion has an effect only with temporal reuse on");
 	if (int rc = ensure_gbuffer(h)) return rc;
 	HIP_TRY(h, hipMemcpyAsync(out, h->fs.gb_inst, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_reproject_deform_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
+                                        const uint32_t *prev_instance, const float prev_eye[3], const float prev_frustum[16], const float *guide,
+                                        const float *albedo, const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t W,
+                                        uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
+                                        const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2,
+                                        const uint32_t *hit, const float *vertices, const float *prev_vertices, uint32_t num_triangles) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!history || !prev_guide || !prev_albedo || !prev_instance || !prev_eye || !prev_frustum || !guide || !albedo || !instance || !eye || !frustum ||
+	    !prev_inv_transforms || !inv_transforms || !prior || !hit || !vertices || !prev_vertices || !p || p->struct_size != sizeof(PolarisTemporalParams) ||
+	    W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) || n_instances == 0 || n_instances > kTpMaxInstances || num_triangles == 0 ||
+	    num_triangles > kTpMaxTriangles || (history_variance == nullptr) != (prior2 == nullptr) || tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_deform_planes: null argument, frame %ux%u (1..2^26 pixels), %u instances (1..%u), %u triangles (1..%u), "
+		            "history_variance without prior2 (or the reverse), or params (max_history 0..%u, normal_threshold [-1, 1], depth_threshold [0, %g])",
+		            W, H, n_instances, kTpMaxInstances, num_triangles, kTpMaxTriangles, kTpMaxHistory, (double)kTpMaxDepthThreshold);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4), nv = (size_t)num_triangles * 3;
+	std::vector<float> table((size_t)n_instances * 32); // the motion table, then the deformation table
+	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
+	tp_deform_table(n_instances, prev_inv_transforms, table.data() + (size_t)n_instances * 16);
+	DevArray<float4> d_table, d_verts;
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(9, 2)); // (the ninth float4 plane holds the HIT words)
+	HIP_TRY(h, d_table.alloc((size_t)n_instances * 8));
+	HIP_TRY(h, d_verts.alloc(2 * nv));
+	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5), *d_hvar = d.f4(6), *d_prior2 = d.f4(7);
+	uint4 *d_hit = (uint4 *)d.f4(8);
+	uint32_t *d_hinst = d.word(0), *d_inst = d.word(1);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane},
+	                                          {d_hvar, history_variance, plane}, {d_hinst, prev_instance, F * sizeof(uint32_t)}, {d_inst, instance, F * sizeof(uint32_t)},
+	                                          {d_hit, hit, F * sizeof(uint4)}, {d_table.get(), table.data(), table.size() * sizeof(float)},
+	                                          {d_verts.get(), vertices, nv * sizeof(float4)}, {d_verts.get() + nv, prev_vertices, nv * sizeof(float4)}}));
+	MotionArgs mo{d_inst, d_hinst, d_table, n_instances};
+	mo.hit = d_hit; mo.verts = d_verts; mo.hverts = d_verts.get() + nv; mo.deform = d_table.get() + (size_t)n_instances * 4; mo.n_tris = num_triangles;
+	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
+	                            W, H, *p, d_prior, history_variance ? d_hvar : nullptr, prior2 ? d_prior2 : nullptr, &mo));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}, {prior2, d_prior2, plane}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_read_hit_plane(polaris_hip_tracer *h, uint32_t *out, size_t n_words) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const size_t need = 4 * (size_t)h->fa.W * h->fa.H;
+	if (!out || n_words < need || need == 0) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_hit_plane: need %zu words", need);
+	if (!h->fs.opt_vertex_motion) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_hit_plane: the option vertex_motion is off");
+	HIP_TRY(h, hipSetDevice(h->device));
+	if (!h->ds.have_scene) return fail(h, POLARIS_E_NO_SCENE_DATA, "no scene data uploaded");
+	if (!h->camera.have_camera) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_hit_plane: camera not set");
+	if (!h->fs.features().deform_on())
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_hit_plane: vertex_motion has an effect only with object_motion in effect on a scene uploaded with vertex_update");
+	if (int rc = ensure_gbuffer(h)) return rc;
+	HIP_TRY(h, hipMemcpyAsync(out, h->fs.gb_hit, need * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	return POLARIS_OK;

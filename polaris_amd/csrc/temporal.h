@@ -11,6 +11,8 @@
 // then blends the running mean with it: (acc + m h) / (n + m).
 // With the option "object_motion"  the history also carries an INSTANCE plane and the instance table it was seen
 // with, and p is first taken to where its instance stood then (tp_motion_matrix on the host, tp_reproject<*, true>).
+// With the option "vertex_motion"  the history also carries the vertices it was seen with, and the first hit of a
+// triangle that a deformation changed is taken to where its barycentric point lay then (tp_reproject<*, true, true>).
 #pragma once
 
 #include <math.h>
@@ -89,6 +91,9 @@ enum : uint32_t { kTpStatic = 0, kTpMoved = 1, kTpInvalid = 2 };
 constexpr uint32_t kTpNoInstance = 0xFFFFFFFFu; // the INSTANCE word of a miss
 constexpr uint32_t kTpMaxInstances = 1u << 20;   // of polaris_hip_reproject_motion_planes / polaris_host_reproject_motion
 struct TpNoMotion {}; // (tp_reproject<*, false> never calls its motion argument)
+constexpr uint32_t kTpNoTriangle = 0xFFFFFFFFu; // the HIT plane's triangle word of a miss (option "vertex_motion")
+constexpr uint32_t kTpMaxTriangles = 1u << 24;   // of polaris_hip_reproject_deform_planes / polaris_host_reproject_deform
+struct TpNoDeform {}; // (tp_reproject<*, *, false> never calls its two deformation arguments)
 
 // ---- host only (plain functions: no device code is generated for them) ----
 // The motion table's entry of one instance from its two inv_transform (PolarisMeshInstance: column major, world -> mesh; the
@@ -143,6 +148,18 @@ inline void tp_motion_table(uint32_t n_instances, const float *inv_hist, const f
 	}
 }
 
+// The deformation table (option "vertex_motion"), beside the motion table and in its layout: per instance M = inverse(Inv_hist), mesh
+// space -> the world of the history, which is tp_motion_matrix against the identity.  STATIC: M is the identity.
+inline void tp_deform_table(uint32_t n_instances, const float *inv_hist, float *table) {
+	const float identity[16] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+	for (uint32_t k = 0; k < n_instances; k++) {
+		float *e = table + 16 * (size_t)k;
+		const uint32_t flag = tp_motion_matrix(inv_hist + 16 * (size_t)k, identity, e);
+		memcpy(e + 12, &flag, sizeof flag);
+		e[13] = e[14] = e[15] = 0.0f;
+	}
+}
+
 // The tap test: a history count > 0, finite history rgb, the same leaf word as pixel i, n_i . n_j >= normal_threshold and
 // |t_j - dist| <= depth_threshold * dist.
 PM_HD bool tp_finite(float x) { return (pm_f2u(x) & 0x7f800000u) != 0x7f800000u; }
@@ -163,10 +180,19 @@ PM_HD bool tp_tap_ok(const TpTap &j, float leaf_i, float nx, float ny, float nz,
 // flag returned and, for MOVED, D's twelve floats filled in (k < n_inst; a word outside the table gives no history).  INVALID:
 // m = 0.  MOVED: p becomes D p, each row ((r.x px + r.y py) + r.z pz) + r.w, before the projection, so the depth test sees
 // |D p - eye'|.  A tap must also carry the INSTANCE word inst_i.  MOTION = false reads neither.
-template <bool M2 = false, bool MOTION = false, class Load, class Motion = TpNoMotion>
+// DEFORM (option "vertex_motion", with MOTION): hit_i is the pixel's HIT word (scene triangle T | bits of u | bits of v) and
+// verts(T, a, b) fills the xyz of T's three vertices, a as the scene holds them now and b as the history saw them (T < n_tris; a
+// word outside gives no history).  36 equal bytes: the pixel takes MOTION's path, unchanged.  Else p becomes M q, q the point of
+// the old triangle at the hit's barycentrics (surface_at's expression) and matrix(k, M) instance k's deformation table entry
+// (tp_deform_table: STATIC p = q, INVALID m = 0, MOVED the rows as D's); a component of q or p that is not finite: m = 0.
+// DEFORM = false reads none of it.
+template <bool M2 = false, bool MOTION = false, bool DEFORM = false, class Load, class Motion = TpNoMotion, class Verts = TpNoDeform,
+          class Matrix = TpNoDeform>
 PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const TpCamera &cur,
                         const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4],
-                        float *out2 = nullptr, uint32_t inst_i = 0, uint32_t n_inst = 0, Motion motion = Motion()) {
+                        float *out2 = nullptr, uint32_t inst_i = 0, uint32_t n_inst = 0, Motion motion = Motion(),
+                        const uint32_t *hit_i = nullptr, uint32_t n_tris = 0, Verts verts = Verts(), Matrix matrix = Matrix()) {
+	static_assert(MOTION || !DEFORM, "DEFORM extends MOTION");
 	out[0] = out[1] = out[2] = out[3] = 0.0f;
 	if (M2) out2[0] = out2[1] = out2[2] = out2[3] = 0.0f;
 	if (!dn_filtered(leaf_i)) return;
@@ -174,16 +200,41 @@ PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const 
 	tp_centre_ray(cur.tl, cur.tr, cur.bl, cur.br, gx, gy, 1.0f / (float)W, 1.0f / (float)H, d);
 	const float t = guide_i[3];
 	float p[3] = {cur.eye[0] + t * d[0], cur.eye[1] + t * d[1], cur.eye[2] + t * d[2]};
+	bool rigid = true; // (the pixel's triangle is as the history saw it)
+	if constexpr (DEFORM) {
+		if (inst_i >= n_inst || hit_i[0] >= n_tris) return;
+		float a[9], b[9];
+		verts(hit_i[0], a, b);
+		for (int k = 0; k < 9; k++) rigid = rigid && pm_f2u(a[k]) == pm_f2u(b[k]);
+		if (!rigid) {
+			const float bu = pm_u2f(hit_i[1]), bv = pm_u2f(hit_i[2]);
+			const float bw = 1.0f - (bu + bv);
+			const float qx = bw * b[0] + bu * b[3] + bv * b[6], qy = bw * b[1] + bu * b[4] + bv * b[7], qz = bw * b[2] + bu * b[5] + bv * b[8];
+			if (!tp_finite(qx) || !tp_finite(qy) || !tp_finite(qz)) return;
+			float M[12];
+			const uint32_t flag = matrix(inst_i, M);
+			if (flag == kTpMoved) {
+				p[0] = ((M[0] * qx + M[1] * qy) + M[2] * qz) + M[3];
+				p[1] = ((M[4] * qx + M[5] * qy) + M[6] * qz) + M[7];
+				p[2] = ((M[8] * qx + M[9] * qy) + M[10] * qz) + M[11];
+			} else if (flag == kTpStatic) {
+				p[0] = qx; p[1] = qy; p[2] = qz;
+			} else return;
+			if (!tp_finite(p[0]) || !tp_finite(p[1]) || !tp_finite(p[2])) return;
+		}
+	}
 	if constexpr (MOTION) {
 		if (inst_i >= n_inst) return;
-		float D[12];
-		const uint32_t flag = motion(inst_i, D);
-		if (flag == kTpMoved) {
-			const float px = p[0], py = p[1], pz = p[2];
-			p[0] = ((D[0] * px + D[1] * py) + D[2] * pz) + D[3];
-			p[1] = ((D[4] * px + D[5] * py) + D[6] * pz) + D[7];
-			p[2] = ((D[8] * px + D[9] * py) + D[10] * pz) + D[11];
-		} else if (flag != kTpStatic) return;
+		if (rigid) {
+			float D[12];
+			const uint32_t flag = motion(inst_i, D);
+			if (flag == kTpMoved) {
+				const float px = p[0], py = p[1], pz = p[2];
+				p[0] = ((D[0] * px + D[1] * py) + D[2] * pz) + D[3];
+				p[1] = ((D[4] * px + D[5] * py) + D[6] * pz) + D[7];
+				p[2] = ((D[8] * px + D[9] * py) + D[10] * pz) + D[11];
+			} else if (flag != kTpStatic) return;
+		}
 	}
 	float u, v, dist;
 	if (!tp_project(hist, p, u, v, dist)) return;

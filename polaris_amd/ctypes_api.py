@@ -470,6 +470,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
+    "polaris_hip_reproject_deform_planes", "polaris_hip_read_hit_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
     "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens", "polaris_hip_set_shutter",
 ]
@@ -581,6 +582,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_reproject_motion_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp,
                                                         C.POINTER(TemporalParams), vp, vp, vp]
     lib.polaris_hip_read_instance_plane.argtypes = [vp, vp, C.c_size_t]
+    lib.polaris_hip_reproject_deform_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp,
+                                                        C.POINTER(TemporalParams), vp, vp, vp, vp, vp, vp, u32]
+    lib.polaris_hip_read_hit_plane.argtypes = [vp, vp, C.c_size_t]
     lib.polaris_hip_update_instances.argtypes = [vp, C.POINTER(InstanceUpdate)]
     lib.polaris_hip_read_scene_records.argtypes = [vp, i32, vp, C.c_size_t]
     lib.polaris_hip_update_vertices.argtypes = [vp, C.POINTER(VertexUpdate)]

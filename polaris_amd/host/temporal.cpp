@@ -98,6 +98,69 @@ int polaris_host_reproject_motion(const float *history, const float *prev_guide,
 	return POLARIS_OK;
 }
 
+// polaris_host_reproject_motion with vertex motion (include/polaris_hip.h, polaris_hip_reproject_deform_planes, minus the handle): the
+// current HIT plane (four words per pixel) and the vertices of the num_triangles scene triangles now and as the history saw them.
+int polaris_host_reproject_deform(const float *history, const float *prev_guide, const float *prev_albedo, const uint32_t *prev_instance,
+                                  const float prev_eye[3], const float prev_frustum[16], const float *guide, const float *albedo,
+                                  const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t frame_w, uint32_t frame_h,
+                                  uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
+                                  const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2,
+                                  const uint32_t *hit, const float *vertices, const float *prev_vertices, uint32_t num_triangles) {
+	if (!history || !prev_guide || !prev_albedo || !prev_instance || !prev_eye || !prev_frustum || !guide || !albedo || !instance || !eye ||
+	    !frustum || !prev_inv_transforms || !inv_transforms || !p || !prior || !hit || !vertices || !prev_vertices)
+		return POLARIS_E_BAD_ARGUMENT;
+	if ((history_variance == nullptr) != (prior2 == nullptr)) return POLARIS_E_BAD_ARGUMENT;
+	if (p->struct_size != sizeof(PolarisTemporalParams)) return POLARIS_E_BAD_ARGUMENT;
+	if (tp_check(p->max_history, p->normal_threshold, p->depth_threshold)) return POLARIS_E_BAD_ARGUMENT;
+	if (frame_w == 0 || frame_h == 0 || (uint64_t)frame_w * frame_h > (1ull << 26)) return POLARIS_E_BAD_ARGUMENT;
+	if (n_instances == 0 || n_instances > kTpMaxInstances || num_triangles == 0 || num_triangles > kTpMaxTriangles) return POLARIS_E_BAD_ARGUMENT;
+	auto camera = [](const float e[3], const float f[16]) {
+		return TpCamera{{f[0], f[1], f[2], f[3]}, {f[4], f[5], f[6], f[7]}, {f[8], f[9], f[10], f[11]}, {f[12], f[13], f[14], f[15]}, {e[0], e[1], e[2]}};
+	};
+	const TpCamera hcam = camera(prev_eye, prev_frustum), cam = camera(eye, frustum);
+	const uint32_t W = frame_w, H = frame_h;
+	const size_t F = (size_t)W * H;
+	const bool ok = tp_projectable(hcam) && p->max_history != 0;
+	std::vector<float> table((size_t)n_instances * 16), dtable((size_t)n_instances * 16);
+	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
+	tp_deform_table(n_instances, prev_inv_transforms, dtable.data());
+	auto load = [&](uint32_t j, TpTap &t) {
+		const float *c = history + 4 * (size_t)j, *n = prev_guide + 4 * (size_t)j;
+		t = TpTap{c[0], c[1], c[2], c[3], n[0], n[1], n[2], n[3], prev_albedo[4 * (size_t)j + 3],
+		          history_variance ? history_variance[4 * (size_t)j + 1] : 0.0f, prev_instance[j]};
+	};
+	auto entry_of = [](const std::vector<float> &tab) {
+		return [&tab](uint32_t k, float *D) -> uint32_t {
+			const float *e = tab.data() + 16 * (size_t)k;
+			for (int c = 0; c < 12; c++) D[c] = e[c];
+			return pm_f2u(e[12]);
+		};
+	};
+	auto triangle = [&](uint32_t T, float *a, float *b) {
+		for (int k = 0; k < 3; k++)
+			for (int c = 0; c < 3; c++) {
+				a[3 * k + c] = vertices[4 * (3 * (size_t)T + k) + c];
+				b[3 * k + c] = prev_vertices[4 * (3 * (size_t)T + k) + c];
+			}
+	};
+	for (size_t i = 0; i < F; i++) {
+		float *o = prior + 4 * i, *o2 = prior2 ? prior2 + 4 * i : nullptr;
+		if (!ok) {
+			o[0] = o[1] = o[2] = o[3] = 0.0f;
+			if (o2) o2[0] = o2[1] = o2[2] = o2[3] = 0.0f;
+			continue;
+		}
+		const uint32_t gx = (uint32_t)(i % W), gy = (uint32_t)(i / W);
+		if (o2)
+			tp_reproject<true, true, true>(gx, gy, W, H, guide + 4 * i, albedo[4 * i + 3], cam, hcam, p->max_history, p->normal_threshold, p->depth_threshold,
+			                               load, o, o2, instance[i], n_instances, entry_of(table), hit + 4 * i, num_triangles, triangle, entry_of(dtable));
+		else
+			tp_reproject<false, true, true>(gx, gy, W, H, guide + 4 * i, albedo[4 * i + 3], cam, hcam, p->max_history, p->normal_threshold, p->depth_threshold,
+			                                load, o, nullptr, instance[i], n_instances, entry_of(table), hit + 4 * i, num_triangles, triangle, entry_of(dtable));
+	}
+	return POLARIS_OK;
+}
+
 // tp_motion_matrix for the tests: the flag (0 STATIC, 1 MOVED, 2 INVALID) and D's twelve floats (rows r0, r1, r2).
 int polaris_host_motion_matrix(const float inv_hist[16], const float inv_cur[16], uint32_t *flag, float D[12]) {
 	if (!inv_hist || !inv_cur || !flag || !D) return POLARIS_E_BAD_ARGUMENT;

@@ -53,6 +53,8 @@ def load() -> C.CDLL:
         lib.polaris_host_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(T.TemporalParams), vp]
         lib.polaris_host_reproject_motion.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(T.TemporalParams),
                                                       vp, vp, vp]
+        lib.polaris_host_reproject_deform.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(T.TemporalParams),
+                                                      vp, vp, vp, vp, vp, vp, u32]
         lib.polaris_host_motion_matrix.argtypes = [vp, vp, C.POINTER(u32), vp]
         lib.polaris_host_temporal_combine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         lib.polaris_host_camera_move.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.c_uint32, vp, vp, vp]
@@ -375,6 +377,40 @@ def reproject_motion(history, prev_guide, prev_albedo, prev_instance, prev_eye, 
                                               out.ctypes.data, None if out2 is None else out2.ctypes.data)
     if rc:
         raise ValueError(f"reproject_motion: bad arguments (code {rc})")
+    return out if out2 is None else (out, out2)
+
+
+def reproject_deform(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
+                     prev_inv_transforms, inv_transforms, hit, vertices, prev_vertices, *, history_variance=None, max_history: int = 32,
+                     normal_threshold: float = 0.9, depth_threshold: float = 0.1):
+    """polaris_host_reproject_deform: reproject_motion() with vertex motion -- the current (H, W, 4) uint32 HIT plane (scene triangle |
+    bits of u | bits of v | 0) and the (3 NT, 4) vertices of the scene now and as the history saw them.  Returns the PRIOR plane, or
+    (PRIOR, PRIOR2) when the history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
+    (hist, pg, pa, g, a), H, W = _planes("reproject_deform", history, prev_guide, prev_albedo, guide, albedo)
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
+    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+    pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
+    pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
+    ht, v, pv = np.ascontiguousarray(hit, np.uint32), f(vertices).reshape(-1, 4), f(prev_vertices).reshape(-1, 4)
+    if pi.shape != (H, W) or ci.shape != (H, W) or pt.shape != ct.shape or ht.shape != (H, W, 4):
+        raise ValueError("reproject_deform: the INSTANCE planes must be (H, W), the HIT plane (H, W, 4), the two tables (n, 16)")
+    if v.shape != pv.shape or len(v) % 3:
+        raise ValueError("reproject_deform: the two vertex arrays must be (3 NT, 4)")
+    hv = None
+    if history_variance is not None:
+        (hv,), _, _ = _planes("reproject_deform", history_variance)
+        if hv.shape != hist.shape:
+            raise ValueError("reproject_deform: history_variance must be (H, W, 4) like the history")
+    out = np.zeros((H, W, 4), np.float32)
+    out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+    rc = load().polaris_host_reproject_deform(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data,
+                                              g.ctypes.data, a.ctypes.data, ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct),
+                                              pt.ctypes.data, ct.ctypes.data, C.byref(p), None if hv is None else hv.ctypes.data,
+                                              out.ctypes.data, None if out2 is None else out2.ctypes.data, ht.ctypes.data, v.ctypes.data,
+                                              pv.ctypes.data, len(v) // 3)
+    if rc:
+        raise ValueError(f"reproject_deform: bad arguments (code {rc})")
     return out if out2 is None else (out, out2)
 
 

@@ -27,6 +27,11 @@ variance.npy.
 material node NODE the colour (r, g, b) + k * step * (1, 1, 1) through polaris_hip_update_materials -- the node
 table in place, no upload_scene -- then render(accumulated=0).
 
+--frames N --ripple AMPLITUDE:WAVELENGTH renders N frames with a deformation of the scene's meshes per frame instead of a camera move:
+frame k displaces every vertex along y by AMPLITUDE * sin(2 pi (x + z) / WAVELENGTH + k) (mesh space) through
+polaris_hip_update_vertices -- the arrays in place, no upload_scene -- then render(accumulated=0).  With --temporal
+the options "object_motion" and "vertex_motion" are on, so the history is carried across every deformation.
+
 --aperture R --focus D renders through a thin lens of radius R focused at distance D along the view axis (polaris_hip_set_lens,
 DESIGN.md 10h; it stays on the camera through --frames moves).  --focus-pixel x,y takes D from the GUIDE plane instead: the first hit
 under that pixel's centre, t * dot(centre direction, axis); a pixel that sees nothing is an error.
@@ -135,6 +140,37 @@ def recolour_frames(r, sc, n: int, spec: str):
         yield r.render(0)
 
 
+def parse_ripple(spec: str):
+    amp, _, wave = spec.partition(":")
+    try:
+        amp, wave = float(amp), float(wave)
+    except ValueError:
+        amp, wave = 0.0, 0.0
+    if not wave > 0:
+        raise ValueError(f"--ripple {spec!r}: AMPLITUDE:WAVELENGTH with WAVELENGTH > 0")
+    return amp, wave
+
+
+def ripple_frames(r, sc, n: int, spec: str, temporal: bool):
+    """Frame k: the scene's vertices with y displaced by AMPLITUDE * sin(2 pi (x + z) / WAVELENGTH + k), given to every tracer in place
+    (Renderer.update_vertices with the boxes and emissive areas of scenes.refit_vertices), then render(accumulated=0).  The scene is
+    uploaded again first, with the option "vertex_update" on -- and, temporal, "object_motion" and "vertex_motion".  Yields (rows, ms)."""
+    from . import scenes
+
+    amp, wave = parse_ripple(spec)
+    for key in ("vertex_update",) + (("object_motion", "vertex_motion") if temporal else ()):
+        r.set_option(key, 1)
+    r.upload_scene(sc)
+    base = np.ascontiguousarray(sc.vertices, np.float32)
+    phase = 2.0 * np.pi * (base[:, 0].astype(np.float64) + base[:, 2].astype(np.float64)) / wave
+    for k in range(n):
+        v = base.copy()
+        v[:, 1] = (base[:, 1].astype(np.float64) + amp * np.sin(phase + k)).astype(np.float32)
+        vertices, boxes, _, _, ems = scenes.vertex_update_args(scenes.refit_vertices(sc, v))
+        r.update_vertices(vertices, boxes, None, None, ems)
+        yield r.render(0)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m polaris_amd.render", description=__doc__.split("\n")[0])
     ap.add_argument("scene", help="scene.obj")
@@ -155,13 +191,16 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=0, help="render this many frames, each after a camera move (--move)")
     ap.add_argument("--move", default="right:0.05", help="DIR:OFFSET of every move with --frames (left, right, up, down, forward, backward)")
     ap.add_argument("--recolour", default="", help="NODE:r,g,b[:step]: with --frames, edit material node NODE per frame in place instead of moving the camera")
+    ap.add_argument("--ripple", default="", help="AMPLITUDE:WAVELENGTH: with --frames, deform the scene's vertices per frame in place instead of moving the camera")
     ap.add_argument("--aperture", type=float, default=0.0, help="thin-lens radius in scene units (0 = pinhole)")
     ap.add_argument("--focus", type=float, default=0.0, help="with --aperture: distance of the plane of focus along the view axis")
     ap.add_argument("--focus-pixel", default="", help="with --aperture, x,y: focus on what this pixel's centre sees instead of --focus")
     ap.add_argument("--shutter", type=float, default=0.0, help="with --frames (camera moves): the shutter stays open this fraction 0..1 of the way to the next frame (0 = off)")
     a = ap.parse_args(argv)
-    if not 0.0 <= a.shutter <= 1.0 or (a.shutter and (not a.frames or a.recolour)):
-        ap.error("--shutter F needs 0 <= F <= 1, --frames and no --recolour")
+    if not 0.0 <= a.shutter <= 1.0 or (a.shutter and (not a.frames or a.recolour or a.ripple)):
+        ap.error("--shutter F needs 0 <= F <= 1, --frames and no --recolour or --ripple")
+    if a.ripple and (not a.frames or a.recolour):
+        ap.error("--ripple AMPLITUDE:WAVELENGTH needs --frames and no --recolour")
     if a.aperture < 0 or (a.aperture and not a.focus_pixel and not a.focus > 0):
         ap.error("--aperture R needs --focus D > 0 or --focus-pixel x,y")
 
@@ -192,7 +231,10 @@ def main(argv=None):
                 focus = focus_of_pixel(r.read_aov(T.AOV_GUIDE), sc.frustum, int(x), int(y))
             r.set_lens(a.aperture, focus)
         if a.frames:
-            frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height, a.shutter)
+            if a.ripple:
+                frames = ripple_frames(r, sc, a.frames, a.ripple, bool(a.temporal))
+            else:
+                frames = recolour_frames(r, sc, a.frames, a.recolour) if a.recolour else move_frames(r, sc, a.frames, a.move, a.width / a.height, a.shutter)
             for path, (rows, ms) in zip(frame_paths(a.out, a.frames), frames):
                 r.save(path)
         else:

@@ -371,6 +371,44 @@ class HipTracer:
         self._check(self._lib.polaris_hip_read_instance_plane(self._h, out.ctypes.data, out.size), self._h)
         return out
 
+    def reproject_deform_planes(self, history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye,
+                                frustum, prev_inv_transforms, inv_transforms, hit, vertices, prev_vertices, *, history_variance=None,
+                                max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1):
+        """polaris_hip_reproject_deform_planes: reproject_motion_planes with vertex motion -- the current (H, W, 4) uint32 HIT plane and
+        the (3 NT, 4) vertices of the scene now and as the history saw them.  Returns the PRIOR plane, or (PRIOR, PRIOR2) when the
+        history's VARIANCE plane is given.  (Null vertices or no triangle are passed on: the library refuses them.)"""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
+        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
+        H, W = g.shape[:2]
+        pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
+        pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
+        ht = np.ascontiguousarray(hit, np.uint32)
+        v = None if vertices is None else f(vertices).reshape(-1, 4)
+        pv = None if prev_vertices is None else f(prev_vertices).reshape(-1, 4)
+        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4) and pi.shape == ci.shape == (H, W) and pt.shape == ct.shape
+        assert ht.shape == (H, W, 4) and (v is None or pv is None or v.shape == pv.shape)
+        hv = None if history_variance is None else f(history_variance)
+        assert hv is None or hv.shape == (H, W, 4)
+        out = np.zeros((H, W, 4), np.float32)
+        out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
+        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+        nt = 0 if v is None and pv is None else len(v if v is not None else pv) // 3
+        self._check(self._lib.polaris_hip_reproject_deform_planes(
+            self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data, a.ctypes.data,
+            ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct), pt.ctypes.data, ct.ctypes.data, C.byref(p),
+            None if hv is None else hv.ctypes.data, out.ctypes.data, None if out2 is None else out2.ctypes.data, ht.ctypes.data,
+            None if v is None else v.ctypes.data, None if pv is None else pv.ctypes.data, nt), self._h)
+        return out if out2 is None else (out, out2)
+
+    def read_hit_plane(self) -> np.ndarray:
+        """(H, W, 4) uint32 HIT plane of the first-hit G-buffer (polaris_hip_read_hit_plane; option "vertex_motion" in effect): the scene
+        triangle of every pixel's first hit | the bits of its barycentric u | of v | 0; 0xFFFFFFFF | 0 | 0 | 0 for a miss."""
+        self._commit()
+        out = np.zeros((self._H, self._W, 4), dtype=np.uint32)
+        self._check(self._lib.polaris_hip_read_hit_plane(self._h, out.ctypes.data, out.size), self._h)
+        return out
+
     def update_instances(self, inv, boxes, emissives=None) -> None:
         """Move the uploaded scene's mesh instances in place (polaris_hip_update_instances): inv (NI, 16) column-major
         inverse matrices, boxes (NI, 6) world-space min.xyz, max.xyz, emissives the scene's emissive array with new transform / area
