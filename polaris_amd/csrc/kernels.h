@@ -1463,8 +1463,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHAD
 // (dealt round-robin to workgroups, LDS cursor inside) and walk the group's live rays 64 at a time, chunk after chunk:
 // after Russian roulette a chunk holds ~20 rays, so one pass shades the survivors of about three chunks with full lanes
 // (round 1 walked one chunk per pass: 11 % of the lanes of a VALU instruction were live).  Every lane knows its ray's
-// chunk (its sample, seed, reference position and emit mask are per lane); outputs go to the ray's own chunk through
-// per-chunk LDS counters (same canonical-order protocol as k_shade; never the first bounce).
+// chunk (its sample, seed, reference position and emit mask are looked up per lane); outputs go to the ray's own chunk
+// through per-chunk LDS counters (same canonical-order protocol as k_shade; never the first bounce).
 // Two stages per wave (ShadeArgs::prefilter): after Russian roulette about five rays in six only count (shade_fate), so
 // a pass formed from whatever is live would again run shade_ray with a sixth of its lanes.
 //   1. SCREEN: the group's live rays 64 at a time, in (chunk, slot) order -- only the throughput, the hit's last word and the
@@ -1474,17 +1474,63 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHAD
 //      their rays loaded and put through shade_ray: full passes of survivors, whichever chunks of the group they are from.
 // The queue is a ring of kWaveQueue entries per wave: at most 63 are left after a shade pass and a screen pass adds at
 // most 64.  (With the option off every ray is a survivor and takes the same way.)
+// ONE loop per group runs both stages: while rays remain to screen and the queue holds fewer than 64 descriptors it screens the
+// next 64 rays; otherwise, while the queue holds any, it shades the oldest (up to) 64; then the group is done.  So shade_ray is
+// inlined once, and the order of passes is what it always was: screen until 64 survivors wait, shade 64, ..., and at the end of
+// the group one last pass of what is left (at most 63).
 // In-place safety: survivors are shaded in ascending (chunk, slot) order, and the m-th ray shaded from a chunk sits at slot
 // >= m - 1.  Emitted rays fill the chunk from slot 0 and are no more than the rays already shaded from it, so a write of
 // the pass that shades that m-th ray lands on a slot <= m - 1: never beyond the rays of its own pass, whose loads precede
 // its stores (program order of one wave), and so never on a slot that is still queued or still to be screened -- those all
-// lie further on in the same order.  (A retired ray's slot may be overwritten: nothing reads it again.)
+// lie further on in the same order.  (A retired ray's slot may be overwritten: nothing reads it again.)  The one loop keeps
+// both premises: descriptors enter the queue in screening order and leave it oldest first, and a pass loads all its rays
+// before shade_ray's first store.
+// Occupancy: five waves per SIMD (<= 96 VGPRs, no scratch; k_shade's shade_ray alone takes 78).  The compiler left to itself
+// carries every per-chunk and per-group value through shade_ray in a register of its own and hoists whatever is invariant in
+// front of the loops (113-118 VGPRs).  So: a lane keeps ONE word across shade_ray, its descriptor; chunk in group, slot and
+// canonical index are taken from it again after the call (desc_again); a ray is addressed by the group's scalar base and a
+// 32-bit offset (streams_at); what is per chunk -- prefix, sample, seed, reference position -- is fetched once per group by
+// lanes 0 .. 7 and parked in the wave's LDS words (w_pre, w_meta: an LDS read where a ray needs it, which also takes the seed
+// and prefix loads off the screen stage's chain); the lane index is two instructions at each use (lane_again); the group scan
+// uses row shifts, which need no lane index; the light count is hidden from hoisting (uniform_again).  Six waves (80 VGPRs)
+// spill 60-84 bytes a lane: not built.  profiles/shade_wave_occupancy_ab.txt.
 constexpr int kSparseGroup = 8;
 constexpr uint32_t kWaveQueue = 128;
 static_assert(kWaveQueue >= 127 && (kWaveQueue & (kWaveQueue - 1)) == 0, "63 descriptors left by a shade pass + 64 of a screen pass; a ring indexed by masking");
 static_assert(kSparseGroup <= 256 && WG <= 256, "a descriptor is chunk in group << 16 | slot << 8 | canonical index");
+constexpr uint32_t kNoDesc = 0xFFFFFFFFu; // a lane of a shade pass without a ray (a descriptor is < kSparseGroup << 16)
+// The streams of a group of chunks, from the group's first slot: the wave addresses its rays by a scalar base and a 32-bit offset
+// (< kSparseGroup * WG), not by a 64-bit address per lane.  (The per-chunk words follow: slot0 is a multiple of WG.)
+__device__ __forceinline__ Streams streams_at(Streams st, size_t slot0) {
+	st.ray_o = reinterpret_cast<float4 *>(reinterpret_cast<char *>(st.ray_o) + slot0 * (st.o12 ? 12u : 16u));
+	st.hit = reinterpret_cast<float4 *>(reinterpret_cast<char *>(st.hit) + slot0 * (st.hit12 ? 12u : 16u));
+	st.ray_d += slot0; st.thr += slot0;
+	st.occ_o += slot0; st.occ_d += slot0; st.occ_e += slot0;
+	st.pfx += slot0 / WG;
+	return st;
+}
+// The same value, opaque to the compiler: what is derived from the copy is computed where it is used -- not kept from an earlier
+// use, nor computed once in front of the kernel's loops and carried through them in a register.
+__device__ __forceinline__ uint32_t desc_again(uint32_t desc) {
+	asm volatile("" : "+v"(desc));
+	return desc;
+}
+// (the lane's index in its wave, == threadIdx.x & 63 in a one-dimensional workgroup: two instructions at each use, no register between them)
+__device__ __forceinline__ uint32_t lane_again() {
+	uint32_t l;
+	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+	return l;
+}
+// (... and of a wave-uniform value)
+__device__ __forceinline__ uint32_t uniform_again(uint32_t u) {
+	asm volatile("" : "+s"(u));
+	return u;
+}
+#ifndef POLARIS_SHADE_WAVE_WAVES
+#define POLARIS_SHADE_WAVE_WAVES 5
+#endif
 template <bool LDS>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4))) // (fits 128 VGPRs without a spill: 4 waves per SIMD instead of 3)
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(POLARIS_SHADE_WAVE_WAVES, POLARIS_SHADE_WAVE_WAVES)))
 void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
 	constexpr int G = kSparseGroup;
 	__shared__ ShadeLds lds;
@@ -1492,105 +1538,136 @@ void k_shade_wave(Streams st, SceneDev Sg, ShadeArgs A, uint32_t num_chunks) {
 	__shared__ uint32_t w_emit[4][G][8]; // per wave and chunk of its group: the emit mask
 	__shared__ uint32_t w_cnt[4][G][3];  // ... indirect rays, shadow rays, event counters (hits | misses << 10 | emitter hits << 20)
 	__shared__ uint32_t w_queue[4][kWaveQueue]; // per wave: the survivors' descriptors, oldest first from q_head
+	__shared__ uint32_t w_pre[4][G];     // per wave: the live rays of its group in front of each chunk
+	__shared__ uint32_t w_meta[4][G][4]; // per wave and chunk of its group: sample, shade seed, position of its first ray in the reference's buffer
 	if (threadIdx.x == 0) wg_cursor = 0;
 	for (uint32_t i = threadIdx.x; i < 4 * G * 8; i += WG) (&w_emit[0][0][0])[i] = 0;
 	for (uint32_t i = threadIdx.x; i < 4 * G * 3; i += WG) (&w_cnt[0][0][0])[i] = 0;
 	const SceneT<LDS> S = stage_scene<LDS>(Sg, lds); // (ends in the __syncthreads that also publishes the LDS words above)
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const unsigned long long below = (1ull << lane) - 1ull;
-	const uint32_t wgs_per_sample = A.Npad / WG;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (the wave's LDS rows at scalar offsets)
 	const uint32_t num_groups = (num_chunks + G - 1) / G;
 	for (;;) {
+		const uint32_t lane = lane_again();
 		uint32_t c = 0;
 		if (lane == 0) c = atomicAdd(&wg_cursor, 1u);
 		const uint32_t group = blockIdx.x + __builtin_amdgcn_readfirstlane(c) * gridDim.x;
 		if (group >= num_groups) break;
 		const uint32_t chunk0 = group * G;
-		// lane k < G holds chunk k's live count and the group's exclusive prefix over them
-		const uint32_t my_cnt = (lane < (uint32_t)G && chunk0 + lane < num_chunks) ? st.cnt_ray[chunk0 + lane] : 0u;
-		uint32_t incl = my_cnt;
-#pragma unroll
-		for (int d = 1; d < G; d <<= 1) {
-			const uint32_t up = __shfl_up(incl, d);
-			if ((int)lane >= d) incl += up;
-		}
-		const uint32_t excl = incl - my_cnt;
-		const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, G - 1);
-		uint32_t q_head = 0, q_tail = 0; // descriptors taken from / appended to the wave's queue so far (uniform)
-		// ---- stage 2: the oldest (up to) 64 survivors through shade_ray ---------------------------------
-		auto shade_pass = [&]() {
-			const uint32_t n = min(q_tail - q_head, 64u);
-			const bool live = lane < n;
-			// (the descriptors were written by other lanes of this wave: LDS operations of one wave execute in order, and the
-			// fences keep the compiler from moving the loads over the stores)
+		const Streams sg = streams_at(st, (size_t)chunk0 * WG); // the group's first slot: a ray of the group is sg.*[desc >> 8]
+		// Lane k < G takes chunk k's live count, sample, seed and reference position in one round trip; the counts are scanned into the
+		// group's exclusive prefix.  All of it is parked in the wave's LDS words: a ray finds its chunk's by k, and nothing per chunk
+		// stays in a register across the passes below.
+		uint32_t total;
+		{
+			const bool has = lane < (uint32_t)G && chunk0 + lane < num_chunks;
+			uint32_t my_cnt = 0, s = 0, seed = 0, pfx0 = 0;
+			if (has) {
+				s = (chunk0 + lane) / uniform_again(A.Npad / WG);
+				my_cnt = st.cnt_ray[chunk0 + lane];
+				seed = A.seeds[(size_t)(A.first_sample + s) * A.seed_stride + 1 + A.bounce];
+				pfx0 = sg.pfx[lane];
+			}
+			// (row shifts: lane l adds lane l - d's value, 0 where there is none -- no lane index is computed, so none is kept)
+			uint32_t incl = my_cnt;
+			incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false); // row_shr:1
+			incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false); // row_shr:2
+			incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false); // row_shr:4
+			static_assert(G == 8, "three steps scan lanes 0 .. 7 of a row of 16");
+			if (lane < (uint32_t)G) {
+				w_pre[wave][lane] = incl - my_cnt;
+				w_meta[wave][lane][0] = s; w_meta[wave][lane][1] = seed; w_meta[wave][lane][2] = pfx0;
+			}
+			total = (uint32_t)__builtin_amdgcn_readlane((int)incl, G - 1);
+			// (read below by other lanes of this wave: LDS operations of one wave execute in order, and the fences keep the compiler
+			// from moving the loads over the stores)
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 			__builtin_amdgcn_wave_barrier();
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-			const uint32_t desc = live ? w_queue[wave][(q_head + lane) & (kWaveQueue - 1)] : 0u;
-			q_head += n;
-			const uint32_t k = desc >> 16, idx = (desc >> 8) & 255u, canon = desc & 255u;
-			const uint32_t chunk = chunk0 + k;
-			const size_t base = (size_t)chunk * WG;
-			ShadeOut R;
-			R.emit_ind = false;
-			R.hit = R.miss = R.emit = 0;
-			if (live) {
-				const uint32_t s = chunk / wgs_per_sample;
-				const uint32_t seed = A.seeds[(size_t)(A.first_sample + s) * A.seed_stride + 1 + A.bounce];
-				shade_ray(S, A, s, seed, st.pfx[chunk] + canon, st.ray_d[base + idx], st.thr[base + idx], load_hit(st, base + idx), R, [&](float4 oo, float4 od, float4 oe) {
-					const size_t d = base + atomicAdd(&w_cnt[wave][k][1], 1u); // (shadow rays have no order to keep)
-					st.occ_o[d] = oo; st.occ_d[d] = od; st.occ_e[d] = oe;
-				});
-			}
-			if (R.emit_ind) {
-				atomicOr(&w_emit[wave][k][canon >> 5], 1u << (canon & 31));
-				const size_t d = base + atomicAdd(&w_cnt[wave][k][0], 1u); // any free slot of the ray's chunk: the order is in thr.w
-				R.thr.w = ibits((int)canon);
-				store_ray_o(st, d, R.ro); st.ray_d[d] = R.rd; st.thr[d] = R.thr;
-			}
-			if (live && (R.hit | R.miss | R.emit) != 0) atomicAdd(&w_cnt[wave][k][2], R.hit | (R.miss << 10) | (R.emit << 20));
-		};
-		// ---- stage 1: screen the group's live rays, 64 at a time ---------------------------------------
-		for (uint32_t j = 0; j < total; j += 64) {
-			const uint32_t r = j + lane; // the group's r-th live ray
-			uint32_t k = 0, first = 0; // its chunk within the group, and the rays of the group before that chunk
+		}
+		uint32_t q_head = 0, q_tail = 0; // descriptors taken from / appended to the wave's queue so far (uniform)
+		uint32_t j = 0;                  // rays of the group screened so far (uniform)
+		for (;;) {
+			const uint32_t queued = q_tail - q_head;
+			if (j < total && queued < 64u) {
+				// ---- stage 1: screen the group's next 64 live rays -------------------------------------------
+				const uint32_t r = j + lane_again(); // the group's r-th live ray
+				j += 64;
+				uint32_t k = 0, first = 0; // its chunk within the group, and the rays of the group before that chunk
 #pragma unroll
-			for (int q = 1; q < G; q++) {
-				const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)excl, q);
-				if (r >= e) { k = q; first = e; }
-			}
-			bool keep = false;
-			uint32_t desc = 0;
-			if (r < total) {
-				const uint32_t chunk = chunk0 + k, idx = r - first;
-				const size_t base = (size_t)chunk * WG;
-				const float4 t4 = st.thr[base + idx];
-				const uint4 m0 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2], m1 = reinterpret_cast<const uint4 *>(A.emask_in)[(size_t)chunk * 2 + 1];
-				const uint32_t pmask[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-				const uint32_t canon = canonical_index(pmask, (uint32_t)fbits(t4.w));
-				uint32_t fate = kFateLive;
-				if (A.prefilter) {
-					const uint32_t seed = A.seeds[(size_t)(A.first_sample + chunk / wgs_per_sample) * A.seed_stride + 1 + A.bounce];
-					fate = shade_fate(S, A, seed, [&]() { return st.pfx[chunk] + canon; }, t4, load_hit_word(st, base + idx));
+				for (int q = 1; q < G; q++) {
+					const uint32_t e = w_pre[wave][q];
+					if (r >= e) { k = q; first = e; }
 				}
-				if (fate == kFateRejected) atomicAdd(&w_cnt[wave][k][2], 1u); // one hit
-				keep = fate == kFateLive;
-				desc = k << 16 | idx << 8 | canon;
+				bool keep = false;
+				uint32_t desc = 0;
+				if (r < total) {
+					const uint32_t idx = r - first;
+					const uint32_t at = k * WG + idx; // (< G * WG: a 32-bit offset from the group's first slot)
+					const float4 t4 = sg.thr[at];
+					const uint4 *em = reinterpret_cast<const uint4 *>(A.emask_in) + (size_t)chunk0 * 2;
+					const uint4 m0 = em[k * 2], m1 = em[k * 2 + 1];
+					const uint32_t pmask[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+					const uint32_t canon = canonical_index(pmask, (uint32_t)fbits(t4.w));
+					uint32_t fate = kFateLive;
+					if (A.prefilter) {
+						fate = shade_fate(S, A, w_meta[wave][k][1], [&]() { return w_meta[wave][k][2] + canon; }, t4, load_hit_word(sg, at));
+					}
+					if (fate == kFateRejected) atomicAdd(&w_cnt[wave][k][2], 1u); // one hit
+					keep = fate == kFateLive;
+					desc = at << 8 | canon;
+				}
+				const unsigned long long mk = __ballot(keep);
+				const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u)); // kept rays below this lane
+				if (keep) w_queue[wave][(q_tail + rank) & (kWaveQueue - 1)] = desc;
+				q_tail += (uint32_t)__popcll(mk);
+			} else if (queued != 0u) {
+				// ---- stage 2: the oldest (up to) 64 survivors through shade_ray --------------------------------
+				const uint32_t n = min(queued, 64u);
+				// (the descriptors were written by other lanes of this wave: LDS operations of one wave execute in order, and the
+				// fences keep the compiler from moving the loads over the stores)
+				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+				__builtin_amdgcn_wave_barrier();
+				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				// The descriptor is ALL a lane keeps of its ray across shade_ray: chunk in group, slot and canonical index are taken
+				// from it again where they are wanted (desc_again hides the copy from the compiler's common subexpressions, which
+				// would otherwise carry every one of them through shade_ray in a register of its own).
+				const uint32_t ql = lane_again();
+				const uint32_t desc = ql < n ? w_queue[wave][(q_head + ql) & (kWaveQueue - 1)] : kNoDesc;
+				q_head += n;
+				ShadeOut R;
+				R.emit_ind = false;
+				R.hit = R.miss = R.emit = 0;
+				if (desc != kNoDesc) {
+					SceneT<LDS> Sp = S; // (what shade_ray derives from the light count is derived in the pass, not in front of the kernel's loops)
+					Sp.num_emissives = uniform_again(S.num_emissives);
+					const uint32_t k = desc >> 16, at = desc >> 8, canon = desc & 255u;
+					shade_ray(Sp, A, w_meta[wave][k][0], w_meta[wave][k][1], w_meta[wave][k][2] + canon, sg.ray_d[at], sg.thr[at], load_hit(sg, at), R, [&](float4 oo, float4 od, float4 oe) {
+						const uint32_t k2 = desc_again(desc) >> 16;
+						const uint32_t d = (k2 * WG + atomicAdd(&w_cnt[wave][k2][1], 1u)) & (G * WG - 1); // (shadow rays have no order to keep; the mask changes nothing: it tells the compiler the range)
+						sg.occ_o[d] = oo; sg.occ_d[d] = od; sg.occ_e[d] = oe;
+					});
+				}
+				const uint32_t k = desc_again(desc) >> 16, canon = desc_again(desc) & 255u; // (only read where the lane held a ray: R is empty otherwise)
+				if (R.emit_ind) {
+					atomicOr(&w_emit[wave][k][canon >> 5], 1u << (canon & 31));
+					const uint32_t d = (k * WG + atomicAdd(&w_cnt[wave][k][0], 1u)) & (G * WG - 1); // any free slot of the ray's chunk: the order is in thr.w
+					R.thr.w = ibits((int)canon);
+					store_ray_o(sg, d, R.ro); sg.ray_d[d] = R.rd; sg.thr[d] = R.thr;
+				}
+				if ((R.hit | R.miss | R.emit) != 0) atomicAdd(&w_cnt[wave][k][2], R.hit | (R.miss << 10) | (R.emit << 20));
+			} else {
+				break;
 			}
-			const unsigned long long mk = __ballot(keep);
-			if (keep) w_queue[wave][(q_tail + (uint32_t)__popcll(mk & below)) & (kWaveQueue - 1)] = desc;
-			q_tail += (uint32_t)__popcll(mk);
-			if (q_tail - q_head >= 64u) shade_pass();
 		}
-		if (q_tail != q_head) shade_pass();
 		// publish the group's chunks (LDS operations of one wave execute in order: the atomics above are done) and clear the wave's words
-		if (lane < (uint32_t)G && chunk0 + lane < num_chunks) {
-			st.cnt_ray[chunk0 + lane] = w_cnt[wave][lane][0];
-			st.cnt_occ[chunk0 + lane] = w_cnt[wave][lane][1];
-			st.wg_stat[chunk0 + lane] = w_cnt[wave][lane][2];
-			w_cnt[wave][lane][0] = 0; w_cnt[wave][lane][1] = 0; w_cnt[wave][lane][2] = 0;
+		const uint32_t pl = lane_again();
+		if (pl < (uint32_t)G && chunk0 + pl < num_chunks) {
+			st.cnt_ray[chunk0 + pl] = w_cnt[wave][pl][0];
+			st.cnt_occ[chunk0 + pl] = w_cnt[wave][pl][1];
+			st.wg_stat[chunk0 + pl] = w_cnt[wave][pl][2];
+			w_cnt[wave][pl][0] = 0; w_cnt[wave][pl][1] = 0; w_cnt[wave][pl][2] = 0;
 		}
-		for (uint32_t i = lane; i < (uint32_t)G * 8; i += 64) {
+		for (uint32_t i = pl; i < (uint32_t)G * 8; i += 64) {
 			if (chunk0 + i / 8 < num_chunks) A.emask_out[(size_t)chunk0 * 8 + i] = (&w_emit[wave][0][0])[i];
 			(&w_emit[wave][0][0])[i] = 0;
 		}

@@ -372,6 +372,7 @@ struct polaris_hip_tracer {
 	DevArray<unsigned long long> d_stats;
 	DevArray<float4> d_cam_o; // eye | FLT_MAX: the one origin record of every camera ray (launch_trace, camera)
 	int num_cus = 256;
+	int shade_wave_resident[2] = {5, 5}; // [LDS tables]: workgroups of k_shade_wave a CU holds at once (occupancy API, at creation)
 	DevArray<uint32_t> d_retag; // polaris_hip_update_materials: the class of every material node (a byte each), then the emissives' new nodes (grow-only)
 
 	// options: what a Trace plans from (trace_plan.h), and the rest
@@ -703,6 +704,14 @@ int trace_occupancy(polaris_hip_tracer *h, bool any_hit) {
 	return std::min(n, 8);
 }
 
+// Resident workgroups per CU of k_shade_wave<lds>: its persistent grid is exactly what the GPU holds at once (trace_plan.h, shade_wave_grid).
+int shade_wave_occupancy(bool lds) {
+	int n = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kShadeWave[lds].address(), WG, 0) != hipSuccess || n < 1) { (void)hipGetLastError(); n = POLARIS_SHADE_WAVE_WAVES; } // (no answer: the kernel's waves per SIMD = its four-wave workgroups per CU)
+	if (getenv("POLARIS_DEBUG")) fprintf(stderr, "[polaris] k_shade_wave<%d>: %d resident workgroups of %d threads per CU\n", (int)lds, n, (int)WG);
+	return std::min(n, 8);
+}
+
 // What a Trace's plan needs to know of the uploaded scene and of the device (trace_plan.h, which holds every rule): filled here only.
 TraceScene plan_scene(const polaris_hip_tracer *h) {
 	TraceScene s;
@@ -713,6 +722,7 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 	s.tri_bits = h->ds.scene.tri_bits;
 	s.packet_primary = h->packet_primary;
 	s.num_cus = h->num_cus;
+	for (int lds = 0; lds < 2; lds++) s.shade_wave_resident[lds] = h->shade_wave_resident[lds];
 	s.lens = h->camera.lens_on();
 	s.shutter = h->camera.shutter_on();
 	return s;
@@ -1096,6 +1106,7 @@ int polaris_hip_create(int device_index, polaris_hip_tracer **out) {
 	if (e == hipSuccess) {
 		hipDeviceProp_t p;
 		if (hipGetDeviceProperties(&p, device_index) == hipSuccess && p.multiProcessorCount > 0) h->num_cus = p.multiProcessorCount;
+		for (int lds = 0; lds < 2; lds++) h->shade_wave_resident[lds] = shade_wave_occupancy(lds != 0);
 	}
 	if (e == hipSuccess) e = h->ev_start.create(hipEventCreate);
 	if (e == hipSuccess) e = h->ev_stop.create(hipEventCreate);
@@ -1395,7 +1406,7 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 	else if (k == "traversal") h->opt.traversal = value != 0; // 0 = one ray per lane (k_intersect / k_occlusion), 1 = persistent waves with lane refill (k_trace)
 	else if (k == "shade_wave") h->opt.shade_wave = value != 0;
 	else if (k == "shade_wave_from") h->opt.shade_wave_from = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));
-	else if (k == "shade_wgs_per_cu") h->opt.shade_wgs_per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(value, 64));
+	else if (k == "shade_wgs_per_cu") h->opt.shade_wgs_per_cu = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
 	else if (k == "stage_lds") h->opt.stage_lds = value != 0;
 	else if (k == "shade_prefilter") h->opt.shade_prefilter = value != 0;
 	else if (k == "shade_sort") h->opt.shade_sort = (int)std::max<int64_t>(-1, std::min<int64_t>(value, POLARIS_MAX_BOUNCES));

@@ -33,7 +33,7 @@ struct TraceOptions {
 	int trace_grid = 0;       // 0 = auto; > 0: the persistent traversal grid in workgroups (A/B aid)
 	int stage_lds = 1;    // k_shade stages material nodes / lights / texture metadata in LDS when they fit
 	int shade_wave = 1;   // 1 = persistent wave-per-chunk shading (k_shade_wave), 0 = one workgroup per chunk (k_shade)
-	int shade_wgs_per_cu = 4;
+	int shade_wgs_per_cu = 0; // k_shade_wave's persistent grid in workgroups per CU; 0 = auto (what a CU holds of it: TraceScene::shade_wave_resident)
 	int shade_wave_from = -1; // first bounce shaded by k_shade_wave; -1 = automatic (plan_shading): the bounce AFTER Russian roulette
 	                          // starts thinning the chunks (min_bounces_for_rr + 1), or the roulette bounce itself where the prefilter
 	                          // thins its chunks and the launch is large; earlier bounces use k_shade
@@ -52,6 +52,7 @@ struct TraceScene {
 	uint32_t tri_bits = 0;            // 31: the hit word has no room for a shading class, nothing to sort by
 	bool packet_primary = true;       // option packet_primary, resolved by the upload where it is -1
 	int num_cus = 256;
+	int shade_wave_resident[2] = {5, 5}; // [LDS tables]: workgroups of k_shade_wave<..> a CU holds at once (occupancy API: 5 waves per SIMD)
 	bool lens = false;                // polaris_hip_set_lens is on: the camera rays start on the lens, each at its own origin
 	bool shutter = false;             // polaris_hip_set_shutter is on: each camera ray starts at the eye of its own time; plans exactly as `lens`
 };
@@ -96,7 +97,10 @@ inline size_t slot_bytes(uint32_t nee_bounces) { return 144 + 17 * (size_t)std::
 constexpr uint32_t kBatchPathBudget = 32u << 20;
 constexpr int64_t kMaxSamplesPerBatch = 4096; // of a caller-chosen samples_per_batch
 // Automatic shade_wave_from: a full batch must hold this many groups of kPlanSparseGroup chunks per CU for k_shade_wave to take the
-// roulette bounce itself (profiles/shade_sparse_ab.txt).
+// roulette bounce itself (profiles/shade_sparse_ab.txt).  The count is per CU, not per resident wave: at the
+// threshold a launch fills half of the 16 waves a CU held when it was measured, and two fifths of the 20 it holds at five waves per
+// SIMD (profiles/shade_wave_occupancy_ab.txt) -- it is the size below which k_shade's one workgroup per chunk was no slower, which the
+// kernel's residency does not move.  (The headline frame's launches hold 32 groups per CU: 2 per wave at 16 waves, 1.6 at 20.)
 constexpr uint32_t kWaveRouletteGroupsPerCu = 8;
 
 // The shade kernel of a bounce, in the order of the shade timers (one timer per kernel symbol): k_shade<.., FIRST> (camera rays),
@@ -179,11 +183,20 @@ struct TracePlan {
 		if (opt.trace_grid > 0) return std::min<uint32_t>(wgs, (uint32_t)opt.trace_grid); // (A/B aid: an absolute persistent grid)
 		return std::min<uint32_t>(wgs, (uint32_t)scene.num_cus * per_cu);
 	}
-	// k_shade_wave's grid: persistent waves pull groups of kPlanSparseGroup chunks: no more workgroups than the GPU holds at once (4 per
-	// CU at the kernel's register count) nor than there are groups for their 4 waves.
+	// k_shade_wave's grid: persistent waves pull groups of kPlanSparseGroup chunks: no more workgroups than the GPU holds at once (the
+	// occupancy of the variant the plan launches, asked of the runtime: 5 per CU at the kernel's 96 registers) nor than there are
+	// groups for their 4 waves -- and, below that, the FEWEST that leave no wave more groups than the full grid would: every wave then
+	// takes the same number.  A group is ~100 us of dependent round trips and a launch holds one or two per wave, so the launch lasts
+	// as long as its busiest wave: the headline frame's 8192 groups on all 5120 resident waves are two groups for three waves in five
+	// and one for the rest -- measured no faster, on one card 0.1 ms per frame slower, than 4096 waves with two each
+	// (profiles/shade_wave_occupancy_ab.txt), which is what this rule gives there (two rounds: 1024 workgroups), the registers the
+	// fifth wave would hold left to the other batch's kernels.  Option shade_wgs_per_cu > 0 (A/B aid): that many per CU, as given.
 	uint32_t shade_wave_grid(uint32_t wgs) const {
 		const uint32_t groups = (wgs + kPlanSparseGroup - 1) / kPlanSparseGroup;
-		return std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)scene.num_cus * (uint32_t)std::max(1, opt.shade_wgs_per_cu)));
+		if (opt.shade_wgs_per_cu > 0) return std::max(1u, std::min<uint32_t>((groups + 3) / 4, (uint32_t)scene.num_cus * (uint32_t)opt.shade_wgs_per_cu));
+		const uint32_t waves = 4u * (uint32_t)scene.num_cus * (uint32_t)std::max(1, scene.shade_wave_resident[staged]); // resident at once
+		const uint32_t rounds = std::max(1u, (groups + waves - 1) / waves); // groups of the busiest wave on the full grid
+		return std::max(1u, (groups + 4u * rounds - 1) / (4u * rounds));
 	}
 
 private:
