@@ -505,6 +505,68 @@ typedef struct PolarisVarianceParams {
 } PolarisVarianceParams;
 int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams *p);
 
+/* The display transform of polaris_hip_sync_framebuffer (no reference counterpart: the reference's is tonemapSimpleReinhard with the
+ * request's exposure and pow(1 / 2.2)).  Off by default (enabled = 0); with it off every sync runs and allocates exactly what it did,
+ * under the same kernel symbols.  With it on the sync's last step -- k_tonemap of the frame accumulator with the sync's weight, or of
+ * the TEMPORAL / DENOISED plane with weight 1 -- is replaced, over the request's rows, by
+ *   auto_exposure = 1:  k_meter   a 256-bin histogram of L = lum(rgb * weight) (Rec. 709, without the request's exposure) of the
+ *                                 pixels whose L is finite and >= 2^-16: 8 bins an octave over [2^-16, 2^16) taken from the float's
+ *                                 exponent and top three mantissa bits, L >= 2^16 in bin 255; integer atomics, exact in any schedule;
+ *                       k_expose  N = the metered count; the window is the pixels of rank [N low_permille / 1000,
+ *                                 max(N high_permille / 1000, that + 1)) in ascending bins (64-bit integers); avg = the window's mean of
+ *                                 the bins' log2 values e + log2(1 + (k + 1/2) / 8); target = clamp(log2(key) - avg + compensation_ev,
+ *                                 min_ev, max_ev); log2E = target at the first metered sync after a reset, else
+ *                                 log2E + (target - log2E) * adapt; E = exp2(log2E).  N = 0 (a black or all-NaN frame): the state
+ *                                 stays, E = exp2(log2E) with a state and 1 without;
+ *   always:             k_display per channel c = rgb * weight * request.exposure * E (E = 1 with auto_exposure = 0), the tone operator,
+ *                                 the transfer function, clamp to [0, 1], times 255, truncated.
+ * Everything runs on the device inside the sync: the exposure a sync meters is the exposure it displays with.  The exposure state
+ * (log2E and whether it is set) is reset by polaris_hip_resize and by a polaris_hip_set_display that changes a byte of the params; it
+ * survives set_camera, upload_scene and the in-place updates.  Metering looks at the rows of the request on this tracer only.
+ * REINHARD with srgb = 0 and auto_exposure = 0 gives k_tonemap's bytes bit for bit.  DESIGN.md 10l has the exact arithmetic.
+ * Tone operators, c -> m:  REINHARD c / (c + 1);  REINHARD_WHITE c (1 + c / white^2) / (1 + c);  ACES (Narkowicz's fit)
+ * c (2.51 c + 0.03) / (c (2.43 c + 0.59) + 0.14);  HABLE f(c) / f(white), f(x) = (x (0.15 x + 0.05) + 0.004) / (x (0.15 x + 0.5) + 0.06)
+ * - 0.02 / 0.3.  Transfer, m -> [0, 1]:  srgb = 0 pow(m, 1 / 2.2);  srgb = 1 the sRGB OETF, 12.92 m up to 0.0031308, else
+ * 1.055 pow(m, 1 / 2.4) - 0.055.
+ * A field out of range is POLARIS_E_BAD_ARGUMENT and leaves the state unchanged: enabled, srgb, auto_exposure 0 or 1; tone_operator
+ * 0..3; white within [1e-3, 1e6] (looked at by REINHARD_WHITE and HABLE, checked always); with auto_exposure = 1 also key within
+ * [1e-6, 1e6], compensation_ev, min_ev and max_ev within [-24, 24] with min_ev <= max_ev, low_permille < high_permille <= 1000 and
+ * adapt within (0, 1].  With enabled = 0 no other field is looked at and any two off states are equal; with auto_exposure = 0 the
+ * metering fields are not looked at.  A call with identical bytes does nothing.  polaris_amd/ctypes_api.py DISPLAY_DEFAULTS has the
+ * suggested settings.  Set struct_size = sizeof(PolarisDisplayParams). */
+#define POLARIS_TONE_REINHARD       0
+#define POLARIS_TONE_REINHARD_WHITE 1
+#define POLARIS_TONE_ACES           2
+#define POLARIS_TONE_HABLE          3
+typedef struct PolarisDisplayParams {
+	uint32_t struct_size;       /* sizeof(PolarisDisplayParams) */
+	uint32_t enabled;           /* 0 = off (default): the sync ends with k_tonemap */
+	uint32_t tone_operator;     /* POLARIS_TONE_* */
+	uint32_t srgb;              /* 0: pow(1 / 2.2), 1: the sRGB OETF */
+	float    white;             /* the radiance mapped to 1 by REINHARD_WHITE and HABLE */
+	uint32_t auto_exposure;     /* 1: meter the frame and multiply by the metered exposure E */
+	float    key;               /* the luminance the metered window's log-average is mapped to (0.18: middle grey) */
+	float    compensation_ev;   /* added to the target log2 exposure */
+	uint32_t low_permille;      /* the metered window: the pixels between these two quantiles of luminance */
+	uint32_t high_permille;
+	float    min_ev, max_ev;    /* the target log2 exposure is clamped to [min_ev, max_ev] */
+	float    adapt;             /* the fraction of the way to the target one sync moves (1: snap) */
+} PolarisDisplayParams;
+int polaris_hip_set_display(polaris_hip_tracer *h, const PolarisDisplayParams *p);
+
+/* What the last sync with auto-exposure on metered: n_metered pixels, the window's mean log2 luminance avg, the state's log2E after
+ * the sync and the exposure E it displayed with; valid = 0: nothing has been metered since the last reset (E = 1).  histogram (may be
+ * NULL): the 256 counts of that sync.  POLARIS_E_BAD_ARGUMENT before any such sync since the last reset of the exposure state, or
+ * with out null or another struct_size. */
+typedef struct PolarisExposureInfo {
+	uint32_t struct_size;       /* sizeof(PolarisExposureInfo) */
+	uint32_t valid;
+	uint64_t n_metered;
+	float    avg, log2E, E;
+	uint32_t reserved;
+} PolarisExposureInfo;
+int polaris_hip_read_exposure(polaris_hip_tracer *h, PolarisExposureInfo *out, uint32_t histogram[256]);
+
 /* frame_w*frame_h*4 bytes RGBA8 (pipeline.go:226-232). */
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes);
 
@@ -577,6 +639,17 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
 int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
                                 uint32_t block_y, uint32_t block_h, uint32_t samples, float exposure, const PolarisDenoiseParams *p,
                                 const PolarisVarianceParams *v, float *variance, float *denoised, uint8_t *rgba);
+
+/* Test entry of the display stage on a caller plane: plane is a W x H float4 plane (rgb | unused); the rows [block_y, block_y + block_h)
+ * are metered (p->auto_exposure) with weight, exposed and displayed with weight and exposure into rgba (W x H x 4 bytes) -- the
+ * launches k_meter, k_expose, k_display of a displayed polaris_hip_sync_framebuffer.  prev_log2E (may be NULL): the exposure state the
+ * sync starts from, as left by an earlier metered sync; NULL: none, as after a reset.  rgba is in / out: its other rows come back as
+ * given.  histogram (256 counts; may be NULL) and info (may be NULL; its struct_size set) are what polaris_hip_read_exposure would
+ * return after the sync; with auto_exposure = 0 the counts are 0 and info is valid = 0, E = 1.  p->enabled must be 1.  Uses buffers
+ * of its own; no state of the tracer is read or changed. */
+int polaris_hip_display_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h,
+                               float weight, float exposure, const PolarisDisplayParams *p, const float *prev_log2E, uint8_t *rgba,
+                               uint32_t histogram[256], PolarisExposureInfo *info);
 
 /* Test entry of the temporal reprojection on caller planes: history (rgb | count), prev_guide, prev_albedo seen under the camera
  * (prev_eye, prev_frustum), and the current guide, albedo under (eye, frustum), all W x H float4 planes; the PRIOR plane of every
@@ -804,7 +877,8 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * per-path radiance), "resolve", "aggregate", "tonemap", "gbuffer" and "denoise" (polaris_hip_set_denoise), "reproject" and "temporal"
  * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance), "instance_extent",
  * "repad" and "refit_top" (polaris_hip_update_instances), "tri_records" and "refit_mesh" (polaris_hip_update_vertices, which runs the
- * former three as well), "retag" (polaris_hip_update_materials). */
+ * former three as well), "retag" (polaris_hip_update_materials), "meter", "expose" and "display" (polaris_hip_set_display: with
+ * it on "tonemap" does not run in a sync). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

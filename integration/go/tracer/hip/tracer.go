@@ -529,6 +529,85 @@ func (tr *Tracer) SetVariance(p VarianceParams) error {
 	return tr.check(C.polaris_hip_set_variance(tr.handle, &c))
 }
 
+// ToneOperator is the display transform's tone curve (POLARIS_TONE_*, include/polaris_hip.h).
+type ToneOperator uint32
+
+const (
+	ToneReinhard ToneOperator = iota
+	ToneReinhardWhite
+	ToneACES
+	ToneHable
+)
+
+// DisplayParams is the display transform of SyncFramebuffer (PolarisDisplayParams, include/polaris_hip.h; DESIGN.md section 10l):
+// the tone operator, the transfer function and, with AutoExposure, the frame's own metered exposure.  Enabled = false is off (the
+// default): the sync ends with the reference's tone-map.
+type DisplayParams struct {
+	Enabled        bool
+	ToneOperator   ToneOperator
+	SRGB           bool    // the sRGB transfer function instead of pow(1 / 2.2)
+	White          float32 // the radiance ToneReinhardWhite and ToneHable map to 1
+	AutoExposure   bool
+	Key            float32 // the luminance the metered window's log-average is mapped to
+	CompensationEV float32
+	LowPermille    uint32 // the metered window: the pixels between these two quantiles of luminance
+	HighPermille   uint32
+	MinEV, MaxEV   float32
+	Adapt          float32 // the fraction of the way to the metered exposure one sync moves, (0, 1]
+}
+
+var DefaultDisplay = DisplayParams{Enabled: true, ToneOperator: ToneReinhard, White: 4, Key: 0.18, LowPermille: 500, HighPermille: 950,
+	MinEV: -16, MaxEV: 16, Adapt: 1}
+
+// SetDisplay turns the display transform on or off.  With AutoExposure every SyncFramebuffer meters the rows it syncs and displays
+// them with the metered exposure times the request's; the exposure state adapts across camera moves, scene uploads and in-place
+// updates and is reset by a resize and by a SetDisplay that changes a field.  The accumulators stay the reference result.
+func (tr *Tracer) SetDisplay(p DisplayParams) error {
+	b := func(v bool) C.uint32_t {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	var c C.PolarisDisplayParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.enabled = b(p.Enabled)
+	c.tone_operator = C.uint32_t(p.ToneOperator)
+	c.srgb = b(p.SRGB)
+	c.white = C.float(p.White)
+	c.auto_exposure = b(p.AutoExposure)
+	c.key = C.float(p.Key)
+	c.compensation_ev = C.float(p.CompensationEV)
+	c.low_permille = C.uint32_t(p.LowPermille)
+	c.high_permille = C.uint32_t(p.HighPermille)
+	c.min_ev = C.float(p.MinEV)
+	c.max_ev = C.float(p.MaxEV)
+	c.adapt = C.float(p.Adapt)
+	return tr.check(C.polaris_hip_set_display(tr.handle, &c))
+}
+
+// ExposureInfo is what the last SyncFramebuffer with auto-exposure on metered (PolarisExposureInfo).
+type ExposureInfo struct {
+	Valid    bool
+	Metered  uint64  // pixels with a finite luminance of at least 2^-16
+	Avg      float32 // the window's mean log2 luminance
+	Log2E, E float32 // the exposure state after the sync, and the exposure it displayed with
+}
+
+// ReadExposure returns the exposure of the last metered sync and, if histogram is not nil, its 256 luminance counts.
+func (tr *Tracer) ReadExposure(histogram *[256]uint32) (ExposureInfo, error) {
+	var c C.PolarisExposureInfo
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	var h *C.uint32_t
+	if histogram != nil {
+		h = (*C.uint32_t)(unsafe.Pointer(&histogram[0]))
+	}
+	if err := tr.check(C.polaris_hip_read_exposure(tr.handle, &c, h)); err != nil {
+		return ExposureInfo{}, err
+	}
+	return ExposureInfo{Valid: c.valid != 0, Metered: uint64(c.n_metered), Avg: float32(c.avg), Log2E: float32(c.log2E), E: float32(c.E)}, nil
+}
+
 // ReadFrameBuffer is what opencl.SaveFrameBuffer reads (tracer/opencl/pipeline.go:226-232).
 func (tr *Tracer) ReadFrameBuffer(pix []uint8) error {
 	if len(pix) == 0 {

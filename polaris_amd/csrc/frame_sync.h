@@ -3,7 +3,7 @@
 // whether an AOV can be read (SyncState::aov_refusal).
 //
 // No HIP here and no device pointer: FrameSync in polaris_hip.hip owns the planes and pairs every transition with the frees and
-// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d and 10k describe the features.
+// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d, 10k and 10l describe the features.
 #pragma once
 
 #include <cstdint>
@@ -52,9 +52,11 @@ struct InstTable {
 // option "vertex_motion" on a scene uploaded with "vertex_update"; it is in effect only with object motion in effect.
 struct SyncFeatures {
 	bool denoise = false, temporal = false, variance = false, motion = false, deform = false;
+	bool display = false, auto_exposure = false; // polaris_hip_set_display: the sync's last step is the display stage, metered or not
 	bool any() const { return denoise || temporal || variance; }
 	bool motion_on() const { return motion && temporal; }
 	bool deform_on() const { return deform && motion_on(); }
+	bool metered() const { return display && auto_exposure; }
 };
 
 class SyncState {
@@ -168,10 +170,11 @@ public:
 	}
 };
 
-// ---- what a sync with features f does under state v (f.any(); the plain sync is one tone-map of the accumulator and asks nothing)
+// ---- what a sync with features f does under state v (f.any(); the plain sync is plan_tail's steps over the accumulator and asks nothing)
 enum class SyncSource { Accumulator, Temporal, Denoised }; // the accumulator is read with the sync's weight, the other two with weight 1
-enum class SyncStep { Temporal, Variance, Denoise, DenoiseVariance, Tonemap };
-constexpr const char *kSyncStepTimer[] = {"temporal", "variance", "denoise", "denoise_variance", "tonemap"}; // one timer per kernel symbol
+enum class SyncStep { Temporal, Variance, Denoise, DenoiseVariance, Tonemap, Meter, Expose, Display };
+constexpr const char *kSyncStepTimer[] = {"temporal", "variance", "denoise", "denoise_variance", "tonemap", "meter", "expose", "display"}; // one timer per kernel symbol
+constexpr int kMaxSyncSteps = 6; // temporal, variance, a filter and the display stage's three
 struct SyncPlan {
 	uint32_t need = 0;      // planes that must exist (allocated on first use)
 	uint32_t clear = 0;     // of those, cleared first: the rows no sync under this camera reaches must read as "no history"
@@ -179,10 +182,21 @@ struct SyncPlan {
 	bool prior = false;     // PRIOR is stale: recomputed from the history (none: cleared) by kReproject[m2][motion]
 	bool history = false, m2 = false, motion = false;
 	bool deform = false;    // the history has a snapshot of the vertices: kReprojectDeform[m2] in kReproject's place
-	SyncStep steps[4] = {}; // the timed steps in launch order
+	SyncStep steps[kMaxSyncSteps] = {}; // the timed steps in launch order
 	int n_steps = 0;
 	SyncSource color = SyncSource::Accumulator, tonemap = SyncSource::Accumulator; // what the filter reads | what the tone-map reads (the filter's output, or its input where none runs)
 };
+// The steps that turn the sync's source into bytes, appended to steps[n]: the tone-map, or with the display stage on
+// Meter and Expose (auto-exposure) and Display.  They read no plane of their own: the histogram and the exposure state are not
+// frame-sized and belong to the display stage's owner.  The plain sync (no other feature) runs these steps alone.
+inline int plan_tail(const SyncFeatures &f, SyncStep *steps, int n) {
+	if (!f.display) steps[n++] = SyncStep::Tonemap;
+	else {
+		if (f.auto_exposure) { steps[n++] = SyncStep::Meter; steps[n++] = SyncStep::Expose; }
+		steps[n++] = SyncStep::Display;
+	}
+	return n;
+}
 inline SyncPlan plan_sync(const SyncFeatures &f, const SyncState &v) {
 	SyncPlan p;
 	p.need = planes(kGuide, kAlbedo) | (f.motion_on() ? planes(kInst) : 0) | (f.deform_on() ? planes(kHit) : 0) | (f.denoise ? planes(kDnOut, kDnPing, kDnPong) : 0) |
@@ -199,7 +213,7 @@ inline SyncPlan plan_sync(const SyncFeatures &f, const SyncState &v) {
 	} else if (f.variance) p.clear_new = planes(kVaOut);
 	if (f.variance) p.steps[p.n_steps++] = SyncStep::Variance;
 	if (f.denoise) p.steps[p.n_steps++] = f.variance ? SyncStep::DenoiseVariance : SyncStep::Denoise;
-	p.steps[p.n_steps++] = SyncStep::Tonemap;
+	p.n_steps = plan_tail(f, p.steps, p.n_steps);
 	p.tonemap = f.denoise ? SyncSource::Denoised : p.color;
 	return p;
 }

@@ -88,6 +88,13 @@ const auto kDenoise = POLARIS_VARIANT(k_denoise);
 const auto kTemporal = POLARIS_VARIANT(k_temporal);
 const auto kVariance = POLARIS_VARIANT(k_variance);
 const auto kDenoiseVariance = POLARIS_VARIANT(k_denoise_variance);
+// polaris_hip_set_display (display.h): k_display<OP, SRGB>: [tone operator][srgb]
+const auto kMeter = POLARIS_VARIANT(k_meter);
+const auto kExpose = POLARIS_VARIANT(k_expose);
+const decltype(POLARIS_VARIANT(k_display<0, false>)) kDisplay[4][2] = {
+	{POLARIS_VARIANT(k_display<0, false>), POLARIS_VARIANT(k_display<0, true>)}, {POLARIS_VARIANT(k_display<1, false>), POLARIS_VARIANT(k_display<1, true>)},
+	{POLARIS_VARIANT(k_display<2, false>), POLARIS_VARIANT(k_display<2, true>)}, {POLARIS_VARIANT(k_display<3, false>), POLARIS_VARIANT(k_display<3, true>)}};
+static_assert(POLARIS_TONE_REINHARD == 0 && POLARIS_TONE_REINHARD_WHITE == 1 && POLARIS_TONE_ACES == 2 && POLARIS_TONE_HABLE == 3, "kDisplay spells OP as a number");
 // polaris_hip_update_instances (instance_update.h)
 const auto kInstanceExtent = POLARIS_VARIANT(k_instance_extent);
 const auto kRepad = POLARIS_VARIANT(k_repad);

@@ -31,6 +31,7 @@
 
 #include "builtin_probe.h"
 #include "denoise.h"
+#include "display.h"
 #include "scene_layout.h"
 #include "shading.h"
 #include "temporal.h"
@@ -1908,6 +1909,88 @@ __global__ __launch_bounds__(WG) void k_tonemap(const float4 *acc, uchar4 *fb, u
 	if (i >= n) return;
 	const float4 a = acc[i];
 	fb[i] = make_uchar4(tonemap_byte(a.x * weight * exposure), tonemap_byte(a.y * weight * exposure), tonemap_byte(a.z * weight * exposure), 255);
+}
+
+// ---- the display stage (display.h).  What the three kernels share on the device: the histogram of the last metered
+// sync, the bins' log2 values, the exposure state with what k_expose computed, and the 1.0f a display without auto-exposure reads as E.
+struct DpDevice {
+	uint32_t hist[kDpBins];
+	float value[kDpBins];
+	DpExposure s;
+	float one;
+};
+
+// The luminance histogram of n pixels of `acc` (rgb * weight): one 256-bin histogram per workgroup in LDS, whose non-zero bins are added
+// to d->hist (cleared on the stream before the launch).  Integer counts: exact whatever the grid and the schedule.  Any grid: the
+// workgroups stride over the pixels, four loads in flight per thread.
+constexpr int kMeterUnroll = 4;
+__global__ __launch_bounds__(WG) void k_meter(const float4 *acc, uint32_t n, float weight, DpDevice *d) {
+	__shared__ uint32_t bins[kDpBins];
+	static_assert(kDpBins == WG, "one bin per thread below");
+	bins[threadIdx.x] = 0u;
+	__syncthreads();
+	const uint32_t stride = gridDim.x * WG;
+	for (uint32_t i0 = blockIdx.x * WG + threadIdx.x; i0 < n; i0 += stride * kMeterUnroll) {
+		float4 a[kMeterUnroll];
+#pragma unroll
+		for (int k = 0; k < kMeterUnroll; k++) {
+			const uint32_t i = i0 + (uint32_t)k * stride;
+			a[k] = i < n ? acc[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // (a zero is not metered)
+		}
+#pragma unroll
+		for (int k = 0; k < kMeterUnroll; k++) {
+			const int b = dp_bin(dp_lum(a[k].x, a[k].y, a[k].z, weight));
+			if (b >= 0) atomicAdd(&bins[b], 1u);
+		}
+	}
+	__syncthreads();
+	const uint32_t c = bins[threadIdx.x];
+	if (c) atomicAdd(&d->hist[threadIdx.x], c);
+}
+
+// The exposure of this sync from the histogram, one wave.  Lane l holds the bins [4 l, 4 l + 4): the 64 lane sums are scanned in LDS
+// (integers: exact), every lane writes its bins' terms (display.h dp_window_term), and lane 0 adds the 256 terms in ascending bins
+// and finishes (dp_exposure), so the result is the host restatement's bit for bit.
+__global__ __launch_bounds__(64) void k_expose(DpDevice *d, DpMeter m) {
+	__shared__ unsigned long long scan[64];
+	__shared__ float term[kDpBins];
+	const uint32_t l = threadIdx.x;
+	uint32_t c[4];
+	unsigned long long mine = 0;
+	for (int k = 0; k < 4; k++) { c[k] = d->hist[4 * l + k]; mine += c[k]; }
+	scan[l] = mine;
+	__syncthreads();
+	for (uint32_t step = 1; step < 64; step <<= 1) { // inclusive scan of the lane sums
+		const unsigned long long below = l >= step ? scan[l - step] : 0ull;
+		__syncthreads();
+		scan[l] += below;
+		__syncthreads();
+	}
+	const uint64_t N = scan[63];
+	uint64_t lo = 0, hi = 1, cum = scan[l] - mine;
+	if (N) dp_window(N, m, lo, hi);
+	for (int k = 0; k < 4; k++) {
+		term[4 * l + k] = dp_window_term(cum, c[k], lo, hi, d->value[4 * l + k]);
+		cum += c[k];
+	}
+	__syncthreads();
+	if (l != 0) return;
+	DpExposure s = d->s;
+	dp_exposure(N, lo, hi, term, m, s);
+	d->s = s;
+}
+
+// The bytes of n pixels of `acc`: rgb * weight * exposure * *E through tone operator OP and the transfer function (display.h dp_pixel).
+// E: the metered exposure (DpDevice::s.E), or the constant 1.0f (DpDevice::one) without auto-exposure.
+template <int OP, bool SRGB>
+__global__ __launch_bounds__(WG) void k_display(const float4 *acc, uchar4 *fb, uint32_t n, float weight, float exposure, const float *E, DpCurve curve) {
+	const uint32_t i = blockIdx.x * WG + threadIdx.x;
+	if (i >= n) return;
+	const float4 a = acc[i];
+	const float rgb[3] = {a.x, a.y, a.z};
+	uint8_t o[4];
+	dp_pixel<OP, SRGB>(rgb, weight, exposure, *E, curve, o);
+	fb[i] = make_uchar4(o[0], o[1], o[2], o[3]);
 }
 
 // polaris_hip_selftest_builtins (builtin_probe.h): inputs [first, first + count) of function fn, kSweepPerThread per thread.

@@ -103,6 +103,26 @@ struct DeviceScene {
 	MaterialUpdateState mup;
 };
 
+// The display stage of polaris_hip_sync_framebuffer (polaris_hip_set_display; display.h): its params and what its kernels
+// share on the device -- the histogram, the bins' values, the exposure state and the constant 1.0f -- allocated by the first displayed
+// sync and freed when the stage is turned off.  reset(): the next displayed sync starts from no exposure state.  Callers hold mu.
+struct DisplayStage {
+	PolarisDisplayParams p{sizeof(PolarisDisplayParams), 0, 0, 0, 0.0f, 0, 0.0f, 0.0f, 0, 0, 0.0f, 0.0f, 0.0f};
+	DevArray<DpDevice> dev;
+	DpDevice init{};      // what a reset uploads (kept here: the copy is asynchronous)
+	bool fresh = false;   // dev holds the values, the 1.0f and an exposure state no older than the last reset
+	bool metered = false; // a sync with auto-exposure on ran since the last reset (polaris_hip_read_exposure)
+	void reset() { fresh = metered = false; }
+	DpMeter meter() const { return DpMeter{p.low_permille, p.high_permille, dp_log2_key(p.key), p.compensation_ev, p.min_ev, p.max_ev, p.adapt}; }
+};
+// d->init: the bins' values, the 1.0f and the exposure state a sync starts from (prev_log2E = null: none).
+inline void dp_init(DpDevice &d, const float *prev_log2E) {
+	d = DpDevice{};
+	for (uint32_t b = 0; b < kDpBins; b++) d.value[b] = dp_bin_value(b);
+	d.one = d.s.E = 1.0f;
+	if (prev_log2E) { d.s.log2E = *prev_log2E; d.s.valid = 1u; }
+}
+
 // Everything behind the features of polaris_hip_sync_framebuffer: the parameters of denoising (polaris_hip_set_denoise),
 // temporal reuse across camera moves (_set_temporal) and variance guidance (_set_variance), the option "object_motion", every plane
 // they use and what of the planes is valid.  frame_sync.h holds the rules: nothing is allocated while its feature is off, the history
@@ -126,8 +146,12 @@ struct FrameSync {
 	DevArray<float4> vert_snap, de_table; // deformation table (temporal.h tp_deform_table), both grow-only
 	std::vector<float> de_table_host;
 	CameraFloats tp_hcam{};               // the history's camera
+	DisplayStage dp;                      // the sync's last step, with the features on or off (its state is not a plane: SyncState does not know it)
 
-	SyncFeatures features() const { return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0, opt_vertex_motion != 0 && scene_deformable}; }
+	SyncFeatures features() const {
+		return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0, opt_vertex_motion != 0 && scene_deformable,
+		        dp.p.enabled != 0, dp.p.enabled != 0 && dp.p.auto_exposure != 0};
+	}
 	void drop(uint32_t set) {
 		for (uint32_t p = 0; p < kNumPlanes4; p++)
 			if (set >> p & 1) pl[p].reset();
@@ -141,7 +165,7 @@ struct FrameSync {
 		if (swaps >> kInst & 1) std::swap(gb_inst, tp_hinst);
 		if (swaps) tp_hcam = cam;
 	}
-	void resized() { drop(v.resized()); }
+	void resized() { drop(v.resized()); dp.reset(); }
 	void camera_moved(const CameraFloats &old) { capture(v.camera_moved(features()), old); }
 	void scene_changed(const InstTable *next, const CameraFloats &cam) { capture(v.scene_changed(features(), next), cam); } // (upload_scene and the in-place updates, before they change the scene)
 	void set_temporal(const PolarisTemporalParams &p) {
@@ -1936,7 +1960,26 @@ struct SyncIo { // what the steps of a sync read and write: the rows [y0, y1) of
 	float4 *tp; const float4 *prior, *prior2, *guide, *albedo;
 	float4 *var, *ping, *pong, *out; uchar4 *fb;
 	uint32_t W, y0, y1; float exposure;
+	const DisplayStage *dp = nullptr; // with the display stage in the plan
 };
+
+// One of plan_tail's steps (frame_sync.h) on stream q over n pixels of src, read with weight w, into fb: the tone-map, or the display
+// stage's k_meter (behind the clear of its histogram), k_expose, k_display.
+constexpr uint32_t kMeterMaxGrid = 128; // k_meter's workgroups stride over the pixels, kMeterUnroll at a time: one flush of a histogram per workgroup
+void launch_tail_step(polaris_hip_tracer *h, hipStream_t q, SyncStep step, const float4 *src, float w, uchar4 *fb, size_t n, float exposure,
+                      const DisplayStage *D) {
+	const PolarisDisplayParams *p = D ? &D->p : nullptr; // (null: the plan has no display step)
+	DpDevice *d = D ? D->dev.get() : nullptr;
+	const char *timer = kSyncStepTimer[(int)step];
+	if (step == SyncStep::Tonemap) (void)launch(h, timer, q, kTonemap, grid_for(n), WG, 0, src, fb, (uint32_t)n, w, exposure);
+	else if (step == SyncStep::Meter) {
+		Timed t(h, timer, kMeter.symbol, q);
+		(void)hipMemsetAsync(d->hist, 0, sizeof d->hist, q);
+		kMeter.enqueue(std::min(grid_for((n + kMeterUnroll - 1) / kMeterUnroll), kMeterMaxGrid), WG, 0, q, src, (uint32_t)n, w, d);
+	} else if (step == SyncStep::Expose) (void)launch(h, timer, q, kExpose, 1u, 64, 0, d, D->meter());
+	else (void)launch(h, timer, q, kDisplay[p->tone_operator][p->srgb], grid_for(n), WG, 0, src, fb, (uint32_t)n, w, exposure,
+	                  p->auto_exposure ? &d->s.E : &d->one, dp_curve(p->white));
+}
 
 // The timed steps of a sync on stream q, in the plan's order (frame_sync.h plan_sync; caller holds mu): k_temporal into TEMPORAL, k_variance
 // into VARIANCE, the filter (variance-guided or not) over the plan's colour -- TEMPORAL with weight 1, or the accumulator with the sync's
@@ -1969,8 +2012,20 @@ void launch_steps(polaris_hip_tracer *h, hipStream_t q, const SyncPlan &P, const
 			atrous(timer, kDenoise.symbol, p.sigma_luminance, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoise.enqueue(grid, WG, 0, q, c, cw, io.guide, io.albedo, in, dst, W, y0, y1, it, last); });
 		else if (step == SyncStep::DenoiseVariance)
 			atrous(timer, kDenoiseVariance.symbol, 0.0f, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoiseVariance.enqueue(grid, WG, 0, q, c, cw, io.var, io.guide, io.albedo, in, dst, W, y0, y1, it, v.sigma_variance, last); });
-		else (void)launch(h, timer, q, kTonemap, grid, WG, 0, (filtered ? io.out : c) + off, io.fb + off, (uint32_t)n, filtered ? 1.0f : cw, io.exposure);
+		else launch_tail_step(h, q, step, (filtered ? io.out : c) + off, filtered ? 1.0f : cw, io.fb + off, n, io.exposure, io.dp);
 	}
+}
+
+// What a displayed sync needs on the device (caller holds mu; the main stream is idle): allocated at the first one, and after a reset
+// the bins' values, the 1.0f and an empty exposure state uploaded on the main stream.
+int ensure_display(polaris_hip_tracer *h) {
+	DisplayStage &D = h->fs.dp;
+	if (!D.dev) { HIP_TRY(h, D.dev.alloc(1)); D.fresh = false; }
+	if (D.fresh) return POLARIS_OK;
+	dp_init(D.init, nullptr);
+	HIP_TRY(h, hipMemcpyAsync(D.dev, &D.init, sizeof(DpDevice), hipMemcpyHostToDevice, h->stream));
+	D.fresh = true;
+	return POLARIS_OK;
 }
 
 // What polaris_hip_sync_framebuffer queues with denoising, temporal reuse or variance guidance on (caller holds mu; request checked), by
@@ -2012,7 +2067,7 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 	HIP_TRY(h, h->fa.join_merges(h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
 	launch_steps(h, h->stream, P, SyncIo{h->fa.frame, (float)(r->accumulated_samples + r->samples_per_pixel), weight, S.pl[kTpOut], S.pl[kTpPrior], S.pl[kTpPrior2],
 	                                     S.pl[kGuide], S.pl[kAlbedo], S.pl[kVaOut], S.pl[kDnPing], S.pl[kDnPong], S.pl[kDnOut], h->framebuffer, h->fa.W, r->block_y,
-	                                     r->block_y + r->block_h, r->exposure}, S.dn, S.va);
+	                                     r->block_y + r->block_h, r->exposure, f.display ? &S.dp : nullptr}, S.dn, S.va);
 	return POLARIS_OK;
 }
 
@@ -2085,6 +2140,45 @@ int polaris_hip_set_variance(polaris_hip_tracer *h, const PolarisVarianceParams 
 	return POLARIS_OK;
 }
 
+int polaris_hip_set_display(polaris_hip_tracer *h, const PolarisDisplayParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisDisplayParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_display: null params or struct_size != %zu", sizeof(PolarisDisplayParams));
+	if (dp_check(*p))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_display: enabled %u, srgb %u, auto_exposure %u (0 or 1), tone_operator %u (0..3), white %g ([%g, %g]), key %g "
+		            "([%g, %g]), compensation_ev %g, min_ev %g <= max_ev %g ([%g, %g]), permille %u < %u (<= 1000), adapt %g ((0, 1])", p->enabled, p->srgb,
+		            p->auto_exposure, p->tone_operator, (double)p->white, (double)kDpMinWhite, (double)kDpMaxWhite, (double)p->key, (double)kDpMinKey,
+		            (double)kDpMaxKey, (double)p->compensation_ev, (double)p->min_ev, (double)p->max_ev, -(double)kDpMaxEv, (double)kDpMaxEv, p->low_permille,
+		            p->high_permille, (double)p->adapt);
+	DisplayStage &D = h->fs.dp;
+	if ((!p->enabled && !D.p.enabled) || memcmp(p, &D.p, sizeof *p) == 0) return POLARIS_OK; // (any two off states are equal)
+	if (!p->enabled) { // its device state goes
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every display launch is on the main stream)
+		D.dev.reset();
+	}
+	D.p = *p;
+	D.reset();
+	return POLARIS_OK;
+}
+
+int polaris_hip_read_exposure(polaris_hip_tracer *h, PolarisExposureInfo *out, uint32_t histogram[256]) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!out || out->struct_size != sizeof(PolarisExposureInfo))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "read_exposure: null info or struct_size != %zu", sizeof(PolarisExposureInfo));
+	DisplayStage &D = h->fs.dp;
+	if (!D.metered || !D.dev) return fail(h, POLARIS_E_BAD_ARGUMENT, "read_exposure: no sync with auto-exposure on since the exposure state was last reset");
+	HIP_TRY(h, hipSetDevice(h->device));
+	DpDevice got;
+	HIP_TRY(h, hipMemcpyAsync(&got, D.dev, sizeof got, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	*out = PolarisExposureInfo{sizeof(PolarisExposureInfo), got.s.valid, (uint64_t)got.s.n_hi << 32 | got.s.n_lo, got.s.avg, got.s.log2E, got.s.E, 0};
+	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
+	return POLARIS_OK;
+}
+
 int polaris_hip_read_aov(polaris_hip_tracer *h, int which, float *out, size_t n_floats) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
@@ -2113,15 +2207,21 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	const size_t off = (size_t)r->block_y * h->fa.W, n = (size_t)r->block_h * h->fa.W;
 	const float weight = (float)(1.0 / (float)(r->accumulated_samples + r->samples_per_pixel)); // resources.go:347
 	const SyncFeatures f = h->fs.features();
+	if (f.display)
+		if (int rc = ensure_display(h)) return rc;
 	if (f.any()) {
 		if (int rc = enqueue_features(h, r, weight, f)) return rc;
 	} else {
 		HIP_TRY(h, h->fa.join_merges(h->stream)); // "wait for pending merges" (tracer.go:258-262): everything queued on the merge stream so far
-		(void)launch(h, "tonemap", h->stream, kTonemap, grid_for(n), WG, 0, h->fa.frame + off, h->framebuffer + off, (uint32_t)n, weight, r->exposure);
+		SyncStep steps[kMaxSyncSteps]; // the tone-map, or the display stage's steps
+		const int n_steps = plan_tail(f, steps, 0);
+		for (int s = 0; s < n_steps; s++)
+			launch_tail_step(h, h->stream, steps[s], h->fa.frame + off, weight, h->framebuffer + off, n, r->exposure, f.display ? &h->fs.dp : nullptr);
 	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	if (f.any()) h->fs.v.synced(f);
+	if (f.metered()) h->fs.dp.metered = true;
 	collect_timers(h);
 	return POLARIS_OK;
 }
@@ -2365,6 +2465,43 @@ int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const f
 	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{variance, d_var, plane}, {denoised, d_out, plane}, {rgba, d_fb, pixels}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
+	return POLARIS_OK;
+}
+
+int polaris_hip_display_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
+                               float exposure, const PolarisDisplayParams *p, const float *prev_log2E, uint8_t *rgba, uint32_t histogram[256],
+                               PolarisExposureInfo *info) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!plane || !rgba || !p || p->struct_size != sizeof(PolarisDisplayParams) || !p->enabled || dp_check(*p) || W == 0 || H == 0 ||
+	    (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H || block_h > H - block_y || (info && info->struct_size != sizeof(PolarisExposureInfo)))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "display_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), info's struct_size, or params "
+		            "polaris_hip_set_display refuses (enabled must be 1)", W, H, block_y, block_h);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, off = (size_t)block_y * W, n = (size_t)block_h * W;
+	DisplayStage D; // (its device state goes after the stream is drained)
+	DpDevice got;   // D.init and got are the source and target of asynchronous copies: both are declared before d, whose StreamDrain waits
+	                // for the stream on every way out, early returns included, before either leaves scope
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(1, 1));
+	HIP_TRY(h, D.dev.alloc(1));
+	D.p = *p;
+	dp_init(D.init, prev_log2E);
+	float4 *d_plane = d.f4(0);
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_plane, plane, F * sizeof(float4)}, {d_fb, rgba, F * sizeof(uchar4)}, {D.dev.get(), &D.init, sizeof(DpDevice)}}));
+	SyncFeatures f;
+	f.display = true;
+	f.auto_exposure = p->auto_exposure != 0;
+	SyncStep steps[kMaxSyncSteps];
+	const int n_steps = plan_tail(f, steps, 0);
+	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, exposure, &D);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {&got, D.dev.get(), sizeof got}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
+	if (info) *info = PolarisExposureInfo{sizeof(PolarisExposureInfo), got.s.valid, (uint64_t)got.s.n_hi << 32 | got.s.n_lo, got.s.avg, got.s.log2E, got.s.E, 0};
 	return POLARIS_OK;
 }
 

@@ -251,6 +251,53 @@ assert C.sizeof(VarianceParams) == 12
 VARIANCE_DEFAULTS = {"sigma_variance": 8.0, "min_samples": 8}
 
 
+TONE_REINHARD, TONE_REINHARD_WHITE, TONE_ACES, TONE_HABLE = 0, 1, 2, 3
+TONE_OPERATORS = {"reinhard": TONE_REINHARD, "reinhard-white": TONE_REINHARD_WHITE, "aces": TONE_ACES, "hable": TONE_HABLE}
+
+
+class DisplayParams(C.Structure):
+    """PolarisDisplayParams (include/polaris_hip.h): the display transform of SyncFramebuffer -- auto-exposure, tone curve, transfer."""
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("tone_operator", C.c_uint32), ("srgb", C.c_uint32), ("white", C.c_float),
+                ("auto_exposure", C.c_uint32), ("key", C.c_float), ("compensation_ev", C.c_float), ("low_permille", C.c_uint32),
+                ("high_permille", C.c_uint32), ("min_ev", C.c_float), ("max_ev", C.c_float), ("adapt", C.c_float)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(DisplayParams)
+
+
+class ExposureInfo(C.Structure):
+    """PolarisExposureInfo (include/polaris_hip.h): what the last sync with auto-exposure on metered."""
+    _fields_ = [("struct_size", C.c_uint32), ("valid", C.c_uint32), ("n_metered", C.c_uint64), ("avg", C.c_float), ("log2E", C.c_float),
+                ("E", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(ExposureInfo)
+
+
+assert C.sizeof(DisplayParams) == 52 and C.sizeof(ExposureInfo) == 32
+# the suggested settings (DESIGN.md section 10l): middle grey, the window between the median and the 95th percentile, snap
+DISPLAY_DEFAULTS = {"tone_operator": TONE_REINHARD, "srgb": 0, "white": 4.0, "auto_exposure": 0, "key": 0.18, "compensation_ev": 0.0,
+                    "low_permille": 500, "high_permille": 950, "min_ev": -16.0, "max_ev": 16.0, "adapt": 1.0}
+
+
+def display_params(enabled=1, **kw) -> DisplayParams:
+    """DisplayParams with DISPLAY_DEFAULTS for the fields not given (tone_operator: a TONE_* number or a TONE_OPERATORS name)."""
+    unknown = set(kw) - set(DISPLAY_DEFAULTS)
+    if unknown:
+        raise TypeError(f"display_params: unknown fields {sorted(unknown)}")
+    f = dict(DISPLAY_DEFAULTS, **kw)
+    p = DisplayParams()
+    p.enabled = int(enabled)
+    p.tone_operator = TONE_OPERATORS[f["tone_operator"]] if isinstance(f["tone_operator"], str) else int(f["tone_operator"])
+    p.srgb, p.auto_exposure = int(f["srgb"]), int(f["auto_exposure"])
+    p.low_permille, p.high_permille = int(f["low_permille"]), int(f["high_permille"])
+    for name in ("white", "key", "compensation_ev", "min_ev", "max_ev", "adapt"):
+        setattr(p, name, float(f[name]))
+    return p
+
+
 def variance_params(sigma_variance=8.0, min_samples=8) -> VarianceParams:
     p = VarianceParams()
     p.sigma_variance, p.min_samples = float(sigma_variance), int(min_samples)
@@ -469,6 +516,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
+    "polaris_hip_set_display", "polaris_hip_read_exposure", "polaris_hip_display_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_reproject_deform_planes", "polaris_hip_read_hit_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
@@ -576,6 +624,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_set_shutter.argtypes = [vp, C.POINTER(ShutterParams)]
     lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
     lib.polaris_hip_set_variance.argtypes = [vp, C.POINTER(VarianceParams)]
+    lib.polaris_hip_set_display.argtypes = [vp, C.POINTER(DisplayParams)]
+    lib.polaris_hip_read_exposure.argtypes = [vp, C.POINTER(ExposureInfo), vp]
+    lib.polaris_hip_display_planes.argtypes = [vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DisplayParams), C.POINTER(C.c_float), vp, vp,
+                                               C.POINTER(ExposureInfo)]
     lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),
                                                 C.POINTER(VarianceParams), vp, vp, vp]
     lib.polaris_hip_reproject_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(TemporalParams), vp]

@@ -197,6 +197,21 @@ int polaris_host_renderer_set_variance(void *h, const PolarisVarianceParams *p) 
 		if (int rc = polaris_hip_set_variance(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// The display transform (polaris_hip_set_display) on every tracer, as set_denoise: only the primary syncs, so only it meters and displays.
+int polaris_host_renderer_set_display(void *h, const PolarisDisplayParams *p) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (int rc = polaris_hip_set_display(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	return 0;
+}
+// What the primary's last sync with auto-exposure on metered (polaris_hip_read_exposure).
+int polaris_host_renderer_read_exposure(void *h, PolarisExposureInfo *out, uint32_t *histogram) {
+	auto *box = static_cast<RendererBox *>(h);
+	auto *p = dynamic_cast<tracer::hip::HipTracer *>(box->r->Primary());
+	if (!p) return POLARIS_E_UNSUPPORTED;
+	if (int rc = polaris_hip_read_exposure(p->Handle(), out, histogram)) { box->error = polaris_hip_last_error(p->Handle()); return rc; }
+	return 0;
+}
 // A camera move: the CameraData of every tracer, as the interactive renderer's UpdateState (renderer/opengl.go:294-301).
 int polaris_host_renderer_set_camera(void *h, const float eye[3], const float frustum[16]) {
 	auto *box = static_cast<RendererBox *>(h);

@@ -45,7 +45,11 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_lens.argtypes = [vp, C.c_float, C.c_float]
         lib.polaris_host_renderer_set_shutter.argtypes = [vp, vp, vp, C.c_float]
         lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
+        lib.polaris_host_renderer_set_display.argtypes = [vp, C.POINTER(T.DisplayParams)]
+        lib.polaris_host_renderer_read_exposure.argtypes = [vp, C.POINTER(T.ExposureInfo), vp]
         u32 = C.c_uint32
+        lib.polaris_host_display.argtypes = [vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(T.DisplayParams), C.POINTER(C.c_float), vp, vp,
+                                             C.POINTER(T.ExposureInfo)]
         lib.polaris_host_variance.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams), C.POINTER(T.VarianceParams), vp]
         lib.polaris_host_denoise_variance.argtypes = [vp, C.c_float, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams),
                                                       C.POINTER(T.VarianceParams), vp]
@@ -212,6 +216,21 @@ class Renderer:
         p = T.variance_params(sigma_variance, min_samples)
         if self._lib.polaris_host_renderer_set_variance(self._h, C.byref(p)):
             raise RuntimeError(f"set_variance failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_display(self, enabled: int = 1, **fields) -> None:
+        """polaris_hip_set_display on every tracer (polaris_host_renderer_set_display): the display transform of the primary's
+        SyncFramebuffer.  fields: those of ctypes_api.DISPLAY_DEFAULTS; enabled = 0 turns it off."""
+        p = T.display_params(enabled, **fields)
+        if self._lib.polaris_host_renderer_set_display(self._h, C.byref(p)):
+            raise RuntimeError(f"set_display failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def read_exposure(self) -> dict:
+        """polaris_hip_read_exposure of the primary: what its last sync with auto-exposure on metered, as display()'s info, with the
+        256 counts under "histogram"."""
+        info, hist = T.ExposureInfo(), np.zeros(256, np.uint32)
+        if self._lib.polaris_host_renderer_read_exposure(self._h, C.byref(info), hist.ctypes.data):
+            raise RuntimeError(f"read_exposure failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+        return dict(exposure_info(info), histogram=hist)
 
     def set_camera(self, eye, frustum) -> None:
         """A camera move: UpdateState(CameraData) on every tracer (DefaultRenderer::UpdateAll)."""
@@ -438,6 +457,29 @@ def _planes(name, *planes):
     if any(a.shape != (H, W, 4) for a in out):
         raise ValueError(f"{name}: the planes must be (H, W, 4) float32 of one size")
     return out, H, W
+
+
+def exposure_info(info) -> dict:
+    """A PolarisExposureInfo as a dict: valid, n_metered and the float32 values avg, log2E, E."""
+    return {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E), "E": np.float32(info.E)}
+
+
+def display(plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None, rgba=None, prev_log2E=None,
+            **fields) -> tuple[np.ndarray, np.ndarray, dict]:
+    """polaris_host_display: the CPU restatement of the display stage (polaris_amd/host/display.cpp) over the request's rows of an
+    (H, W, 4) float32 plane.  fields: those of ctypes_api.DISPLAY_DEFAULTS.  Returns (RGBA8 -- `rgba` (a copy) with the request's rows
+    written --, the 256 counts, exposure_info).  ValueError where refused."""
+    (c,), H, W = _planes("display", plane)
+    fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, dtype=np.uint8, order="C", copy=True)
+    if fb.shape != (H, W, 4):
+        raise ValueError("display: rgba must be (H, W, 4) uint8")
+    p, info, hist = T.display_params(1, **fields), T.ExposureInfo(), np.zeros(256, np.uint32)
+    prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
+    rc = load().polaris_host_display(c.ctypes.data, W, H, int(block_y), int(H - block_y if block_h is None else block_h), float(weight), float(exposure),
+                                     C.byref(p), prev, fb.ctypes.data, hist.ctypes.data, C.byref(info))
+    if rc:
+        raise ValueError(f"display: bad arguments (code {rc})")
+    return fb, hist, exposure_info(info)
 
 
 def variance(frame_acc, samples: int, guide, albedo, *, temporal=None, prior2=None, block_y: int = 0, block_h: int | None = None, out=None,

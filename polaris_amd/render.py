@@ -38,8 +38,16 @@ under that pixel's centre, t * dot(centre direction, axis); a pixel that sees no
 
 --frames N --shutter F (0 <= F <= 1, default 0 = an instantaneous exposure) leaves the shutter open for the fraction F of the way to
 the next frame (polaris_hip_set_shutter): frame k's camera rays spread in time between its camera and the camera one
-more move of F * OFFSET on -- camera motion blur.  A lens stays on both ends, with the same radius and focus distance."""
+more move of F * OFFSET on -- camera motion blur.  A lens stays on both ends, with the same radius and focus distance.
+
+--tonemap {reinhard,reinhard-white,aces,hable} [--white W] [--srgb] [--auto-exposure [--ev-comp X] [--adapt A]] replaces the sync's
+tone-map by the display transform (polaris_hip_set_display): the tone operator (white: the radiance reinhard-white and
+hable map to 1), the sRGB transfer function instead of pow(1 / 2.2), and the frame's own metered exposure (key 0.18, the window
+between the median and the 95th percentile; X stops of compensation; A the fraction of the way to the target per frame) times
+--exposure.  With --aov-dir the last frame's exposure and histogram are written as exposure.json.  A flag that would be ignored is an
+error: --white without reinhard-white or hable, --ev-comp or --adapt without --auto-exposure."""
 import argparse
+import json
 import os
 import sys
 import time
@@ -196,7 +204,18 @@ def main(argv=None):
     ap.add_argument("--focus", type=float, default=0.0, help="with --aperture: distance of the plane of focus along the view axis")
     ap.add_argument("--focus-pixel", default="", help="with --aperture, x,y: focus on what this pixel's centre sees instead of --focus")
     ap.add_argument("--shutter", type=float, default=0.0, help="with --frames (camera moves): the shutter stays open this fraction 0..1 of the way to the next frame (0 = off)")
+    ap.add_argument("--tonemap", choices=sorted(T.TONE_OPERATORS), default=None, help="the display transform's tone operator (default: the plain tone-map)")
+    ap.add_argument("--white", type=float, default=T.DISPLAY_DEFAULTS["white"], help="with --tonemap reinhard-white / hable: the radiance mapped to 1")
+    ap.add_argument("--srgb", action="store_true", help="the sRGB transfer function instead of pow(1 / 2.2)")
+    ap.add_argument("--auto-exposure", action="store_true", help="meter every frame and expose it to middle grey")
+    ap.add_argument("--ev-comp", type=float, default=0.0, help="with --auto-exposure: exposure compensation in stops")
+    ap.add_argument("--adapt", type=float, default=1.0, help="with --auto-exposure: the fraction (0, 1] of the way to the metered exposure per frame")
     a = ap.parse_args(argv)
+    display = a.tonemap is not None or a.srgb or a.auto_exposure
+    if (a.ev_comp or a.adapt != 1.0) and not a.auto_exposure:
+        ap.error("--ev-comp and --adapt need --auto-exposure")
+    if a.white != T.DISPLAY_DEFAULTS["white"] and a.tonemap not in ("reinhard-white", "hable"):
+        ap.error("--white needs --tonemap reinhard-white or hable")
     if not 0.0 <= a.shutter <= 1.0 or (a.shutter and (not a.frames or a.recolour or a.ripple)):
         ap.error("--shutter F needs 0 <= F <= 1, --frames and no --recolour or --ripple")
     if a.ripple and (not a.frames or a.recolour):
@@ -224,6 +243,9 @@ def main(argv=None):
             r.set_temporal(max_history=a.temporal)
         if a.variance:
             r.set_variance(sigma_variance=a.variance, min_samples=T.VARIANCE_DEFAULTS["min_samples"])
+        if display:
+            r.set_display(1, tone_operator=a.tonemap or "reinhard", white=a.white, srgb=int(a.srgb), auto_exposure=int(a.auto_exposure),
+                          compensation_ev=a.ev_comp, adapt=a.adapt)
         if a.aperture:
             focus = a.focus
             if a.focus_pixel:
@@ -247,6 +269,11 @@ def main(argv=None):
                 host_api.write_png(os.path.join(a.aov_dir, name + ".png"), img)
             if a.variance:
                 np.save(os.path.join(a.aov_dir, "variance.npy"), r.read_aov(T.AOV_VARIANCE))
+            if a.auto_exposure:
+                e = r.read_exposure()
+                with open(os.path.join(a.aov_dir, "exposure.json"), "w") as f:
+                    json.dump({"valid": e["valid"], "n_metered": e["n_metered"], "avg": float(e["avg"]), "log2E": float(e["log2E"]), "E": float(e["E"]),
+                               "histogram": e["histogram"].tolist()}, f)
     finally:
         r.close()
     print(f"{a.scene}: {sc.vertices.shape[0] // 3} triangles, {len(sc.mesh_instances)} instances, {len(sc.material_nodes)} material nodes; "

@@ -223,6 +223,38 @@ class HipTracer:
         p = T.variance_params(sigma_variance, min_samples)
         self._check(self._lib.polaris_hip_set_variance(self._h, C.byref(p)), self._h)
 
+    def set_display(self, enabled: int = 1, **fields) -> None:
+        """The display transform of every SyncFramebuffer (polaris_hip_set_display): auto-exposure, tone operator and transfer function
+        in place of the plain tone-map.  fields: those of T.DISPLAY_DEFAULTS (tone_operator also by its T.TONE_OPERATORS name);
+        enabled = 0 turns it off (the default)."""
+        p = T.display_params(enabled, **fields)
+        self._check(self._lib.polaris_hip_set_display(self._h, C.byref(p)), self._h)
+
+    def read_exposure(self) -> dict:
+        """polaris_hip_read_exposure: what the last sync with auto-exposure on metered -- valid, n_metered, the float32 values avg,
+        log2E and E, and the 256 counts under "histogram"."""
+        info, hist = T.ExposureInfo(), np.zeros(256, np.uint32)
+        self._check(self._lib.polaris_hip_read_exposure(self._h, C.byref(info), hist.ctypes.data), self._h)
+        return {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E),
+                "E": np.float32(info.E), "histogram": hist}
+
+    def display_planes(self, plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None, rgba=None,
+                       prev_log2E=None, **fields) -> tuple[np.ndarray, np.ndarray, dict]:
+        """polaris_hip_display_planes: the launches of the display stage on a caller (H, W, 4) float32 plane.  fields: those of
+        T.DISPLAY_DEFAULTS.  Returns (RGBA8, the 256 counts, the exposure info as read_exposure's without the histogram); rows outside
+        the request come back as passed (zeros by default)."""
+        plane = np.ascontiguousarray(plane, dtype=np.float32)
+        H, W = plane.shape[:2]
+        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
+        assert plane.shape == fb.shape == (H, W, 4)
+        p, info, hist = T.display_params(1, **fields), T.ExposureInfo(), np.zeros(256, np.uint32)
+        prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
+        bh = H - block_y if block_h is None else block_h
+        self._check(self._lib.polaris_hip_display_planes(self._h, plane.ctypes.data, W, H, int(block_y), int(bh), float(weight), float(exposure),
+                                                         C.byref(p), prev, fb.ctypes.data, hist.ctypes.data, C.byref(info)), self._h)
+        return fb, hist, {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E),
+                          "E": np.float32(info.E)}
+
     def read_aov(self, which: int) -> np.ndarray:
         """(H, W, 4) float32 plane of the denoiser: T.AOV_GUIDE (normal | hit distance), T.AOV_ALBEDO (albedo | leaf type bits)
         or T.AOV_DENOISED (the filtered running mean of the last denoised sync); T.AOV_TEMPORAL / T.AOV_PRIOR (temporal reuse),
