@@ -214,7 +214,11 @@ int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p
  *                        the history and invalidates the G-buffer, as changing "object_motion" does; setting the same value does
  *                        nothing.  It never changes an accumulator or a counter; off or without effect, every upload, update, sync
  *                        and G-buffer allocates and launches exactly what it does without the option
- *   "guide_specular"     0 (default) .. 8, anything else POLARIS_E_BAD_ARGUMENT: the number N of delta interactions the G-buffer's
+ *   "bloom_fused"        0 (default) or 1, anything else POLARIS_E_BAD_ARGUMENT: with polaris_hip_set_bloom in effect, 1 runs every
+ *                        pyramid level of at most 1024 pixels, down and up, in one launch (k_bloom_tail); 0 runs one launch per
+ *                        level.  An A/B switch: the pyramid's values are the same bit for bit.  Off by default: measured on an
+ *                        MI355X it saves 0.6 us of 32 at 512 x 512 and costs 3 us of 39 at 1024 x 1024
+ *   "guide_specular"    0 (default) .. 8, anything else POLARIS_E_BAD_ARGUMENT: the number N of delta interactions the G-buffer's
  *                        guide ray follows.  With N > 0 a pixel whose hit is a CONDUCTOR or DIELECTRIC leaf -- both
  *                        delta BxDFs: a mirror, smooth glass -- continues in the mirror direction, or through the glass (refracted
  *                        wherever refraction exists, reflected on total internal reflection), up to N times, and GUIDE / ALBEDO /
@@ -567,6 +571,40 @@ typedef struct PolarisExposureInfo {
 } PolarisExposureInfo;
 int polaris_hip_read_exposure(polaris_hip_tracer *h, PolarisExposureInfo *out, uint32_t histogram[256]);
 
+/* Bloom: a glare term of the display stage (no reference counterpart).  Off by default (enabled = 0), and in effect only while the display
+ * stage is enabled (polaris_hip_set_display): a set_bloom with the display off is accepted, stored, and takes effect when the display is
+ * turned on.  While it is off or not in effect every sync runs and allocates exactly what it did, under the same kernel symbols.
+ * In effect, between k_expose and the display step, over the request's rows [y0, y1) alone (rows outside are never read; every
+ * coordinate is clamped to its level's extent), everything in float32 in the order written:
+ *   levels      w_0 = W, h_0 = y1 - y0; w_l = (w_{l-1} + 1) / 2, h_l = (h_{l-1} + 1) / 2; L = min(levels, the first l with w_l = h_l = 1);
+ *   bright pass per source pixel and channel c = rgb * weight * exposure * E (the display step's value); NaN or <= 0 becomes 0, above 65536
+ *               becomes 65536; m = max(r, g, b), k = threshold * knee, s = clamp(m - threshold + k, 0, 2 k), s = s s / (4 k + 1e-5);
+ *               b = c * (max(s, m - threshold) / max(m, 1e-5));
+ *   down        D_l(x, y) = sum over j = 0..3 of K[j] * (sum over i = 0..3 of K[i] * src(2 x - 1 + i, 2 y - 1 + j)), K = {1, 3, 3, 1} / 8,
+ *               src = b for l = 1 (fused: the bright pass has no plane) and D_{l-1} above; karis = 1, level 1 only: every tap is
+ *               weighted by 1 / (1 + luminance(b)) and the sum divided by the same sum of the weights (firefly suppression);
+ *   up          U_L = D_L; U_l = D_l + up(U_{l+1}), in place; up is the 2 x tent: fine index i takes coarse (i >> 1) - 1 and i >> 1 with
+ *               weights 1/4, 3/4 (even i), i >> 1 and (i >> 1) + 1 with 3/4, 1/4 (odd i), x inside y;
+ *   display     k_display_bloom<OP, SRGB>: c + intensity * (up(U_1)(x, y) / L) per channel through the tone operator and the transfer
+ *               function of PolarisDisplayParams (no full-resolution bloom plane exists).
+ * The accumulators and counters are never touched.  The pyramid (sum of w_l h_l float4, about a third of a frame) is allocated by the first
+ * bloomed sync and freed when bloom or the display goes off and by polaris_hip_resize.  A call with identical bytes does nothing; a changed
+ * call touches only the pyramid: the exposure state, the temporal history and the G-buffer stay.  POLARIS_E_BAD_ARGUMENT with the state
+ * unchanged: enabled or karis > 1; with enabled = 1 levels outside 1..8, or a float that is not finite or outside threshold [0, 65536],
+ * knee [0, 1], intensity [0, 16].  With enabled = 0 nothing after it but karis is looked at and any two off states are equal.  The option
+ * "bloom_fused" (default 0: one launch per level) set to 1 runs the levels of at most 1024 pixels in one launch (k_bloom_tail); the values
+ * are the same bit for bit.  polaris_amd/ctypes_api.py BLOOM_DEFAULTS has the suggested settings.  DESIGN.md 10m. */
+typedef struct PolarisBloomParams {
+	uint32_t struct_size;  /* sizeof(PolarisBloomParams) */
+	uint32_t enabled;      /* 0 = off (default) */
+	uint32_t levels;       /* 1..8 pyramid levels asked for; fewer are used where the region runs out */
+	float    threshold;    /* the displayed-linear value (after weight, exposure and E) above which a pixel blooms */
+	float    knee;         /* 0..1: soft-knee fraction of threshold */
+	float    intensity;    /* 0..16: factor of the bloom term added before the tone operator */
+	uint32_t karis;        /* 0 / 1: weight the first downsample by 1 / (1 + luminance) */
+} PolarisBloomParams;
+int polaris_hip_set_bloom(polaris_hip_tracer *h, const PolarisBloomParams *p);
+
 /* frame_w*frame_h*4 bytes RGBA8 (pipeline.go:226-232). */
 int polaris_hip_read_framebuffer(polaris_hip_tracer *h, uint8_t *rgba, size_t n_bytes);
 
@@ -650,6 +688,15 @@ int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const f
 int polaris_hip_display_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h,
                                float weight, float exposure, const PolarisDisplayParams *p, const float *prev_log2E, uint8_t *rgba,
                                uint32_t histogram[256], PolarisExposureInfo *info);
+
+/* Test entry of a bloomed displayed sync on a caller plane, as polaris_hip_display_planes: the rows [block_y, block_y + block_h) of plane
+ * are metered (dp->auto_exposure), exposed from prev_log2E (may be NULL), bloomed (bp) and displayed into rgba (in / out: its other rows
+ * come back as given) -- the launches k_meter, k_expose, the pyramid's and k_display_bloom of such a sync, with the tracer's option
+ * "bloom_fused".  level1 (may be NULL): U_1, h_1 x w_1 x 4 floats; levels_used (may be NULL): L.  dp->enabled and bp->enabled must be 1.
+ * Uses buffers of its own; no state of the tracer is read or changed. */
+int polaris_hip_bloom_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
+                             float exposure, const PolarisDisplayParams *dp, const PolarisBloomParams *bp, const float *prev_log2E, uint8_t *rgba,
+                             float *level1, uint32_t *levels_used);
 
 /* Test entry of the temporal reprojection on caller planes: history (rgb | count), prev_guide, prev_albedo seen under the camera
  * (prev_eye, prev_frustum), and the current guide, albedo under (eye, frustum), all W x H float4 planes; the PRIOR plane of every
@@ -878,7 +925,8 @@ const char *polaris_hip_build_bvh_error(void); /* text of the calling thread's l
  * (polaris_hip_set_temporal), "variance" and "denoise_variance" (polaris_hip_set_variance), "instance_extent",
  * "repad" and "refit_top" (polaris_hip_update_instances), "tri_records" and "refit_mesh" (polaris_hip_update_vertices, which runs the
  * former three as well), "retag" (polaris_hip_update_materials), "meter", "expose" and "display" (polaris_hip_set_display: with
- * it on "tonemap" does not run in a sync). */
+ * it on "tonemap" does not run in a sync), "bloom" (polaris_hip_set_bloom: one bracket around all pyramid launches of a sync; the bloomed
+ * display step stays under "display"). */
 int polaris_hip_kernel_ms(polaris_hip_tracer *h, const char *kernel, double *ms, uint64_t *launches);
 
 /* The kernel symbol (as rocprofv3 prints it, e.g. "pol::k_trace<false, 16, 2>") the named timer last

@@ -586,6 +586,40 @@ func (tr *Tracer) SetDisplay(p DisplayParams) error {
 	return tr.check(C.polaris_hip_set_display(tr.handle, &c))
 }
 
+// BloomParams is PolarisBloomParams: the bloom of the display transform, a bright-pass pyramid added before the tone operator.
+type BloomParams struct {
+	Enabled   bool
+	Levels    uint32  // 1..8 pyramid levels asked for
+	Threshold float32 // the displayed-linear value above which a pixel blooms
+	Knee      float32 // 0..1: soft-knee fraction of Threshold
+	Intensity float32 // 0..16
+	Karis     bool    // weight the first downsample by 1 / (1 + luminance)
+}
+
+// DefaultBloom is polaris_amd/ctypes_api.py BLOOM_DEFAULTS.
+var DefaultBloom = BloomParams{Enabled: true, Levels: 5, Threshold: 1, Knee: 0.5, Intensity: 0.25, Karis: true}
+
+// SetBloom turns the bloom of the display transform on or off.  It is in effect only while SetDisplay has the transform on; a call
+// with the transform off is stored.  A changed call touches only the bloom pyramid.  (Written without a Go toolchain at hand: not
+// compiled.)
+func (tr *Tracer) SetBloom(p BloomParams) error {
+	b := func(v bool) C.uint32_t {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	var c C.PolarisBloomParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.enabled = b(p.Enabled)
+	c.levels = C.uint32_t(p.Levels)
+	c.threshold = C.float(p.Threshold)
+	c.knee = C.float(p.Knee)
+	c.intensity = C.float(p.Intensity)
+	c.karis = b(p.Karis)
+	return tr.check(C.polaris_hip_set_bloom(tr.handle, &c))
+}
+
 // ExposureInfo is what the last SyncFramebuffer with auto-exposure on metered (PolarisExposureInfo).
 type ExposureInfo struct {
 	Valid    bool

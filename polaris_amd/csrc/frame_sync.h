@@ -3,7 +3,7 @@
 // whether an AOV can be read (SyncState::aov_refusal).
 //
 // No HIP here and no device pointer: FrameSync in polaris_hip.hip owns the planes and pairs every transition with the frees and
-// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d, 10k and 10l describe the features.
+// swaps it returns; tests/tools/frame_sync_check.cpp asks the same functions on a CPU.  DESIGN.md sections 10-10d and 10k-10m describe the features.
 #pragma once
 
 #include <cstdint>
@@ -53,10 +53,12 @@ struct InstTable {
 struct SyncFeatures {
 	bool denoise = false, temporal = false, variance = false, motion = false, deform = false;
 	bool display = false, auto_exposure = false; // polaris_hip_set_display: the sync's last step is the display stage, metered or not
+	bool bloom = false;                          // polaris_hip_set_bloom: in effect only with the display stage on
 	bool any() const { return denoise || temporal || variance; }
 	bool motion_on() const { return motion && temporal; }
 	bool deform_on() const { return deform && motion_on(); }
 	bool metered() const { return display && auto_exposure; }
+	bool bloomed() const { return display && bloom; }
 };
 
 class SyncState {
@@ -172,9 +174,9 @@ public:
 
 // ---- what a sync with features f does under state v (f.any(); the plain sync is plan_tail's steps over the accumulator and asks nothing)
 enum class SyncSource { Accumulator, Temporal, Denoised }; // the accumulator is read with the sync's weight, the other two with weight 1
-enum class SyncStep { Temporal, Variance, Denoise, DenoiseVariance, Tonemap, Meter, Expose, Display };
-constexpr const char *kSyncStepTimer[] = {"temporal", "variance", "denoise", "denoise_variance", "tonemap", "meter", "expose", "display"}; // one timer per kernel symbol
-constexpr int kMaxSyncSteps = 6; // temporal, variance, a filter and the display stage's three
+enum class SyncStep { Temporal, Variance, Denoise, DenoiseVariance, Tonemap, Meter, Expose, Display, Bloom };
+constexpr const char *kSyncStepTimer[] = {"temporal", "variance", "denoise", "denoise_variance", "tonemap", "meter", "expose", "display", "bloom"}; // one timer per kernel symbol (denoise and bloom: one around their launches)
+constexpr int kMaxSyncSteps = 7; // temporal, variance, a filter and the display stage's four
 struct SyncPlan {
 	uint32_t need = 0;      // planes that must exist (allocated on first use)
 	uint32_t clear = 0;     // of those, cleared first: the rows no sync under this camera reaches must read as "no history"
@@ -187,12 +189,14 @@ struct SyncPlan {
 	SyncSource color = SyncSource::Accumulator, tonemap = SyncSource::Accumulator; // what the filter reads | what the tone-map reads (the filter's output, or its input where none runs)
 };
 // The steps that turn the sync's source into bytes, appended to steps[n]: the tone-map, or with the display stage on
-// Meter and Expose (auto-exposure) and Display.  They read no plane of their own: the histogram and the exposure state are not
-// frame-sized and belong to the display stage's owner.  The plain sync (no other feature) runs these steps alone.
+// Meter and Expose (auto-exposure), Bloom (behind Expose: its bright pass reads the exposure) and Display.  They read
+// no plane of their own: the histogram, the exposure state and the bloom pyramid belong to the display stage's owner.  The plain sync
+// (no other feature) runs these steps alone.
 inline int plan_tail(const SyncFeatures &f, SyncStep *steps, int n) {
 	if (!f.display) steps[n++] = SyncStep::Tonemap;
 	else {
 		if (f.auto_exposure) { steps[n++] = SyncStep::Meter; steps[n++] = SyncStep::Expose; }
+		if (f.bloom) steps[n++] = SyncStep::Bloom;
 		steps[n++] = SyncStep::Display;
 	}
 	return n;

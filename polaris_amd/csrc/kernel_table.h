@@ -95,6 +95,16 @@ const decltype(POLARIS_VARIANT(k_display<0, false>)) kDisplay[4][2] = {
 	{POLARIS_VARIANT(k_display<0, false>), POLARIS_VARIANT(k_display<0, true>)}, {POLARIS_VARIANT(k_display<1, false>), POLARIS_VARIANT(k_display<1, true>)},
 	{POLARIS_VARIANT(k_display<2, false>), POLARIS_VARIANT(k_display<2, true>)}, {POLARIS_VARIANT(k_display<3, false>), POLARIS_VARIANT(k_display<3, true>)}};
 static_assert(POLARIS_TONE_REINHARD == 0 && POLARIS_TONE_REINHARD_WHITE == 1 && POLARIS_TONE_ACES == 2 && POLARIS_TONE_HABLE == 3, "kDisplay spells OP as a number");
+// polaris_hip_set_bloom (bloom.h): k_bloom_down<FIRST, KARIS> and k_bloom_tail<FIRST, KARIS>: [0 a coarser level, 1 level 1, 2 level 1 with karis];
+// k_display_bloom<OP, SRGB> as kDisplay
+const decltype(POLARIS_VARIANT(k_bloom_down<false, false>)) kBloomDown[3] = {POLARIS_VARIANT(k_bloom_down<false, false>), POLARIS_VARIANT(k_bloom_down<true, false>),
+                                                                             POLARIS_VARIANT(k_bloom_down<true, true>)};
+const decltype(POLARIS_VARIANT(k_bloom_tail<false, false>)) kBloomTail[3] = {POLARIS_VARIANT(k_bloom_tail<false, false>), POLARIS_VARIANT(k_bloom_tail<true, false>),
+                                                                             POLARIS_VARIANT(k_bloom_tail<true, true>)};
+const auto kBloomUp = POLARIS_VARIANT(k_bloom_up);
+const decltype(POLARIS_VARIANT(k_display_bloom<0, false>)) kDisplayBloom[4][2] = {
+	{POLARIS_VARIANT(k_display_bloom<0, false>), POLARIS_VARIANT(k_display_bloom<0, true>)}, {POLARIS_VARIANT(k_display_bloom<1, false>), POLARIS_VARIANT(k_display_bloom<1, true>)},
+	{POLARIS_VARIANT(k_display_bloom<2, false>), POLARIS_VARIANT(k_display_bloom<2, true>)}, {POLARIS_VARIANT(k_display_bloom<3, false>), POLARIS_VARIANT(k_display_bloom<3, true>)}};
 // polaris_hip_update_instances (instance_update.h)
 const auto kInstanceExtent = POLARIS_VARIANT(k_instance_extent);
 const auto kRepad = POLARIS_VARIANT(k_repad);

@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "bloom.h"
 #include "builtin_probe.h"
 #include "denoise.h"
 #include "display.h"
@@ -1990,6 +1991,124 @@ __global__ __launch_bounds__(WG) void k_display(const float4 *acc, uchar4 *fb, u
 	const float rgb[3] = {a.x, a.y, a.z};
 	uint8_t o[4];
 	dp_pixel<OP, SRGB>(rgb, weight, exposure, *E, curve, o);
+	fb[i] = make_uchar4(o[0], o[1], o[2], o[3]);
+}
+
+// ---- bloom (bloom.h): the pyramid of a bloomed displayed sync.  Level l >= 1 lies at pyramid + BlLevels::off[l], row
+// major, rgb | 0.  The sources bloom.h's functions read through (they pass clamped coordinates):
+struct BlPlane { // a level in global memory or LDS
+	const float4 *p; int w;
+	__device__ void operator()(int x, int y, float t[4]) const { const float4 v = p[y * w + x]; t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w; }
+};
+struct BlTile { // a staged window of a level: slot (x - x0, y - y0) of a tile w wide holds the level's pixel (x, y)
+	const float4 *p; int x0, y0, w;
+	__device__ void operator()(int x, int y, float t[4]) const { const float4 v = p[(y - y0) * w + (x - x0)]; t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w; }
+};
+template <bool KARIS>
+struct BlBrightPlane { // the bright pass of the source plane (the sync's source at the request's first row), per tap
+	const float4 *p; int w; BlBright b;
+	__device__ void operator()(int x, int y, float t[4]) const { const float4 v = p[y * w + x]; const float rgb[3] = {v.x, v.y, v.z}; bl_bright<KARIS>(rgb, b, t); }
+};
+constexpr int kBlTile = 16;                // a workgroup's outputs: kBlTile x kBlTile, one per thread
+constexpr int kBlFoot = 2 * kBlTile + 2;   // k_bloom_down: their 4 x 4 footprints cover this many source pixels a side ...
+constexpr int kBlUpFoot = kBlTile / 2 + 2; // ... k_bloom_up: their tent taps this many coarse pixels a side
+static_assert(kBlTile * kBlTile == WG, "one output pixel per thread");
+
+// D of a level dw x dh from the level below (sw x sh) -- FIRST: from the bright pass of the sync's source, E read as k_display reads
+// it (KARIS: level 1's weighting).  The tile's footprint is staged in LDS, bright-passed once per source pixel; slot f of a side holds
+// source coordinate clamp(2 o - 1 + f), so a clamped coordinate c is slot c - (2 o - 1): within [0, kBlFoot) for every output of the level.
+template <bool FIRST, bool KARIS>
+__global__ __launch_bounds__(WG) void k_bloom_down(const float4 *src, int sw, int sh, float4 *dst, int dw, int dh, BlBright bp, const float *E) {
+	__shared__ float4 tile[kBlFoot * kBlFoot];
+	const int bx = 2 * (int)blockIdx.x * kBlTile - 1, by = 2 * (int)blockIdx.y * kBlTile - 1;
+	if (FIRST) bp.E = *E;
+	for (int s = threadIdx.x; s < kBlFoot * kBlFoot; s += WG) {
+		const float4 v = src[(size_t)bl_clampi(by + s / kBlFoot, sh) * sw + bl_clampi(bx + s % kBlFoot, sw)];
+		if (FIRST) {
+			const float rgb[3] = {v.x, v.y, v.z};
+			float t[4];
+			bl_bright<KARIS>(rgb, bp, t);
+			tile[s] = make_float4(t[0], t[1], t[2], t[3]);
+		} else tile[s] = v;
+	}
+	__syncthreads();
+	const int x = blockIdx.x * kBlTile + threadIdx.x % kBlTile, y = blockIdx.y * kBlTile + threadIdx.x / kBlTile;
+	if (x >= dw || y >= dh) return;
+	float o[4];
+	bl_down<KARIS>(BlTile{tile, bx, by, kBlFoot}, x, y, sw, sh, o);
+	dst[(size_t)y * dw + x] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// U_l = D_l + up(U_{l+1}) in place over a level fw x fh from the level above (cw x ch), whose taps of the tile are staged as k_bloom_down's.
+__global__ __launch_bounds__(WG) void k_bloom_up(float4 *fine, int fw, int fh, const float4 *coarse, int cw, int ch) {
+	__shared__ float4 tile[kBlUpFoot * kBlUpFoot];
+	const int bx = (int)blockIdx.x * (kBlTile / 2) - 1, by = (int)blockIdx.y * (kBlTile / 2) - 1;
+	if (threadIdx.x < kBlUpFoot * kBlUpFoot)
+		tile[threadIdx.x] = coarse[(size_t)bl_clampi(by + (int)threadIdx.x / kBlUpFoot, ch) * cw + bl_clampi(bx + (int)threadIdx.x % kBlUpFoot, cw)];
+	__syncthreads();
+	const int x = blockIdx.x * kBlTile + threadIdx.x % kBlTile, y = blockIdx.y * kBlTile + threadIdx.x / kBlTile;
+	if (x >= fw || y >= fh) return;
+	const float4 d4 = fine[(size_t)y * fw + x];
+	const float d[4] = {d4.x, d4.y, d4.z, d4.w};
+	float o[4];
+	bl_merge(d, BlTile{tile, bx, by, kBlUpFoot}, x, y, cw, ch, o);
+	fine[(size_t)y * fw + x] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// Every level from `first` (at most kBlTailPixels pixels; bl_tail_start) to g.L, down and up, by one workgroup in LDS: level l at
+// lds + g.off[l] - g.off[first].  D_first from the level below in the pyramid -- FIRST (first = 1): from the bright pass of src --, the
+// coarser D's from LDS, then U_l = D_l + up(U_{l+1}) from g.L - 1 back to first, whose U goes to the pyramid.  Each value is the
+// expression k_bloom_down / k_bloom_up evaluate, so the pyramid is the same bit for bit with this kernel or a launch per level.
+template <bool FIRST, bool KARIS>
+__global__ __launch_bounds__(WG) void k_bloom_tail(const float4 *src, float4 *pyramid, BlLevels g, uint32_t first, BlBright bp, const float *E) {
+	__shared__ float4 lds[kBlTailLds];
+	const uint32_t base = g.off[first];
+	const int w0 = (int)g.w[first], n0 = w0 * (int)g.h[first], sw = (int)g.w[first - 1], sh = (int)g.h[first - 1];
+	if (FIRST) bp.E = *E;
+	for (int p = threadIdx.x; p < n0; p += WG) {
+		float o[4];
+		if (FIRST) bl_down<KARIS>(BlBrightPlane<KARIS>{src, sw, bp}, p % w0, p / w0, sw, sh, o);
+		else bl_down<false>(BlPlane{pyramid + g.off[first - 1], sw}, p % w0, p / w0, sw, sh, o);
+		lds[p] = make_float4(o[0], o[1], o[2], o[3]);
+	}
+	__syncthreads();
+	for (uint32_t l = first + 1; l <= g.L; l++) {
+		const int w = (int)g.w[l], n = w * (int)g.h[l];
+		for (int p = threadIdx.x; p < n; p += WG) {
+			float o[4];
+			bl_down<false>(BlPlane{lds + (g.off[l - 1] - base), (int)g.w[l - 1]}, p % w, p / w, (int)g.w[l - 1], (int)g.h[l - 1], o);
+			lds[g.off[l] - base + p] = make_float4(o[0], o[1], o[2], o[3]);
+		}
+		__syncthreads();
+	}
+	for (uint32_t l = g.L - 1; l >= first; l--) { // (first >= 1: the loop ends)
+		const int w = (int)g.w[l], n = w * (int)g.h[l];
+		float4 *mine = lds + (g.off[l] - base);
+		for (int p = threadIdx.x; p < n; p += WG) {
+			const float4 d4 = mine[p];
+			const float d[4] = {d4.x, d4.y, d4.z, d4.w};
+			float o[4];
+			bl_merge(d, BlPlane{lds + (g.off[l + 1] - base), (int)g.w[l + 1]}, p % w, p / w, (int)g.w[l + 1], (int)g.h[l + 1], o);
+			mine[p] = make_float4(o[0], o[1], o[2], o[3]);
+		}
+		__syncthreads();
+	}
+	for (int p = threadIdx.x; p < n0; p += WG) pyramid[base + p] = lds[p];
+}
+
+// k_display with the bloom term: the bytes of n pixels of `acc`, rows W wide, from rgb * weight * exposure * *E + intensity * up(U_1) / L
+// (bloom.h bl_term, bl_pixel) -- the last upsample inline with four taps of u1 (w1 x h1): there is no full-resolution bloom plane.
+template <int OP, bool SRGB>
+__global__ __launch_bounds__(WG) void k_display_bloom(const float4 *acc, uchar4 *fb, uint32_t n, uint32_t W, float weight, float exposure, const float *E,
+                                                      DpCurve curve, const float4 *u1, int w1, int h1, uint32_t L, float intensity) {
+	const uint32_t i = blockIdx.x * WG + threadIdx.x;
+	if (i >= n) return;
+	const float4 a = acc[i];
+	const float rgb[3] = {a.x, a.y, a.z};
+	float term[3];
+	bl_term(BlPlane{u1, w1}, (int)(i % W), (int)(i / W), w1, h1, L, term);
+	uint8_t o[4];
+	bl_pixel<OP, SRGB>(rgb, term, weight, exposure, *E, intensity, curve, o);
 	fb[i] = make_uchar4(o[0], o[1], o[2], o[3]);
 }
 

@@ -123,6 +123,15 @@ inline void dp_init(DpDevice &d, const float *prev_log2E) {
 	if (prev_log2E) { d.s.log2E = *prev_log2E; d.s.valid = 1u; }
 }
 
+// The bloom of the display stage (polaris_hip_set_bloom; bloom.h): its params and its pyramid -- every level of the
+// whole frame in one allocation, made by the first bloomed sync and freed when bloom or the display goes off, by a changed set_bloom
+// and by a resize.  Not a Plane: SyncState does not know it.  Callers hold mu.
+struct BloomStage {
+	PolarisBloomParams p{sizeof(PolarisBloomParams), 0, 0, 0.0f, 0.0f, 0.0f, 0};
+	DevArray<float4> pyramid;
+	int fused = 0; // the option "bloom_fused": k_bloom_tail runs the small levels in one launch (off by default: not faster at 1024 x 1024)
+};
+
 // Everything behind the features of polaris_hip_sync_framebuffer: the parameters of denoising (polaris_hip_set_denoise),
 // temporal reuse across camera moves (_set_temporal) and variance guidance (_set_variance), the option "object_motion", every plane
 // they use and what of the planes is valid.  frame_sync.h holds the rules: nothing is allocated while its feature is off, the history
@@ -147,10 +156,11 @@ struct FrameSync {
 	std::vector<float> de_table_host;
 	CameraFloats tp_hcam{};               // the history's camera
 	DisplayStage dp;                      // the sync's last step, with the features on or off (its state is not a plane: SyncState does not know it)
+	BloomStage bl;                        // its bloom, in effect only with dp on
 
 	SyncFeatures features() const {
 		return {dn.iterations != 0, tp.max_history != 0, va.sigma_variance != 0.0f, opt_object_motion != 0, opt_vertex_motion != 0 && scene_deformable,
-		        dp.p.enabled != 0, dp.p.enabled != 0 && dp.p.auto_exposure != 0};
+		        dp.p.enabled != 0, dp.p.enabled != 0 && dp.p.auto_exposure != 0, bl.p.enabled != 0};
 	}
 	void drop(uint32_t set) {
 		for (uint32_t p = 0; p < kNumPlanes4; p++)
@@ -165,7 +175,7 @@ struct FrameSync {
 		if (swaps >> kInst & 1) std::swap(gb_inst, tp_hinst);
 		if (swaps) tp_hcam = cam;
 	}
-	void resized() { drop(v.resized()); dp.reset(); }
+	void resized() { drop(v.resized()); dp.reset(); bl.pyramid.reset(); }
 	void camera_moved(const CameraFloats &old) { capture(v.camera_moved(features()), old); }
 	void scene_changed(const InstTable *next, const CameraFloats &cam) { capture(v.scene_changed(features(), next), cam); } // (upload_scene and the in-place updates, before they change the scene)
 	void set_temporal(const PolarisTemporalParams &p) {
@@ -1460,6 +1470,10 @@ int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value
 			h->fs.set_vertex_motion((int)value);
 		}
 	}
+	else if (k == "bloom_fused") { // an A/B switch, the pyramid's values do not depend on it
+		if (value != 0 && value != 1) return fail(h, POLARIS_E_BAD_ARGUMENT, "bloom_fused is 0 or 1");
+		h->fs.bl.fused = (int)value;
+	}
 	else if (k == "guide_specular") {
 		if (value < 0 || value > 8) return fail(h, POLARIS_E_BAD_ARGUMENT, "guide_specular is 0..8");
 		if ((int)value != h->fs.opt_guide_specular) h->fs.set_guide_specular((int)value); // (no plane is freed: nothing to wait for)
@@ -1961,16 +1975,44 @@ struct SyncIo { // what the steps of a sync read and write: the rows [y0, y1) of
 	float4 *var, *ping, *pong, *out; uchar4 *fb;
 	uint32_t W, y0, y1; float exposure;
 	const DisplayStage *dp = nullptr; // with the display stage in the plan
+	const BloomStage *bl = nullptr;   // with bloom in the plan
 };
 
-// One of plan_tail's steps (frame_sync.h) on stream q over n pixels of src, read with weight w, into fb: the tone-map, or the display
-// stage's k_meter (behind the clear of its histogram), k_expose, k_display.
+// The pyramid launches of a bloomed sync under one bracket (bloom.h): D_1 .. D_L down -- level 1 from the bright pass of src --, then
+// U_{L-1} .. U_1 up in place.  fused: k_bloom_tail takes every level from bl_tail_start on, down and up, in one launch.
+void launch_bloom(polaris_hip_tracer *h, hipStream_t q, const float4 *src, float w, float exposure, const float *E, const BlLevels &g, const BloomStage &B) {
+	const PolarisBloomParams &p = B.p;
+	float4 *pyr = B.pyramid.get();
+	const BlBright bp{w, exposure, 1.0f, p.threshold, p.knee}; // (E is read on the device)
+	const uint32_t tail = B.fused ? bl_tail_start(g) : g.L + 1;
+	const int first = p.karis ? 2 : 1;
+	auto tiles = [](uint32_t lw, uint32_t lh) { return dim3((lw + kBlTile - 1) / kBlTile, (lh + kBlTile - 1) / kBlTile); };
+	Timed t(h, kSyncStepTimer[(int)SyncStep::Bloom], tail == 1 ? kBloomTail[first].symbol : kBloomDown[first].symbol, q);
+	for (uint32_t l = 1; l < tail; l++)
+		kBloomDown[l == 1 ? first : 0].enqueue(tiles(g.w[l], g.h[l]), WG, 0, q, l == 1 ? src : pyr + g.off[l - 1], (int)g.w[l - 1], (int)g.h[l - 1], pyr + g.off[l],
+		                                       (int)g.w[l], (int)g.h[l], bp, E);
+	if (tail <= g.L) kBloomTail[tail == 1 ? first : 0].enqueue(1u, WG, 0, q, src, pyr, g, tail, bp, E);
+	for (uint32_t l = std::min(tail, g.L) - 1; l >= 1; l--) // (with a tail: U_tail is in the pyramid)
+		kBloomUp.enqueue(tiles(g.w[l], g.h[l]), WG, 0, q, pyr + g.off[l], (int)g.w[l], (int)g.h[l], pyr + g.off[l + 1], (int)g.w[l + 1], (int)g.h[l + 1]);
+}
+
+// One of plan_tail's steps (frame_sync.h) on stream q over n pixels of src (rows W wide), read with weight w, into fb: the tone-map, or
+// the display stage's k_meter (behind the clear of its histogram), k_expose, the bloom pyramid (B: bloom is in the plan) and k_display
+// or k_display_bloom.
 constexpr uint32_t kMeterMaxGrid = 128; // k_meter's workgroups stride over the pixels, kMeterUnroll at a time: one flush of a histogram per workgroup
-void launch_tail_step(polaris_hip_tracer *h, hipStream_t q, SyncStep step, const float4 *src, float w, uchar4 *fb, size_t n, float exposure,
-                      const DisplayStage *D) {
+void launch_tail_step(polaris_hip_tracer *h, hipStream_t q, SyncStep step, const float4 *src, float w, uchar4 *fb, size_t n, uint32_t W, float exposure,
+                      const DisplayStage *D, const BloomStage *B) {
 	const PolarisDisplayParams *p = D ? &D->p : nullptr; // (null: the plan has no display step)
 	DpDevice *d = D ? D->dev.get() : nullptr;
 	const char *timer = kSyncStepTimer[(int)step];
+	if (B && (step == SyncStep::Bloom || step == SyncStep::Display)) { // (B: the plan has the bloom step, so D is there)
+		const BlLevels g = bl_levels(W, (uint32_t)(n / W), B->p.levels);
+		const float *E = p->auto_exposure ? &d->s.E : &d->one;
+		if (step == SyncStep::Bloom) launch_bloom(h, q, src, w, exposure, E, g, *B);
+		else (void)launch(h, timer, q, kDisplayBloom[p->tone_operator][p->srgb], grid_for(n), WG, 0, src, fb, (uint32_t)n, W, w, exposure, E, dp_curve(p->white),
+		                  (const float4 *)B->pyramid.get() + g.off[1], (int)g.w[1], (int)g.h[1], g.L, B->p.intensity);
+		return;
+	}
 	if (step == SyncStep::Tonemap) (void)launch(h, timer, q, kTonemap, grid_for(n), WG, 0, src, fb, (uint32_t)n, w, exposure);
 	else if (step == SyncStep::Meter) {
 		Timed t(h, timer, kMeter.symbol, q);
@@ -2012,7 +2054,7 @@ void launch_steps(polaris_hip_tracer *h, hipStream_t q, const SyncPlan &P, const
 			atrous(timer, kDenoise.symbol, p.sigma_luminance, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoise.enqueue(grid, WG, 0, q, c, cw, io.guide, io.albedo, in, dst, W, y0, y1, it, last); });
 		else if (step == SyncStep::DenoiseVariance)
 			atrous(timer, kDenoiseVariance.symbol, 0.0f, [&](const float4 *in, float4 *dst, const DnIter &it, int last) { kDenoiseVariance.enqueue(grid, WG, 0, q, c, cw, io.var, io.guide, io.albedo, in, dst, W, y0, y1, it, v.sigma_variance, last); });
-		else launch_tail_step(h, q, step, (filtered ? io.out : c) + off, filtered ? 1.0f : cw, io.fb + off, n, io.exposure, io.dp);
+		else launch_tail_step(h, q, step, (filtered ? io.out : c) + off, filtered ? 1.0f : cw, io.fb + off, n, W, io.exposure, io.dp, io.bl);
 	}
 }
 
@@ -2025,6 +2067,15 @@ int ensure_display(polaris_hip_tracer *h) {
 	dp_init(D.init, nullptr);
 	HIP_TRY(h, hipMemcpyAsync(D.dev, &D.init, sizeof(DpDevice), hipMemcpyHostToDevice, h->stream));
 	D.fresh = true;
+	return POLARIS_OK;
+}
+
+// The pyramid of a bloomed sync (caller holds mu): allocated at the first one for the whole frame, which no request's rows exceed.
+int ensure_bloom(polaris_hip_tracer *h) {
+	BloomStage &B = h->fs.bl;
+	if (B.pyramid) return POLARIS_OK;
+	const BlLevels g = bl_levels(h->fa.W, h->fa.H, B.p.levels);
+	HIP_TRY(h, B.pyramid.alloc(g.off[g.L + 1]));
 	return POLARIS_OK;
 }
 
@@ -2067,7 +2118,7 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 	HIP_TRY(h, h->fa.join_merges(h->stream)); // (as the plain sync: the merges queued so far are part of the frame)
 	launch_steps(h, h->stream, P, SyncIo{h->fa.frame, (float)(r->accumulated_samples + r->samples_per_pixel), weight, S.pl[kTpOut], S.pl[kTpPrior], S.pl[kTpPrior2],
 	                                     S.pl[kGuide], S.pl[kAlbedo], S.pl[kVaOut], S.pl[kDnPing], S.pl[kDnPong], S.pl[kDnOut], h->framebuffer, h->fa.W, r->block_y,
-	                                     r->block_y + r->block_h, r->exposure, f.display ? &S.dp : nullptr}, S.dn, S.va);
+	                                     r->block_y + r->block_h, r->exposure, f.display ? &S.dp : nullptr, f.bloomed() ? &S.bl : nullptr}, S.dn, S.va);
 	return POLARIS_OK;
 }
 
@@ -2153,13 +2204,34 @@ int polaris_hip_set_display(polaris_hip_tracer *h, const PolarisDisplayParams *p
 		            p->high_permille, (double)p->adapt);
 	DisplayStage &D = h->fs.dp;
 	if ((!p->enabled && !D.p.enabled) || memcmp(p, &D.p, sizeof *p) == 0) return POLARIS_OK; // (any two off states are equal)
-	if (!p->enabled) { // its device state goes
+	if (!p->enabled) { // its device state goes, the bloom pyramid with it
 		HIP_TRY(h, hipSetDevice(h->device));
 		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every display launch is on the main stream)
 		D.dev.reset();
+		h->fs.bl.pyramid.reset();
 	}
 	D.p = *p;
 	D.reset();
+	return POLARIS_OK;
+}
+
+int polaris_hip_set_bloom(polaris_hip_tracer *h, const PolarisBloomParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!p || p->struct_size != sizeof(PolarisBloomParams))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_bloom: null params or struct_size != %zu", sizeof(PolarisBloomParams));
+	if (bl_check(*p))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "set_bloom: enabled %u, karis %u (0 or 1), levels %u (1..%u), threshold %g ([0, %g]), knee %g ([0, 1]), intensity %g ([0, %g])",
+		            p->enabled, p->karis, p->levels, kBlMaxLevels, (double)p->threshold, (double)kBlMaxThreshold, (double)p->knee, (double)p->intensity,
+		            (double)kBlMaxIntensity);
+	BloomStage &B = h->fs.bl;
+	if ((!p->enabled && !B.p.enabled) || memcmp(p, &B.p, sizeof *p) == 0) return POLARIS_OK; // (any two off states are equal)
+	if (B.pyramid) { // the pyramid goes: off, or its levels may differ
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every bloom launch is on the main stream)
+		B.pyramid.reset();
+	}
+	B.p = *p;
 	return POLARIS_OK;
 }
 
@@ -2209,6 +2281,8 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 	const SyncFeatures f = h->fs.features();
 	if (f.display)
 		if (int rc = ensure_display(h)) return rc;
+	if (f.bloomed())
+		if (int rc = ensure_bloom(h)) return rc;
 	if (f.any()) {
 		if (int rc = enqueue_features(h, r, weight, f)) return rc;
 	} else {
@@ -2216,7 +2290,8 @@ int polaris_hip_sync_framebuffer(polaris_hip_tracer *h, const PolarisBlockReques
 		SyncStep steps[kMaxSyncSteps]; // the tone-map, or the display stage's steps
 		const int n_steps = plan_tail(f, steps, 0);
 		for (int s = 0; s < n_steps; s++)
-			launch_tail_step(h, h->stream, steps[s], h->fa.frame + off, weight, h->framebuffer + off, n, r->exposure, f.display ? &h->fs.dp : nullptr);
+			launch_tail_step(h, h->stream, steps[s], h->fa.frame + off, weight, h->framebuffer + off, n, h->fa.W, r->exposure, f.display ? &h->fs.dp : nullptr,
+			                 f.bloomed() ? &h->fs.bl : nullptr);
 	}
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2495,13 +2570,53 @@ int polaris_hip_display_planes(polaris_hip_tracer *h, const float *plane, uint32
 	f.auto_exposure = p->auto_exposure != 0;
 	SyncStep steps[kMaxSyncSteps];
 	const int n_steps = plan_tail(f, steps, 0);
-	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, exposure, &D);
+	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, W, exposure, &D, nullptr);
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {&got, D.dev.get(), sizeof got}}));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	collect_timers(h);
 	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
 	if (info) *info = PolarisExposureInfo{sizeof(PolarisExposureInfo), got.s.valid, (uint64_t)got.s.n_hi << 32 | got.s.n_lo, got.s.avg, got.s.log2E, got.s.E, 0};
+	return POLARIS_OK;
+}
+
+int polaris_hip_bloom_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
+                             float exposure, const PolarisDisplayParams *dp, const PolarisBloomParams *bp, const float *prev_log2E, uint8_t *rgba,
+                             float *level1, uint32_t *levels_used) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (!plane || !rgba || !dp || dp->struct_size != sizeof(PolarisDisplayParams) || !dp->enabled || dp_check(*dp) || !bp ||
+	    bp->struct_size != sizeof(PolarisBloomParams) || !bp->enabled || bl_check(*bp) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) ||
+	    block_h == 0 || block_y >= H || block_h > H - block_y)
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "bloom_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), or params polaris_hip_set_display / "
+		            "_set_bloom refuse (enabled must be 1 in both)", W, H, block_y, block_h);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, off = (size_t)block_y * W, n = (size_t)block_h * W;
+	const BlLevels g = bl_levels(W, block_h, bp->levels);
+	DisplayStage D; // (D.init is the source of an asynchronous copy: declared, as the stages' device memory, before d, whose StreamDrain waits
+	BloomStage B;   // for the stream on every way out before any of them leaves scope)
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(1, 1));
+	HIP_TRY(h, D.dev.alloc(1));
+	HIP_TRY(h, B.pyramid.alloc(g.off[g.L + 1]));
+	D.p = *dp;
+	B.p = *bp;
+	B.fused = h->fs.bl.fused;
+	dp_init(D.init, prev_log2E);
+	float4 *d_plane = d.f4(0);
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_plane, plane, F * sizeof(float4)}, {d_fb, rgba, F * sizeof(uchar4)}, {D.dev.get(), &D.init, sizeof(DpDevice)}}));
+	SyncFeatures f;
+	f.display = f.bloom = true;
+	f.auto_exposure = dp->auto_exposure != 0;
+	SyncStep steps[kMaxSyncSteps];
+	const int n_steps = plan_tail(f, steps, 0);
+	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, W, exposure, &D, &B);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {level1, B.pyramid.get() + g.off[1], (size_t)g.w[1] * g.h[1] * sizeof(float4)}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	if (levels_used) *levels_used = g.L;
 	return POLARIS_OK;
 }
 

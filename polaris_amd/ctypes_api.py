@@ -298,6 +298,33 @@ def display_params(enabled=1, **kw) -> DisplayParams:
     return p
 
 
+class BloomParams(C.Structure):
+    """PolarisBloomParams (include/polaris_hip.h): the bloom of the display transform -- a bright-pass pyramid added before the tone curve."""
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("levels", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float),
+                ("intensity", C.c_float), ("karis", C.c_uint32)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(BloomParams)
+
+
+assert C.sizeof(BloomParams) == 28
+# the suggested settings (DESIGN.md section 10m), chosen on the Cornell boxes with the CPU restatement
+BLOOM_DEFAULTS = {"levels": 5, "threshold": 1.0, "knee": 0.5, "intensity": 0.25, "karis": 1}
+
+
+def bloom_params(enabled=1, **kw) -> BloomParams:
+    """BloomParams with BLOOM_DEFAULTS for the fields not given."""
+    unknown = set(kw) - set(BLOOM_DEFAULTS)
+    if unknown:
+        raise TypeError(f"bloom_params: unknown fields {sorted(unknown)}")
+    f = dict(BLOOM_DEFAULTS, **kw)
+    p = BloomParams()
+    p.enabled, p.levels, p.karis = int(enabled), int(f["levels"]), int(f["karis"])
+    p.threshold, p.knee, p.intensity = float(f["threshold"]), float(f["knee"]), float(f["intensity"])
+    return p
+
+
 def variance_params(sigma_variance=8.0, min_samples=8) -> VarianceParams:
     p = VarianceParams()
     p.sigma_variance, p.min_samples = float(sigma_variance), int(min_samples)
@@ -516,7 +543,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_device_identity", "polaris_hip_can_access_peer", "polaris_hip_peer_info", "polaris_hip_merge_counts",
     "polaris_hip_set_denoise", "polaris_hip_read_aov", "polaris_hip_selftest_builtins", "polaris_hip_denoise_planes",
     "polaris_hip_set_temporal", "polaris_hip_reproject_planes", "polaris_hip_set_variance", "polaris_hip_variance_planes",
-    "polaris_hip_set_display", "polaris_hip_read_exposure", "polaris_hip_display_planes",
+    "polaris_hip_set_display", "polaris_hip_read_exposure", "polaris_hip_display_planes", "polaris_hip_set_bloom", "polaris_hip_bloom_planes",
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_reproject_deform_planes", "polaris_hip_read_hit_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
@@ -628,6 +655,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_read_exposure.argtypes = [vp, C.POINTER(ExposureInfo), vp]
     lib.polaris_hip_display_planes.argtypes = [vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DisplayParams), C.POINTER(C.c_float), vp, vp,
                                                C.POINTER(ExposureInfo)]
+    lib.polaris_hip_set_bloom.argtypes = [vp, C.POINTER(BloomParams)]
+    lib.polaris_hip_bloom_planes.argtypes = [vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DisplayParams), C.POINTER(BloomParams),
+                                             C.POINTER(C.c_float), vp, vp, C.POINTER(u32)]
     lib.polaris_hip_variance_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, C.c_float, C.POINTER(DenoiseParams),
                                                 C.POINTER(VarianceParams), vp, vp, vp]
     lib.polaris_hip_reproject_planes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, C.POINTER(TemporalParams), vp]

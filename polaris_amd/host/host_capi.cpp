@@ -204,6 +204,13 @@ int polaris_host_renderer_set_display(void *h, const PolarisDisplayParams *p) {
 		if (int rc = polaris_hip_set_display(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
 	return 0;
 }
+// The bloom of the display transform (polaris_hip_set_bloom) on every tracer, as set_display.
+int polaris_host_renderer_set_bloom(void *h, const PolarisBloomParams *p) {
+	auto *box = static_cast<RendererBox *>(h);
+	for (auto *t : box->hips)
+		if (int rc = polaris_hip_set_bloom(t->Handle(), p)) { box->error = polaris_hip_last_error(t->Handle()); return rc; }
+	return 0;
+}
 // What the primary's last sync with auto-exposure on metered (polaris_hip_read_exposure).
 int polaris_host_renderer_read_exposure(void *h, PolarisExposureInfo *out, uint32_t *histogram) {
 	auto *box = static_cast<RendererBox *>(h);

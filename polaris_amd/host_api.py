@@ -47,7 +47,13 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
         lib.polaris_host_renderer_set_display.argtypes = [vp, C.POINTER(T.DisplayParams)]
         lib.polaris_host_renderer_read_exposure.argtypes = [vp, C.POINTER(T.ExposureInfo), vp]
+        lib.polaris_host_renderer_set_bloom.argtypes = [vp, C.POINTER(T.BloomParams)]
         u32 = C.c_uint32
+        lib.polaris_host_bloom.argtypes = [vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(T.DisplayParams), C.POINTER(T.BloomParams),
+                                           C.POINTER(C.c_float), vp, vp, vp, C.POINTER(u32)]
+        lib.polaris_host_bloom_check.argtypes = [C.POINTER(T.BloomParams)]
+        lib.polaris_host_bloom_levels.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+        lib.polaris_host_bloom_levels.restype = u32
         lib.polaris_host_display.argtypes = [vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(T.DisplayParams), C.POINTER(C.c_float), vp, vp,
                                              C.POINTER(T.ExposureInfo)]
         lib.polaris_host_variance.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, C.POINTER(T.DenoiseParams), C.POINTER(T.VarianceParams), vp]
@@ -223,6 +229,13 @@ class Renderer:
         p = T.display_params(enabled, **fields)
         if self._lib.polaris_host_renderer_set_display(self._h, C.byref(p)):
             raise RuntimeError(f"set_display failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
+    def set_bloom(self, enabled: int = 1, **fields) -> None:
+        """polaris_hip_set_bloom on every tracer (polaris_host_renderer_set_bloom): the bloom of the primary's displayed SyncFramebuffer,
+        in effect while set_display is on.  fields: those of ctypes_api.BLOOM_DEFAULTS; enabled = 0 turns it off."""
+        p = T.bloom_params(enabled, **fields)
+        if self._lib.polaris_host_renderer_set_bloom(self._h, C.byref(p)):
+            raise RuntimeError(f"set_bloom failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
     def read_exposure(self) -> dict:
         """polaris_hip_read_exposure of the primary: what its last sync with auto-exposure on metered, as display()'s info, with the
@@ -480,6 +493,38 @@ def display(plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int =
     if rc:
         raise ValueError(f"display: bad arguments (code {rc})")
     return fb, hist, exposure_info(info)
+
+
+def bloom_levels(W: int, rows: int, levels: int) -> tuple[int, int, int]:
+    """(levels used, w_1, h_1) of the bloom pyramid over a region W x rows with `levels` asked for (bloom.h bl_levels)."""
+    w1, h1 = C.c_uint32(), C.c_uint32()
+    L = load().polaris_host_bloom_levels(int(W), int(rows), int(levels), C.byref(w1), C.byref(h1))
+    return int(L), int(w1.value), int(h1.value)
+
+
+def bloom(plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None, rgba=None, prev_log2E=None,
+          display: dict | None = None, **fields) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """polaris_host_bloom: the CPU restatement of a bloomed displayed sync (polaris_amd/host/bloom.cpp) over the request's rows of an
+    (H, W, 4) float32 plane.  display: fields of ctypes_api.DISPLAY_DEFAULTS; fields: those of ctypes_api.BLOOM_DEFAULTS.  Returns
+    (RGBA8 -- `rgba` (a copy) with the request's rows written --, U_1 (h_1, w_1, 4), the full-resolution term of the request's rows
+    (block_h, W, 4), levels used).  ValueError where refused."""
+    (c,), H, W = _planes("bloom", plane)
+    fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, dtype=np.uint8, order="C", copy=True)
+    if fb.shape != (H, W, 4):
+        raise ValueError("bloom: rgba must be (H, W, 4) uint8")
+    bh = int(H - block_y if block_h is None else block_h)
+    dp, bp = T.display_params(1, **(display or {})), T.bloom_params(1, **fields)
+    if not (0 <= block_y < H and 0 < bh <= H - block_y) or load().polaris_host_bloom_check(C.byref(bp)):
+        raise ValueError("bloom: bad rows or bloom params")
+    L, w1, h1 = bloom_levels(W, bh, bp.levels)
+    u1, term, used = np.zeros((h1, w1, 4), np.float32), np.zeros((bh, W, 4), np.float32), C.c_uint32()
+    prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
+    rc = load().polaris_host_bloom(c.ctypes.data, W, H, int(block_y), bh, float(weight), float(exposure), C.byref(dp), C.byref(bp), prev, fb.ctypes.data,
+                                   u1.ctypes.data, term.ctypes.data, C.byref(used))
+    if rc:
+        raise ValueError(f"bloom: bad arguments (code {rc})")
+    assert used.value == L
+    return fb, u1, term, L
 
 
 def variance(frame_acc, samples: int, guide, albedo, *, temporal=None, prior2=None, block_y: int = 0, block_h: int | None = None, out=None,

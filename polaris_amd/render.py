@@ -45,7 +45,12 @@ tone-map by the display transform (polaris_hip_set_display): the 
 hable map to 1), the sRGB transfer function instead of pow(1 / 2.2), and the frame's own metered exposure (key 0.18, the window
 between the median and the 95th percentile; X stops of compensation; A the fraction of the way to the target per frame) times
 --exposure.  With --aov-dir the last frame's exposure and histogram are written as exposure.json.  A flag that would be ignored is an
-error: --white without reinhard-white or hable, --ev-comp or --adapt without --auto-exposure."""
+error: --white without reinhard-white or hable, --ev-comp or --adapt without --auto-exposure.
+
+--bloom [INTENSITY] [--bloom-threshold T] [--bloom-levels N] adds bloom to the display transform (polaris_hip_set_bloom): a
+bright-pass pyramid of N levels over the displayed values above T, added INTENSITY times before the tone operator (the other fields
+are ctypes_api.BLOOM_DEFAULTS).  Bloom is part of the display transform: --bloom without --tonemap, --srgb or --auto-exposure is an
+error, and so are --bloom-threshold and --bloom-levels without --bloom."""
 import argparse
 import json
 import os
@@ -210,8 +215,16 @@ def main(argv=None):
     ap.add_argument("--auto-exposure", action="store_true", help="meter every frame and expose it to middle grey")
     ap.add_argument("--ev-comp", type=float, default=0.0, help="with --auto-exposure: exposure compensation in stops")
     ap.add_argument("--adapt", type=float, default=1.0, help="with --auto-exposure: the fraction (0, 1] of the way to the metered exposure per frame")
+    ap.add_argument("--bloom", type=float, nargs="?", const=T.BLOOM_DEFAULTS["intensity"], default=None, metavar="INTENSITY",
+                    help="with a display flag: add bloom, INTENSITY times the bright-pass pyramid (default %(const)s)")
+    ap.add_argument("--bloom-threshold", type=float, default=None, help="with --bloom: the displayed value above which a pixel blooms")
+    ap.add_argument("--bloom-levels", type=int, default=None, help="with --bloom: pyramid levels 1..8")
     a = ap.parse_args(argv)
     display = a.tonemap is not None or a.srgb or a.auto_exposure
+    if a.bloom is not None and not display:
+        ap.error("--bloom needs --tonemap, --srgb or --auto-exposure")
+    if (a.bloom_threshold is not None or a.bloom_levels is not None) and a.bloom is None:
+        ap.error("--bloom-threshold and --bloom-levels need --bloom")
     if (a.ev_comp or a.adapt != 1.0) and not a.auto_exposure:
         ap.error("--ev-comp and --adapt need --auto-exposure")
     if a.white != T.DISPLAY_DEFAULTS["white"] and a.tonemap not in ("reinhard-white", "hable"):
@@ -246,6 +259,9 @@ def main(argv=None):
         if display:
             r.set_display(1, tone_operator=a.tonemap or "reinhard", white=a.white, srgb=int(a.srgb), auto_exposure=int(a.auto_exposure),
                           compensation_ev=a.ev_comp, adapt=a.adapt)
+        if a.bloom is not None:
+            r.set_bloom(1, intensity=a.bloom, threshold=T.BLOOM_DEFAULTS["threshold"] if a.bloom_threshold is None else a.bloom_threshold,
+                        levels=T.BLOOM_DEFAULTS["levels"] if a.bloom_levels is None else a.bloom_levels)
         if a.aperture:
             focus = a.focus
             if a.focus_pixel:

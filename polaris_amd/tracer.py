@@ -230,6 +230,30 @@ class HipTracer:
         p = T.display_params(enabled, **fields)
         self._check(self._lib.polaris_hip_set_display(self._h, C.byref(p)), self._h)
 
+    def set_bloom(self, enabled: int = 1, **fields) -> None:
+        """The bloom of the display transform (polaris_hip_set_bloom): a bright-pass pyramid added before the tone curve, in effect while
+        set_display is on.  fields: those of T.BLOOM_DEFAULTS; enabled = 0 turns it off (the default)."""
+        p = T.bloom_params(enabled, **fields)
+        self._check(self._lib.polaris_hip_set_bloom(self._h, C.byref(p)), self._h)
+
+    def bloom_planes(self, plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None, rgba=None,
+                     prev_log2E=None, display: dict | None = None, **fields) -> tuple[np.ndarray, np.ndarray, int]:
+        """polaris_hip_bloom_planes: the launches of a bloomed displayed sync on a caller (H, W, 4) float32 plane.  display: fields of
+        T.DISPLAY_DEFAULTS; fields: those of T.BLOOM_DEFAULTS.  Returns (RGBA8, U_1 (h_1, w_1, 4), levels used); rows outside the
+        request come back as passed (zeros by default)."""
+        plane = np.ascontiguousarray(plane, dtype=np.float32)
+        H, W = plane.shape[:2]
+        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
+        assert plane.shape == fb.shape == (H, W, 4)
+        bh = int(H - block_y if block_h is None else block_h)
+        dp, bp, used = T.display_params(1, **(display or {})), T.bloom_params(1, **fields), C.c_uint32()
+        w1, h1 = (W + 1) // 2, (max(bh, 1) + 1) // 2
+        u1 = np.zeros((h1, w1, 4), np.float32)
+        prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
+        self._check(self._lib.polaris_hip_bloom_planes(self._h, plane.ctypes.data, W, H, int(block_y), bh, float(weight), float(exposure), C.byref(dp),
+                                                       C.byref(bp), prev, fb.ctypes.data, u1.ctypes.data, C.byref(used)), self._h)
+        return fb, u1, int(used.value)
+
     def read_exposure(self) -> dict:
         """polaris_hip_read_exposure: what the last sync with auto-exposure on metered -- valid, n_metered, the float32 values avg,
         log2E and E, and the 256 counts under "histogram"."""
