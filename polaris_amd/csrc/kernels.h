@@ -2297,6 +2297,31 @@ __global__ __launch_bounds__(WG) void k_denoise(const float4 *acc, float weight,
 // MOTION (option "object_motion"): the two INSTANCE planes (inst current, hinst the history's: one more word per tap) and the
 // motion table (four float4 per instance, temporal.h tp_motion_table; n_inst entries) -- at most four float4 of it per pixel, by
 // plain global loads: the instance index is nearly wave-uniform.  The variants without MOTION read none of the three.
+// History tap j as both reprojection kernels gather it: three float4, the VARIANCE plane's M2 with M2 and the INSTANCE word with MOTION.
+template <bool M2, bool MOTION>
+__device__ __forceinline__ void reproject_tap(const float4 *hist, const float4 *hguide, const float4 *halbedo, const float4 *hvar, const uint32_t *hinst,
+                                              uint32_t j, TpTap &t) {
+	const float4 c = hist[j], n = hguide[j];
+	t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
+	t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
+	t.leaf = halbedo[j].w;
+	if (M2) t.m2 = hvar[j].y;
+	if (MOTION) t.inst = hinst[j];
+}
+// Entry k of a motion or deformation table (four float4 per instance; k < n_inst: tp_reproject checks): the flag, and for MOVED the
+// twelve floats of its rows into D.
+__device__ __forceinline__ uint32_t reproject_table_entry(const float4 *tab, uint32_t k, float *D) {
+	const float4 *e = tab + 4 * (size_t)k;
+	const uint32_t flag = pm_f2u(e[3].x);
+	if (flag == kTpMoved) {
+		const float4 r0 = e[0], r1 = e[1], r2 = e[2];
+		D[0] = r0.x; D[1] = r0.y; D[2] = r0.z; D[3] = r0.w;
+		D[4] = r1.x; D[5] = r1.y; D[6] = r1.z; D[7] = r1.w;
+		D[8] = r2.x; D[9] = r2.y; D[10] = r2.z; D[11] = r2.w;
+	}
+	return flag;
+}
+
 template <bool M2, bool MOTION>
 __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
                                                   const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
@@ -2307,27 +2332,10 @@ __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const floa
 	if (i >= W * H) return;
 	const float4 g = guide[i];
 	const float gi[4] = {g.x, g.y, g.z, g.w};
-	auto load = [&](uint32_t j, TpTap &t) {
-		const float4 c = hist[j], n = hguide[j];
-		t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
-		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
-		t.leaf = halbedo[j].w;
-		if (M2) t.m2 = hvar[j].y;
-		if (MOTION) t.inst = hinst[j];
-	};
+	auto load = [&](uint32_t j, TpTap &t) { reproject_tap<M2, MOTION>(hist, hguide, halbedo, hvar, hinst, j, t); };
 	float o[4], o2[4];
 	if constexpr (MOTION) {
-		auto entry = [&](uint32_t k, float *D) -> uint32_t { // (k < n_inst: tp_reproject checks)
-			const float4 *e = motion + 4 * (size_t)k;
-			const uint32_t flag = pm_f2u(e[3].x);
-			if (flag == kTpMoved) {
-				const float4 r0 = e[0], r1 = e[1], r2 = e[2];
-				D[0] = r0.x; D[1] = r0.y; D[2] = r0.z; D[3] = r0.w;
-				D[4] = r1.x; D[5] = r1.y; D[6] = r1.z; D[7] = r1.w;
-				D[8] = r2.x; D[9] = r2.y; D[10] = r2.z; D[11] = r2.w;
-			}
-			return flag;
-		};
+		auto entry = [&](uint32_t k, float *D) -> uint32_t { return reproject_table_entry(motion, k, D); };
 		tp_reproject<M2, true>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2, inst[i],
 		                       n_inst, entry);
 	} else tp_reproject<M2>(i % W, i / W, W, H, gi, albedo[i].w, cam, hcam, max_history, normal_threshold, depth_threshold, load, o, o2);
@@ -2353,27 +2361,8 @@ __global__ __launch_bounds__(WG) void k_reproject_deform(const float4 *hist, con
 	const float gi[4] = {g.x, g.y, g.z, g.w};
 	const uint4 h4 = hit[i];
 	const uint32_t hi[3] = {h4.x, h4.y, h4.z};
-	auto load = [&](uint32_t j, TpTap &t) {
-		const float4 c = hist[j], n = hguide[j];
-		t.r = c.x; t.g = c.y; t.b = c.z; t.count = c.w;
-		t.nx = n.x; t.ny = n.y; t.nz = n.z; t.t = n.w;
-		t.leaf = halbedo[j].w;
-		if (M2) t.m2 = hvar[j].y;
-		t.inst = hinst[j];
-	};
-	auto table = [](const float4 *tab) {
-		return [tab](uint32_t k, float *D) -> uint32_t { // (k < n_inst: tp_reproject checks)
-			const float4 *e = tab + 4 * (size_t)k;
-			const uint32_t flag = pm_f2u(e[3].x);
-			if (flag == kTpMoved) {
-				const float4 r0 = e[0], r1 = e[1], r2 = e[2];
-				D[0] = r0.x; D[1] = r0.y; D[2] = r0.z; D[3] = r0.w;
-				D[4] = r1.x; D[5] = r1.y; D[6] = r1.z; D[7] = r1.w;
-				D[8] = r2.x; D[9] = r2.y; D[10] = r2.z; D[11] = r2.w;
-			}
-			return flag;
-		};
-	};
+	auto load = [&](uint32_t j, TpTap &t) { reproject_tap<M2, true>(hist, hguide, halbedo, hvar, hinst, j, t); };
+	auto table = [](const float4 *tab) { return [tab](uint32_t k, float *D) -> uint32_t { return reproject_table_entry(tab, k, D); }; };
 	auto triangle = [&](uint32_t T, float *a, float *b) { // (T < n_tris: tp_reproject checks)
 		const size_t off = 3 * (size_t)T;
 		for (int k = 0; k < 3; k++) {

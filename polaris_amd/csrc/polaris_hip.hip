@@ -32,6 +32,7 @@
 #include "kernel_table.h"
 #include "merge_plan.h"
 #include "polaris_hip.h"
+#include "reproject_io.h"
 #include "trace_plan.h"
 
 using namespace pol;
@@ -1932,11 +1933,6 @@ int polaris_hip_wait_reset(polaris_hip_tracer *h, uint64_t epoch) {
 } // extern "C"
 
 namespace {
-TpCamera tp_camera(const float eye[3], const float fr[16]) {
-	return TpCamera{{fr[0], fr[1], fr[2], fr[3]}, {fr[4], fr[5], fr[6], fr[7]}, {fr[8], fr[9], fr[10], fr[11]}, {fr[12], fr[13], fr[14], fr[15]},
-	                {eye[0], eye[1], eye[2]}};
-}
-
 // The PRIOR plane of a W x H frame on stream q (caller holds mu): the history (hist, hguide, halbedo under hcam; hist = null: none)
 // reprojected onto the G-buffer (guide, albedo) under cam.  polaris_hip_sync_framebuffer and polaris_hip_reproject_planes both
 // launch it through here.
@@ -2140,6 +2136,132 @@ struct PlaneScratch {
 		return hipSuccess;
 	}
 };
+
+// The refusal of a *_planes test entry (caller holds mu): the entry, the text of the broken rule (reproject_io.h, or the entry's own
+// about its params) and the numbers the rules are about.
+int refuse_planes(polaris_hip_tracer *h, const char *name, const char *rule, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h) {
+	return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: %s (frame %ux%u, rows [%u, +%u))", name, rule, W, H, block_y, block_h);
+}
+const char *frame_rows_rule(uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h) { // (null: both hold)
+	int rule = check_frame(W, H);
+	if (!rule) rule = check_rows(H, block_y, block_h);
+	return rule ? plane_rule_text(rule) : nullptr;
+}
+
+PolarisExposureInfo exposure_info(const DpDevice &d) {
+	return PolarisExposureInfo{sizeof(PolarisExposureInfo), d.s.valid, (uint64_t)d.s.n_hi << 32 | d.s.n_lo, d.s.avg, d.s.log2E, d.s.E, 0};
+}
+
+// THE body of polaris_hip_denoise_planes (variance = null: no VARIANCE plane) and polaris_hip_variance_planes (arguments checked; caller holds
+// mu): the planes of a sync with the features f uploaded, its steps over the rows, VARIANCE (if any), DENOISED and the frame read back.
+int filter_planes_entry(polaris_hip_tracer *h, const SyncFeatures &f, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
+                        uint32_t block_y, uint32_t block_h, float nf, float weight, float exposure, const PolarisDenoiseParams &p,
+                        const PolarisVarianceParams &v, float *variance, float *denoised, uint8_t *rgba) {
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, plane = F * sizeof(float4), pixels = F * sizeof(uchar4);
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(variance ? 7 : 6, 1));
+	float4 *d_acc = d.f4(0), *d_guide = d.f4(1), *d_albedo = d.f4(2), *d_ping = d.f4(3), *d_pong = d.f4(4), *d_out = d.f4(5), *d_var = variance ? d.f4(6) : nullptr;
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_acc, acc, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}, {d_var, variance, plane}, {d_out, denoised, plane},
+	                                          {d_fb, rgba, pixels}}));
+	launch_steps(h, h->stream, plan_sync(f, SyncState()),
+	             SyncIo{d_acc, nf, weight, nullptr, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure}, p, v);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{variance, d_var, plane}, {denoised, d_out, plane}, {rgba, d_fb, pixels}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
+
+// THE body of polaris_hip_display_planes (bp = null: display only) and polaris_hip_bloom_planes: the tail of a displayed sync over the
+// rows of a caller plane, on a display stage (and a pyramid) of its own.
+int display_planes_entry(polaris_hip_tracer *h, const char *name, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
+                         float exposure, const PolarisDisplayParams *dp, const PolarisBloomParams *bp, bool bloom, const float *prev_log2E, uint8_t *rgba,
+                         uint32_t histogram[256], PolarisExposureInfo *info, float *level1, uint32_t *levels_used) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const char *rule = !plane || !rgba || !dp || (bloom && !bp) ? plane_rule_text(kRuleNull) : frame_rows_rule(W, H, block_y, block_h);
+	if (!rule && (dp->struct_size != sizeof(PolarisDisplayParams) || !dp->enabled || dp_check(*dp)))
+		rule = "params polaris_hip_set_display refuses (enabled must be 1)";
+	if (!rule && bloom && (bp->struct_size != sizeof(PolarisBloomParams) || !bp->enabled || bl_check(*bp)))
+		rule = "params polaris_hip_set_bloom refuses (enabled must be 1)";
+	if (!rule && info && info->struct_size != sizeof(PolarisExposureInfo)) rule = "info's struct_size";
+	if (rule) return refuse_planes(h, name, rule, W, H, block_y, block_h);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t F = (size_t)W * H, off = (size_t)block_y * W, n = (size_t)block_h * W;
+	const BlLevels g = bloom ? bl_levels(W, block_h, bp->levels) : BlLevels{};
+	const bool metered = histogram || info;
+	DisplayStage D; // (its device state and the pyramid go after the stream is drained)
+	BloomStage B;
+	DpDevice got;   // D.init and got are the source and target of asynchronous copies: all are declared before d, whose StreamDrain waits
+	                // for the stream on every way out, early returns included, before any of them leaves scope
+	PlaneScratch d{h->stream, F};
+	HIP_TRY(h, d.alloc(1, 1));
+	HIP_TRY(h, D.dev.alloc(1));
+	if (bloom) HIP_TRY(h, B.pyramid.alloc(g.off[g.L + 1]));
+	D.p = *dp;
+	if (bloom) B.p = *bp;
+	B.fused = h->fs.bl.fused;
+	dp_init(D.init, prev_log2E);
+	float4 *d_plane = d.f4(0);
+	uchar4 *d_fb = (uchar4 *)d.word(0);
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_plane, plane, F * sizeof(float4)}, {d_fb, rgba, F * sizeof(uchar4)}, {D.dev.get(), &D.init, sizeof(DpDevice)}}));
+	SyncFeatures f;
+	f.display = true;
+	f.bloom = bloom;
+	f.auto_exposure = dp->auto_exposure != 0;
+	SyncStep steps[kMaxSyncSteps];
+	const int n_steps = plan_tail(f, steps, 0);
+	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, W, exposure, &D, bloom ? &B : nullptr);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {metered ? &got : nullptr, D.dev.get(), sizeof got},
+	                                          {level1, bloom ? B.pyramid.get() + g.off[1] : nullptr, (size_t)g.w[1] * g.h[1] * sizeof(float4)}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
+	if (info) *info = exposure_info(got);
+	if (levels_used) *levels_used = g.L;
+	return POLARIS_OK;
+}
+
+// THE body of polaris_hip_reproject_planes, _reproject_motion_planes and _reproject_deform_planes: the PRIOR (and PRIOR2) of a
+// description, by the kernel launch_reproject selects for its groups.  Reads and writes no tracer state.
+int reproject_planes_entry(polaris_hip_tracer *h, const char *name, const ReprojectIo &io) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	if (const int rule = check_reproject(io))
+		return fail(h, POLARIS_E_BAD_ARGUMENT, "%s: %s (frame %ux%u, %u instances, %u triangles)", name, plane_rule_text(rule), io.W, io.H, io.n_instances, io.num_triangles);
+	HIP_TRY(h, hipSetDevice(h->device));
+	const bool motion = io.motion(), deform = io.deform();
+	const uint32_t ni = io.n_instances;
+	const size_t F = (size_t)io.W * io.H, plane = F * sizeof(float4), words = F * sizeof(uint32_t), nv = (size_t)io.num_triangles * 3;
+	std::vector<float> table((size_t)ni * (deform ? 32 : 16)); // the motion table, then the deformation table
+	if (motion) tp_motion_table(ni, io.prev_inv_transforms, io.inv_transforms, table.data());
+	if (deform) tp_deform_table(ni, io.prev_inv_transforms, table.data() + (size_t)ni * 16);
+	DevArray<float4> d_table, d_verts;
+	PlaneScratch d{h->stream, F}; // (declared after the tables and the side arrays: its StreamDrain waits for the stream on every way out,
+	                              // early returns included, before the memory and the host vector that asynchronous copies read leave scope)
+	HIP_TRY(h, d.alloc(deform ? 9 : (motion ? 8 : 6), motion ? 2 : 0)); // (the ninth float4 plane holds the HIT words)
+	if (motion) HIP_TRY(h, d_table.alloc((size_t)ni * (deform ? 8 : 4)));
+	if (deform) HIP_TRY(h, d_verts.alloc(2 * nv));
+	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5);
+	float4 *d_hvar = io.m2() ? d.f4(6) : nullptr, *d_prior2 = io.m2() ? d.f4(7) : nullptr;
+	uint4 *d_hit = deform ? (uint4 *)d.f4(8) : nullptr;
+	uint32_t *d_hinst = motion ? d.word(0) : nullptr, *d_inst = motion ? d.word(1) : nullptr;
+	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, io.history, plane}, {d_hguide, io.prev_guide, plane}, {d_halbedo, io.prev_albedo, plane}, {d_guide, io.guide, plane},
+	                                          {d_albedo, io.albedo, plane}, {d_hvar, io.history_variance, plane}, {d_hinst, io.prev_instance, words}, {d_inst, io.instance, words},
+	                                          {d_hit, io.hit, F * sizeof(uint4)}, {d_table.get(), table.data(), table.size() * sizeof(float)},
+	                                          {d_verts.get(), io.vertices, nv * sizeof(float4)}, {deform ? d_verts.get() + nv : nullptr, io.prev_vertices, nv * sizeof(float4)}}));
+	MotionArgs mo{d_inst, d_hinst, d_table, ni};
+	if (deform) { mo.hit = d_hit; mo.verts = d_verts; mo.hverts = d_verts.get() + nv; mo.deform = d_table.get() + (size_t)ni * 4; mo.n_tris = io.num_triangles; }
+	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(io.prev_eye, io.prev_frustum), d_guide, d_albedo, tp_camera(io.eye, io.frustum),
+	                            io.W, io.H, *io.p, d_prior, d_hvar, d_prior2, motion ? &mo : nullptr));
+	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{io.prior, d_prior, plane}, {io.prior2, d_prior2, plane}}));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	collect_timers(h);
+	return POLARIS_OK;
+}
 } // namespace
 
 extern "C" {
@@ -2246,7 +2368,7 @@ int polaris_hip_read_exposure(polaris_hip_tracer *h, PolarisExposureInfo *out, u
 	DpDevice got;
 	HIP_TRY(h, hipMemcpyAsync(&got, D.dev, sizeof got, hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	*out = PolarisExposureInfo{sizeof(PolarisExposureInfo), got.s.valid, (uint64_t)got.s.n_hi << 32 | got.s.n_lo, got.s.avg, got.s.log2E, got.s.E, 0};
+	*out = exposure_info(got);
 	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
 	return POLARIS_OK;
 }
@@ -2492,25 +2614,12 @@ int polaris_hip_denoise_planes(polaris_hip_tracer *h, const float *acc, const fl
                                float *denoised, uint8_t *rgba) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!acc || !guide || !albedo || !denoised || !rgba || !p || p->struct_size != sizeof(PolarisDenoiseParams) || W == 0 || H == 0 ||
-	    (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H || block_h > H - block_y || p->iterations == 0 ||
-	    dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "denoise_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), or params "
-		            "(iterations 1..%u)", W, H, block_y, block_h, kDnMaxIterations);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4), pixels = F * sizeof(uchar4);
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(6, 1));
-	float4 *d_acc = d.f4(0), *d_guide = d.f4(1), *d_albedo = d.f4(2), *d_ping = d.f4(3), *d_pong = d.f4(4), *d_out = d.f4(5);
-	uchar4 *d_fb = (uchar4 *)d.word(0);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_acc, acc, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}, {d_out, denoised, plane}, {d_fb, rgba, pixels}}));
-	launch_steps(h, h->stream, plan_sync(SyncFeatures{true, false, false, false}, SyncState()),
-	             SyncIo{d_acc, 0.0f, weight, nullptr, nullptr, nullptr, d_guide, d_albedo, nullptr, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure}, *p, PolarisVarianceParams{});
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{denoised, d_out, plane}, {rgba, d_fb, pixels}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	return POLARIS_OK;
+	const char *rule = !acc || !guide || !albedo || !denoised || !rgba || !p ? plane_rule_text(kRuleNull) : frame_rows_rule(W, H, block_y, block_h);
+	if (!rule && (p->struct_size != sizeof(PolarisDenoiseParams) || p->iterations == 0 || dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance)))
+		rule = "params polaris_hip_set_denoise refuses, or iterations 0";
+	if (rule) return refuse_planes(h, "denoise_planes", rule, W, H, block_y, block_h);
+	return filter_planes_entry(h, SyncFeatures{true, false, false, false}, acc, guide, albedo, W, H, block_y, block_h, 0.0f, weight, exposure, *p, PolarisVarianceParams{},
+	                           nullptr, denoised, rgba);
 }
 
 int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const float *guide, const float *albedo, uint32_t W, uint32_t H,
@@ -2518,131 +2627,33 @@ int polaris_hip_variance_planes(polaris_hip_tracer *h, const float *acc, const f
                                 const PolarisVarianceParams *v, float *variance, float *denoised, uint8_t *rgba) {
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
-	if (!acc || !guide || !albedo || !variance || !denoised || !rgba || !p || !v || p->struct_size != sizeof(PolarisDenoiseParams) ||
-	    v->struct_size != sizeof(PolarisVarianceParams) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H ||
-	    block_h > H - block_y || samples == 0 || dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance) ||
-	    v->sigma_variance == 0.0f || va_check(v->sigma_variance, v->min_samples))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "variance_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), samples %u (> 0), or "
-		            "params (sigma_variance [%g, %g], min_samples 1..%u)", W, H, block_y, block_h, samples, (double)kDnSigmaMin, (double)kDnSigmaMax,
-		            kVaMaxMinSamples);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4), pixels = F * sizeof(uchar4);
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(7, 1));
-	float4 *d_acc = d.f4(0), *d_guide = d.f4(1), *d_albedo = d.f4(2), *d_var = d.f4(3), *d_ping = d.f4(4), *d_pong = d.f4(5), *d_out = d.f4(6);
-	uchar4 *d_fb = (uchar4 *)d.word(0);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_acc, acc, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}, {d_var, variance, plane}, {d_out, denoised, plane},
-	                                          {d_fb, rgba, pixels}}));
+	const char *rule = !acc || !guide || !albedo || !variance || !denoised || !rgba || !p || !v ? plane_rule_text(kRuleNull) : frame_rows_rule(W, H, block_y, block_h);
+	if (!rule && (p->struct_size != sizeof(PolarisDenoiseParams) || v->struct_size != sizeof(PolarisVarianceParams) || samples == 0 ||
+	              dn_check(p->iterations, p->normal_power_log2, p->sigma_depth, p->sigma_luminance) || v->sigma_variance == 0.0f || va_check(v->sigma_variance, v->min_samples)))
+		rule = "samples 0, or params polaris_hip_set_denoise / _set_variance refuse, or sigma_variance 0";
+	if (rule) return refuse_planes(h, "variance_planes", rule, W, H, block_y, block_h);
 	const float weight = (float)(1.0 / (float)samples); // (polaris_hip_sync_framebuffer's)
-	launch_steps(h, h->stream, plan_sync(SyncFeatures{p->iterations != 0, false, true, false}, SyncState()),
-	             SyncIo{d_acc, (float)samples, weight, nullptr, nullptr, nullptr, d_guide, d_albedo, d_var, d_ping, d_pong, d_out, d_fb, W, block_y, block_y + block_h, exposure}, *p, *v);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{variance, d_var, plane}, {denoised, d_out, plane}, {rgba, d_fb, pixels}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	return POLARIS_OK;
+	return filter_planes_entry(h, SyncFeatures{p->iterations != 0, false, true, false}, acc, guide, albedo, W, H, block_y, block_h, (float)samples, weight, exposure, *p, *v,
+	                           variance, denoised, rgba);
 }
 
 int polaris_hip_display_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
                                float exposure, const PolarisDisplayParams *p, const float *prev_log2E, uint8_t *rgba, uint32_t histogram[256],
                                PolarisExposureInfo *info) {
-	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::lock_guard<std::mutex> lk(h->mu);
-	if (!plane || !rgba || !p || p->struct_size != sizeof(PolarisDisplayParams) || !p->enabled || dp_check(*p) || W == 0 || H == 0 ||
-	    (uint64_t)W * H > (1ull << 26) || block_h == 0 || block_y >= H || block_h > H - block_y || (info && info->struct_size != sizeof(PolarisExposureInfo)))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "display_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), info's struct_size, or params "
-		            "polaris_hip_set_display refuses (enabled must be 1)", W, H, block_y, block_h);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, off = (size_t)block_y * W, n = (size_t)block_h * W;
-	DisplayStage D; // (its device state goes after the stream is drained)
-	DpDevice got;   // D.init and got are the source and target of asynchronous copies: both are declared before d, whose StreamDrain waits
-	                // for the stream on every way out, early returns included, before either leaves scope
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(1, 1));
-	HIP_TRY(h, D.dev.alloc(1));
-	D.p = *p;
-	dp_init(D.init, prev_log2E);
-	float4 *d_plane = d.f4(0);
-	uchar4 *d_fb = (uchar4 *)d.word(0);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_plane, plane, F * sizeof(float4)}, {d_fb, rgba, F * sizeof(uchar4)}, {D.dev.get(), &D.init, sizeof(DpDevice)}}));
-	SyncFeatures f;
-	f.display = true;
-	f.auto_exposure = p->auto_exposure != 0;
-	SyncStep steps[kMaxSyncSteps];
-	const int n_steps = plan_tail(f, steps, 0);
-	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, W, exposure, &D, nullptr);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {&got, D.dev.get(), sizeof got}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	if (histogram) memcpy(histogram, got.hist, sizeof got.hist);
-	if (info) *info = PolarisExposureInfo{sizeof(PolarisExposureInfo), got.s.valid, (uint64_t)got.s.n_hi << 32 | got.s.n_lo, got.s.avg, got.s.log2E, got.s.E, 0};
-	return POLARIS_OK;
+	return display_planes_entry(h, "display_planes", plane, W, H, block_y, block_h, weight, exposure, p, nullptr, false, prev_log2E, rgba, histogram, info, nullptr, nullptr);
 }
 
 int polaris_hip_bloom_planes(polaris_hip_tracer *h, const float *plane, uint32_t W, uint32_t H, uint32_t block_y, uint32_t block_h, float weight,
                              float exposure, const PolarisDisplayParams *dp, const PolarisBloomParams *bp, const float *prev_log2E, uint8_t *rgba,
                              float *level1, uint32_t *levels_used) {
-	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::lock_guard<std::mutex> lk(h->mu);
-	if (!plane || !rgba || !dp || dp->struct_size != sizeof(PolarisDisplayParams) || !dp->enabled || dp_check(*dp) || !bp ||
-	    bp->struct_size != sizeof(PolarisBloomParams) || !bp->enabled || bl_check(*bp) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) ||
-	    block_h == 0 || block_y >= H || block_h > H - block_y)
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "bloom_planes: null argument, frame %ux%u (1..2^26 pixels), rows [%u, +%u), or params polaris_hip_set_display / "
-		            "_set_bloom refuse (enabled must be 1 in both)", W, H, block_y, block_h);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, off = (size_t)block_y * W, n = (size_t)block_h * W;
-	const BlLevels g = bl_levels(W, block_h, bp->levels);
-	DisplayStage D; // (D.init is the source of an asynchronous copy: declared, as the stages' device memory, before d, whose StreamDrain waits
-	BloomStage B;   // for the stream on every way out before any of them leaves scope)
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(1, 1));
-	HIP_TRY(h, D.dev.alloc(1));
-	HIP_TRY(h, B.pyramid.alloc(g.off[g.L + 1]));
-	D.p = *dp;
-	B.p = *bp;
-	B.fused = h->fs.bl.fused;
-	dp_init(D.init, prev_log2E);
-	float4 *d_plane = d.f4(0);
-	uchar4 *d_fb = (uchar4 *)d.word(0);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_plane, plane, F * sizeof(float4)}, {d_fb, rgba, F * sizeof(uchar4)}, {D.dev.get(), &D.init, sizeof(DpDevice)}}));
-	SyncFeatures f;
-	f.display = f.bloom = true;
-	f.auto_exposure = dp->auto_exposure != 0;
-	SyncStep steps[kMaxSyncSteps];
-	const int n_steps = plan_tail(f, steps, 0);
-	for (int s = 0; s < n_steps; s++) launch_tail_step(h, h->stream, steps[s], d_plane + off, weight, d_fb + off, n, W, exposure, &D, &B);
-	HIP_TRY(h, hipGetLastError());
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{rgba, d_fb, F * sizeof(uchar4)}, {level1, B.pyramid.get() + g.off[1], (size_t)g.w[1] * g.h[1] * sizeof(float4)}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	if (levels_used) *levels_used = g.L;
-	return POLARIS_OK;
+	return display_planes_entry(h, "bloom_planes", plane, W, H, block_y, block_h, weight, exposure, dp, bp, true, prev_log2E, rgba, nullptr, nullptr, level1, levels_used);
 }
 
 int polaris_hip_reproject_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
                                  const float prev_eye[3], const float prev_frustum[16], const float *guide, const float *albedo,
                                  const float eye[3], const float frustum[16], uint32_t W, uint32_t H, const PolarisTemporalParams *p,
                                  float *prior) {
-	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::lock_guard<std::mutex> lk(h->mu);
-	if (!history || !prev_guide || !prev_albedo || !prev_eye || !prev_frustum || !guide || !albedo || !eye || !frustum || !prior || !p ||
-	    p->struct_size != sizeof(PolarisTemporalParams) || W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) ||
-	    tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_planes: null argument, frame %ux%u (1..2^26 pixels), or params (max_history 0..%u, "
-		            "normal_threshold [-1, 1], depth_threshold [0, %g])", W, H, kTpMaxHistory, (double)kTpMaxDepthThreshold);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(6, 0));
-	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane}}));
-	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
-	                            W, H, *p, d_prior));
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	return POLARIS_OK;
+	return reproject_planes_entry(h, "reproject_planes", ReprojectIo{history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, W, H, p, prior});
 }
 
 int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *history, const float *prev_guide, const float *prev_albedo,
@@ -2650,35 +2661,9 @@ int polaris_hip_reproject_motion_planes(polaris_hip_tracer *h, const float *hist
                                         const float *albedo, const uint32_t *instance, const float eye[3], const float frustum[16], uint32_t W,
                                         uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
                                         const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2) {
-	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::lock_guard<std::mutex> lk(h->mu);
-	if (!history || !prev_guide || !prev_albedo || !prev_instance || !prev_eye || !prev_frustum || !guide || !albedo || !instance || !eye || !frustum ||
-	    !prev_inv_transforms || !inv_transforms || !prior || !p || p->struct_size != sizeof(PolarisTemporalParams) || W == 0 || H == 0 ||
-	    (uint64_t)W * H > (1ull << 26) || n_instances == 0 || n_instances > kTpMaxInstances || (history_variance == nullptr) != (prior2 == nullptr) ||
-	    tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_motion_planes: null argument, frame %ux%u (1..2^26 pixels), %u instances (1..%u), "
-		            "history_variance without prior2 (or the reverse), or params (max_history 0..%u, normal_threshold [-1, 1], depth_threshold [0, %g])",
-		            W, H, n_instances, kTpMaxInstances, kTpMaxHistory, (double)kTpMaxDepthThreshold);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4);
-	std::vector<float> table((size_t)n_instances * 16);
-	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
-	DevArray<float4> d_table;
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(8, 2));
-	HIP_TRY(h, d_table.alloc((size_t)n_instances * 4));
-	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5), *d_hvar = d.f4(6), *d_prior2 = d.f4(7);
-	uint32_t *d_hinst = d.word(0), *d_inst = d.word(1);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane},
-	                                          {d_hvar, history_variance, plane}, {d_hinst, prev_instance, F * sizeof(uint32_t)}, {d_inst, instance, F * sizeof(uint32_t)},
-	                                          {d_table.get(), table.data(), table.size() * sizeof(float)}}));
-	const MotionArgs mo{d_inst, d_hinst, d_table, n_instances};
-	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
-	                            W, H, *p, d_prior, history_variance ? d_hvar : nullptr, prior2 ? d_prior2 : nullptr, &mo));
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}, {prior2, d_prior2, plane}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	return POLARIS_OK;
+	return reproject_planes_entry(h, "reproject_motion_planes",
+	                              ReprojectIo{history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, W, H, p, prior, kRpMotion, history_variance,
+	                                          prior2, prev_instance, instance, n_instances, prev_inv_transforms, inv_transforms});
 }
 
 int polaris_hip_read_instance_plane(polaris_hip_tracer *h, uint32_t *out, size_t n) {
@@ -2704,40 +2689,9 @@ int polaris_hip_reproject_deform_planes(polaris_hip_tracer *h, const float *hist
                                         uint32_t H, uint32_t n_instances, const float *prev_inv_transforms, const float *inv_transforms,
                                         const PolarisTemporalParams *p, const float *history_variance, float *prior, float *prior2,
                                         const uint32_t *hit, const float *vertices, const float *prev_vertices, uint32_t num_triangles) {
-	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
-	std::lock_guard<std::mutex> lk(h->mu);
-	if (!history || !prev_guide || !prev_albedo || !prev_instance || !prev_eye || !prev_frustum || !guide || !albedo || !instance || !eye || !frustum ||
-	    !prev_inv_transforms || !inv_transforms || !prior || !hit || !vertices || !prev_vertices || !p || p->struct_size != sizeof(PolarisTemporalParams) ||
-	    W == 0 || H == 0 || (uint64_t)W * H > (1ull << 26) || n_instances == 0 || n_instances > kTpMaxInstances || num_triangles == 0 ||
-	    num_triangles > kTpMaxTriangles || (history_variance == nullptr) != (prior2 == nullptr) || tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
-		return fail(h, POLARIS_E_BAD_ARGUMENT, "reproject_deform_planes: null argument, frame %ux%u (1..2^26 pixels), %u instances (1..%u), %u triangles (1..%u), "
-		            "history_variance without prior2 (or the reverse), or params (max_history 0..%u, normal_threshold [-1, 1], depth_threshold [0, %g])",
-		            W, H, n_instances, kTpMaxInstances, num_triangles, kTpMaxTriangles, kTpMaxHistory, (double)kTpMaxDepthThreshold);
-	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t F = (size_t)W * H, plane = F * sizeof(float4), nv = (size_t)num_triangles * 3;
-	std::vector<float> table((size_t)n_instances * 32); // the motion table, then the deformation table
-	tp_motion_table(n_instances, prev_inv_transforms, inv_transforms, table.data());
-	tp_deform_table(n_instances, prev_inv_transforms, table.data() + (size_t)n_instances * 16);
-	DevArray<float4> d_table, d_verts;
-	PlaneScratch d{h->stream, F};
-	HIP_TRY(h, d.alloc(9, 2)); // (the ninth float4 plane holds the HIT words)
-	HIP_TRY(h, d_table.alloc((size_t)n_instances * 8));
-	HIP_TRY(h, d_verts.alloc(2 * nv));
-	float4 *d_hist = d.f4(0), *d_hguide = d.f4(1), *d_halbedo = d.f4(2), *d_guide = d.f4(3), *d_albedo = d.f4(4), *d_prior = d.f4(5), *d_hvar = d.f4(6), *d_prior2 = d.f4(7);
-	uint4 *d_hit = (uint4 *)d.f4(8);
-	uint32_t *d_hinst = d.word(0), *d_inst = d.word(1);
-	HIP_TRY(h, d.copy(hipMemcpyHostToDevice, {{d_hist, history, plane}, {d_hguide, prev_guide, plane}, {d_halbedo, prev_albedo, plane}, {d_guide, guide, plane}, {d_albedo, albedo, plane},
-	                                          {d_hvar, history_variance, plane}, {d_hinst, prev_instance, F * sizeof(uint32_t)}, {d_inst, instance, F * sizeof(uint32_t)},
-	                                          {d_hit, hit, F * sizeof(uint4)}, {d_table.get(), table.data(), table.size() * sizeof(float)},
-	                                          {d_verts.get(), vertices, nv * sizeof(float4)}, {d_verts.get() + nv, prev_vertices, nv * sizeof(float4)}}));
-	MotionArgs mo{d_inst, d_hinst, d_table, n_instances};
-	mo.hit = d_hit; mo.verts = d_verts; mo.hverts = d_verts.get() + nv; mo.deform = d_table.get() + (size_t)n_instances * 4; mo.n_tris = num_triangles;
-	HIP_TRY(h, launch_reproject(h, h->stream, d_hist, d_hguide, d_halbedo, tp_camera(prev_eye, prev_frustum), d_guide, d_albedo, tp_camera(eye, frustum),
-	                            W, H, *p, d_prior, history_variance ? d_hvar : nullptr, prior2 ? d_prior2 : nullptr, &mo));
-	HIP_TRY(h, d.copy(hipMemcpyDeviceToHost, {{prior, d_prior, plane}, {prior2, d_prior2, plane}}));
-	HIP_TRY(h, hipStreamSynchronize(h->stream));
-	collect_timers(h);
-	return POLARIS_OK;
+	return reproject_planes_entry(h, "reproject_deform_planes",
+	                              ReprojectIo{history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, W, H, p, prior, kRpDeform, history_variance,
+	                                          prior2, prev_instance, instance, n_instances, prev_inv_transforms, inv_transforms, hit, vertices, prev_vertices, num_triangles});
 }
 
 int polaris_hip_read_hit_plane(polaris_hip_tracer *h, uint32_t *out, size_t n_words) {

@@ -96,6 +96,12 @@ constexpr uint32_t kTpMaxTriangles = 1u << 24;   // of polaris_hip_reproject_def
 struct TpNoDeform {}; // (tp_reproject<*, *, false> never calls its two deformation arguments)
 
 // ---- host only (plain functions: no device code is generated for them) ----
+// The camera of an eye and the sixteen floats of its frustum corners (tl, tr, bl, br), as CameraData and the test entries carry them.
+inline TpCamera tp_camera(const float eye[3], const float fr[16]) {
+	return TpCamera{{fr[0], fr[1], fr[2], fr[3]}, {fr[4], fr[5], fr[6], fr[7]}, {fr[8], fr[9], fr[10], fr[11]}, {fr[12], fr[13], fr[14], fr[15]},
+	                {eye[0], eye[1], eye[2]}};
+}
+
 // The motion table's entry of one instance from its two inv_transform (PolarisMeshInstance: column major, world -> mesh; the
 // affine rows 0-2 are what the traversal uses): STATIC when the two are byte-equal, else D = inverse(Inv_hist) . Inv_cur in double
 // precision (cofactor inversion of the upper 3 x 3), rounded to float once at the end.  INVALID when either upper 3 x 3 has a

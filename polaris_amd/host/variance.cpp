@@ -1,11 +1,10 @@
-// variance.cpp -- the CPU restatement of variance guidance (kernels.h k_variance, k_denoise_variance, k_reproject<true>), for the
-// tests: the same per-pixel arithmetic from polaris_amd/csrc/variance.h, the same iteration order, so the VARIANCE, PRIOR2 and
+// variance.cpp -- the CPU restatement of variance guidance (kernels.h k_variance, k_denoise_variance), for the
+// tests: the same per-pixel arithmetic from polaris_amd/csrc/variance.h, the same iteration order, so the VARIANCE and
 // DENOISED planes of polaris_hip_sync_framebuffer are compared with these bit for bit (tests/test_gpu_variance.py), and their
 // numbers are checked against an independent numpy statement of the algorithm (tests/test_variance_cpu.py).
 #include <vector>
 
 #include "polaris_hip.h"
-#include "temporal.h"
 #include "variance.h"
 
 using namespace pol;
@@ -117,41 +116,6 @@ int polaris_host_denoise_variance(const float *acc, float weight, const float *v
 			for (int ch = 0; ch < 3; ch++) o[ch] = cur[4 * q + ch] * dn_demod_albedo(a[ch]);
 			o[3] = va_remod(cur[4 * q + 3], a);
 		}
-	}
-	return POLARIS_OK;
-}
-
-// PRIOR2 (h2 | 0 | 0 | m) of every pixel: polaris_host_reproject's arguments plus the history's VARIANCE plane hvar.  The PRIOR it
-// implies is written to prior (the same bytes as polaris_host_reproject's).
-int polaris_host_reproject_moments(const float *history, const float *hvar, const float *prev_guide, const float *prev_albedo, const float prev_eye[3],
-                                   const float prev_frustum[16], const float *guide, const float *albedo, const float eye[3], const float frustum[16],
-                                   uint32_t frame_w, uint32_t frame_h, const PolarisTemporalParams *p, float *prior, float *prior2) {
-	if (!history || !hvar || !prev_guide || !prev_albedo || !prev_eye || !prev_frustum || !guide || !albedo || !eye || !frustum || !p || !prior ||
-	    !prior2)
-		return POLARIS_E_BAD_ARGUMENT;
-	if (p->struct_size != sizeof(PolarisTemporalParams)) return POLARIS_E_BAD_ARGUMENT;
-	if (tp_check(p->max_history, p->normal_threshold, p->depth_threshold)) return POLARIS_E_BAD_ARGUMENT;
-	if (frame_w == 0 || frame_h == 0 || (uint64_t)frame_w * frame_h > (1ull << 26)) return POLARIS_E_BAD_ARGUMENT;
-	auto camera = [](const float e[3], const float f[16]) {
-		return TpCamera{{f[0], f[1], f[2], f[3]}, {f[4], f[5], f[6], f[7]}, {f[8], f[9], f[10], f[11]}, {f[12], f[13], f[14], f[15]}, {e[0], e[1], e[2]}};
-	};
-	const TpCamera hcam = camera(prev_eye, prev_frustum), cam = camera(eye, frustum);
-	const uint32_t W = frame_w, H = frame_h;
-	const size_t F = (size_t)W * H;
-	const bool ok = tp_projectable(hcam) && p->max_history != 0;
-	auto load = [&](uint32_t j, TpTap &t) {
-		const float *c = history + 4 * (size_t)j, *n = prev_guide + 4 * (size_t)j;
-		t = TpTap{c[0], c[1], c[2], c[3], n[0], n[1], n[2], n[3], prev_albedo[4 * (size_t)j + 3], hvar[4 * (size_t)j + 1], 0u};
-	};
-	for (size_t i = 0; i < F; i++) {
-		float *o = prior + 4 * i, *o2 = prior2 + 4 * i;
-		if (!ok) {
-			o[0] = o[1] = o[2] = o[3] = 0.0f;
-			o2[0] = o2[1] = o2[2] = o2[3] = 0.0f;
-			continue;
-		}
-		tp_reproject<true>((uint32_t)(i % W), (uint32_t)(i / W), W, H, guide + 4 * i, albedo[4 * i + 3], cam, hcam, p->max_history,
-		                   p->normal_threshold, p->depth_threshold, load, o, o2);
 	}
 	return POLARIS_OK;
 }

@@ -347,24 +347,101 @@ def denoise(frame_acc, weight: float, guide, albedo, *, block_y: int = 0, block_
     return res
 
 
+def _planes(name, *planes):
+    out = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+    H, W = out[0].shape[:2]
+    if any(a.shape != (H, W, 4) for a in out):
+        raise ValueError(f"{name}: the planes must be (H, W, 4) float32 of one size")
+    return out, H, W
+
+
+def _own(name, a, H, W, dtype):
+    """A caller's (H, W, 4) output plane as a copy the library may write (None: zeros)."""
+    out = np.zeros((H, W, 4), dtype) if a is None else np.array(a, dtype=dtype, order="C", copy=True)
+    if out.shape != (H, W, 4):
+        raise ValueError(f"{name}: an output plane must be (H, W, 4) like the input")
+    return out
+
+
+def _reproject(name, call, history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, params, *, history_variance=None,
+               moments=False, instances=None, tables=None, deform=None):
+    """THE marshalling of every reprojection entry, host and device (tracer.py): the arguments as contiguous arrays of the right type
+    and shape, then call(*C arguments) in the entry's order.  moments: polaris_host_reproject_moments' order (history_variance second);
+    instances = (prev, current) INSTANCE planes with tables = (prev, current) inv_transform: the motion entries' order; deform = (hit,
+    vertices, prev_vertices) behind it.  Null vertices and empty tables are passed on: the library refuses them.  Returns the PRIOR
+    plane, or (PRIOR, PRIOR2) with history_variance.  ValueError on shapes no entry takes; `call` raises the entry's own error."""
+    (hist, pg, pa, g, a), H, W = _planes(name, history, prev_guide, prev_albedo, guide, albedo)
+    f = lambda x, *shape: np.ascontiguousarray(x, dtype=np.float32).reshape(*shape)  # noqa: E731
+    pe, pf, e, fr = f(prev_eye, 3), f(prev_frustum, 16), f(eye, 3), f(frustum, 16)
+    hv = None
+    if history_variance is not None:
+        (hv,), _, _ = _planes(name, history_variance)
+        if hv.shape != hist.shape:
+            raise ValueError(f"{name}: history_variance must be (H, W, 4) like the history")
+    prior = np.zeros((H, W, 4), np.float32)
+    prior2 = None if hv is None else np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(*params)
+    if instances is None:
+        args = [hist, hv, pg, pa, pe, pf, g, a, e, fr, W, H, p, prior, prior2] if moments else [hist, pg, pa, pe, pf, g, a, e, fr, W, H, p, prior]
+    else:
+        pi, ci = (np.ascontiguousarray(x, np.uint32) for x in instances)
+        pt, ct = (f(x, -1, 16) for x in tables)
+        if pi.shape != (H, W) or ci.shape != (H, W) or pt.shape != ct.shape:
+            raise ValueError(f"{name}: the INSTANCE planes must be (H, W), the two tables (n, 16)")
+        args = [hist, pg, pa, pi, pe, pf, g, a, ci, e, fr, W, H, len(ct), pt, ct, p, hv, prior, prior2]
+    if deform is not None:
+        ht = np.ascontiguousarray(deform[0], np.uint32)
+        v, pv = (None if x is None else f(x, -1, 4) for x in deform[1:])
+        if ht.shape != (H, W, 4):
+            raise ValueError(f"{name}: the HIT plane must be (H, W, 4)")
+        if (v is not None and pv is not None and v.shape != pv.shape) or any(x is not None and len(x) % 3 for x in (v, pv)):
+            raise ValueError(f"{name}: the two vertex arrays must be (3 NT, 4)")
+        args += [ht, v, pv, 0 if v is None and pv is None else len(v if v is not None else pv) // 3]
+    call(*[C.byref(x) if x is p else x.ctypes.data if isinstance(x, np.ndarray) else x for x in args])
+    return prior if prior2 is None else (prior, prior2)
+
+
+def _host_call(name):
+    def call(*args):
+        rc = getattr(load(), "polaris_host_" + name)(*args)
+        if rc:
+            raise ValueError(f"{name}: bad arguments (code {rc})")
+    return call
+
+
 def reproject(history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *, max_history: int = 32,
               normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
     """polaris_host_reproject: the CPU restatement of the temporal reprojection (polaris_amd/host/temporal.cpp).  The planes are
-    (H, W, 4) float32, the cameras eye (3,) and frustum (4, 4) / (16,); returns the PRIOR plane (h rgb | m).  Raises ValueError where
-    the library refuses the arguments."""
-    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
-    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-    H, W = g.shape[:2]
-    if not hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4):
-        raise ValueError("reproject: the planes must be (H, W, 4) of one size")
-    out = np.zeros((H, W, 4), np.float32)
-    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-    rc = load().polaris_host_reproject(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data,
-                                       a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p), out.ctypes.data)
-    if rc:
-        raise ValueError(f"reproject: bad arguments (code {rc})")
-    return out
+    (H, W, 4) float32, the cameras eye (3,) and frustum (4, 4) / (16,); returns the PRIOR plane (h rgb | m).  Raises ValueError where the library refuses the arguments."""
+    return _reproject("reproject", _host_call("reproject"), history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, (max_history, normal_threshold, depth_threshold))
+
+
+def reproject_moments(history, hvar, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *, max_history: int = 32,
+                      normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
+    """polaris_host_reproject_moments: reproject() plus the history VARIANCE plane's M2 -- returns (PRIOR, PRIOR2 = h2 | 0 | 0 | m)."""
+    return _reproject("reproject_moments", _host_call("reproject_moments"), history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                      (max_history, normal_threshold, depth_threshold), history_variance=hvar, moments=True)
+
+
+def reproject_motion(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
+                     prev_inv_transforms, inv_transforms, *, history_variance=None, max_history: int = 32, normal_threshold: float = 0.9,
+                     depth_threshold: float = 0.1):
+    """polaris_host_reproject_motion: reproject() with object motion -- the two (H, W) uint32 INSTANCE planes and the two (n, 16)
+    inv_transform tables the history and the current frame were seen with.  Returns the PRIOR plane, or (PRIOR, PRIOR2) when the
+    history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
+    return _reproject("reproject_motion", _host_call("reproject_motion"), history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                      (max_history, normal_threshold, depth_threshold), history_variance=history_variance, instances=(prev_instance, instance), tables=(prev_inv_transforms, inv_transforms))
+
+
+def reproject_deform(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
+                     prev_inv_transforms, inv_transforms, hit, vertices, prev_vertices, *, history_variance=None, max_history: int = 32,
+                     normal_threshold: float = 0.9, depth_threshold: float = 0.1):
+    """polaris_host_reproject_deform: reproject_motion() with vertex motion -- the current (H, W, 4) uint32 HIT plane (scene triangle |
+    bits of u | bits of v | 0) and the (3 NT, 4) vertices of the scene now and as the history saw them.  Returns the PRIOR plane, or
+    (PRIOR, PRIOR2) when the history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
+    return _reproject("reproject_deform", _host_call("reproject_deform"), history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                      (max_history, normal_threshold, depth_threshold), history_variance=history_variance, instances=(prev_instance, instance), tables=(prev_inv_transforms, inv_transforms),
+                      deform=(hit, vertices, prev_vertices))
 
 
 MOTION_STATIC, MOTION_MOVED, MOTION_INVALID = 0, 1, 2
@@ -380,70 +457,6 @@ def motion_matrix(inv_hist, inv_cur) -> tuple[int, np.ndarray]:
     if load().polaris_host_motion_matrix(a.ctypes.data, b.ctypes.data, C.byref(flag), D.ctypes.data):
         raise ValueError("motion_matrix: bad arguments")
     return int(flag.value), D
-
-
-def reproject_motion(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
-                     prev_inv_transforms, inv_transforms, *, history_variance=None, max_history: int = 32, normal_threshold: float = 0.9,
-                     depth_threshold: float = 0.1):
-    """polaris_host_reproject_motion: reproject() with object motion -- the two (H, W) uint32 INSTANCE planes and the two (n, 16)
-    inv_transform tables the history and the current frame were seen with.  Returns the PRIOR plane, or (PRIOR, PRIOR2) when the
-    history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
-    (hist, pg, pa, g, a), H, W = _planes("reproject_motion", history, prev_guide, prev_albedo, guide, albedo)
-    f = lambda x: np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
-    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-    pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
-    pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
-    if pi.shape != (H, W) or ci.shape != (H, W) or pt.shape != ct.shape:
-        raise ValueError("reproject_motion: the INSTANCE planes must be (H, W), the two tables (n, 16)")
-    hv = None
-    if history_variance is not None:
-        (hv,), _, _ = _planes("reproject_motion", history_variance)
-        if hv.shape != hist.shape:
-            raise ValueError("reproject_motion: history_variance must be (H, W, 4) like the history")
-    out = np.zeros((H, W, 4), np.float32)
-    out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
-    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-    rc = load().polaris_host_reproject_motion(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data,
-                                              g.ctypes.data, a.ctypes.data, ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct),
-                                              pt.ctypes.data, ct.ctypes.data, C.byref(p), None if hv is None else hv.ctypes.data,
-                                              out.ctypes.data, None if out2 is None else out2.ctypes.data)
-    if rc:
-        raise ValueError(f"reproject_motion: bad arguments (code {rc})")
-    return out if out2 is None else (out, out2)
-
-
-def reproject_deform(history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye, frustum,
-                     prev_inv_transforms, inv_transforms, hit, vertices, prev_vertices, *, history_variance=None, max_history: int = 32,
-                     normal_threshold: float = 0.9, depth_threshold: float = 0.1):
-    """polaris_host_reproject_deform: reproject_motion() with vertex motion -- the current (H, W, 4) uint32 HIT plane (scene triangle |
-    bits of u | bits of v | 0) and the (3 NT, 4) vertices of the scene now and as the history saw them.  Returns the PRIOR plane, or
-    (PRIOR, PRIOR2) when the history's VARIANCE plane is given.  Raises ValueError where the library refuses the arguments."""
-    (hist, pg, pa, g, a), H, W = _planes("reproject_deform", history, prev_guide, prev_albedo, guide, albedo)
-    f = lambda x: np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
-    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-    pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
-    pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
-    ht, v, pv = np.ascontiguousarray(hit, np.uint32), f(vertices).reshape(-1, 4), f(prev_vertices).reshape(-1, 4)
-    if pi.shape != (H, W) or ci.shape != (H, W) or pt.shape != ct.shape or ht.shape != (H, W, 4):
-        raise ValueError("reproject_deform: the INSTANCE planes must be (H, W), the HIT plane (H, W, 4), the two tables (n, 16)")
-    if v.shape != pv.shape or len(v) % 3:
-        raise ValueError("reproject_deform: the two vertex arrays must be (3 NT, 4)")
-    hv = None
-    if history_variance is not None:
-        (hv,), _, _ = _planes("reproject_deform", history_variance)
-        if hv.shape != hist.shape:
-            raise ValueError("reproject_deform: history_variance must be (H, W, 4) like the history")
-    out = np.zeros((H, W, 4), np.float32)
-    out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
-    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-    rc = load().polaris_host_reproject_deform(hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data,
-                                              g.ctypes.data, a.ctypes.data, ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct),
-                                              pt.ctypes.data, ct.ctypes.data, C.byref(p), None if hv is None else hv.ctypes.data,
-                                              out.ctypes.data, None if out2 is None else out2.ctypes.data, ht.ctypes.data, v.ctypes.data,
-                                              pv.ctypes.data, len(v) // 3)
-    if rc:
-        raise ValueError(f"reproject_deform: bad arguments (code {rc})")
-    return out if out2 is None else (out, out2)
 
 
 def temporal_combine(frame_acc, prior, accumulated_samples: int, samples_per_pixel: int, *, block_y: int = 0, block_h: int | None = None,
@@ -464,14 +477,6 @@ def temporal_combine(frame_acc, prior, accumulated_samples: int, samples_per_pix
     return res
 
 
-def _planes(name, *planes):
-    out = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
-    H, W = out[0].shape[:2]
-    if any(a.shape != (H, W, 4) for a in out):
-        raise ValueError(f"{name}: the planes must be (H, W, 4) float32 of one size")
-    return out, H, W
-
-
 def exposure_info(info) -> dict:
     """A PolarisExposureInfo as a dict: valid, n_metered and the float32 values avg, log2E, E."""
     return {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E), "E": np.float32(info.E)}
@@ -483,9 +488,7 @@ def display(plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int =
     (H, W, 4) float32 plane.  fields: those of ctypes_api.DISPLAY_DEFAULTS.  Returns (RGBA8 -- `rgba` (a copy) with the request's rows
     written --, the 256 counts, exposure_info).  ValueError where refused."""
     (c,), H, W = _planes("display", plane)
-    fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, dtype=np.uint8, order="C", copy=True)
-    if fb.shape != (H, W, 4):
-        raise ValueError("display: rgba must be (H, W, 4) uint8")
+    fb = _own("display", rgba, H, W, np.uint8)
     p, info, hist = T.display_params(1, **fields), T.ExposureInfo(), np.zeros(256, np.uint32)
     prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
     rc = load().polaris_host_display(c.ctypes.data, W, H, int(block_y), int(H - block_y if block_h is None else block_h), float(weight), float(exposure),
@@ -509,9 +512,7 @@ def bloom(plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0
     (RGBA8 -- `rgba` (a copy) with the request's rows written --, U_1 (h_1, w_1, 4), the full-resolution term of the request's rows
     (block_h, W, 4), levels used).  ValueError where refused."""
     (c,), H, W = _planes("bloom", plane)
-    fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, dtype=np.uint8, order="C", copy=True)
-    if fb.shape != (H, W, 4):
-        raise ValueError("bloom: rgba must be (H, W, 4) uint8")
+    fb = _own("bloom", rgba, H, W, np.uint8)
     bh = int(H - block_y if block_h is None else block_h)
     dp, bp = T.display_params(1, **(display or {})), T.bloom_params(1, **fields)
     if not (0 <= block_y < H and 0 < bh <= H - block_y) or load().polaris_host_bloom_check(C.byref(bp)):
@@ -565,22 +566,6 @@ def denoise_variance(acc, weight: float, variance_plane, guide, albedo, *, block
     if rc:
         raise ValueError(f"denoise_variance: bad arguments (code {rc})")
     return res
-
-
-def reproject_moments(history, hvar, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, *, max_history: int = 32,
-                      normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> tuple[np.ndarray, np.ndarray]:
-    """polaris_host_reproject_moments: reproject() plus the history VARIANCE plane's M2 -- returns (PRIOR, PRIOR2 = h2 | 0 | 0 | m)."""
-    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    (hist, hv, pg, pa, g, a), H, W = _planes("reproject_moments", history, hvar, prev_guide, prev_albedo, guide, albedo)
-    pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-    prior, prior2 = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)
-    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-    rc = load().polaris_host_reproject_moments(hist.ctypes.data, hv.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data,
-                                               g.ctypes.data, a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p), prior.ctypes.data,
-                                               prior2.ctypes.data)
-    if rc:
-        raise ValueError(f"reproject_moments: bad arguments (code {rc})")
-    return prior, prior2
 
 
 CAMERA_MOVES = {"up": 0, "down": 1, "left": 2, "right": 3, "forward": 4, "backward": 5}   # scene.CameraDirection (camera.go:12-19)

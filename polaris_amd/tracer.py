@@ -15,6 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import ctypes_api as T
+from . import host_api as HA   # (the marshalling the device entries share with their CPU restatements; no library is loaded by the import)
 
 
 class Flag(enum.IntFlag):          # tracer/tracer.go:49-61
@@ -241,10 +242,8 @@ class HipTracer:
         """polaris_hip_bloom_planes: the launches of a bloomed displayed sync on a caller (H, W, 4) float32 plane.  display: fields of
         T.DISPLAY_DEFAULTS; fields: those of T.BLOOM_DEFAULTS.  Returns (RGBA8, U_1 (h_1, w_1, 4), levels used); rows outside the
         request come back as passed (zeros by default)."""
-        plane = np.ascontiguousarray(plane, dtype=np.float32)
-        H, W = plane.shape[:2]
-        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
-        assert plane.shape == fb.shape == (H, W, 4)
+        (plane,), H, W = HA._planes("bloom_planes", plane)
+        fb = HA._own("bloom_planes", rgba, H, W, np.uint8)
         bh = int(H - block_y if block_h is None else block_h)
         dp, bp, used = T.display_params(1, **(display or {})), T.bloom_params(1, **fields), C.c_uint32()
         w1, h1 = (W + 1) // 2, (max(bh, 1) + 1) // 2
@@ -259,25 +258,21 @@ class HipTracer:
         log2E and E, and the 256 counts under "histogram"."""
         info, hist = T.ExposureInfo(), np.zeros(256, np.uint32)
         self._check(self._lib.polaris_hip_read_exposure(self._h, C.byref(info), hist.ctypes.data), self._h)
-        return {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E),
-                "E": np.float32(info.E), "histogram": hist}
+        return {**HA.exposure_info(info), "histogram": hist}
 
     def display_planes(self, plane, *, weight: float = 1.0, exposure: float = 1.0, block_y: int = 0, block_h: int | None = None, rgba=None,
                        prev_log2E=None, **fields) -> tuple[np.ndarray, np.ndarray, dict]:
         """polaris_hip_display_planes: the launches of the display stage on a caller (H, W, 4) float32 plane.  fields: those of
         T.DISPLAY_DEFAULTS.  Returns (RGBA8, the 256 counts, the exposure info as read_exposure's without the histogram); rows outside
         the request come back as passed (zeros by default)."""
-        plane = np.ascontiguousarray(plane, dtype=np.float32)
-        H, W = plane.shape[:2]
-        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
-        assert plane.shape == fb.shape == (H, W, 4)
+        (plane,), H, W = HA._planes("display_planes", plane)
+        fb = HA._own("display_planes", rgba, H, W, np.uint8)
         p, info, hist = T.display_params(1, **fields), T.ExposureInfo(), np.zeros(256, np.uint32)
         prev = None if prev_log2E is None else C.byref(C.c_float(float(prev_log2E)))
         bh = H - block_y if block_h is None else block_h
         self._check(self._lib.polaris_hip_display_planes(self._h, plane.ctypes.data, W, H, int(block_y), int(bh), float(weight), float(exposure),
                                                          C.byref(p), prev, fb.ctypes.data, hist.ctypes.data, C.byref(info)), self._h)
-        return fb, hist, {"valid": int(info.valid), "n_metered": int(info.n_metered), "avg": np.float32(info.avg), "log2E": np.float32(info.log2E),
-                          "E": np.float32(info.E)}
+        return fb, hist, HA.exposure_info(info)
 
     def read_aov(self, which: int) -> np.ndarray:
         """(H, W, 4) float32 plane of the denoiser: T.AOV_GUIDE (normal | hit distance), T.AOV_ALBEDO (albedo | leaf type bits)
@@ -347,12 +342,8 @@ class HipTracer:
                        sigma_luminance: float = 4.0) -> tuple[np.ndarray, np.ndarray]:
         """polaris_hip_denoise_planes: the launches of a denoised sync on caller (H, W, 4) float32 planes.  Returns (DENOISED plane,
         RGBA8 frame); rows outside [block_y, block_y + block_h) come back as `denoised` / `rgba` gave them (zeros by default)."""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-        acc, guide, albedo = f(acc), f(guide), f(albedo)
-        H, W = acc.shape[:2]
-        out = np.zeros((H, W, 4), np.float32) if denoised is None else np.array(denoised, np.float32, copy=True, order="C")
-        fb = np.zeros((H, W, 4), np.uint8) if rgba is None else np.array(rgba, np.uint8, copy=True, order="C")
-        assert guide.shape == albedo.shape == out.shape == fb.shape == (H, W, 4)
+        (acc, guide, albedo), H, W = HA._planes("denoise_planes", acc, guide, albedo)
+        out, fb = HA._own("denoise_planes", denoised, H, W, np.float32), HA._own("denoise_planes", rgba, H, W, np.uint8)
         p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
         bh = H - block_y if block_h is None else block_h
         self._check(self._lib.polaris_hip_denoise_planes(self._h, acc.ctypes.data, guide.ctypes.data, albedo.ctypes.data, W, H, int(block_y),
@@ -365,12 +356,8 @@ class HipTracer:
                         sigma_luminance: float = 4.0, sigma_variance: float = 8.0, min_samples: int = 8) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """polaris_hip_variance_planes: the launches of a variance sync on caller (H, W, 4) float32 planes (acc: rgb | sum L^2 of
         `samples` samples).  Returns (VARIANCE, DENOISED, RGBA8); rows outside the request come back as passed (zeros by default)."""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-        acc, guide, albedo = f(acc), f(guide), f(albedo)
-        H, W = acc.shape[:2]
-        own = lambda a, dt: np.zeros((H, W, 4), dt) if a is None else np.array(a, dt, copy=True, order="C")  # noqa: E731
-        var, out, fb = own(variance, np.float32), own(denoised, np.float32), own(rgba, np.uint8)
-        assert guide.shape == albedo.shape == var.shape == out.shape == fb.shape == (H, W, 4)
+        (acc, guide, albedo), H, W = HA._planes("variance_planes", acc, guide, albedo)
+        var, out, fb = (HA._own("variance_planes", a, H, W, dt) for a, dt in ((variance, np.float32), (denoised, np.float32), (rgba, np.uint8)))
         p = T.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_luminance)
         v = T.variance_params(sigma_variance, min_samples)
         bh = H - block_y if block_h is None else block_h
@@ -383,17 +370,14 @@ class HipTracer:
                          max_history: int = 32, normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
         """polaris_hip_reproject_planes: the PRIOR plane ((H, W, 4) float32, h rgb | m) of the history planes seen under
         (prev_eye, prev_frustum), reprojected onto the G-buffer (guide, albedo) under (eye, frustum), on the device."""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
-        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-        H, W = g.shape[:2]
-        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4)
-        out = np.zeros((H, W, 4), np.float32)
-        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-        self._check(self._lib.polaris_hip_reproject_planes(self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pe.ctypes.data, pf.ctypes.data,
-                                                           g.ctypes.data, a.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, C.byref(p),
-                                                           out.ctypes.data), self._h)
-        return out
+        return self._reproject_planes("reproject_planes", history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                                      (max_history, normal_threshold, depth_threshold))
+
+    def _reproject_planes(self, name, *args, **groups):
+        """One of the three polaris_hip_reproject*_planes entries through the marshalling of their CPU restatements (host_api._reproject:
+        ValueError on shapes no entry takes; what the library refuses is a TracerError)."""
+        entry = getattr(self._lib, "polaris_hip_" + name)
+        return HA._reproject(name, lambda *a: self._check(entry(self._h, *a), self._h), *args, **groups)
 
     def reproject_motion_planes(self, history, prev_guide, prev_albedo, prev_instance, prev_eye, prev_frustum, guide, albedo, instance, eye,
                                 frustum, prev_inv_transforms, inv_transforms, *, history_variance=None, max_history: int = 32,
@@ -401,23 +385,9 @@ class HipTracer:
         """polaris_hip_reproject_motion_planes: reproject_planes with object motion -- the two (H, W) uint32 INSTANCE planes and the two
         (n, 16) inv_transform tables (column major, as MESH_INSTANCE) the history and the current frame were seen with.  Returns the
         PRIOR plane, or (PRIOR, PRIOR2) when the history's VARIANCE plane is given."""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
-        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-        H, W = g.shape[:2]
-        pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
-        pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
-        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4) and pi.shape == ci.shape == (H, W) and pt.shape == ct.shape
-        hv = None if history_variance is None else f(history_variance)
-        assert hv is None or hv.shape == (H, W, 4)
-        out = np.zeros((H, W, 4), np.float32)
-        out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
-        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-        self._check(self._lib.polaris_hip_reproject_motion_planes(
-            self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data, a.ctypes.data,
-            ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct), pt.ctypes.data, ct.ctypes.data, C.byref(p),
-            None if hv is None else hv.ctypes.data, out.ctypes.data, None if out2 is None else out2.ctypes.data), self._h)
-        return out if out2 is None else (out, out2)
+        return self._reproject_planes("reproject_motion_planes", history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                                      (max_history, normal_threshold, depth_threshold), history_variance=history_variance,
+                                      instances=(prev_instance, instance), tables=(prev_inv_transforms, inv_transforms))
 
     def read_instance_plane(self) -> np.ndarray:
         """(H, W) uint32 INSTANCE plane of the first-hit G-buffer (polaris_hip_read_instance_plane; option "object_motion" with temporal
@@ -433,29 +403,10 @@ class HipTracer:
         """polaris_hip_reproject_deform_planes: reproject_motion_planes with vertex motion -- the current (H, W, 4) uint32 HIT plane and
         the (3 NT, 4) vertices of the scene now and as the history saw them.  Returns the PRIOR plane, or (PRIOR, PRIOR2) when the
         history's VARIANCE plane is given.  (Null vertices or no triangle are passed on: the library refuses them.)"""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-        hist, pg, pa, g, a = f(history), f(prev_guide), f(prev_albedo), f(guide), f(albedo)
-        pe, pf, e, fr = f(prev_eye).reshape(3), f(prev_frustum).reshape(16), f(eye).reshape(3), f(frustum).reshape(16)
-        H, W = g.shape[:2]
-        pi, ci = np.ascontiguousarray(prev_instance, np.uint32), np.ascontiguousarray(instance, np.uint32)
-        pt, ct = f(prev_inv_transforms).reshape(-1, 16), f(inv_transforms).reshape(-1, 16)
-        ht = np.ascontiguousarray(hit, np.uint32)
-        v = None if vertices is None else f(vertices).reshape(-1, 4)
-        pv = None if prev_vertices is None else f(prev_vertices).reshape(-1, 4)
-        assert hist.shape == pg.shape == pa.shape == g.shape == a.shape == (H, W, 4) and pi.shape == ci.shape == (H, W) and pt.shape == ct.shape
-        assert ht.shape == (H, W, 4) and (v is None or pv is None or v.shape == pv.shape)
-        hv = None if history_variance is None else f(history_variance)
-        assert hv is None or hv.shape == (H, W, 4)
-        out = np.zeros((H, W, 4), np.float32)
-        out2 = None if hv is None else np.zeros((H, W, 4), np.float32)
-        p = T.temporal_params(max_history, normal_threshold, depth_threshold)
-        nt = 0 if v is None and pv is None else len(v if v is not None else pv) // 3
-        self._check(self._lib.polaris_hip_reproject_deform_planes(
-            self._h, hist.ctypes.data, pg.ctypes.data, pa.ctypes.data, pi.ctypes.data, pe.ctypes.data, pf.ctypes.data, g.ctypes.data, a.ctypes.data,
-            ci.ctypes.data, e.ctypes.data, fr.ctypes.data, W, H, len(ct), pt.ctypes.data, ct.ctypes.data, C.byref(p),
-            None if hv is None else hv.ctypes.data, out.ctypes.data, None if out2 is None else out2.ctypes.data, ht.ctypes.data,
-            None if v is None else v.ctypes.data, None if pv is None else pv.ctypes.data, nt), self._h)
-        return out if out2 is None else (out, out2)
+        return self._reproject_planes("reproject_deform_planes", history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
+                                      (max_history, normal_threshold, depth_threshold), history_variance=history_variance,
+                                      instances=(prev_instance, instance), tables=(prev_inv_transforms, inv_transforms),
+                                      deform=(hit, vertices, prev_vertices))
 
     def read_hit_plane(self) -> np.ndarray:
         """(H, W, 4) uint32 HIT plane of the first-hit G-buffer (polaris_hip_read_hit_plane; option "vertex_motion" in effect): the scene
