@@ -47,8 +47,8 @@ extern "C" {
  * itself); PolarisIpcExport carries the exporting GPU's PCI bus id (544 -> 576 bytes); PolarisBvhBuildInput LEADS with `struct_size`
  * (72 -> 80 bytes): a caller built against another layout is refused instead of being read past its end.  Still 5: + update_instances,
  * + update_vertices / PolarisVertexUpdate, + update_materials / PolarisMaterialUpdate / update_texture and the record kinds
- * POLARIS_REC_TRIS / POLARIS_REC_SHADING, + set_lens / PolarisLensParams, + set_shutter / PolarisShutterParams (additions only: older
- * callers keep working). */
+ * POLARIS_REC_TRIS / POLARIS_REC_SHADING, + set_lens / PolarisLensParams, + set_shutter / PolarisShutterParams, + set_projection / PolarisProjectionParams
+ * (additions only: older callers keep working). */
 #define POLARIS_HIP_ABI_VERSION 5
 
 /* status codes (0 = ok).  The first three mirror tracer/opencl/errors.go sentinels. */
@@ -170,6 +170,37 @@ typedef struct PolarisShutterParams {
 	float    axis1[3], u1[3], v1[3];
 } PolarisShutterParams;
 int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p);
+
+/* Camera projection: orthographic and equirectangular (latitude-longitude) cameras beside the perspective frustum of
+ * polaris_hip_set_camera (no reference counterpart).  Off by default and while kind = 0: nothing else in the struct is looked at, any
+ * two off states are equal, and every Trace, tap, G-buffer and sync launches exactly what it did, under the same kernel symbols.
+ * The eye is polaris_hip_set_camera's; its frustum stays stored and is not read while kind != 0.  The view basis is explicit, as the
+ * lens' vectors are: the library derives nothing, polaris_hip_set_camera does NOT touch it, and a caller that turns the camera sets the
+ * projection again (the layers above do it for their callers).
+ * With tx, ty the sample's frame coordinates in [0, 1) (k_generate's: pixel + tent-filtered offset, times 1 / W and 1 / H):
+ *   ORTHOGRAPHIC     the ray starts at eye + right (2 tx - 1) half_width + up (1 - 2 ty) half_height and runs along `axis`, verbatim;
+ *   EQUIRECTANGULAR  the ray starts at the eye; lon = (tx - 0.5) lon_range, lat = (0.5 - ty) lat_range, and its direction is
+ *                    normalise(axis cos(lat) cos(lon) + right cos(lat) sin(lon) + up sin(lat)).
+ * The camera rays of a Trace and of polaris_hip_tap_primary come from k_generate_proj<kind>; the G-buffer casts the same ray through the
+ * pixel centre and the temporal reprojection inverts the same projection (GUIDE t under ORTHOGRAPHIC is the distance along the axis).
+ * There is no wrap across the equirectangular seam.  DESIGN.md 10n has the exact float32 arithmetic.
+ * A call that changes the state drops the G-buffer and the temporal history (the planes stay) and the caller restarts accumulation; a
+ * call whose bytes equal the stored ones does nothing.  polaris_hip_set_camera under a projection is an ordinary camera move: the
+ * history survives a translation of the eye.
+ * POLARIS_E_BAD_ARGUMENT, state unchanged: a null handle or params, another struct_size, kind > 2; with kind != 0 also: no camera set
+ * yet, any of the 13 floats not finite, |axis|^2, |right|^2 or |up|^2 outside [0.998, 1.002], a pairwise |dot| above 1e-3,
+ * ORTHOGRAPHIC with half_width or half_height outside [1e-6, 1e30], EQUIRECTANGULAR with lon_range outside [1e-3, 6.2831855] or
+ * lat_range outside [1e-3, 3.1415927] (the two fields of the other kind must only be finite), the lens on or the shutter on.  While a
+ * projection is on, a polaris_hip_set_lens that would switch the lens on and a polaris_hip_set_shutter with enabled = 1 are refused. */
+enum { POLARIS_PROJECTION_PERSPECTIVE = 0, POLARIS_PROJECTION_ORTHOGRAPHIC = 1, POLARIS_PROJECTION_EQUIRECTANGULAR = 2 };
+typedef struct PolarisProjectionParams {
+	uint32_t struct_size;     /* = sizeof(PolarisProjectionParams) = 60 */
+	uint32_t kind;            /* POLARIS_PROJECTION_*; 0 = off (default): nothing else is looked at */
+	float    axis[3], right[3], up[3]; /* orthonormal view basis, world space: +axis forward, +right to image right, +up to image top */
+	float    half_width, half_height;  /* ORTHOGRAPHIC: half extents of the window through the eye, world units */
+	float    lon_range, lat_range;     /* EQUIRECTANGULAR: radians spanned by the frame's width and height */
+} PolarisProjectionParams;
+int polaris_hip_set_projection(polaris_hip_tracer *h, const PolarisProjectionParams *p);
 
 /* Tunables (not part of the reference interface).  Keys:
  *   "samples_per_batch"  samples traced concurrently as one wavefront batch (default: auto)

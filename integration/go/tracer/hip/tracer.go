@@ -352,6 +352,44 @@ func (tr *Tracer) SetShutter(p *ShutterParams) error {
 	return tr.check(C.polaris_hip_set_shutter(tr.handle, &c))
 }
 
+// Projection kinds of ProjectionParams.Kind (POLARIS_PROJECTION_*).
+const (
+	ProjectionPerspective     = 0 // off: the frustum of UpdateState(CameraData)
+	ProjectionOrthographic    = 1
+	ProjectionEquirectangular = 2
+)
+
+// ProjectionParams is the camera's projection (PolarisProjectionParams, include/polaris_hip.h; DESIGN.md section 10n): an
+// orthographic window through the eye, or an equirectangular (latitude-longitude) panorama around it, on an orthonormal view basis.
+// Kind = ProjectionPerspective turns it off (the default); nothing else is looked at then.
+type ProjectionParams struct {
+	Kind                  uint32
+	Axis, Right, Up       [3]float32 // world space: +Axis forward, +Right to image right, +Up to image top
+	HalfWidth, HalfHeight float32    // orthographic: half extents of the window, world units
+	LonRange, LatRange    float32    // equirectangular: radians spanned by the frame's width and height
+}
+
+// SetProjection sets the projection.  The eye is UpdateState(CameraData)'s, which does not touch the basis: a caller that turns the
+// camera derives Axis, Right and Up from the new frustum (axis = normalize(TL + TR + BL + BR), right = normalize(TR - TL),
+// up = normalize(TL - BL) made orthogonal to the axis) and calls SetProjection again.  A projection excludes the lens and the
+// shutter.  A changed projection drops the G-buffer and the temporal history; the caller restarts accumulation as after a camera
+// change.  (Written without a Go toolchain at hand, as the rest of this package: it has not been compiled.)
+func (tr *Tracer) SetProjection(p ProjectionParams) error {
+	var c C.PolarisProjectionParams
+	c.struct_size = C.uint32_t(unsafe.Sizeof(c))
+	c.kind = C.uint32_t(p.Kind)
+	for i := 0; i < 3; i++ {
+		c.axis[i] = C.float(p.Axis[i])
+		c.right[i] = C.float(p.Right[i])
+		c.up[i] = C.float(p.Up[i])
+	}
+	c.half_width = C.float(p.HalfWidth)
+	c.half_height = C.float(p.HalfHeight)
+	c.lon_range = C.float(p.LonRange)
+	c.lat_range = C.float(p.LatRange)
+	return tr.check(C.polaris_hip_set_projection(tr.handle, &c))
+}
+
 // SetObjectMotion turns the option "object_motion" on or off: with it on (and temporal reuse on) the history survives an
 // UpdateState(SceneData) that only moves mesh instances -- same instances, same meshes, same triangle count -- and is reprojected
 // through each instance's motion (DESIGN.md section 10d).  Changing it drops the history.

@@ -73,6 +73,18 @@ const decltype(POLARIS_VARIANT(k_reproject<false, false>)) kReproject[2][2] = {
 const decltype(POLARIS_VARIANT(k_reproject_deform<false>)) kReprojectDeform[2] = {POLARIS_VARIANT(k_reproject_deform<false>), POLARIS_VARIANT(k_reproject_deform<true>)};
 // k_generate_shutter<LENS>: [LENS].  polaris_hip_set_shutter: in k_generate's (k_generate_lens') place while the shutter is on
 const decltype(POLARIS_VARIANT(k_generate_shutter<false>)) kGenerateShutter[2] = {POLARIS_VARIANT(k_generate_shutter<false>), POLARIS_VARIANT(k_generate_shutter<true>)};
+// polaris_hip_set_projection, while the projection is on: k_generate_proj<PROJ>: [kind - 1] in k_generate's place,
+// k_gbuffer_proj / k_gbuffer_chain_proj in the G-buffer kernels', k_reproject_proj<M2, MOTION> and k_reproject_deform_proj<M2> in the reprojection's
+const decltype(POLARIS_VARIANT(k_generate_proj<1>)) kGenerateProj[2] = {POLARIS_VARIANT(k_generate_proj<1>), POLARIS_VARIANT(k_generate_proj<2>)};
+static_assert(POLARIS_PROJECTION_ORTHOGRAPHIC == 1 && POLARIS_PROJECTION_EQUIRECTANGULAR == 2 && kTpOrthographic == 1 && kTpEquirectangular == 2,
+              "kGenerateProj spells PROJ as a number");
+const auto kGbufferProj = POLARIS_VARIANT(k_gbuffer_proj);
+const auto kGbufferChainProj = POLARIS_VARIANT(k_gbuffer_chain_proj);
+const decltype(POLARIS_VARIANT(k_reproject_proj<false, false>)) kReprojectProj[2][2] = {
+	{POLARIS_VARIANT(k_reproject_proj<false, false>), POLARIS_VARIANT(k_reproject_proj<false, true>)},
+	{POLARIS_VARIANT(k_reproject_proj<true, false>), POLARIS_VARIANT(k_reproject_proj<true, true>)}};
+const decltype(POLARIS_VARIANT(k_reproject_deform_proj<false>)) kReprojectDeformProj[2] = {POLARIS_VARIANT(k_reproject_deform_proj<false>),
+                                                                                         POLARIS_VARIANT(k_reproject_deform_proj<true>)};
 
 // the kernels of one variant (k_intersect / k_occlusion: the plain traversal, option traversal = 0)
 const auto kIntersect = POLARIS_VARIANT(k_intersect);

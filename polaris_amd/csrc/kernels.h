@@ -152,11 +152,16 @@ struct CameraArgs { float4 tl, tr, bl, br; float3 eye; float2 texel; };
 
 // camera_direction's arithmetic after the first draw of the camera stream, camera.cl:40-56: the unit direction of the camera ray of
 // pixel (gx, gy + blockY) whose sub-pixel draw is s0, under the corners of `cam` (k_generate_shutter passes the corners at the ray's time).
-__device__ __forceinline__ f3 camera_direction_from(const CameraArgs &cam, f2 s0, uint32_t gx, uint32_t gy, uint32_t blockY) {
+// Its first four lines, which every projection shares: the tent-filtered sub-pixel offsets of the draw and the sample's frame coordinates.
+__device__ __forceinline__ void camera_sample_coords(float2 texel, f2 s0, uint32_t gx, uint32_t gy, uint32_t blockY, float &tx, float &ty) {
 	float ox = s0.x < 0.5f ? pm_sqrt(2.0f * s0.x) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.x);
 	float oy = s0.y < 0.5f ? pm_sqrt(2.0f * s0.y) - 0.5f : 1.5f - pm_sqrt(2.0f - 2.0f * s0.y);
-	float tx = ((float)gx + ox) * cam.texel.x;
-	float ty = ((float)(gy + blockY) + oy) * cam.texel.y;
+	tx = ((float)gx + ox) * texel.x;
+	ty = ((float)(gy + blockY) + oy) * texel.y;
+}
+__device__ __forceinline__ f3 camera_direction_from(const CameraArgs &cam, f2 s0, uint32_t gx, uint32_t gy, uint32_t blockY) {
+	float tx, ty;
+	camera_sample_coords(cam.texel, s0, gx, gy, blockY, tx, ty);
 	// mix(mix(TL, BL, ty), mix(TR, BR, ty), tx), then normalize over all four lanes (w = 0)
 	float lx = pm_mix(cam.tl.x, cam.bl.x, ty), ly = pm_mix(cam.tl.y, cam.bl.y, ty), lz = pm_mix(cam.tl.z, cam.bl.z, ty), lw = pm_mix(cam.tl.w, cam.bl.w, ty);
 	float rx = pm_mix(cam.tr.x, cam.br.x, ty), ry = pm_mix(cam.tr.y, cam.br.y, ty), rz = pm_mix(cam.tr.z, cam.br.z, ty), rw = pm_mix(cam.tr.w, cam.br.w, ty);
@@ -200,15 +205,19 @@ __device__ __forceinline__ void lens_ray(const LensArgs &lens, f2 s1, f3 &o, f3 
 __device__ __forceinline__ float3 mix3(float3 a, float3 b, float t) { return make_float3(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t)); }
 __device__ __forceinline__ float4 mix4(float4 a, float4 b, float t) { return make_float4(pm_mix(a.x, b.x, t), pm_mix(a.y, b.y, t), pm_mix(a.z, b.z, t), pm_mix(a.w, b.w, t)); }
 
-// THE body of the four generators: one lane = one camera ray of sample s = workgroup / (Npad / WG), pixel idx of the block.  The
+// THE body of the six generators: one lane = one camera ray of sample s = workgroup / (Npad / WG), pixel idx of the block.  The
 // camera stream Rng{gx + seed, gy + seed} (camera.cl:38) is drawn in this order: the sub-pixel offset (the reference draws no more),
 // with LENS the lens point, with SHUTTER the ray's time.  cam1 / lens1 (the close state) are read with SHUTTER only, lens / lens1
 // with LENS only.  A lens or a shutter always writes the origins -- every kernel that traces their rays reads the origin stream --;
 // write_origin is the pinhole's alone (the wave-packet kernel and k_trace's camera launch take the eye from elsewhere).
-template <bool LENS, bool SHUTTER>
+// PROJ != 0 (polaris_hip_set_projection; neither LENS nor SHUTTER): the orthographic or the equirectangular camera pc,
+// whose ray is temporal.h's tp_proj_ray_of<PROJ> at the sample's frame coordinates; of cam only the eye and the texel are read.  The
+// origins are always written.  tests/projection_oracle.py restates it.
+template <bool LENS, bool SHUTTER, uint32_t PROJ = 0>
 __device__ __forceinline__ void generate_rays(const Streams &st, const CameraArgs &cam, const CameraArgs &cam1, const LensArgs &lens, const LensArgs &lens1,
                                               const uint32_t *seeds, uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W,
-                                              uint32_t blockY, int zero_lsum, int write_origin) {
+                                              uint32_t blockY, int zero_lsum, int write_origin, const TpProjection *pc = nullptr) {
+	static_assert(PROJ == 0 || (!LENS && !SHUTTER), "a projection excludes the lens and the shutter");
 	const uint32_t wgs_per_sample = Npad / WG;
 	const uint32_t s = blockIdx.x / wgs_per_sample;
 	const uint32_t idx0 = (blockIdx.x % wgs_per_sample) * WG;
@@ -233,10 +242,20 @@ __device__ __forceinline__ void generate_rays(const Streams &st, const CameraArg
 		ct.eye = mix3(cam.eye, cam1.eye, t); // (the texel stays the open camera's)
 		if (LENS) lt = {pm_mix(lens.focus_distance, lens1.focus_distance, t), mix3(lens.axis, lens1.axis, t), mix3(lens.u, lens1.u, t), mix3(lens.v, lens1.v, t)};
 	}
-	f3 d = camera_direction_from(ct, s0, gx, gy, blockY);
-	f3 o = mk3(ct.eye.x, ct.eye.y, ct.eye.z);
+	f3 d, o;
+	if constexpr (PROJ != 0) {
+		float tx, ty;
+		camera_sample_coords(cam.texel, s0, gx, gy, blockY, tx, ty);
+		const float eye[3] = {cam.eye.x, cam.eye.y, cam.eye.z};
+		const TpRay r = tp_proj_ray_of<PROJ>(*pc, eye, tx, ty);
+		o = mk3(r.ox, r.oy, r.oz);
+		d = mk3(r.dx, r.dy, r.dz);
+	} else {
+		d = camera_direction_from(ct, s0, gx, gy, blockY);
+		o = mk3(ct.eye.x, ct.eye.y, ct.eye.z);
+	}
 	if (LENS) lens_ray(lt, s1, o, d);
-	if (LENS || SHUTTER || write_origin) store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
+	if (LENS || SHUTTER || PROJ != 0 || write_origin) store_ray_o(st, slot, make_float4(o.x, o.y, o.z, kFltMax));
 	st.ray_d[slot] = make_float4(d.x, d.y, d.z, ibits((int)idx));
 	// (the throughput of a camera ray is 1: the first shade step does not read it, so it is not written)
 	if (zero_lsum) st.lsum[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -257,6 +276,16 @@ __global__ __launch_bounds__(WG) void k_generate_shutter(Streams st, CameraArgs 
                                                           uint32_t seed_stride, uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY,
                                                           int zero_lsum) {
 	generate_rays<LENS, true>(st, cam, cam1, lens, lens1, seeds, seed_stride, first_sample, N, Npad, W, blockY, zero_lsum, 1);
+}
+
+// polaris_hip_set_projection: in k_generate's place while the projection is on.  PROJ = 1 orthographic, 2 equirectangular (pc.kind).
+// eye_texel: the eye | 1 / W | 1 / H -- all of CameraArgs these generators read.
+template <uint32_t PROJ>
+__global__ __launch_bounds__(WG) void k_generate_proj(Streams st, TpProjection pc, float3 eye, float2 texel, const uint32_t *seeds, uint32_t seed_stride,
+                                                       uint32_t first_sample, uint32_t N, uint32_t Npad, uint32_t W, uint32_t blockY, int zero_lsum) {
+	CameraArgs cam{};
+	cam.eye = eye; cam.texel = texel;
+	generate_rays<false, false, PROJ>(st, cam, cam, LensArgs{}, LensArgs{}, seeds, seed_stride, first_sample, N, Npad, W, blockY, zero_lsum, 1, &pc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2165,6 +2194,19 @@ __device__ __forceinline__ f3 gbuffer_centre_ray(const CameraArgs &cam, uint32_t
 	tp_centre_ray(tl, tr, bl, br, gx, gy, cam.texel.x, cam.texel.y, dc);
 	return mk3(dc[0], dc[1], dc[2]);
 }
+// The guide ray of a camera as the G-buffer kernels' bodies take it: CameraArgs (the perspective frustum), or under
+// polaris_hip_set_projection a GbufferProjCamera, whose ray is tp_guide_ray's of the projected camera.
+struct GbufferProjCamera { TpProjCamera cam; float2 texel; };
+__device__ __forceinline__ void gbuffer_guide_ray(const CameraArgs &cam, uint32_t gx, uint32_t gy, f3 &o, f3 &d) {
+	o = mk3(cam.eye.x, cam.eye.y, cam.eye.z);
+	d = gbuffer_centre_ray(cam, gx, gy);
+}
+__device__ __forceinline__ void gbuffer_guide_ray(const GbufferProjCamera &c, uint32_t gx, uint32_t gy, f3 &o, f3 &d) {
+	float po[3], pd[3];
+	tp_guide_ray(c.cam, gx, gy, c.texel.x, c.texel.y, po, pd);
+	o = mk3(po[0], po[1], po[2]);
+	d = mk3(pd[0], pd[1], pd[2]);
+}
 __device__ __forceinline__ void gbuffer_miss(uint32_t idx, float4 *guide, float4 *albedo, uint32_t *inst, uint4 *hit) {
 	guide[idx] = make_float4(0.0f, 0.0f, 0.0f, kFltMax);
 	albedo[idx] = make_float4(1.0f, 1.0f, 1.0f, ibits(-1));
@@ -2177,13 +2219,16 @@ __device__ __forceinline__ f3 gbuffer_albedo(const MatT<false> &m, f3 tint) {
 	return mk3(pm_clamp(c.x, 0.0f, 1.0f), pm_clamp(c.y, 0.0f, 1.0f), pm_clamp(c.z, 0.0f, 1.0f));
 }
 
-__global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
-                                                uint32_t *inst, uint4 *hit) {
+template <class Camera>
+__device__ __forceinline__ void gbuffer_body(const BvhDev &B, const SceneDev &S, const Camera &cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                             uint32_t *inst, uint4 *hit) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
 	HitRec h;
-	traverse<false>(B, mk3(cam.eye.x, cam.eye.y, cam.eye.z), gbuffer_centre_ray(cam, idx % W, idx / W), kFltMax, stk, h);
+	f3 o, d;
+	gbuffer_guide_ray(cam, idx % W, idx / W, o, d);
+	traverse<false>(B, o, d, kFltMax, stk, h);
 	if (h.tri < 0) return gbuffer_miss(idx, guide, albedo, inst, hit);
 	if (inst) inst[idx] = (uint32_t)h.inst; // (traverse enters the one instance of a root_is_instance scene through its leaf reference too)
 	const int tri = h.tri & (int)((1u << S.tri_bits) - 1u); // (the shading class rides above the index)
@@ -2198,6 +2243,15 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 	guide[idx] = make_float4(sf.n.x, sf.n.y, sf.n.z, h.t);
 	albedo[idx] = make_float4(a.x, a.y, a.z, ibits((int)m.type));
 }
+__global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                uint32_t *inst, uint4 *hit) {
+	gbuffer_body(B, S, cam, W, n, guide, albedo, inst, hit);
+}
+// polaris_hip_set_projection: in k_gbuffer's place while the projection is on; the kind is wave-uniform.
+__global__ __launch_bounds__(WG) void k_gbuffer_proj(BvhDev B, SceneDev S, GbufferProjCamera cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                     uint32_t *inst, uint4 *hit) {
+	gbuffer_body(B, S, cam, W, n, guide, albedo, inst, hit);
+}
 
 // The G-buffer with the option "guide_specular" = max_links > 0, in k_gbuffer's place: the guide ray follows up to
 // max_links delta interactions (CONDUCTOR: the mirror direction; DIELECTRIC: bxdf_sample with the sample (1, 0), which refracts
@@ -2210,12 +2264,14 @@ __global__ __launch_bounds__(WG) void k_gbuffer(BvhDev B, SceneDev S, CameraArgs
 // word where no link was followed, else the miss word.
 // A direction with a component that fails |c| <= 2^10 (NaN included), or all zero, ends the chain at its surface (the direction
 // rule of polaris_hip_probe_intersect): a degenerate IOR sends no such ray into the traversal.  max_links <= 8: every lane ends.
-__global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
-                                                      uint32_t *inst, uint4 *hit, int max_links) {
+template <class Camera>
+__device__ __forceinline__ void gbuffer_chain_body(const BvhDev &B, const SceneDev &S, const Camera &cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                   uint32_t *inst, uint4 *hit, int max_links) {
 	__shared__ int stk[kTraversalStack][WG];
 	const uint32_t idx = blockIdx.x * WG + threadIdx.x;
 	if (idx >= n) return;
-	f3 o = mk3(cam.eye.x, cam.eye.y, cam.eye.z), d = gbuffer_centre_ray(cam, idx % W, idx / W);
+	f3 o, d;
+	gbuffer_guide_ray(cam, idx % W, idx / W, o, d);
 	f3 A = splat(1.0f);
 	float T = 0.0f;
 	for (int k = 0;; k++) {
@@ -2250,6 +2306,14 @@ __global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, Came
 		if (hit) hit[idx] = k == 0 ? make_uint4((uint32_t)tri, pm_f2u(h.u), pm_f2u(h.v), 0u) : make_uint4(kTpNoTriangle, 0u, 0u, 0u);
 		return;
 	}
+}
+__global__ __launch_bounds__(WG) void k_gbuffer_chain(BvhDev B, SceneDev S, CameraArgs cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                      uint32_t *inst, uint4 *hit, int max_links) {
+	gbuffer_chain_body(B, S, cam, W, n, guide, albedo, inst, hit, max_links);
+}
+__global__ __launch_bounds__(WG) void k_gbuffer_chain_proj(BvhDev B, SceneDev S, GbufferProjCamera cam, uint32_t W, uint32_t n, float4 *guide, float4 *albedo,
+                                                           uint32_t *inst, uint4 *hit, int max_links) {
+	gbuffer_chain_body(B, S, cam, W, n, guide, albedo, inst, hit, max_links);
 }
 
 // One a-trous iteration over the rows [y0, y1) (n = (y1 - y0) * W pixels, rows in order from y0 * W).  r_in = null: iteration 0,
@@ -2322,12 +2386,12 @@ __device__ __forceinline__ uint32_t reproject_table_entry(const float4 *tab, uin
 	return flag;
 }
 
-template <bool M2, bool MOTION>
-__global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
-                                                  const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
-                                                  uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
-                                                  const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
-                                                  const float4 *motion, uint32_t n_inst) {
+template <bool M2, bool MOTION, class Camera>
+__device__ __forceinline__ void reproject_body(const float4 *hist, const float4 *hguide, const float4 *halbedo, const Camera &hcam,
+                                               const float4 *guide, const float4 *albedo, const Camera &cam, uint32_t W, uint32_t H,
+                                               uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                               const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                               const float4 *motion, uint32_t n_inst) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= W * H) return;
 	const float4 g = guide[i];
@@ -2342,19 +2406,40 @@ __global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const floa
 	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
 	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
 }
+template <bool M2, bool MOTION>
+__global__ __launch_bounds__(WG) void k_reproject(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
+                                                  const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
+                                                  uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                  const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                  const float4 *motion, uint32_t n_inst) {
+	reproject_body<M2, MOTION>(hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, max_history, normal_threshold, depth_threshold, prior, hvar, prior2, inst,
+	                           hinst, motion, n_inst);
+}
+// polaris_hip_set_projection: in k_reproject's place while the projection is on.  The history camera and the current
+// one share the projection pc and differ in the eye (heye, eye); the kind is wave-uniform.
+template <bool M2, bool MOTION>
+__global__ __launch_bounds__(WG) void k_reproject_proj(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpProjection pc, float3 heye,
+                                                       const float4 *guide, const float4 *albedo, float3 eye, uint32_t W, uint32_t H,
+                                                       uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                       const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                       const float4 *motion, uint32_t n_inst) {
+	const TpProjCamera hcam{pc, {heye.x, heye.y, heye.z}}, cam{pc, {eye.x, eye.y, eye.z}};
+	reproject_body<M2, MOTION>(hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, max_history, normal_threshold, depth_threshold, prior, hvar, prior2, inst,
+	                           hinst, motion, n_inst);
+}
 
 // k_reproject<M2, true> with the option "vertex_motion" in effect and a history that has a snapshot of the vertices:
 // each pixel also loads its HIT word (one uint4); a filtered pixel with a triangle < n_tris gathers the triangle's three vertices as
 // the scene holds them (verts) and as the history saw them (hverts), six float4, and takes k_reproject's path when their xyz are
 // equal; a pixel whose triangle changed reads its instance's entry of the deformation table (deform: four float4 per instance,
 // temporal.h tp_deform_table) and not the motion table.  One thread per pixel, no LDS.
-template <bool M2>
-__global__ __launch_bounds__(WG) void k_reproject_deform(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
-                                                         const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
-                                                         uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
-                                                         const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
-                                                         const float4 *motion, uint32_t n_inst, const uint4 *hit, const float4 *verts,
-                                                         const float4 *hverts, const float4 *deform, uint32_t n_tris) {
+template <bool M2, class Camera>
+__device__ __forceinline__ void reproject_deform_body(const float4 *hist, const float4 *hguide, const float4 *halbedo, const Camera &hcam,
+                                                      const float4 *guide, const float4 *albedo, const Camera &cam, uint32_t W, uint32_t H,
+                                                      uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                      const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                      const float4 *motion, uint32_t n_inst, const uint4 *hit, const float4 *verts,
+                                                      const float4 *hverts, const float4 *deform, uint32_t n_tris) {
 	const uint32_t i = blockIdx.x * WG + threadIdx.x;
 	if (i >= W * H) return;
 	const float4 g = guide[i];
@@ -2376,6 +2461,27 @@ __global__ __launch_bounds__(WG) void k_reproject_deform(const float4 *hist, con
 	                             n_inst, table(motion), hi, n_tris, triangle, table(deform));
 	prior[i] = make_float4(o[0], o[1], o[2], o[3]);
 	if (M2) prior2[i] = make_float4(o2[0], o2[1], o2[2], o2[3]);
+}
+template <bool M2>
+__global__ __launch_bounds__(WG) void k_reproject_deform(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpCamera hcam,
+                                                         const float4 *guide, const float4 *albedo, TpCamera cam, uint32_t W, uint32_t H,
+                                                         uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                         const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                         const float4 *motion, uint32_t n_inst, const uint4 *hit, const float4 *verts,
+                                                         const float4 *hverts, const float4 *deform, uint32_t n_tris) {
+	reproject_deform_body<M2>(hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, max_history, normal_threshold, depth_threshold, prior, hvar, prior2, inst,
+	                          hinst, motion, n_inst, hit, verts, hverts, deform, n_tris);
+}
+template <bool M2>
+__global__ __launch_bounds__(WG) void k_reproject_deform_proj(const float4 *hist, const float4 *hguide, const float4 *halbedo, TpProjection pc, float3 heye,
+                                                              const float4 *guide, const float4 *albedo, float3 eye, uint32_t W, uint32_t H,
+                                                              uint32_t max_history, float normal_threshold, float depth_threshold, float4 *prior,
+                                                              const float4 *hvar, float4 *prior2, const uint32_t *inst, const uint32_t *hinst,
+                                                              const float4 *motion, uint32_t n_inst, const uint4 *hit, const float4 *verts,
+                                                              const float4 *hverts, const float4 *deform, uint32_t n_tris) {
+	const TpProjCamera hcam{pc, {heye.x, heye.y, heye.z}}, cam{pc, {eye.x, eye.y, eye.z}};
+	reproject_deform_body<M2>(hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, max_history, normal_threshold, depth_threshold, prior, hvar, prior2, inst,
+	                          hinst, motion, n_inst, hit, verts, hverts, deform, n_tris);
 }
 
 // TEMPORAL plane over the rows [y0, y1): the frame accumulator blended with the PRIOR (n = accumulated + spp as a float,

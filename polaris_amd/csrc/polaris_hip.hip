@@ -185,6 +185,7 @@ struct FrameSync {
 			v.temporal_params_changed();
 		tp = p;
 	}
+	void projection_changed() { v.guide_rule_changed(); } // the G-buffer and the history were seen through another projection (camera_state.h, kCamProjection): both go, the planes stay
 	void lens_changed() { if (tp.max_history) drop(v.temporal_off()); } // the history saw another lens or shutter (camera_state.h, kCamDropHistory): it goes as with max_history = 0; the (pinhole) G-buffer stays
 	void set_variance(const PolarisVarianceParams &p) {
 		if ((p.sigma_variance != 0.0f) != (va.sigma_variance != 0.0f)) drop(v.variance_toggled(p.sigma_variance != 0.0f));
@@ -610,6 +611,14 @@ CameraDev camera_args(const polaris_hip_tracer *h) {
 	};
 	return {cam(c.open.eye, c.open.frustum), cam(c.shutter.eye1, c.shutter.frustum1), lens(&c.lens.focus_distance), lens(&c.shutter.focus_distance1)};
 }
+// The projection of the handle's camera as the kernels and temporal.h take it (polaris_hip_set_projection is on): the basis and the two
+// extents of the kind in force.
+TpProjection projection_args(const CameraState &c) {
+	const PolarisProjectionParams &p = c.projection;
+	const bool ortho = p.kind == POLARIS_PROJECTION_ORTHOGRAPHIC;
+	return TpProjection{p.kind, {p.axis[0], p.axis[1], p.axis[2]}, {p.right[0], p.right[1], p.right[2]}, {p.up[0], p.up[1], p.up[2]},
+	                    ortho ? p.half_width : p.lon_range, ortho ? p.half_height : p.lat_range};
+}
 
 // The planes of the set `need` exist from their first use on, each of the frame's size; those of `clear` are cleared on the main stream,
 // those of `clear_new` if they are allocated here (caller holds mu).
@@ -636,7 +645,16 @@ int ensure_gbuffer(polaris_hip_tracer *h) {
 	const size_t F = (size_t)h->fa.W * h->fa.H;
 	if (int rc = ensure_planes(h, planes(kGuide, kAlbedo) | (want_inst ? planes(kInst) : 0) | (want_hit ? planes(kHit) : 0))) return rc;
 	const CameraArgs cam = camera_args(h).cam;
-	if (S.opt_guide_specular == 0)
+	uint32_t *const inst = want_inst ? S.gb_inst.get() : nullptr;
+	uint4 *const hit = want_hit ? S.gb_hit.get() : nullptr;
+	if (h->camera.projection_on()) { //  the same planes from the projected camera's guide rays
+		const GbufferProjCamera pc{TpProjCamera{projection_args(h->camera), {cam.eye.x, cam.eye.y, cam.eye.z}}, cam.texel};
+		if (S.opt_guide_specular == 0)
+			(void)launch(h, "gbuffer", h->stream, kGbufferProj, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, pc, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo], inst, hit);
+		else
+			(void)launch(h, "gbuffer", h->stream, kGbufferChainProj, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, pc, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
+			             inst, hit, S.opt_guide_specular);
+	} else if (S.opt_guide_specular == 0)
 		(void)launch(h, "gbuffer", h->stream, kGbuffer, grid_for(F), WG, 0, h->ds.bvh, h->ds.scene, cam, h->fa.W, (uint32_t)F, S.pl[kGuide], S.pl[kAlbedo],
 		             want_inst ? S.gb_inst.get() : nullptr, want_hit ? S.gb_hit.get() : nullptr);
 	else
@@ -760,6 +778,7 @@ TraceScene plan_scene(const polaris_hip_tracer *h) {
 	for (int lds = 0; lds < 2; lds++) s.shade_wave_resident[lds] = h->shade_wave_resident[lds];
 	s.lens = h->camera.lens_on();
 	s.shutter = h->camera.shutter_on();
+	s.projection = h->camera.projection_on();
 	return s;
 }
 
@@ -782,6 +801,9 @@ hipError_t launch_generate(polaris_hip_tracer *h, const char *timer, hipStream_t
 	const uint32_t *seeds = h->d_seeds;
 	switch (const Generator g = h->camera.generator()) {
 	case Generator::Pinhole: return launch(h, timer, q, kGenerate, wgs, WG, 0, st, c.cam, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum, write_origin);
+	case Generator::Ortho: case Generator::Equirect:
+		return launch(h, timer, q, kGenerateProj[g == Generator::Equirect], wgs, WG, 0, st, projection_args(h->camera), c.cam.eye, c.cam.texel, seeds, stride, first_sample, N,
+		              Npad, h->fa.W, block_y, zero_lsum);
 	case Generator::Lens: return launch(h, timer, q, kGenerateLens, wgs, WG, 0, st, c.cam, c.lens, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum);
 	default: return launch(h, timer, q, kGenerateShutter[g == Generator::ShutterLens], wgs, WG, 0, st, c.cam, c.cam1, c.lens, c.lens1, seeds, stride, first_sample, N, Npad, h->fa.W, block_y, zero_lsum);
 	}
@@ -1389,14 +1411,16 @@ int polaris_hip_read_scene_records(polaris_hip_tracer *h, int which, void *out, 
 static int apply_camera_step(polaris_hip_tracer *h, const CameraStep &s, const float *eye = nullptr) {
 	if (!s.refusal.empty()) return fail(h, POLARIS_E_BAD_ARGUMENT, "%s", s.refusal.c_str());
 	const bool drop = (s.todo & kCamDropHistory) && h->fs.tp.max_history;
-	if (drop || eye) HIP_TRY(h, hipSetDevice(h->device));
-	if (drop) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the history's planes are freed: the main stream, where every temporal launch runs, is idle first
+	const bool projection = (s.todo & kCamProjection) != 0;
+	if (drop || eye || projection) HIP_TRY(h, hipSetDevice(h->device));
+	if (drop || projection) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the history's planes are freed: the main stream, where every temporal launch runs, is idle first
 	if (eye) { // the one origin record of every camera ray: what k_generate would write per ray (kernels.h)
 		const float4 o4 = make_float4(eye[0], eye[1], eye[2], kFltMax);
 		// (nothing of this handle reads the record now: the caller holds mu, and a Trace returns only when its kernels are done)
 		HIP_TRY(h, hipMemcpy(h->d_cam_o, &o4, sizeof o4, hipMemcpyHostToDevice));
 	}
 	if (drop) h->fs.lens_changed();
+	if (projection) h->fs.projection_changed();
 	if (s.todo & kCamMoved) h->fs.camera_moved(h->camera.open); // (with temporal reuse the last temporal sync's planes under the old camera become the history)
 	h->camera = s.next;
 	return POLARIS_OK;
@@ -1418,6 +1442,12 @@ int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p
 	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
 	std::lock_guard<std::mutex> lk(h->mu);
 	return apply_camera_step(h, h->camera.set_shutter(p));
+}
+
+int polaris_hip_set_projection(polaris_hip_tracer *h, const PolarisProjectionParams *p) {
+	if (!h) return fail(nullptr, POLARIS_E_BAD_ARGUMENT, "handle is null");
+	std::lock_guard<std::mutex> lk(h->mu);
+	return apply_camera_step(h, h->camera.set_projection(p));
 }
 
 int polaris_hip_set_option(polaris_hip_tracer *h, const char *key, int64_t value) {
@@ -1945,16 +1975,29 @@ struct MotionArgs {
 };
 hipError_t launch_reproject(polaris_hip_tracer *h, hipStream_t q, const float4 *hist, const float4 *hguide, const float4 *halbedo, const TpCamera &hcam,
                       const float4 *guide, const float4 *albedo, const TpCamera &cam, uint32_t W, uint32_t H, const PolarisTemporalParams &p,
-                      float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr, const MotionArgs *mo = nullptr) {
+                      float4 *prior, const float4 *hvar = nullptr, float4 *prior2 = nullptr, const MotionArgs *mo = nullptr, const TpProjection *proj = nullptr) {
+	// proj != null (polaris_hip_set_projection is on): both cameras are this projection's, only their eyes are read, and the *_proj kernels run
 	const size_t F = (size_t)W * H;
-	const bool none = !hist || !tp_projectable(hcam) || p.max_history == 0; // no history anywhere: m = 0
+	const bool none = !hist || (!proj && !tp_projectable(hcam)) || p.max_history == 0; // no history anywhere: m = 0
 	const bool m2 = prior2 && hvar && !none;                                // (else the PRIOR as without variance guidance, PRIOR2 = 0)
 	const bool deform = mo && mo->hit;
 	const auto &variant = kReproject[m2][mo != nullptr];
-	Timed t(h, "reproject", none ? nullptr : (deform ? kReprojectDeform[m2].symbol : variant.symbol), q);
+	const char *const symbol = proj ? (deform ? kReprojectDeformProj[m2].symbol : kReprojectProj[m2][mo != nullptr].symbol) : (deform ? kReprojectDeform[m2].symbol : variant.symbol);
+	Timed t(h, "reproject", none ? nullptr : symbol, q);
 	if (prior2 && !m2)
 		if (hipError_t e = hipMemsetAsync(prior2, 0, F * sizeof(float4), q)) return e;
 	if (none) return hipMemsetAsync(prior, 0, F * sizeof(float4), q);
+	if (proj) {
+		const float3 heye = make_float3(hcam.eye[0], hcam.eye[1], hcam.eye[2]), eye = make_float3(cam.eye[0], cam.eye[1], cam.eye[2]);
+		if (deform)
+			kReprojectDeformProj[m2].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, *proj, heye, guide, albedo, eye, W, H, p.max_history, p.normal_threshold,
+			                                 p.depth_threshold, prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo->inst, mo->hinst, mo->table, mo->n_inst,
+			                                 mo->hit, mo->verts, mo->hverts, mo->deform, mo->n_tris);
+		else kReprojectProj[m2][mo != nullptr].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, *proj, heye, guide, albedo, eye, W, H, p.max_history,
+		                                              p.normal_threshold, p.depth_threshold, prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo ? mo->inst : nullptr,
+		                                              mo ? mo->hinst : nullptr, mo ? mo->table : nullptr, mo ? mo->n_inst : 0u);
+		return hipGetLastError();
+	}
 	if (deform)
 		kReprojectDeform[m2].enqueue(grid_for(F), WG, 0, q, hist, hguide, halbedo, hcam, guide, albedo, cam, W, H, p.max_history, p.normal_threshold,
 		                             p.depth_threshold, prior, m2 ? hvar : nullptr, m2 ? prior2 : nullptr, mo->inst, mo->hinst, mo->table, mo->n_inst,
@@ -2106,9 +2149,11 @@ int enqueue_features(polaris_hip_tracer *h, const PolarisBlockRequest *r, float 
 				mo.hit = S.gb_hit; mo.verts = h->ds.vup.vertices; mo.hverts = S.vert_snap; mo.deform = S.de_table; mo.n_tris = h->ds.vup.num_triangles;
 			}
 		}
+		const TpProjection proj = projection_args(h->camera); // (read only while the projection is on)
 		HIP_TRY(h, launch_reproject(h, h->stream, P.history ? S.pl[kTpHist].get() : nullptr, S.pl[kTpHGuide], S.pl[kTpHAlbedo], tp_camera(S.tp_hcam.eye, S.tp_hcam.frustum),
 		                            S.pl[kGuide], S.pl[kAlbedo], tp_camera(h->camera.open.eye, h->camera.open.frustum), h->fa.W, h->fa.H, S.tp, S.pl[kTpPrior],
-		                            P.m2 ? S.pl[kVaHist].get() : nullptr, f.variance ? S.pl[kTpPrior2].get() : nullptr, P.motion ? &mo : nullptr));
+		                            P.m2 ? S.pl[kVaHist].get() : nullptr, f.variance ? S.pl[kTpPrior2].get() : nullptr, P.motion ? &mo : nullptr,
+		                            h->camera.projection_on() ? &proj : nullptr));
 		S.v.prior_computed();
 	}
 	HIP_TRY(h, h->fa.join_merges(h->stream)); // (as the plain sync: the merges queued so far are part of the frame)

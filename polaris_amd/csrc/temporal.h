@@ -80,6 +80,80 @@ PM_HD bool tp_project(const TpCamera &c, const float p[3], float &u, float &v, f
 	return true;
 }
 
+// ---- polaris_hip_set_projection: the orthographic and the equirectangular camera.  The view basis and the two extents of
+// the kind in force (ORTHOGRAPHIC: half_width, half_height; EQUIRECTANGULAR: lon_range, lat_range) with the eye.  The history camera and
+// the current one always share one projection (a changed projection drops the history): they differ in the eye alone.
+constexpr uint32_t kTpOrthographic = 1, kTpEquirectangular = 2; // POLARIS_PROJECTION_*
+struct TpProjection { uint32_t kind; float axis[3], right[3], up[3], ex, ey; };
+struct TpProjCamera { TpProjection proj; float eye[3]; };
+
+// The ray of a projected camera at the frame coordinates (tx, ty) in [0, 1): k_generate_proj's lines after tx and ty, every operation
+// rounded once in the order written.  ORTHOGRAPHIC: the origin moves in the window, the direction is the axis verbatim.
+// EQUIRECTANGULAR: the origin is the eye, the direction the unit vector at longitude (tx - 0.5) lon_range, latitude (0.5 - ty) lat_range.
+// KIND is the projection's kind, which k_generate_proj<KIND> knows as it is compiled; tp_proj_ray reads it from P.
+// (The ray is returned by value and the two kinds' results meet as values: written through o[] and d[] inside the branch, the device
+// compiler keeps the arrays in scratch memory.)
+struct TpRay { float ox, oy, oz, dx, dy, dz; };
+template <uint32_t KIND>
+PM_HD TpRay tp_proj_ray_of(const TpProjection &P, const float eye[3], float tx, float ty) {
+	if constexpr (KIND == kTpOrthographic) {
+		const float sx = 2.0f * tx - 1.0f, sy = 1.0f - 2.0f * ty;
+		const float a = sx * P.ex, b = sy * P.ey;
+		return TpRay{(eye[0] + P.right[0] * a) + P.up[0] * b, (eye[1] + P.right[1] * a) + P.up[1] * b, (eye[2] + P.right[2] * a) + P.up[2] * b,
+		             P.axis[0], P.axis[1], P.axis[2]};
+	} else {
+		const float lon = (tx - 0.5f) * P.ex, lat = (0.5f - ty) * P.ey;
+		const float cl = pm_cos(lat), sl = pm_sin(lat), co = pm_cos(lon), so = pm_sin(lon);
+		const float a = cl * co, b = cl * so;
+		const float ex = (P.axis[0] * a + P.right[0] * b) + P.up[0] * sl;
+		const float ey = (P.axis[1] * a + P.right[1] * b) + P.up[1] * sl;
+		const float ez = (P.axis[2] * a + P.right[2] * b) + P.up[2] * sl;
+		const float inv = 1.0f / pm_sqrt((ex * ex + ey * ey) + ez * ez);
+		return TpRay{eye[0], eye[1], eye[2], ex * inv, ey * inv, ez * inv};
+	}
+}
+PM_HD void tp_proj_ray(const TpProjection &P, const float eye[3], float tx, float ty, float o[3], float d[3]) {
+	const TpRay r = P.kind == kTpOrthographic ? tp_proj_ray_of<kTpOrthographic>(P, eye, tx, ty) : tp_proj_ray_of<kTpEquirectangular>(P, eye, tx, ty);
+	o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
+	d[0] = r.dx; d[1] = r.dy; d[2] = r.dz;
+}
+
+// The guide ray of pixel (gx, gy): the ray through the pixel's centre, which the G-buffer kernels cast and the reprojection re-derives.
+// The perspective camera's starts at the eye along tp_centre_ray; a projected camera's is tp_proj_ray with the offset fixed at 0.5.
+PM_HD void tp_guide_ray(const TpCamera &c, uint32_t gx, uint32_t gy, float texel_x, float texel_y, float o[3], float d[3]) {
+	tp_centre_ray(c.tl, c.tr, c.bl, c.br, gx, gy, texel_x, texel_y, d);
+	o[0] = c.eye[0]; o[1] = c.eye[1]; o[2] = c.eye[2];
+}
+PM_HD void tp_guide_ray(const TpProjCamera &c, uint32_t gx, uint32_t gy, float texel_x, float texel_y, float o[3], float d[3]) {
+	tp_proj_ray(c.proj, c.eye, ((float)gx + 0.5f) * texel_x, ((float)gy + 0.5f) * texel_y, o, d);
+}
+
+// tp_project for a projected camera: q = p - eye in the view basis, x = q . axis, y = q . right, z = q . up, each dot summed left to
+// right.  ORTHOGRAPHIC: fails unless x > 0; dist = x, the distance along the axis, which is what GUIDE t holds under it.
+// EQUIRECTANGULAR: dist = |q|, fails unless dist > 0 (NaN fails).  No wrap across the seam: a point outside the frame gets a (u, v)
+// outside [0, 1] and falls under tp_reproject's bounds rule.
+PM_HD bool tp_project(const TpProjCamera &c, const float p[3], float &u, float &v, float &dist) {
+	const TpProjection &P = c.proj;
+	const float q[3] = {p[0] - c.eye[0], p[1] - c.eye[1], p[2] - c.eye[2]};
+	const float x = (q[0] * P.axis[0] + q[1] * P.axis[1]) + q[2] * P.axis[2];
+	const float y = (q[0] * P.right[0] + q[1] * P.right[1]) + q[2] * P.right[2];
+	const float z = (q[0] * P.up[0] + q[1] * P.up[1]) + q[2] * P.up[2];
+	if (P.kind == kTpOrthographic) {
+		if (!(x > 0.0f)) return false;
+		u = (y / P.ex + 1.0f) * 0.5f;
+		v = (1.0f - z / P.ey) * 0.5f;
+		dist = x;
+		return true;
+	}
+	dist = tp_len3(q[0], q[1], q[2]);
+	if (!(dist > 0.0f)) return false;
+	const float lon = pm_atan2(y, x), lat = pm_atan2(z, pm_sqrt(x * x + y * y));
+	u = lon / P.ex + 0.5f;
+	v = 0.5f - lat / P.ey;
+	return true;
+}
+PM_HD bool tp_projectable(const TpProjCamera &) { return true; } // (polaris_hip_set_projection checked the basis and the extents)
+
 // One history tap as k_reproject gathers it (m2: the history's M2, gathered only by k_reproject<true, *>, variance.h; inst: the
 // history's INSTANCE word, gathered only by k_reproject<*, true>).
 struct TpTap { float r, g, b, count; float nx, ny, nz, t; float leaf; float m2; uint32_t inst; };
@@ -192,20 +266,22 @@ PM_HD bool tp_tap_ok(const TpTap &j, float leaf_i, float nx, float ny, float nz,
 // the old triangle at the hit's barycentrics (surface_at's expression) and matrix(k, M) instance k's deformation table entry
 // (tp_deform_table: STATIC p = q, INVALID m = 0, MOVED the rows as D's); a component of q or p that is not finite: m = 0.
 // DEFORM = false reads none of it.
+// Camera: TpCamera, or TpProjCamera under polaris_hip_set_projection (cur and hist of one projection): tp_guide_ray and tp_project are
+// the camera's, everything else is the same.
 template <bool M2 = false, bool MOTION = false, bool DEFORM = false, class Load, class Motion = TpNoMotion, class Verts = TpNoDeform,
-          class Matrix = TpNoDeform>
-PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const TpCamera &cur,
-                        const TpCamera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4],
+          class Matrix = TpNoDeform, class Camera = TpCamera>
+PM_HD void tp_reproject(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, const float guide_i[4], float leaf_i, const Camera &cur,
+                        const Camera &hist, uint32_t max_history, float normal_threshold, float depth_threshold, Load load, float out[4],
                         float *out2 = nullptr, uint32_t inst_i = 0, uint32_t n_inst = 0, Motion motion = Motion(),
                         const uint32_t *hit_i = nullptr, uint32_t n_tris = 0, Verts verts = Verts(), Matrix matrix = Matrix()) {
 	static_assert(MOTION || !DEFORM, "DEFORM extends MOTION");
 	out[0] = out[1] = out[2] = out[3] = 0.0f;
 	if (M2) out2[0] = out2[1] = out2[2] = out2[3] = 0.0f;
 	if (!dn_filtered(leaf_i)) return;
-	float d[3];
-	tp_centre_ray(cur.tl, cur.tr, cur.bl, cur.br, gx, gy, 1.0f / (float)W, 1.0f / (float)H, d);
+	float o[3], d[3];
+	tp_guide_ray(cur, gx, gy, 1.0f / (float)W, 1.0f / (float)H, o, d);
 	const float t = guide_i[3];
-	float p[3] = {cur.eye[0] + t * d[0], cur.eye[1] + t * d[1], cur.eye[2] + t * d[2]};
+	float p[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
 	bool rigid = true; // (the pixel's triangle is as the history saw it)
 	if constexpr (DEFORM) {
 		if (inst_i >= n_inst || hit_i[0] >= n_tris) return;

@@ -55,6 +55,7 @@ struct TraceScene {
 	int shade_wave_resident[2] = {5, 5}; // [LDS tables]: workgroups of k_shade_wave<..> a CU holds at once (occupancy API: 5 waves per SIMD)
 	bool lens = false;                // polaris_hip_set_lens is on: the camera rays start on the lens, each at its own origin
 	bool shutter = false;             // polaris_hip_set_shutter is on: each camera ray starts at the eye of its own time; plans exactly as `lens`
+	bool projection = false;          // polaris_hip_set_projection is on: the generator writes every ray's origin (the orthographic camera's differ); plans exactly as `lens`
 };
 
 // ---- which traversal kernel traces a set of rays
@@ -128,7 +129,7 @@ struct TracePlan {
 	bool staged = false;     // the shade kernels' LDS-table variants
 	bool moments = false, prefilter = true, hit12 = true, o12 = true; // the options the launches pass on
 	bool generate_writes_origins = true; // (neither the wave-packet kernel nor k_trace's camera launch reads the origin stream)
-	RayKind primary = RayKind::Camera;   // bounce 0's closest-hit rays; Closest under a lens or a shutter: the same kernel family, reading the origin stream
+	RayKind primary = RayKind::Camera;   // bounce 0's closest-hit rays; Closest under a lens, a shutter or a projection: the same kernel family, reading the origin stream
 	BouncePlan bounce[POLARIS_MAX_BOUNCES];
 
 	uint32_t pipes_wanted() const { return (uint32_t)std::max(1, std::min(opt.overlap, kMaxPipes)); }
@@ -233,7 +234,7 @@ inline TracePlan plan_trace(const TraceOptions &opt, const TraceScene &scene, bo
 	p.k_chosen = opt.samples_per_batch > 0;
 	p.staged = tables_staged(opt, scene);
 	p.moments = moments; p.prefilter = opt.shade_prefilter != 0; p.hit12 = opt.hit12 != 0; p.o12 = opt.o12 != 0;
-	const bool own_origins = scene.lens || scene.shutter; // a generator that gives every camera ray its own origin
+	const bool own_origins = scene.lens || scene.shutter || scene.projection; // a generator that gives every camera ray its own origin
 	p.generate_writes_origins = own_origins || !(bounces > 0 && (scene.packet_primary || opt.traversal));
 	p.primary = own_origins ? RayKind::Closest : RayKind::Camera;
 	for (uint32_t b = 0; b < bounces; b++) {

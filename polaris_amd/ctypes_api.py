@@ -237,6 +237,63 @@ def shutter_params(eye1=None, frustum1=None, focus_distance1=0.0, axis1=(0.0, 0.
     return p
 
 
+PROJECTION_PERSPECTIVE, PROJECTION_ORTHOGRAPHIC, PROJECTION_EQUIRECTANGULAR = 0, 1, 2
+PROJECTION_KINDS = {"perspective": PROJECTION_PERSPECTIVE, "orthographic": PROJECTION_ORTHOGRAPHIC, "equirect": PROJECTION_EQUIRECTANGULAR}
+
+
+class ProjectionParams(C.Structure):
+    """PolarisProjectionParams (include/polaris_hip.h): the orthographic or the equirectangular camera.  kind = 0 is the projection OFF
+    (the default): the perspective frustum of polaris_hip_set_camera."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("axis", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
+                ("half_width", C.c_float), ("half_height", C.c_float), ("lon_range", C.c_float), ("lat_range", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(self)
+
+
+assert C.sizeof(ProjectionParams) == 60
+
+
+def projection_params(kind=PROJECTION_PERSPECTIVE, axis=(0.0, 0.0, 0.0), right=(0.0, 0.0, 0.0), up=(0.0, 0.0, 0.0), half_width=0.0, half_height=0.0,
+                      lon_range=0.0, lat_range=0.0) -> ProjectionParams:
+    p = ProjectionParams()
+    p.kind = int(kind)
+    for name, vec in (("axis", axis), ("right", right), ("up", up)):
+        setattr(p, name, (C.c_float * 3)(*[float(x) for x in vec]))
+    p.half_width, p.half_height, p.lon_range, p.lat_range = float(half_width), float(half_height), float(lon_range), float(lat_range)
+    return p
+
+
+def projection_from_frustum(frustum):
+    """(axis, right, up, aspect) of the view basis a perspective frustum looks through: axis = normalize(TL + TR + BL + BR),
+    right = normalize(TR - TL), up = normalize(TL - BL) made orthogonal to axis, aspect = |TR - TL| / |TL - BL|; computed in float64,
+    the vectors rounded to float32 once."""
+    fr = np.asarray(frustum, np.float64).reshape(4, 4)[:, :3]
+    tl, tr, bl, br = fr
+    length = lambda x: np.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])  # noqa: E731  (spelled out: the host layer's C++ derives the same bits)
+    axis = (tl + tr + bl + br) / length(tl + tr + bl + br)
+    right = (tr - tl) / length(tr - tl)
+    up = (tl - bl) / length(tl - bl)
+    up = up - axis * ((up[0] * axis[0] + up[1] * axis[1]) + up[2] * axis[2])
+    up = up / length(up)
+    return axis.astype(np.float32), right.astype(np.float32), up.astype(np.float32), float(length(tr - tl) / length(tl - bl))
+
+
+def projection_for(kind, frustum, height=None, lon_range=2.0 * np.pi, lat_range=np.pi) -> ProjectionParams:
+    """The projection `kind` (a PROJECTION_* number) looking the way the frustum looks.  ORTHOGRAPHIC: a window `height` world units
+    high, as wide as the frustum's aspect makes it.  EQUIRECTANGULAR: lon_range x lat_range radians."""
+    if kind == PROJECTION_PERSPECTIVE:
+        return projection_params()
+    axis, right, up, aspect = projection_from_frustum(frustum)
+    if kind == PROJECTION_ORTHOGRAPHIC:
+        if height is None:
+            raise ValueError("an orthographic projection needs the height of its window")
+        half_height = float(height) / 2.0
+        return projection_params(kind, axis, right, up, half_width=half_height * aspect, half_height=half_height)
+    return projection_params(kind, axis, right, up, lon_range=lon_range, lat_range=lat_range)
+
+
 class VarianceParams(C.Structure):
     """PolarisVarianceParams (include/polaris_hip.h): variance-guided denoising from per-pixel luminance moments."""
     _fields_ = [("struct_size", C.c_uint32), ("sigma_variance", C.c_float), ("min_samples", C.c_uint32)]
@@ -547,7 +604,7 @@ C_ABI_SYMBOLS = [
     "polaris_hip_reproject_motion_planes", "polaris_hip_read_instance_plane",
     "polaris_hip_reproject_deform_planes", "polaris_hip_read_hit_plane",
     "polaris_hip_update_instances", "polaris_hip_read_scene_records", "polaris_hip_update_vertices",
-    "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens", "polaris_hip_set_shutter",
+    "polaris_hip_update_materials", "polaris_hip_update_texture", "polaris_hip_set_lens", "polaris_hip_set_shutter", "polaris_hip_set_projection",
 ]
 
 _lib = None
@@ -649,6 +706,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.polaris_hip_denoise_planes.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, C.c_float, C.c_float, C.POINTER(DenoiseParams), vp, vp]
     lib.polaris_hip_set_lens.argtypes = [vp, C.POINTER(LensParams)]
     lib.polaris_hip_set_shutter.argtypes = [vp, C.POINTER(ShutterParams)]
+    lib.polaris_hip_set_projection.argtypes = [vp, C.POINTER(ProjectionParams)]
     lib.polaris_hip_set_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
     lib.polaris_hip_set_variance.argtypes = [vp, C.POINTER(VarianceParams)]
     lib.polaris_hip_set_display.argtypes = [vp, C.POINTER(DisplayParams)]

@@ -8,6 +8,8 @@
 extern "C" int polaris_hip_set_lens(polaris_hip_tracer *h, const PolarisLensParams *p) __attribute__((weak));
 // polaris_hip_set_shutter likewise: without it only a CameraData that has a close state is refused.
 extern "C" int polaris_hip_set_shutter(polaris_hip_tracer *h, const PolarisShutterParams *p) __attribute__((weak));
+// polaris_hip_set_projection likewise: without it only a CameraData that has a projection is refused.
+extern "C" int polaris_hip_set_projection(polaris_hip_tracer *h, const PolarisProjectionParams *p) __attribute__((weak));
 
 namespace polaris {
 namespace tracer {
@@ -76,6 +78,39 @@ static PolarisShutterParams shutterOf(const CameraData &c) {
 	return p;
 }
 
+// The projection of a CameraData (polaris_amd/ctypes_api.py projection_for, the same derivation): axis = normalize(TL + TR + BL + BR),
+// right = normalize(TR - TL), up = normalize(TL - BL) made orthogonal to the axis, half_height = ortho_height / 2, half_width =
+// half_height |TR - TL| / |TL - BL|, in double, rounded to float once.  projection = 0: all zero (off).
+static PolarisProjectionParams projectionOf(const CameraData &c) {
+	PolarisProjectionParams p{};
+	p.struct_size = sizeof p;
+	if (c.projection == POLARIS_PROJECTION_PERSPECTIVE) return p;
+	p.kind = c.projection;
+	const float *tl = c.frustum, *tr = c.frustum + 4, *bl = c.frustum + 8, *br = c.frustum + 12;
+	double a[3], r[3], u[3];
+	for (int k = 0; k < 3; k++) {
+		a[k] = (((double)tl[k] + (double)tr[k]) + (double)bl[k]) + (double)br[k];
+		r[k] = (double)tr[k] - (double)tl[k];
+		u[k] = (double)tl[k] - (double)bl[k];
+	}
+	auto length = [](const double x[3]) { return std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]); };
+	const double la = length(a), lr = length(r), lu = length(u);
+	for (int k = 0; k < 3; k++) { a[k] = a[k] / la; r[k] = r[k] / lr; u[k] = u[k] / lu; }
+	const double ua = (u[0] * a[0] + u[1] * a[1]) + u[2] * a[2];
+	for (int k = 0; k < 3; k++) u[k] = u[k] - a[k] * ua;
+	const double lu2 = length(u);
+	for (int k = 0; k < 3; k++) { p.axis[k] = (float)a[k]; p.right[k] = (float)r[k]; p.up[k] = (float)(u[k] / lu2); }
+	if (c.projection == POLARIS_PROJECTION_ORTHOGRAPHIC) {
+		const double half_height = (double)c.ortho_height / 2.0;
+		p.half_height = (float)half_height;
+		p.half_width = (float)(half_height * (lr / lu));
+	} else {
+		p.lon_range = c.lon_range;
+		p.lat_range = c.lat_range;
+	}
+	return p;
+}
+
 Error HipTracer::Init() {
 	std::lock_guard<std::mutex> lk(mu_);
 	return check(polaris_hip_create(dev_.Index, &h_));
@@ -110,6 +145,9 @@ Error HipTracer::commitChanges(Duration *took) { // tracer/opencl/tracer.go:161-
 	if (has_scene_ && !err) { err = check(polaris_hip_upload_scene(h_, scene_)); has_scene_ = false; scene_ = nullptr; }
 	if (has_cam_ && !err) {
 		err = check(polaris_hip_set_camera(h_, cam_.eye, cam_.frustum));
+		// the projection excludes the lens and the shutter: one that goes off goes before they may come on, one that is on comes after them
+		const PolarisProjectionParams projection = projectionOf(cam_);
+		if (!err && polaris_hip_set_projection && projection.kind == POLARIS_PROJECTION_PERSPECTIVE) err = check(polaris_hip_set_projection(h_, &projection));
 		// set_camera leaves the lens vectors alone: they follow the new frustum here (identical bytes ask nothing of the library)
 		const PolarisLensParams lens = lensFromFrustum(cam_.frustum, cam_.lens_radius, cam_.focus_distance);
 		if (!err && polaris_hip_set_lens) err = check(polaris_hip_set_lens(h_, &lens));
@@ -118,6 +156,11 @@ Error HipTracer::commitChanges(Duration *took) { // tracer/opencl/tracer.go:161-
 		const PolarisShutterParams shutter = shutterOf(cam_);
 		if (!err && polaris_hip_set_shutter) err = check(polaris_hip_set_shutter(h_, &shutter));
 		else if (!err && cam_.has_close) err = Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: this C ABI has no polaris_hip_set_shutter"};
+		// camera, then projection: set_camera keeps the projection's basis, which follows the new frustum here (identical bytes ask nothing)
+		if (!err && projection.kind != POLARIS_PROJECTION_PERSPECTIVE) {
+			if (polaris_hip_set_projection) err = check(polaris_hip_set_projection(h_, &projection));
+			else err = Error{POLARIS_E_BAD_ARGUMENT, "hip tracer: this C ABI has no polaris_hip_set_projection"};
+		}
 		has_cam_ = false;
 	}
 	stats_.UpdateTime = std::chrono::duration_cast<Duration>(clock_::now() - start);

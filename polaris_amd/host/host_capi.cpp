@@ -227,6 +227,7 @@ int polaris_host_renderer_set_camera(void *h, const float eye[3], const float fr
 	memcpy(cam.eye, eye, sizeof cam.eye);
 	memcpy(cam.frustum, frustum, sizeof cam.frustum);
 	cam.lens_radius = box->cam.lens_radius; cam.focus_distance = box->cam.focus_distance; // (the lens stays on the camera as it moves; the close state went with the old camera)
+	cam.projection = box->cam.projection; cam.ortho_height = box->cam.ortho_height; cam.lon_range = box->cam.lon_range; cam.lat_range = box->cam.lat_range; // (so does the projection)
 	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
 	box->cam = cam;
 	return 0;
@@ -253,6 +254,17 @@ int polaris_host_renderer_set_shutter(void *h, const float eye1[3], const float 
 		memcpy(cam.frustum1, frustum1, sizeof cam.frustum1);
 		cam.focus_distance1 = focus_distance1 > 0.0f ? focus_distance1 : 0.0f;
 	}
+	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
+	box->cam = cam;
+	return 0;
+}
+// The projection (CameraData.projection / ortho_height / lon_range / lat_range; polaris_hip_set_projection): the CameraData of
+// every tracer again, now with this projection, which every later polaris_host_renderer_set_camera keeps with the new frustum's basis.
+// kind = 0 turns it off.  Refused by the tracers while the lens or the shutter is on.
+int polaris_host_renderer_set_projection(void *h, uint32_t kind, float ortho_height, float lon_range, float lat_range) {
+	auto *box = static_cast<RendererBox *>(h);
+	tracer::CameraData cam = box->cam;
+	cam.projection = kind; cam.ortho_height = ortho_height; cam.lon_range = lon_range; cam.lat_range = lat_range;
 	if (Error e = box->r->UpdateAll(tracer::ChangeType::CameraData, &cam)) { box->error = e.msg; return e.code; }
 	box->cam = cam;
 	return 0;

@@ -2,7 +2,7 @@
 // tests: the same per-pixel arithmetic from polaris_amd/csrc/temporal.h, so the PRIOR, PRIOR2 and TEMPORAL planes of
 // polaris_hip_sync_framebuffer are compared with these bit for bit (tests/test_gpu_temporal.py, test_gpu_variance.py,
 // test_gpu_motion.py, test_gpu_vertex_motion.py), and their numbers are checked against independent numpy statements of the
-// algorithm (tests/test_temporal_cpu.py and its relatives).  The four reprojection entries share their description and argument
+// algorithm (tests/test_temporal_cpu.py and its relatives).  The four perspective reprojection entries share their description and argument
 // rules with the device's test entries (polaris_amd/csrc/reproject_io.h).
 #include <vector>
 
@@ -112,6 +112,71 @@ int polaris_host_reproject_deform(const float *history, const float *prev_guide,
 	return reproject(ReprojectIo{history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum, frame_w, frame_h, p, prior,
 	                             kRpDeform, history_variance, prior2, prev_instance, instance, n_instances, prev_inv_transforms, inv_transforms,
 	                             hit, vertices, prev_vertices, num_triangles});
+}
+
+// ---- polaris_hip_set_projection.  The entries above are untouched and mean kind 0.
+namespace {
+// The projection as temporal.h takes it; false where polaris_hip_set_projection would not have stored it (the entries below check only
+// what they read: the kind and the struct's size).
+bool host_projection(const PolarisProjectionParams *proj, TpProjection &P) {
+	if (!proj || proj->struct_size != sizeof(PolarisProjectionParams)) return false;
+	if (proj->kind != POLARIS_PROJECTION_ORTHOGRAPHIC && proj->kind != POLARIS_PROJECTION_EQUIRECTANGULAR) return false;
+	const bool ortho = proj->kind == POLARIS_PROJECTION_ORTHOGRAPHIC;
+	P = TpProjection{proj->kind, {proj->axis[0], proj->axis[1], proj->axis[2]}, {proj->right[0], proj->right[1], proj->right[2]},
+	                 {proj->up[0], proj->up[1], proj->up[2]}, ortho ? proj->half_width : proj->lon_range, ortho ? proj->half_height : proj->lat_range};
+	return true;
+}
+} // namespace
+
+// polaris_host_reproject under a projection (k_reproject_proj<false, false>): the history camera and the current one share `proj` and
+// differ in the eye; there is no frustum.
+int polaris_host_reproject_projection(const float *history, const float *prev_guide, const float *prev_albedo, const float prev_eye[3],
+                                      const float *guide, const float *albedo, const float eye[3], const PolarisProjectionParams *proj,
+                                      uint32_t frame_w, uint32_t frame_h, const PolarisTemporalParams *p, float *prior) {
+	TpProjection P;
+	if (!history || !prev_guide || !prev_albedo || !prev_eye || !guide || !albedo || !eye || !p || !prior || !host_projection(proj, P)) return POLARIS_E_BAD_ARGUMENT;
+	if (frame_w == 0 || frame_h == 0 || p->struct_size != sizeof(PolarisTemporalParams) || tp_check(p->max_history, p->normal_threshold, p->depth_threshold))
+		return POLARIS_E_BAD_ARGUMENT;
+	const TpProjCamera hcam{P, {prev_eye[0], prev_eye[1], prev_eye[2]}}, cam{P, {eye[0], eye[1], eye[2]}};
+	auto load = [&](uint32_t j, TpTap &t) {
+		const float *c = history + 4 * (size_t)j, *n = prev_guide + 4 * (size_t)j;
+		t = TpTap{c[0], c[1], c[2], c[3], n[0], n[1], n[2], n[3], prev_albedo[4 * (size_t)j + 3], 0.0f, 0u};
+	};
+	const size_t F = (size_t)frame_w * frame_h;
+	for (size_t i = 0; i < F; i++) {
+		float *o = prior + 4 * i;
+		if (p->max_history == 0) { o[0] = o[1] = o[2] = o[3] = 0.0f; continue; }
+		tp_reproject((uint32_t)(i % frame_w), (uint32_t)(i / frame_w), frame_w, frame_h, guide + 4 * i, albedo[4 * i + 3], cam, hcam, p->max_history,
+		             p->normal_threshold, p->depth_threshold, load, o);
+	}
+	return POLARIS_OK;
+}
+
+// The guide rays of a projected camera (tp_guide_ray: what k_gbuffer_proj casts): origin and direction of every pixel's centre ray,
+// frame_w * frame_h times three floats each.
+int polaris_host_projection_rays(const PolarisProjectionParams *proj, const float eye[3], uint32_t frame_w, uint32_t frame_h, float *origins, float *directions) {
+	TpProjection P;
+	if (!eye || !origins || !directions || frame_w == 0 || frame_h == 0 || !host_projection(proj, P)) return POLARIS_E_BAD_ARGUMENT;
+	const TpProjCamera cam{P, {eye[0], eye[1], eye[2]}};
+	for (uint32_t gy = 0; gy < frame_h; gy++)
+		for (uint32_t gx = 0; gx < frame_w; gx++) {
+			const size_t i = (size_t)gy * frame_w + gx;
+			tp_guide_ray(cam, gx, gy, 1.0f / (float)frame_w, 1.0f / (float)frame_h, origins + 3 * i, directions + 3 * i);
+		}
+	return POLARIS_OK;
+}
+
+// tp_project of a projected camera for n points (three floats each): uvd = u | v | dist per point, ok = 1 where the projection exists.
+int polaris_host_projection_project(const PolarisProjectionParams *proj, const float eye[3], const float *points, uint32_t n, float *uvd, uint8_t *ok) {
+	TpProjection P;
+	if (!eye || !points || !uvd || !ok || !host_projection(proj, P)) return POLARIS_E_BAD_ARGUMENT;
+	const TpProjCamera cam{P, {eye[0], eye[1], eye[2]}};
+	for (uint32_t i = 0; i < n; i++) {
+		float u = 0.0f, v = 0.0f, dist = 0.0f;
+		ok[i] = tp_project(cam, points + 3 * (size_t)i, u, v, dist) ? 1 : 0;
+		uvd[3 * (size_t)i] = u; uvd[3 * (size_t)i + 1] = v; uvd[3 * (size_t)i + 2] = dist;
+	}
+	return POLARIS_OK;
 }
 
 // tp_motion_matrix for the tests: the flag (0 STATIC, 1 MOVED, 2 INVALID) and D's twelve floats (rows r0, r1, r2).

@@ -42,9 +42,13 @@ struct FrameDims { uint32_t w, h; };                 // payload of FrameDimensio
 // lens_radius focused at focus_distance along the view axis, which the tracer sets after the camera (hip_tracer.cpp, lensFromFrustum).
 // has_close: the camera at shutter close (polaris_hip_set_shutter, set after the lens): eye1, frustum1, and under a lens its focus distance
 // there (focus_distance1, 0: the open one; the close lens' vectors follow frustum1 with the same radius).  Without it the shutter is off.
+// projection: POLARIS_PROJECTION_* (polaris_hip_set_projection, set after the camera; 0 = off, the perspective frustum): the orthographic
+// camera's window is ortho_height high and as wide as the frustum's aspect makes it, the equirectangular camera spans lon_range x lat_range
+// radians; the view basis follows the frustum (hip_tracer.cpp, projectionOf).  It excludes the lens and the shutter.
 struct CameraData {
 	float eye[3]; float frustum[16]; float lens_radius = 0, focus_distance = 0;
 	bool has_close = false; float eye1[3] = {0, 0, 0}; float frustum1[16] = {}; float focus_distance1 = 0;
+	uint32_t projection = 0; float ortho_height = 0, lon_range = 0, lat_range = 0;
 };
 
 class Tracer { // tracer/tracer.go:80-111

@@ -44,6 +44,7 @@ def load() -> C.CDLL:
         lib.polaris_host_renderer_set_camera.argtypes = [vp, vp, vp]
         lib.polaris_host_renderer_set_lens.argtypes = [vp, C.c_float, C.c_float]
         lib.polaris_host_renderer_set_shutter.argtypes = [vp, vp, vp, C.c_float]
+        lib.polaris_host_renderer_set_projection.argtypes = [vp, C.c_uint32, C.c_float, C.c_float, C.c_float]
         lib.polaris_host_renderer_set_variance.argtypes = [vp, C.POINTER(T.VarianceParams)]
         lib.polaris_host_renderer_set_display.argtypes = [vp, C.POINTER(T.DisplayParams)]
         lib.polaris_host_renderer_read_exposure.argtypes = [vp, C.POINTER(T.ExposureInfo), vp]
@@ -66,6 +67,9 @@ def load() -> C.CDLL:
         lib.polaris_host_reproject_deform.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(T.TemporalParams),
                                                       vp, vp, vp, vp, vp, vp, u32]
         lib.polaris_host_motion_matrix.argtypes = [vp, vp, C.POINTER(u32), vp]
+        lib.polaris_host_reproject_projection.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(T.ProjectionParams), u32, u32, C.POINTER(T.TemporalParams), vp]
+        lib.polaris_host_projection_rays.argtypes = [C.POINTER(T.ProjectionParams), vp, u32, u32, vp, vp]
+        lib.polaris_host_projection_project.argtypes = [C.POINTER(T.ProjectionParams), vp, vp, u32, vp, vp]
         lib.polaris_host_temporal_combine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         lib.polaris_host_camera_move.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.c_uint32, vp, vp, vp]
         lib.polaris_host_denoise.argtypes = [vp, C.c_float, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -272,6 +276,17 @@ class Renderer:
         if rc:
             raise RuntimeError(f"set_shutter failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
 
+    def set_projection(self, kind, height: float | None = None, lon_range: float = 2.0 * np.pi, lat_range: float = np.pi) -> None:
+        """The camera projection on every tracer (CameraData.projection: each tracer's UpdateState(CameraData) sets camera, then
+        projection, with the view basis of the frustum): "orthographic" with a window `height` world units high, or "equirect" spanning
+        lon_range x lat_range radians, also by their T.PROJECTION_* numbers.  Every later set_camera keeps it.  set_projection(None)
+        turns it off.  Refused while the lens or the shutter is on."""
+        number = T.PROJECTION_PERSPECTIVE if kind is None else (T.PROJECTION_KINDS[kind] if isinstance(kind, str) else int(kind))
+        if number == T.PROJECTION_ORTHOGRAPHIC and height is None:
+            raise ValueError("an orthographic projection needs the height of its window")
+        if self._lib.polaris_host_renderer_set_projection(self._h, number, float(height or 0.0), float(lon_range), float(lat_range)):
+            raise RuntimeError(f"set_projection failed: {self._lib.polaris_host_renderer_error(self._h).decode()}")
+
     def read_aov(self, which: int) -> np.ndarray:
         """The primary's (H, W, 4) denoiser plane (polaris_hip_read_aov)."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
@@ -442,6 +457,40 @@ def reproject_deform(history, prev_guide, prev_albedo, prev_instance, prev_eye, 
     return _reproject("reproject_deform", _host_call("reproject_deform"), history, prev_guide, prev_albedo, prev_eye, prev_frustum, guide, albedo, eye, frustum,
                       (max_history, normal_threshold, depth_threshold), history_variance=history_variance, instances=(prev_instance, instance), tables=(prev_inv_transforms, inv_transforms),
                       deform=(hit, vertices, prev_vertices))
+
+
+def reproject_projection(history, prev_guide, prev_albedo, prev_eye, guide, albedo, eye, projection, *, max_history: int = 32,
+                         normal_threshold: float = 0.9, depth_threshold: float = 0.1) -> np.ndarray:
+    """polaris_host_reproject_projection: reproject() under polaris_hip_set_projection -- the history camera and the current one share
+    `projection` (a ctypes_api.ProjectionParams with kind != 0) and differ in the eye.  Returns the PRIOR plane."""
+    planes = [np.ascontiguousarray(x, dtype=np.float32) for x in (history, prev_guide, prev_albedo, guide, albedo)]
+    H, W = planes[0].shape[:2]
+    if any(x.shape != (H, W, 4) for x in planes):
+        raise ValueError("reproject_projection: the planes must all be (H, W, 4)")
+    e0, e1 = (np.ascontiguousarray(x, dtype=np.float32).reshape(3) for x in (prev_eye, eye))
+    prior = np.zeros((H, W, 4), np.float32)
+    p = T.temporal_params(max_history, normal_threshold, depth_threshold)
+    _host_call("reproject_projection")(planes[0].ctypes.data, planes[1].ctypes.data, planes[2].ctypes.data, e0.ctypes.data, planes[3].ctypes.data,
+                                       planes[4].ctypes.data, e1.ctypes.data, C.byref(projection), W, H, C.byref(p), prior.ctypes.data)
+    return prior
+
+
+def projection_rays(projection, eye, W: int, H: int) -> tuple[np.ndarray, np.ndarray]:
+    """polaris_host_projection_rays: (origins, directions), each (H * W, 3) float32 -- the guide ray through every pixel's centre under
+    `projection`, from the header the G-buffer kernels use (polaris_amd/csrc/temporal.h, tp_guide_ray)."""
+    e = np.ascontiguousarray(eye, dtype=np.float32).reshape(3)
+    o, d = np.zeros((H * W, 3), np.float32), np.zeros((H * W, 3), np.float32)
+    _host_call("projection_rays")(C.byref(projection), e.ctypes.data, W, H, o.ctypes.data, d.ctypes.data)
+    return o, d
+
+
+def projection_project(projection, eye, points) -> tuple[np.ndarray, np.ndarray]:
+    """polaris_host_projection_project: tp_project of the projected camera for (n, 3) points -- ((n, 3) u | v | dist, (n,) bool ok)."""
+    e = np.ascontiguousarray(eye, dtype=np.float32).reshape(3)
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    uvd, ok = np.zeros((pts.shape[0], 3), np.float32), np.zeros(pts.shape[0], np.uint8)
+    _host_call("projection_project")(C.byref(projection), e.ctypes.data, pts.ctypes.data, pts.shape[0], uvd.ctypes.data, ok.ctypes.data)
+    return uvd, ok.astype(bool)
 
 
 MOTION_STATIC, MOTION_MOVED, MOTION_INVALID = 0, 1, 2

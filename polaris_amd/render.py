@@ -36,6 +36,10 @@ the options "object_motion" and "vertex_motion" are on, so the history is carrie
 DESIGN.md 10h; it stays on the camera through --frames moves).  --focus-pixel x,y takes D from the GUIDE plane instead: the first hit
 under that pixel's centre, t * dot(centre direction, axis); a pixel that sees nothing is an error.
 
+--projection orthographic --ortho-height F renders through a window F scene units high with parallel rays; --projection equirect
+renders a latitude-longitude panorama of --lon-range x --lat-range degrees (default 360 x 180) around the eye
+(polaris_hip_set_projection; either stays on the camera through --frames moves and excludes --aperture and --shutter).
+
 --frames N --shutter F (0 <= F <= 1, default 0 = an instantaneous exposure) leaves the shutter open for the fraction F of the way to
 the next frame (polaris_hip_set_shutter): frame k's camera rays spread in time between its camera and the camera one
 more move of F * OFFSET on -- camera motion blur.  A lens stays on both ends, with the same radius and focus distance.
@@ -53,6 +57,7 @@ are ctypes_api.BLOOM_DEFAULTS).  Bloom is part of the display transform: --bloom
 error, and so are --bloom-threshold and --bloom-levels without --bloom."""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -209,6 +214,10 @@ def main(argv=None):
     ap.add_argument("--focus", type=float, default=0.0, help="with --aperture: distance of the plane of focus along the view axis")
     ap.add_argument("--focus-pixel", default="", help="with --aperture, x,y: focus on what this pixel's centre sees instead of --focus")
     ap.add_argument("--shutter", type=float, default=0.0, help="with --frames (camera moves): the shutter stays open this fraction 0..1 of the way to the next frame (0 = off)")
+    ap.add_argument("--projection", choices=sorted(T.PROJECTION_KINDS), default="perspective", help="the camera's projection (orthographic needs --ortho-height)")
+    ap.add_argument("--ortho-height", type=float, default=None, help="with --projection orthographic: the height of the window through the eye, scene units")
+    ap.add_argument("--lon-range", type=float, default=360.0, help="with --projection equirect: degrees of longitude the frame's width spans")
+    ap.add_argument("--lat-range", type=float, default=180.0, help="with --projection equirect: degrees of latitude the frame's height spans")
     ap.add_argument("--tonemap", choices=sorted(T.TONE_OPERATORS), default=None, help="the display transform's tone operator (default: the plain tone-map)")
     ap.add_argument("--white", type=float, default=T.DISPLAY_DEFAULTS["white"], help="with --tonemap reinhard-white / hable: the radiance mapped to 1")
     ap.add_argument("--srgb", action="store_true", help="the sRGB transfer function instead of pow(1 / 2.2)")
@@ -235,6 +244,12 @@ def main(argv=None):
         ap.error("--ripple AMPLITUDE:WAVELENGTH needs --frames and no --recolour")
     if a.aperture < 0 or (a.aperture and not a.focus_pixel and not a.focus > 0):
         ap.error("--aperture R needs --focus D > 0 or --focus-pixel x,y")
+    if a.projection != "perspective" and (a.aperture or a.shutter):
+        ap.error("--projection orthographic / equirect excludes --aperture and --shutter")
+    if (a.projection == "orthographic") != (a.ortho_height is not None) or (a.ortho_height is not None and not a.ortho_height > 0):
+        ap.error("--projection orthographic needs --ortho-height F > 0, and nothing else takes it")
+    if a.projection != "equirect" and (a.lon_range != 360.0 or a.lat_range != 180.0):
+        ap.error("--lon-range and --lat-range need --projection equirect")
 
     rr = a.rr_bounces
     if rr == 0 or rr >= a.num_bounces:
@@ -268,6 +283,8 @@ def main(argv=None):
                 x, _, y = a.focus_pixel.partition(",")
                 focus = focus_of_pixel(r.read_aov(T.AOV_GUIDE), sc.frustum, int(x), int(y))
             r.set_lens(a.aperture, focus)
+        if a.projection != "perspective":   # (every later camera move keeps it, with the new frustum's basis)
+            r.set_projection(a.projection, height=a.ortho_height, lon_range=math.radians(a.lon_range), lat_range=math.radians(a.lat_range))
         if a.frames:
             if a.ripple:
                 frames = ripple_frames(r, sc, a.frames, a.ripple, bool(a.temporal))

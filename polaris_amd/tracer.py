@@ -73,6 +73,7 @@ class HipTracer:
         self._camera = None   # the CameraData last committed (set_lens derives its vectors from it)
         self._lens = None     # (radius, focus_distance) of set_lens: re-applied after every camera update
         self._shutter = None  # (eye_close, frustum_close, focus_close) of set_shutter: forgotten at every camera update, re-sent after a set_lens
+        self._projection = None  # (kind, height, lon_range, lat_range) of set_projection: re-sent with the new basis after every camera update
 
     # ---- tracer.Tracer ---------------------------------------------------------------------
     def Id(self) -> str:
@@ -215,6 +216,35 @@ class HipTracer:
         else:
             axis1, u1, v1 = T.lens_from_frustum(frustum1, self._lens[0])
             self.set_shutter_params(T.shutter_params(eye1, frustum1, self._lens[1] if focus1 is None else focus1, axis1, u1, v1))
+
+    def set_projection(self, kind, height: float | None = None, lon_range: float = 2.0 * np.pi, lat_range: float = np.pi) -> None:
+        """Camera projection (polaris_hip_set_projection): kind "orthographic" (a window `height` world units high through the eye, as
+        wide as the frustum's aspect makes it) or "equirect" (a lon_range x lat_range radians panorama), also by their T.PROJECTION_*
+        numbers, looking along the view basis of the camera last given through UpdateState (T.projection_from_frustum); re-sent with the
+        new basis after every later camera update.  set_projection(None) (or "perspective") turns it off (the default).  Refused with the
+        lens or the shutter on.  The caller restarts accumulation, as after a camera change."""
+        self._commit()
+        number = T.PROJECTION_PERSPECTIVE if kind is None else (T.PROJECTION_KINDS[kind] if isinstance(kind, str) else int(kind))
+        if number == T.PROJECTION_PERSPECTIVE:
+            self._projection = None
+            self.set_projection_params(T.projection_params())
+            return
+        previous, self._projection = self._projection, (number, height, float(lon_range), float(lat_range))
+        try:
+            self._apply_projection()
+        except (TracerError, ValueError):
+            self._projection = previous   # (a refusal changed nothing in the library)
+            raise
+
+    def set_projection_params(self, p: T.ProjectionParams) -> None:
+        """The raw call (T.projection_params builds the struct): the basis is the caller's and is not re-derived at a camera update."""
+        self._check(self._lib.polaris_hip_set_projection(self._h, C.byref(p)), self._h)
+
+    def _apply_projection(self) -> None:
+        if self._camera is None:
+            raise TracerError(2, "set_projection: no camera given through UpdateState yet")
+        kind, height, lon_range, lat_range = self._projection
+        self.set_projection_params(T.projection_for(kind, self._camera.frustum, height, lon_range, lat_range))
 
     def set_variance(self, sigma_variance: float = 8.0, min_samples: int = 8) -> None:
         """Variance-guided denoising at every SyncFramebuffer (polaris_hip_set_variance): turns the option "moments" on first, then
@@ -591,6 +621,8 @@ class HipTracer:
                 self._shutter = None         # (set_camera switched the shutter off: its close camera belonged to the camera that went)
                 if self._lens is not None:   # (set_camera leaves the lens vectors alone: they follow the new frustum here)
                     self._apply_lens()
+                if self._projection is not None:   # (... and the projection's basis)
+                    self._apply_projection()
             else:
                 raise TracerError(2, f"unsupported change type {change}")
         self._changes.clear()
